@@ -12,6 +12,12 @@ sums.  `ms_per_step` is therefore the proof-generation wall-clock and `value` th
 committed per second of proving (the metric's two halves); the MSM and NTT kernels' own rates are
 reported next to them.  Multi-GPU: independent proofs per rank (weak scaling, no data-path collective;
 DESIGN.md section "Multi-GPU").
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the line.  `--full` adds everything
+else the line used to carry: the per-kernel HIP-event timings of the timed steps and the roofline blocks built on them
+(with the stand-alone NTT and the modmul peak), the k=20 leg (BASELINE configs[3]), the secondary legs and the CPU
+baseline.  `--dump-outputs DIR` writes the proof of the last timed step (rank 0) as DIR/proof.npy: its bytes as float64,
+one element per byte; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -130,6 +136,9 @@ def main():
     ap.add_argument("--no-extra-legs", action="store_true", help="skip host_advice / dense_witness / ntt_ext / msm_standalone / batched_k22")
     ap.add_argument("--no-k20", action="store_true", help="skip the BASELINE configs[3] leg (k=20, one proof over all ranks)")
     ap.add_argument("--k20-child", action="store_true", help=argparse.SUPPRESS)  # internal: the configs[3] leg in a process of its own
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel timings + roofline blocks, the k=20 leg, the secondary legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's proof to DIR/proof.npy (float64, one per byte)")
     args = ap.parse_args()
     if args.k20_child:
         return k20_child_main()
@@ -164,12 +173,14 @@ def main():
     barrier = D.barrier
 
     proof = b""
-    ctx.profile_enable(True)  # before the warm-up: the profiling events are created on first use, not in the timed region
+    if args.full:  # per-kernel HIP events for the roofline blocks; the headline does not need them
+        ctx.profile_enable(True)  # before the warm-up: the profiling events are created on first use, not in the timed region
     for i in range(args.warmup):
         proof = step(i)
-    ctx.profile_read(PROF_MSM_ACCUMULATE)
-    ctx.profile_read(PROF_NTT_PASS)
-    ctx.profile_read(PROF_MSM_ENTRIES)
+    if args.full:
+        ctx.profile_read(PROF_MSM_ACCUMULATE)
+        ctx.profile_read(PROF_NTT_PASS)
+        ctx.profile_read(PROF_MSM_ENTRIES)
     import gc
 
     gc.disable()  # a generation-2 collection of the interpreter (torch's module graph) is milliseconds; it is not proving.
@@ -184,10 +195,13 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    acc_ms, acc_calls = ctx.profile_read(PROF_MSM_ACCUMULATE)
-    ntt_ms, ntt_calls = ctx.profile_read(PROF_NTT_PASS)
-    _, msm_entries = ctx.profile_read(PROF_MSM_ENTRIES)
-    ctx.profile_enable(False)
+    if args.full:
+        acc_ms, acc_calls = ctx.profile_read(PROF_MSM_ACCUMULATE)
+        ntt_ms, ntt_calls = ctx.profile_read(PROF_NTT_PASS)
+        _, msm_entries = ctx.profile_read(PROF_MSM_ENTRIES)
+        ctx.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proof)
 
     elapsed = D.max_over_ranks([elapsed])[0]
 
@@ -232,7 +246,7 @@ def main():
     # ---- BASELINE configs[3]: ONE k = 20 proof over all the ranks of the job (strong scaling).  Collective: every rank
     #      takes part; rank 0 keeps the figures.  A watchdog prints the line without it should a collective hang. ----
     k20 = None
-    if not args.no_k20 and k == 18:
+    if args.full and not args.no_k20 and k == 18:
         if world == 1 and os.environ.get("CQ_BENCH_K20_CHILD", "0") != "1":  # (the env switch: the child path on one GPU, for testing)
             try:
                 k20 = config3_k20(ctx, D)
@@ -243,9 +257,18 @@ def main():
     if rank == 0:
         if k20 is not None:
             out["config3_k20"] = k20
-        _finish_line(out, ctx, wl, args, k, acc_ms, acc_calls, ntt_ms, ntt_calls, msm_entries, world)
+        if args.full:
+            _finish_line(out, ctx, wl, args, k, acc_ms, acc_calls, ntt_ms, ntt_calls, msm_entries, world)
+        else:
+            print(json.dumps(out), flush=True)
     ctx.close()
     D.finish()
+
+
+def dump_outputs(directory, proof):
+    """What a caller of the timed path receives: the proof bytes, as float64 (one element per byte; exact)."""
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "proof.npy"), np.frombuffer(proof, dtype=np.uint8).astype(np.float64))
 
 
 def _finish_line(out, ctx, wl, args, k, acc_ms, acc_calls, ntt_ms, ntt_calls, msm_entries, world, light=False):

@@ -2,7 +2,7 @@
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`, here with CQ_BENCH_DIST_BACKEND=gloo (every rank on
 cuda:0, the sharded legs over the library's host-callback transport instead of RCCL, which refuses two ranks on one device):
 the replicas headline with its barriers and MAX reduction, the configs[3] leg in child processes (k20_in_children), the JSON
-merge on rank 0.  The line is validated, and the sharded proof's digest must equal the unsharded proof's."""
+merge on rank 0 (the legs beyond the headline: `--full`).  The line is validated, and the sharded proof's digest must equal the unsharded proof's."""
 import hashlib
 import json
 import os
@@ -30,7 +30,8 @@ def test_bench_two_ranks_on_one_gpu(ctx):
     from sha2_on_cq_halo2_amd.sha_circuit import ShaCqWorkload
 
     kk, steps = 16, 2
-    line = _run_bench(2, {"CQ_BENCH_K20_K": str(kk), "CQ_BENCH_K20_STEPS": str(steps), "CQ_BENCH_K20_TIMEOUT": "300"}, 29731)
+    line = _run_bench(2, {"CQ_BENCH_K20_K": str(kk), "CQ_BENCH_K20_STEPS": str(steps), "CQ_BENCH_K20_TIMEOUT": "300"}, 29731,
+                      args=("--full",))
     assert line["n_gpus"] == 2 and line["steps"] == 3 and line["warmup"] == 1 and line["scaling"] == "weak"
     assert line["unit"] == "Mscalar/s" and line["value"] > 0 and line["higher_is_better"] is True
     assert line["config"]["dist_backend"] == "gloo" and "replicas x2" in line["config"]["parallelism"]

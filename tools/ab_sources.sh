@@ -10,7 +10,7 @@ for v in old new; do
   CQ_BUILD_JOBS=12 python3 sha2_on_cq_halo2_amd/build.py --force > /dev/null
   echo "== $v"
   for k in ${AB_KS:-16 18}; do python3 tools/prove_large.py $k | grep prove | tail -2; done
-  python3 bench.py --no-extra-legs --steps ${AB_STEPS:-60} --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
+  python3 bench.py --full --no-extra-legs --steps ${AB_STEPS:-60} --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; t=sorted(d['step_ms_all_this_rank'])
 print('bench mean %.3f  median %.3f  min %.3f  p25 %.3f  p75 %.3f' % (d['ms_per_step'], t[len(t)//2], t[0], t[len(t)//4], t[3*len(t)//4]), ' acc avg_launch_ms %.4f' % r['avg_launch_ms'], 'valu_frac %.3f' % r['valu_frac'])"

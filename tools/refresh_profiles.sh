@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r2f
 mkdir -p $O
 # 1. timed-region stats (headline workload only)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/timed -o run -- python3 bench.py --steps 20 --warmup 5 --no-plonk-variant --no-in-flight --no-cpu-baseline --no-k20 --no-generic-rng > $O/timed_line.json 2> $O/timed.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/timed -o run -- python3 bench.py --full --steps 20 --warmup 5 --no-plonk-variant --no-in-flight --no-cpu-baseline --no-k20 --no-generic-rng > $O/timed_line.json 2> $O/timed.err
 python3 tools/kstats.py $O/timed > $O/timed_summary.txt
 cp $O/timed/run_kernel_stats.csv $O/timed_kernel_stats.csv
 # 2. timeline of one proof

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r3prof
 mkdir -p $O
 # 1. timed-region stats (headline workload only)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/timed -o run -- python3 bench.py --steps 20 --warmup 5 --no-plonk-variant --no-in-flight --no-cpu-baseline --no-k20 --no-generic-rng --no-extra-legs > $O/r03_bench_timed_region_line.json 2> $O/timed.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/timed -o run -- python3 bench.py --full --steps 20 --warmup 5 --no-plonk-variant --no-in-flight --no-cpu-baseline --no-k20 --no-generic-rng --no-extra-legs > $O/r03_bench_timed_region_line.json 2> $O/timed.err
 python3 tools/kstats.py $O/timed > $O/r03_bench_timed_region_summary.txt
 cp $O/timed/run_kernel_stats.csv $O/r03_bench_timed_region_kernel_stats.csv
 echo "timed region done"
@@ -29,7 +29,7 @@ python3 tools/pmc_sq.py $O/pmc_sq msm_accumulate_kernel $O/r03_pmc_sq_accumulate
 echo "pmc done"
 # 4. the host's milestones of one proof, no profiler attached (what the gaps between rounds are made of)
 CQ_TRACE_HOST=1 python3 tools/prove_large.py 18 > $O/host_trace.out 2> $O/r03_host_trace_k18.txt
-# 5. the plain bench line on the same box
-python3 bench.py --steps 20 --warmup 5 > $O/r03_bench_create_proof_k18_line_unprofiled.json 2> $O/bench.err
+# 5. the unprofiled bench line (every leg) on the same box
+python3 bench.py --full --steps 20 --warmup 5 > $O/r03_bench_create_proof_k18_line_unprofiled.json 2> $O/bench.err
 rm -rf $O/timed $O/tl $O/tl20 $O/pmc_fetch $O/pmc_write $O/pmc_sq
 ls $O
