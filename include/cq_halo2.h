@@ -44,6 +44,7 @@ typedef struct cq_domain cq_domain;   /* EvaluationDomain<Fr>, poly/domain.rs:19
 typedef struct cq_params cq_params;   /* ParamsKZG<Bn256> G1 part, poly/kzg/commitment.rs:31-39 */
 typedef struct cq_table_config cq_table_config; /* StaticTableConfig, plonk/static_lookup.rs:47-66 */
 typedef struct cq_static_table cq_static_table; /* StaticTableValues, plonk/static_lookup.rs:68-75 */
+typedef struct cq_g2_srs cq_g2_srs;   /* the G2 powers of TableSRS, poly/kzg/commitment.rs:73-123 (`g2`) */
 typedef struct cq_pk cq_pk;           /* ProvingKey slice read by the CQ-only prover, plonk.rs:291-308 */
 /* `R: RngCore` of create_proof (plonk/prover.rs:65): the library calls next_u64 exactly as
  * `Fr::random` does (8 calls per scalar, low limb first, bn256/fr.rs:159-170). */
@@ -139,6 +140,17 @@ int cq_msm_batch_dev(cq_ctx* ctx, const uint64_t* const* coeffs_dev, const uint6
  * (derive/curve.rs:399-412). */
 int cq_g1_sum(const uint64_t* jac_points, size_t count, uint64_t out_jac[12]);
 int cq_g1_to_affine(const uint64_t jac[12], uint64_t out_affine[8]);
+/* best_multiexp(coeffs, bases) over G2Affine  arithmetic.rs:132-159.  G2 affine points are 16 limbs (x.c0, x.c1, y.c0,
+ * y.c1, each 4 Montgomery limbs: halo2curves' SerdeObject raw layout; all zero = identity); the result is Jacobian,
+ * 24 limbs (x, y, z; z = 0 = identity) in HOST memory.  Host arrays; the _dev form takes device arrays.  Used for the
+ * table commitment of StaticTableValues::commit (static_lookup.rs:141). */
+int cq_best_multiexp_g2(cq_ctx* ctx, const uint64_t* coeffs, const uint64_t* bases, size_t len, uint64_t out_jac[24]);
+int cq_best_multiexp_g2_dev(cq_ctx* ctx, const uint64_t* coeffs_dev, const uint64_t* bases_dev, size_t len,
+                            uint64_t out_jac[24]);
+/* The G2 twins of cq_g1_sum / cq_g1_to_affine: sum of `count` Jacobian G2 points, and Curve::to_affine
+ * (derive/curve.rs:399-412) on the host. */
+int cq_g2_sum(const uint64_t* jac_points, size_t count, uint64_t out_jac[24]);
+int cq_g2_to_affine(const uint64_t jac[24], uint64_t out_affine[16]);
 /* Fixed-base acceleration: builds per-window tables T[w][i] = 2^(c*w) * bases[i] (ceil(255/c) x n x 64 B of
  * HBM) for a device-resident base array and registers them with the context; later multiexps over
  * that array (or a prefix of it) then need a single bucket set and no window folding.  cq_params_*
@@ -251,6 +263,27 @@ int cq_static_table_new(cq_ctx* ctx, size_t size, const uint64_t* values, const 
 int cq_static_table_new_fk(cq_ctx* ctx, size_t size, const uint64_t* values, const uint64_t* srs_g1, cq_static_table** out);
 void cq_static_table_destroy(cq_static_table* table);
 int cq_static_table_download_qs(cq_static_table* table, uint64_t* qs_affine);
+/* The G2 powers of TableSRS (kzg/commitment.rs:73-123, field `g2`): `count` affine points [s^i]_2 resident in HBM.
+ * cq_g2_srs_create uploads them from host memory (16 limbs each); with `checked` != 0 every coordinate must be below the
+ * modulus and every point on the twist y^2 = x^3 + 3/(9+i) (the identity passes), else CQ_ERR_ARG -- as the
+ * RawBytes reads of G1 points.  cq_g2_srs_setup_from_toxic_waste builds [s^i]_2, i < count, on the GPU: the G2 half of
+ * TableSRS::setup_from_toxic_waste (tests/benches).  cq_g2_srs_dev: the device array. */
+int cq_g2_srs_create(cq_ctx* ctx, size_t count, const uint64_t* points, int checked, cq_g2_srs** out);
+int cq_g2_srs_setup_from_toxic_waste(cq_ctx* ctx, size_t count, const uint64_t s[4], cq_g2_srs** out);
+int cq_g2_srs_download(cq_g2_srs* srs, uint64_t* points);
+size_t cq_g2_srs_len(const cq_g2_srs* srs);
+const uint64_t* cq_g2_srs_dev(const cq_g2_srs* srs);
+void cq_g2_srs_destroy(cq_g2_srs* srs);
+/* StaticTableValues::commit(srs_g2, srs_g1_len, circuit_n)  static_lookup.rs:128-157: the StaticCommittedTable that
+ * keygen_vk stores in vk.static_table_mapping (plonk/keygen.rs:261-265), as three affine G2 points (16 limbs each):
+ *   t          = best_multiexp(iNTT(values in ascending canonical order), srs_g2[..N])  -- the reference interpolates
+ *                the keys of its value -> index BTreeMap, so the table's own order does not matter;
+ *   zv         = srs_g2[N] - srs_g2[0];
+ *   x_b0_bound = srs_g2[srs_g1_len - 1 - (circuit_n - 2)].
+ * CQ_ERR_ARG (where the reference would panic) when srs_g2 has fewer than N + 1 points, circuit_n < 2, or the
+ * x_b0_bound index is negative or past the end of srs_g2. */
+int cq_static_table_commit(cq_static_table* table, cq_g2_srs* srs_g2, size_t srs_g1_len, size_t circuit_n, uint64_t zv[16],
+                           uint64_t t[16], uint64_t x_b0_bound[16]);
 
 /* Gate polynomials (`Expression`, plonk/circuit.rs:780-1100, as stored in vk.cs.gates after selector
  * compression) cross the boundary as postfix programs of u32 words: word = op | arg << 8.  A column query

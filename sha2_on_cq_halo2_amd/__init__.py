@@ -8,5 +8,5 @@ the tests and the bench; arrays are numpy uint64[..., 4] Montgomery limbs, exact
 the Rust side holds.
 """
 from ._lib import CqError, load, header_symbols  # noqa: F401
-from .api import (Context, DevBuf, EvaluationDomain, ParamsKZG, ProvingKey, StaticTable,  # noqa: F401
+from .api import (Context, DevBuf, EvaluationDomain, G2Srs, ParamsKZG, ProvingKey, StaticTable,  # noqa: F401
                   TableConfig)

@@ -165,6 +165,31 @@ def _ctx_permute_expression_pair(self, k: int, input_values: np.ndarray, table_v
     return oa.download((usable, 4), np.uint64), ot.download((usable, 4), np.uint64)
 
 
+def _g2(a) -> np.ndarray:
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    assert a.ndim == 2 and a.shape[1] == 16, "expected uint64[n,16] G2 affine points"
+    return a
+
+
+def _ctx_best_multiexp_g2(self, coeffs: np.ndarray, bases: np.ndarray) -> np.ndarray:
+    """`best_multiexp(coeffs, bases)` over G2Affine (arithmetic.rs:132): Jacobian result, uint64[24]."""
+    coeffs = _fr(coeffs) if len(coeffs) else np.zeros((0, 4), dtype=np.uint64)
+    bases = _g2(bases) if len(bases) else np.zeros((0, 16), dtype=np.uint64)
+    if coeffs.shape[0] != bases.shape[0]:  # arithmetic.rs:133 assert_eq
+        raise CqError(-1, "best_multiexp: coeffs.len() != bases.len()")
+    out = np.zeros(24, dtype=np.uint64)
+    self._chk(self.lib.cq_best_multiexp_g2(self.h, coeffs.ctypes.data, bases.ctypes.data, coeffs.shape[0], out.ctypes.data))
+    return out
+
+
+def _ctx_best_multiexp_g2_dev(self, coeffs: DevBuf, bases_ptr: int, n: int) -> np.ndarray:
+    out = np.zeros(24, dtype=np.uint64)
+    self._chk(self.lib.cq_best_multiexp_g2_dev(self.h, coeffs.ptr, bases_ptr, n, out.ctypes.data))
+    return out
+
+
+Context.best_multiexp_g2 = _ctx_best_multiexp_g2
+Context.best_multiexp_g2_dev = _ctx_best_multiexp_g2_dev
 Context.set_msm_table_window = _ctx_set_msm_table_window
 Context.permute_expression_pair = _ctx_permute_expression_pair
 Context.best_multiexp = _ctx_best_multiexp
@@ -458,6 +483,49 @@ class StaticTable(_Handle):
         q = np.empty((self.size, 8), dtype=np.uint64)
         self.ctx._chk(self.ctx.lib.cq_static_table_download_qs(self.h, q.ctypes.data))
         return q
+
+    def commit(self, srs_g2: "G2Srs", srs_g1_len: int, circuit_n: int):
+        """`StaticTableValues::commit(srs_g2, srs_g1_len, circuit_n)` (static_lookup.rs:128-157): the verifying key's
+        StaticCommittedTable as (zv, t, x_b0_bound), three affine G2 points (uint64[16] each)."""
+        zv, t, xb = (np.zeros(16, dtype=np.uint64) for _ in range(3))
+        self.ctx._chk(self.ctx.lib.cq_static_table_commit(self.h, srs_g2.h, srs_g1_len, circuit_n, zv.ctypes.data, t.ctypes.data,
+                                                          xb.ctypes.data))
+        return zv, t, xb
+
+
+class G2Srs(_Handle):
+    """The G2 powers [s^i]_2 of `TableSRS` (poly/kzg/commitment.rs:73-123, field `g2`), resident on the GPU."""
+
+    _destroy = "cq_g2_srs_destroy"
+
+    def __init__(self, ctx: Context, points: np.ndarray, checked: bool = True):
+        p = _g2(points) if len(points) else np.zeros((0, 16), dtype=np.uint64)
+        self.ctx, self.count = ctx, p.shape[0]
+        h = C.c_void_p()
+        ctx._chk(ctx.lib.cq_g2_srs_create(ctx.h, self.count, p.ctypes.data, 1 if checked else 0, C.byref(h)))
+        self.h = h
+        ctx._children.add(self)
+
+    @classmethod
+    def setup_from_toxic_waste(cls, ctx: Context, count: int, s: np.ndarray) -> "G2Srs":
+        """[s^i]_2 for i < count, built on the GPU (the G2 half of TableSRS::setup_from_toxic_waste)."""
+        self = cls.__new__(cls)
+        self.ctx, self.count = ctx, count
+        sm = np.ascontiguousarray(s, dtype=np.uint64).reshape(4)
+        h = C.c_void_p()
+        ctx._chk(ctx.lib.cq_g2_srs_setup_from_toxic_waste(ctx.h, count, sm.ctypes.data, C.byref(h)))
+        self.h = h
+        ctx._children.add(self)
+        return self
+
+    @property
+    def dev(self) -> int:
+        return self.ctx.lib.cq_g2_srs_dev(self.h)
+
+    def download(self) -> np.ndarray:
+        p = np.empty((self.count, 16), dtype=np.uint64)
+        self.ctx._chk(self.ctx.lib.cq_g2_srs_download(self.h, p.ctypes.data))
+        return p
 
 
 class _CqPlonk(C.Structure):

@@ -291,4 +291,22 @@ int lookup_permute_dev(cq_ctx* c, uint64_t* in_canon, uint64_t* tab_canon, uint3
   return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "lookup_permute launch failed");
 }
 
+// sorts n (a power of two) canonical 256-bit keys in place, ascending -- the same network on one array (the key order
+// of the reference's `Ord` for field elements; StaticTableValues::commit sorts the table's values with it)
+int sort_canonical_dev(cq_ctx* c, uint64_t* keys, uint32_t n) {
+  hipStream_t s = c->stream;
+  if (n & (n - 1)) return c->fail(CQ_ERR_ARG, "sort_canonical: n not a power of two");
+  if (n < SORT_CHUNK) {
+    if (n >= 2) sort_small_kernel<<<dim3(1, 1), SORT_THREADS, 0, s>>>(keys, keys, n);
+  } else {
+    const dim3 lgrid(n / SORT_CHUNK, 1), ggrid((n / 2 + SORT_THREADS - 1) / SORT_THREADS, 1);
+    sort_lds_kernel<<<lgrid, SORT_THREADS, 0, s>>>(keys, keys, n, 2, SORT_CHUNK);
+    for (uint32_t kk = SORT_CHUNK << 1; kk <= n && kk != 0; kk <<= 1) {
+      for (uint32_t j = kk >> 1; j >= SORT_CHUNK; j >>= 1) sort_global_step_kernel<<<ggrid, SORT_THREADS, 0, s>>>(keys, keys, n, kk, j);
+      sort_lds_kernel<<<lgrid, SORT_THREADS, 0, s>>>(keys, keys, n, kk, kk);
+    }
+  }
+  return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "sort_canonical launch failed");
+}
+
 }  // namespace cq

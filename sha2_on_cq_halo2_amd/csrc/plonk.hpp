@@ -99,5 +99,7 @@ size_t lookup_permute_scratch_bytes(uint32_t k);
 int lookup_permute_dev(cq_ctx* c, uint64_t* in_canon, uint64_t* tab_canon, uint32_t u, uint32_t k, uint64_t* out_tab, void* scratch,
                        uint32_t* status_dev);
 int fr_from_canonical(cq_ctx* c, const uint64_t* in, uint32_t n, Fr* out);
+// n (a power of two) canonical keys sorted in place, ascending (lksort.hip)
+int sort_canonical_dev(cq_ctx* c, uint64_t* keys, uint32_t n);
 
 }  // namespace cq
