@@ -428,7 +428,8 @@ struct Fp29 {
     r.normalise();
     return r;
   }
-  // K p - b, normalised
+  // K p - b, normalised; in (0, K p] -- K p itself, not 0, for b = 0 (harmless where it feeds a product: the bound
+  // products of the call sites hold for values <= K p as well)
   template <uint32_t K>
   static __device__ __forceinline__ Fp29 neg(const Fp29& y) {
     Fp29 r;
@@ -476,7 +477,8 @@ struct Fp29 {
     Fp<P>::cond_sub_p(o.v.l, 0);
     return o;
   }
-  // reduce a normalised value < 64 p to < 2 p (one product with the field's 1)
+  // reduce a normalised value < 128 p to < 2 p (one product with the field's 1 < p: 128 * 1; ntt.hip's wide pass reduces
+  // values up to 128 p)
   __device__ __forceinline__ Fp29 reduced() const { return mul(*this, one()); }
 };
 
