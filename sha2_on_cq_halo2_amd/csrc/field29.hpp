@@ -236,10 +236,10 @@ struct Fp29 {
   // v_mad_u64_u32 that accumulates in place right behind another one with s_nop (gfx950 hazard recogniser): one product
   // written that way came out as 1 467 multiply-adds + 1 237 s_nop in the accumulate kernel's addition.  Two independent
   // products with their links alternating need a sixth of those -- and the group law and the radix-4 butterfly offer their
-  // products in pairs (curve29.hpp, ntt.hip).  Measured on one MI355X, same box (tools/ab_pairs.sh, round 3): accumulate
-  // kernel -2.0 % at k = 18 and -4.5 % at k = 22, NTT +3 %, proofs 7.9 -> 7.75 / 25.2 -> 24.2 / 91.3 -> 88.2 ms.
-  // CQ_MUL_NO_PAIRS falls back to two plain products (the A/B).  Bounds per product exactly as for mul() / sqr(): the
-  // columns hold the same sums.
+  // products in pairs (curve29.hpp, ntt.hip).  Measured against two plain products on one MI355X
+  // (profiles/r03_mul_pairs_ab.txt): accumulate kernel -2.0 % at k = 18 and -4.5 % at k = 22, NTT +3 %, proofs
+  // 7.9 -> 7.75 / 25.2 -> 24.2 / 91.3 -> 88.2 ms.  Bounds per product exactly as for mul() / sqr(): the columns hold the
+  // same sums.
   // (compile-time loops: with the asm statements in the body the unroller gives up on ordinary ones)
   template <int I, int N, class F>
   static __device__ __forceinline__ void static_for(F&& f) {
@@ -272,10 +272,6 @@ struct Fp29 {
   }
   // r1 = x1 y1, r2 = x2 y2
   static __device__ __forceinline__ void mul_pair(const Fp29& x1, const Fp29& y1, const Fp29& x2, const Fp29& y2, Fp29& r1, Fp29& r2) {
-#ifdef CQ_MUL_NO_PAIRS
-    r1 = mul(x1, y1);
-    r2 = mul(x2, y2);
-#else
     uint64_t a1 = 0, a2 = 0;
     uint32_t m1[9], m2[9];
     Fp29 o1, o2;  // (the outputs may alias the inputs)
@@ -294,17 +290,11 @@ struct Fp29 {
     o2.a[8] = (uint32_t)a2;
     r1 = o1;
     r2 = o2;
-#endif
   }
   // r0 = x y + z w (one reduction, as mul2), r1 = a b, r2 = c d: three chains, their links in the order 0 1 0 2 so that no
   // chain follows itself (the group law's last step: Y3 = R (Q - X3) - Y1 PPP next to ZZ PP and ZZZ PPP)
   static __device__ __forceinline__ void mul2_mul_mul(const Fp29& x, const Fp29& y, const Fp29& z, const Fp29& w, const Fp29& a, const Fp29& b,
                                                       const Fp29& c, const Fp29& d, Fp29& r0, Fp29& r1, Fp29& r2) {
-#ifdef CQ_MUL_NO_PAIRS
-    r0 = mul2(x, y, z, w);
-    r1 = mul(a, b);
-    r2 = mul(c, d);
-#else
     uint64_t a0 = 0, a1 = 0, a2 = 0;
     uint32_t m0[9], m1[9], m2[9];
     Fp29 o0, o1, o2;
@@ -349,14 +339,9 @@ struct Fp29 {
     r0 = o0;
     r1 = o1;
     r2 = o2;
-#endif
   }
   // r1 = x1^2, r2 = x2^2 (cross products once, against doubled limbs, as in sqr())
   static __device__ __forceinline__ void sqr_pair(const Fp29& x1, const Fp29& x2, Fp29& r1, Fp29& r2) {
-#if defined(CQ_MUL_NO_PAIRS) || defined(CQ_NO_SQR)
-    r1 = x1.sqr();
-    r2 = x2.sqr();
-#else
     uint64_t a1 = 0, a2 = 0;
     uint32_t m1[9], m2[9], d1[9], d2[9];
     Fp29 o1, o2;
@@ -383,14 +368,11 @@ struct Fp29 {
     o2.a[8] = (uint32_t)a2;
     r1 = o1;
     r2 = o2;
-#endif
   }
-  // x^2: the 36 cross products once, against doubled limbs (45 multiplies instead of 81).  Limbs < 2^30 as for mul():
-  // a column holds at most 4 cross products < 2^61, a square < 2^60 and the reduction's 9 * 2^58 -- below 2^64.
+  // x^2: the 36 cross products once, against doubled limbs (45 multiplies instead of 81; accumulate kernel 1.10 -> 1.07 ms
+  // per k = 18 launch against mul(x, x)).  Limbs < 2^30 as for mul(): a column holds at most 4 cross products < 2^61, a
+  // square < 2^60 and the reduction's 9 * 2^58 -- below 2^64.
   __device__ __forceinline__ Fp29 sqr() const {
-#ifdef CQ_NO_SQR  // A/B knob (tools/ab_flags_stats.sh): accumulate kernel 1.10 -> 1.07 ms per k = 18 launch with the squaring
-    return mul(*this, *this);
-#endif
     uint64_t c[18];
     uint32_t d[9];
     CQ_UNROLL for (int k = 0; k < 18; k++) c[k] = 0;
@@ -477,8 +459,7 @@ struct Fp29 {
     Fp<P>::cond_sub_p(o.v.l, 0);
     return o;
   }
-  // reduce a normalised value < 128 p to < 2 p (one product with the field's 1 < p: 128 * 1; ntt.hip's wide pass reduces
-  // values up to 128 p)
+  // reduce a normalised value < 128 p to < 2 p (one product with the field's 1 < p: 128 * 1)
   __device__ __forceinline__ Fp29 reduced() const { return mul(*this, one()); }
 };
 

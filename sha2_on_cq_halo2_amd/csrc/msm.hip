@@ -869,15 +869,15 @@ int msm_precompute_tables(cq_ctx* ctx, const G1Affine* bases, uint32_t n, uint32
 // Every dependent EC addition costs a lone wave ~9 us whatever the number of busy lanes, so the reduction is shaped
 // for depth, not work.  Buckets are read as a rows x cols matrix (b = cols * hi + lo + 1, cols = min(M, 128)):
 //     sum_b b B_b  =  cols * sum_hi hi R_hi  +  sum_lo (lo + 1) C_lo,     R = row sums, C = column sums.
-// Kernel 1: 16 or 64 lanes per row / column sum (a few buckets per lane serially, then a shuffle tree), all lines
+// Kernel 1: 16 or 32 lanes per row / column sum (a few buckets per lane serially, then a shuffle tree), all lines
 // independent.  Kernel 2: per bucket set two waves, one per weighted sum of <= 128 terms
 // (pair sums, suffix scan by shuffles, one tree); the host applies "cols *" and joins the two.  ~11 + ~16 dependent
 // operations instead of the ~46 of a lane-serial running sum over 1024-bucket groups.
 // A wave serves 64 / SEG rows (or columns): SEG lanes per line, each summing cols / SEG consecutive buckets of it
 // serially, then a log2(SEG)-level shuffle tree.  SEG = 16 (depth 8 + 4, every lane busy in the serial part) when a
 // launch has many bucket sets -- with one wave per line and a 6-level tree only a quarter of the lane-operations were
-// useful and the kernel was VALU-throughput bound at batch 16; SEG = 64 (depth 2 + 6) for launches of a few sets,
-// which are latency-bound and leave most SIMDs idle anyway.
+// useful and the kernel was VALU-throughput bound at batch 16; SEG = 32 for a middling number of sets.  Launches of a few
+// sets, which are latency-bound and leave most SIMDs idle anyway, take msm_rowcol_quad_kernel instead.
 template <uint32_t SEG>
 __global__ __launch_bounds__(64) void msm_rowcol_kernel(const XYZZ* __restrict__ buckets, const uint32_t* __restrict__ t1, uint32_t M,
                                                         uint32_t rows, uint32_t cols, XYZZ* __restrict__ sums /*[sets][rows + cols]*/) {
@@ -1286,9 +1286,9 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
   // whenever the accumulate kernel has none left to place, i.e. they fill its drain (~0.3 ms of half-empty GPU at k = 22).
   // Measured (profiles/r03_msm_tail_early_ab.txt): k = 22 -0.6 .. -0.8 ms, k = 20 -0.05 .. -0.5; at k = 18 the transforms
   // that get in first delay the accumulate kernel's start by more than its shorter drain gives back (+0.25 ms on one box,
-  // -0.07 on another), hence the size floor.  CQ_MSM_TAIL_EARLY=0/1 pins it.
-  static const int tail_env = getenv("CQ_MSM_TAIL_EARLY") ? atoi(getenv("CQ_MSM_TAIL_EARLY")) : -1;
-  const bool tail_early = tail_env >= 0 ? tail_env != 0 : n >= ((size_t)1 << 20);
+  // -0.07 on another), hence the size floor.
+  constexpr size_t TAIL_EARLY_POINTS = (size_t)1 << 20;
+  const bool tail_early = n >= TAIL_EARLY_POINTS;
   if (tail_early && ctx->msm_tail_event) {
     (void)hipEventRecord(ctx->msm_tail_event, s);
     ctx->msm_tail_seq++;
@@ -1319,23 +1319,18 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
   }
   const uint32_t sets = batch * L.Wb;
   // (few sets: the launch waits for chains of dependent additions, and four lanes per addition shorten them; many sets: the
-  // SIMDs are busy, and one lane per addition is half the instructions.  CQ_MSM_QUAD=0/1 pins the choice.)
-  static const int quad_env = getenv("CQ_MSM_QUAD") ? atoi(getenv("CQ_MSM_QUAD")) : -1;
-  static const uint32_t seg32_sets = getenv("CQ_MSM_ROWCOL_SEG32_SETS") ? (uint32_t)atoi(getenv("CQ_MSM_ROWCOL_SEG32_SETS")) : 12u;
-  static const uint32_t quad_rowcol_sets = getenv("CQ_MSM_QUAD_ROWCOL_SETS") ? (uint32_t)atoi(getenv("CQ_MSM_QUAD_ROWCOL_SETS")) : 4u;
-  if (quad_env != 0 && sets <= quad_rowcol_sets)
+  // SIMDs are busy, and one lane per addition is half the instructions.)
+  constexpr uint32_t QUAD_ROWCOL_SETS = 4, SEG32_SETS = 12;
+  if (sets <= QUAD_ROWCOL_SETS)
     msm_rowcol_quad_kernel<<<dim3(L.rows + L.cols, sets), 256, 0, s>>>(buckets, tk, M, L.rows, L.cols, pairs);
-  else if (sets <= 4)
-    msm_rowcol_kernel<64><<<dim3(L.rows + L.cols, sets), 64, 0, s>>>(buckets, tk, M, L.rows, L.cols, pairs);
-  else if (sets <= seg32_sets)
+  else if (sets <= SEG32_SETS)
     msm_rowcol_kernel<32><<<dim3((L.rows + L.cols + 1) / 2, sets), 64, 0, s>>>(buckets, tk, M, L.rows, L.cols, pairs);
   else
     msm_rowcol_kernel<16><<<dim3((L.rows + L.cols + 3) / 4, sets), 64, 0, s>>>(buckets, tk, M, L.rows, L.cols, pairs);
   // (measured at k = 18: 21 sets -- 1 260 four-wave blocks -- 88 -> 54 us; from ~2 waves per SIMD on the plain kernel's
   // half-as-many instructions win)
-  static const uint32_t quad_weighted_waves = getenv("CQ_MSM_QUAD_WEIGHTED_WAVES") ? (uint32_t)atoi(getenv("CQ_MSM_QUAD_WEIGHTED_WAVES")) : 2048u;
-  const bool quad = quad_env >= 0 ? quad_env != 0 : sets * MSM_SET_POINTS * 4 <= quad_weighted_waves;
-  if (quad) msm_weighted_quad_kernel<<<MSM_SET_POINTS * sets, 256, 0, s>>>(pairs, L.rows, L.cols, window_sums_dev);
+  constexpr uint32_t QUAD_WEIGHTED_WAVES = 2048;
+  if (sets * MSM_SET_POINTS * 4 <= QUAD_WEIGHTED_WAVES) msm_weighted_quad_kernel<<<MSM_SET_POINTS * sets, 256, 0, s>>>(pairs, L.rows, L.cols, window_sums_dev);
   else msm_weighted_kernel<<<MSM_SET_POINTS * sets, 64, 0, s>>>(pairs, L.rows, L.cols, window_sums_dev);
   return 0;
   };

@@ -2,7 +2,6 @@
 // between transforms and commitments.  Each replaces a rayon `parallelize` loop or a serial
 // recurrence of the reference (cited per function).  All are HBM-bandwidth bound: one 16-byte-per-lane
 // coalesced read and write per element, arithmetic fused so every vector is touched once.
-#include <cstdlib>
 #include "poly.hpp"
 #include "field29.hpp"
 #include <algorithm>
@@ -308,15 +307,7 @@ __global__ __launch_bounds__(256) void batch_invert_kernel(Fr* __restrict__ a, u
     Fr tc;
     total.pack(tc.v.l);
     Fr::cond_sub_p(tc.v.l, 0);
-#if defined(CQ_BI_EXP) && CQ_BI_EXP == 1  // timing experiment (wrong results): no inversion
-    bi_put(lo, hi, 0, tc);
-#else
-#if defined(CQ_BI_CT)  // A/B: the constant-time division steps
-    bi_put(lo, hi, 0, tc.inv_safegcd());
-#else
     bi_put(lo, hi, 0, tc.inv_safegcd_var());  // Y = R^2 / T as canonical words (one lane: the variable-time form)
-#endif
-#endif
   }
   const Fr29 exc_b = Fr29::mul(exc, total_a);  // ... and this lane's first half-chain (while lane 0 inverts)
   __syncthreads();
@@ -337,10 +328,6 @@ __global__ __launch_bounds__(256) void batch_invert_kernel(Fr* __restrict__ a, u
     dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
     dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
   };
-#if defined(CQ_BI_EXP) && CQ_BI_EXP == 2  // timing experiment (wrong results): no unwinding
-  emit(0, r);
-  return;
-#endif
   Fr29::static_for<0, H>([&](auto K) {
     constexpr int k1 = BI_PER_LANE - 1 - 2 * decltype(K)::value, k0 = k1 - 1;  // two elements per step, last first
     Fr29 b1, b0, o1, o0;
@@ -572,8 +559,7 @@ int poly_kate_division(cq_ctx* c, const Fr* a, uint32_t n, const Fr& z, Fr* q) {
   if (n == 0) return c->fail(CQ_ERR_ARG, "kate_division of an empty polynomial");
   void* scr;
   int rc;
-  static const bool blocks_off = getenv("CQ_KATE_BLOCKS") && atoi(getenv("CQ_KATE_BLOCKS")) == 0;  // A/B knob
-  if (!blocks_off && n >= 4096 && n <= (1u << 22)) {
+  if (n >= 4096 && n <= (1u << 22)) {
     uint32_t E = 4;
     while ((uint64_t)1024 * 256 * E < n) E <<= 1;  // at most 1024 blocks (one scan block for their carries)
     const uint32_t nblk = (n + 256 * E - 1) / (256 * E);
@@ -605,10 +591,9 @@ int poly_kate_division(cq_ctx* c, const Fr* a, uint32_t n, const Fr& z, Fr* q) {
 
 int poly_batch_invert(cq_ctx* c, Fr* a, uint32_t n) {
   if (!n) return CQ_OK;
-  static const int forced = getenv("CQ_BI_PER_LANE") ? atoi(getenv("CQ_BI_PER_LANE")) : 0;
   // measured stand-alone on one box (tools/batch_invert_perf.py, profiles/r03_batch_invert_per_lane.txt): 4 elements per lane
   // up to ~5 x 2^16 (the lane's chain is what the launch waits for), 8 up to ~3 M (k=18's 1.3 M: 127 us against 140), 16 beyond
-  const int per = forced ? forced : (n <= 5u * (1u << 16) ? 4 : n <= 3u * (1u << 20) ? 8 : 16);
+  const int per = n <= 5u * (1u << 16) ? 4 : n <= 3u * (1u << 20) ? 8 : 16;
   if (per == 4) batch_invert_kernel<4><<<(n + 256 * 4 - 1) / (256 * 4), 256, 0, c->stream>>>(a, n);
   else if (per == 8) batch_invert_kernel<8><<<(n + 256 * 8 - 1) / (256 * 8), 256, 0, c->stream>>>(a, n);
   else batch_invert_kernel<16><<<(n + 256 * 16 - 1) / (256 * 16), 256, 0, c->stream>>>(a, n);

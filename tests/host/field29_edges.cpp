@@ -2,8 +2,7 @@
 //
 // Reads records of raw operand limbs, applies one named operation per record and writes the raw output limbs back; nothing
 // is normalised or reduced by the driver.  The operands and the checks live in tests/field29_model.py.  One body, two builds:
-//   host:   g++ -std=c++17 -I sha2_on_cq_halo2_amd/csrc tests/host/field29_edges.cpp            (tests/test_field29_edges_cpu.py,
-//           also with -DCQ_MUL_NO_PAIRS and -DCQ_NO_SQR, whose outputs must be the same bytes)
+//   host:   g++ -std=c++17 -I sha2_on_cq_halo2_amd/csrc tests/host/field29_edges.cpp            (tests/test_field29_edges_cpu.py)
 //   device: hipcc --offload-arch=gfx950 -x hip ... (one thread per record; tests/test_field29_edges_gpu.py)
 //   usage:  field29_edges IN OUT   -- IN: n records of REC_IN u32, OUT: n records of REC_OUT u32
 #if !defined(__HIPCC__)

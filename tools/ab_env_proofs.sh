@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of environment settings (no rebuild): alternates the settings, AB_ROUNDS rounds (2), proof-time medians per k.
-#   AB_KS="18 20" bash tools/ab_env_proofs.sh "CQ_RANDOM_EARLY=0" "CQ_RANDOM_EARLY=1"
+#   AB_KS="18 20" bash tools/ab_env_proofs.sh "CQ_RANDOM_LATE=0" "CQ_RANDOM_LATE=1"
 cd $GRAFT_REPO_ROOT
 for round in $(seq 1 ${AB_ROUNDS:-2}); do for setting in "$@"; do
   echo "== $setting"

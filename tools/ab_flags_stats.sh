@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of hipcc -D flags with per-kernel times (run on the GPU box): rebuilds the library for every flag set, proves at
 # k = 18 and k = 22 under rocprofv3 --stats and prints the MSM kernels' average durations.
-#   bash tools/ab_flags_stats.sh "-DCQ_NO_SQR" "-DCQ_SQR_ON"
+#   bash tools/ab_flags_stats.sh "-DCQ_CRIT_PRIO=0" "-DCQ_CRIT_PRIO=3"
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/ab
