@@ -56,13 +56,11 @@ void cq_ctx_destroy(cq_ctx* c) {
   hipStreamSynchronize(c->stream);
   if (c->aux_stream) hipStreamSynchronize(c->aux_stream);
   c->ntt_cache.clear();
-  for (int i = 0; i < cq_ctx::NSCRATCH; i++)
-    if (c->scratch[i]) hipFree(c->scratch[i]);
-  if (c->pinned) hipHostFree(c->pinned);
-  if (c->pinned_msm) hipHostFree(c->pinned_msm);
-  if (c->pinned_small) hipHostFree(c->pinned_small);
   cq::comm_rccl_destroy(c);
-  if (c->pinned_comm) hipHostFree(c->pinned_comm);
+  for (const cq::GrowBuf& b : c->scratch)
+    if (b.ptr) hipFree(b.ptr);
+  for (const cq::GrowBuf* b : {&c->pinned, &c->pinned_msm, &c->pinned_small, &c->pinned_comm})
+    if (b->ptr) hipHostFree(b->ptr);
   if (c->comm_event) hipEventDestroy(c->comm_event);
   for (auto& g : c->graphs) hipGraphExecDestroy(g.exec);
   if (c->prof_entries) hipHostFree(c->prof_entries);
@@ -209,8 +207,8 @@ int cq_best_fft(cq_ctx* c, uint64_t* a, uint32_t log_n, const uint64_t omega[4])
   const size_t bytes = ((size_t)1 << log_n) * sizeof(Fr);
   void *din, *dout;
   int rc;
-  if ((rc = c->ensure_scratch(1, bytes, &din)) != CQ_OK) return rc;
-  if ((rc = c->ensure_scratch(2, bytes, &dout)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryA, bytes, &din)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryB, bytes, &dout)) != CQ_OK) return rc;
   CQ_HIP(c, hipMemcpyAsync(din, a, bytes, hipMemcpyHostToDevice, c->stream));
   if ((rc = fft_dev(c, (const Fr*)din, (Fr*)dout, log_n, Fr::from_limbs64(omega))) != CQ_OK) return rc;
   CQ_HIP(c, hipMemcpyAsync(a, dout, bytes, hipMemcpyDeviceToHost, c->stream));

@@ -94,7 +94,7 @@ int cq_table_config_setup_from_toxic_waste(cq_ctx* c, size_t size, const uint64_
     return c->fail(CQ_ERR_HIP, "hipMalloc(table config)");
   void* tmp;
   int rc;
-  if ((rc = c->ensure_scratch(1, 2 * size * sizeof(Fr), &tmp)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryA, 2 * size * sizeof(Fr), &tmp)) != CQ_OK) return rc;
   Fr* lag_sc = (Fr*)tmp;
   Fr* tmp_sc = lag_sc + size;
   const Fr sf = Fr::from_limbs64(s);
@@ -171,7 +171,7 @@ int cq_static_table_setup_from_toxic_waste(cq_ctx* c, size_t size, const uint64_
   if ((rc = domain_create(c, 2, log2u(size), &guard.dom)) != CQ_OK) return rc;
   cq_domain* dom = guard.dom;
   void* tmp;
-  if ((rc = c->ensure_scratch(1, 2 * size * sizeof(Fr), &tmp)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryA, 2 * size * sizeof(Fr), &tmp)) != CQ_OK) return rc;
   Fr* coeffs = (Fr*)tmp;
   Fr* sc = coeffs + size;
   const Fr sf = Fr::from_limbs64(s);
@@ -442,7 +442,7 @@ static int pk_create_impl(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq
   if ((rc = domain_create(c, pk->cs_degree, pk->k, &pk->domain)) != CQ_OK) return pk_abort(pk, rc);
   const size_t ext = pk->domain->ext();
   void* tmp;
-  if ((rc = c->ensure_scratch(1, n * sizeof(Fr), &tmp)) != CQ_OK) return pk_abort(pk, rc);
+  if ((rc = c->ensure_scratch(Scratch::EntryA, n * sizeof(Fr), &tmp)) != CQ_OK) return pk_abort(pk, rc);
   // l_active_row = 1 - (l_last + l_blind) on the extended coset (keygen.rs:344-373); by linearity it is
   // the coset extension of the indicator of the usable rows
   if (hipMalloc(&pk->l_active_row, ext * sizeof(Fr)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(l_active_row)"));
@@ -559,7 +559,7 @@ static int pk_create_impl(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq
       cur = cur * delta;
     }
     void* stage;
-    if ((rc = c->ensure_scratch(2, PC * n * 2 * sizeof(uint32_t) + PC * sizeof(Fr), &stage)) != CQ_OK) return pk_abort(pk, rc);
+    if ((rc = c->ensure_scratch(Scratch::EntryB, PC * n * 2 * sizeof(uint32_t) + PC * sizeof(Fr), &stage)) != CQ_OK) return pk_abort(pk, rc);
     Fr* dp_dev = (Fr*)stage;
     uint32_t* map_dev = (uint32_t*)(dp_dev + PC);
     CQ_HIP(c, hipMemcpy(dp_dev, dp.data(), PC * sizeof(Fr), hipMemcpyHostToDevice));
@@ -575,7 +575,7 @@ static int pk_create_impl(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq
   if (raw && rd.left != 0) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: trailing bytes after the serialized key"));
   if (raw && checked) {  // SerdeFormat::RawBytes: every field element below the modulus (helpers.rs:62-79)
     void* flag;
-    if ((rc = c->ensure_scratch(1, 64, &flag)) != CQ_OK) return pk_abort(pk, rc);
+    if ((rc = c->ensure_scratch(Scratch::EntryA, 64, &flag)) != CQ_OK) return pk_abort(pk, rc);
     CQ_HIP(c, hipMemsetAsync(flag, 0, 4, c->stream));
     for (auto& v : to_check)
       if ((rc = fr_validate(c, v.first, v.second, (uint32_t*)flag)) != CQ_OK) return pk_abort(pk, rc);
@@ -664,7 +664,7 @@ int cq_pk_write_raw(cq_pk* pk, const uint8_t* selector_bits, uint32_t num_select
   };
   // l0, l_last (a CQ-only key does not keep them: computed here), l_active_row
   void* tmp;
-  if ((rc = c->ensure_scratch(1, (n + 2 * ext) * sizeof(Fr), &tmp)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryA, (n + 2 * ext) * sizeof(Fr), &tmp)) != CQ_OK) return rc;
   Fr* l0 = pk->l0;
   Fr* l_last = pk->l_last;
   if (!l0) {
@@ -900,7 +900,7 @@ static int create_proof_host_any(cq_pk* pk, const uint64_t* const* advice, const
   const size_t n = (size_t)1 << pk->k;
   void* stage;
   int rc;
-  if ((rc = c->ensure_scratch(7, (size_t)pk->num_advice * n * sizeof(Fr) + 64, &stage)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::HostAdvice, (size_t)pk->num_advice * n * sizeof(Fr) + 64, &stage)) != CQ_OK) return rc;
   std::vector<const uint64_t*> ptrs(pk->num_advice);
   for (uint32_t a = 0; a < pk->num_advice; a++) {
     Fr* d = (Fr*)stage + (size_t)a * n;

@@ -73,8 +73,8 @@ int cq_best_multiexp_g2(cq_ctx* c, const uint64_t* coeffs, const uint64_t* bases
   }
   void *ds, *db;
   int rc;
-  if ((rc = c->ensure_scratch(1, len * sizeof(Fr), &ds)) != CQ_OK) return rc;
-  if ((rc = c->ensure_scratch(2, len * sizeof(G2Affine), &db)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryA, len * sizeof(Fr), &ds)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryB, len * sizeof(G2Affine), &db)) != CQ_OK) return rc;
   CQ_HIP(c, hipMemcpyAsync(ds, coeffs, len * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
   CQ_HIP(c, hipMemcpyAsync(db, bases, len * sizeof(G2Affine), hipMemcpyHostToDevice, c->stream));
   G2Jac r;

@@ -93,7 +93,7 @@ int msm_multi_begin(cq_ctx* c, const Fr* const* scalars, const G1Affine* const* 
   void *wsums = nullptr, *host = nullptr;
   int rc;
   if (slots) {
-    if ((rc = c->ensure_scratch(4, slots * sizeof(G1Jac), &wsums)) != CQ_OK) return rc;
+    if ((rc = c->ensure_scratch(Scratch::MsmSums, slots * sizeof(G1Jac), &wsums)) != CQ_OK) return rc;
     if ((rc = c->ensure_pinned_msm(slots * sizeof(G1Jac), &host)) != CQ_OK) return rc;
   }
   pend.host = host;
@@ -110,7 +110,7 @@ int msm_multi_begin(cq_ctx* c, const Fr* const* scalars, const G1Affine* const* 
       strides[j] = ln.pre ? t->n : 0;
     }
     void* ws;
-    if ((rc = c->ensure_scratch(3, L.total, &ws)) != CQ_OK) return rc;
+    if ((rc = c->ensure_scratch(Scratch::MsmWork, L.total, &ws)) != CQ_OK) return rc;
     int r = msm_run(c, scalars + ln.first, bp.data(), lens + ln.first, ln.nmax, ln.c, ln.batch, ln.pre, strides.data(), ws,
                     (G1Jac*)wsums + ln.slot);
     if (r != 0) return c->fail(CQ_ERR_HIP, "msm launch failed");
@@ -323,8 +323,8 @@ int cq_best_multiexp(cq_ctx* c, const uint64_t* coeffs, const uint64_t* bases, s
   }
   void *ds, *db;
   int rc;
-  if ((rc = c->ensure_scratch(1, len * sizeof(Fr), &ds)) != CQ_OK) return rc;
-  if ((rc = c->ensure_scratch(2, len * sizeof(G1Affine), &db)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryA, len * sizeof(Fr), &ds)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryB, len * sizeof(G1Affine), &db)) != CQ_OK) return rc;
   CQ_HIP(c, hipMemcpyAsync(ds, coeffs, len * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
   CQ_HIP(c, hipMemcpyAsync(db, bases, len * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
   const Fr* sc = (const Fr*)ds;
@@ -367,7 +367,7 @@ int cq_params_setup_from_toxic_waste(cq_ctx* c, uint32_t k, const uint64_t s[4],
     return c->hip_fail(e, "hipMalloc(params)");
   void* tmp;
   int rc;
-  if ((rc = c->ensure_scratch(1, p->n * sizeof(Fr), &tmp)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryA, p->n * sizeof(Fr), &tmp)) != CQ_OK) return rc;
   rc = srs_powers_and_lagrange(c, k, Fr::from_limbs64(s), p->g, p->g_lagrange, (Fr*)tmp, nullptr);
   if (rc != CQ_OK) return rc;
   if (c->msm_precompute) {
@@ -407,7 +407,7 @@ int cq_params_read_raw(cq_ctx* c, const uint8_t* buf, size_t len, int checked, c
   if (checked) {  // SerdeFormat::RawBytes: coordinates < q and on the curve
     void* tmp;
     int rc;
-    if ((rc = c->ensure_scratch(1, 64, &tmp)) != CQ_OK) return rc;
+    if ((rc = c->ensure_scratch(Scratch::EntryA, 64, &tmp)) != CQ_OK) return rc;
     CQ_HIP(c, hipMemsetAsync(tmp, 0, 4, c->stream));
     if ((rc = g1_validate(c, p->g, (uint32_t)n, (uint32_t*)tmp)) != CQ_OK) return rc;
     if ((rc = g1_validate(c, p->g_lagrange, (uint32_t)n, (uint32_t*)tmp)) != CQ_OK) return rc;
@@ -500,7 +500,7 @@ static int commit_host(cq_params* p, const G1Affine* bases, const uint64_t* poly
   }
   void* ds;
   int rc;
-  if ((rc = c->ensure_scratch(1, len * sizeof(Fr), &ds)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryA, len * sizeof(Fr), &ds)) != CQ_OK) return rc;
   CQ_HIP(c, hipMemcpyAsync(ds, poly, len * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
   const Fr* sc = (const Fr*)ds;
   return msm_batch(c, &sc, bases, len, 1, out_jac);

@@ -12,8 +12,8 @@ struct HostStage {
   void* dout = nullptr;
   int rc = CQ_OK;
   HostStage(cq_ctx* c_, size_t in_bytes, size_t out_bytes) : c(c_) {
-    if ((rc = c->ensure_scratch(1, in_bytes ? in_bytes : 32, &din)) != CQ_OK) return;
-    rc = c->ensure_scratch(2, out_bytes ? out_bytes : 32, &dout);
+    if ((rc = c->ensure_scratch(Scratch::EntryA, in_bytes ? in_bytes : 32, &din)) != CQ_OK) return;
+    rc = c->ensure_scratch(Scratch::EntryB, out_bytes ? out_bytes : 32, &dout);
   }
 };
 }  // namespace

@@ -63,7 +63,7 @@ int cq_cq_round1_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
   // evaluated inputs, m as field elements, the error flag
   void* scr;
   const size_t elems = (A + I) * n + (pk->lookup_exprs ? wsum * n : 0) + L * N + NC + 16;
-  CQ_TRY(c->ensure_scratch(7, elems * sizeof(Fr), &scr));
+  CQ_TRY(c->ensure_scratch(Scratch::ProverStage, elems * sizeof(Fr), &scr));
   Fr* adv = (Fr*)scr;
   Fr* inst = adv + A * n;
   Fr* inputs = inst + I * n;
@@ -158,7 +158,7 @@ int cq_cq_round2_dev(cq_pk* pk, const uint64_t* f_dev, const uint32_t* m_dev, co
   size_t wsum = 0;
   for (auto& lk : pk->lookups) wsum += lk.cols.size();
   void* scr;
-  CQ_TRY(c->ensure_scratch(7, (N + 2 * L * N + wsum * N + 64) * sizeof(Fr), &scr));
+  CQ_TRY(c->ensure_scratch(Scratch::ProverStage, (N + 2 * L * N + wsum * N + 64) * sizeof(Fr), &scr));
   Fr* t_comp = (Fr*)scr;
   Fr* den = t_comp + N;
   Fr* a_val = den + L * N;
@@ -227,7 +227,7 @@ int cq_quotient_dev(cq_pk* pk, const uint64_t* b_coeff_dev, const uint64_t* f_co
   const size_t L = pk->lookups.size(), n = (size_t)1 << pk->k, ext = pk->domain->ext();
   if (L && (!b_coeff_dev || !f_coeff_dev)) return CQ_ERR_ARG;
   void* scr;
-  CQ_TRY(c->ensure_scratch(7, (2 * L * ext + 16) * sizeof(Fr), &scr));
+  CQ_TRY(c->ensure_scratch(Scratch::ProverStage, (2 * L * ext + 16) * sizeof(Fr), &scr));
   Fr* cosets = (Fr*)scr;  // b, then f, on the extended coset (evaluation.rs:535-536)
   if (L) {
     CQ_TRY(domain_coeff_to_extended(pk->domain, (const Fr*)b_coeff_dev, cosets, (uint32_t)L, n, ext));
@@ -256,7 +256,7 @@ int cq_permute_expression_pair_dev(cq_ctx* c, uint32_t k, uint32_t usable, const
   CQ_HIP(c, hipSetDevice(c->device));
   const size_t slot = ((size_t)1 << k) * 4;
   void* scr;
-  CQ_TRY(c->ensure_scratch(7, 3 * slot * sizeof(uint64_t) + lookup_permute_scratch_bytes(k) + 64, &scr));
+  CQ_TRY(c->ensure_scratch(Scratch::ProverStage, 3 * slot * sizeof(uint64_t) + lookup_permute_scratch_bytes(k) + 64, &scr));
   uint64_t* stage = (uint64_t*)scr;
   void* lk_scratch = stage + 3 * slot;
   uint32_t* status = (uint32_t*)((char*)lk_scratch + lookup_permute_scratch_bytes(k));

@@ -89,7 +89,7 @@ int comm_rccl_init(cq_ctx* c, uint32_t rank, uint32_t world, const uint8_t id[12
   // its peers inside a collective.
   void* dummy;
   int rc;
-  if ((rc = c->ensure_scratch(9, (size_t)1 << 20, &dummy)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::CommGather, (size_t)1 << 20, &dummy)) != CQ_OK) return rc;
   if ((rc = c->ensure_pinned_comm((size_t)1 << 18, &dummy)) != CQ_OK) return rc;
   if ((rc = c->ensure_aux_stream()) != CQ_OK) return rc;
   if (!c->comm_event) CQ_HIP(c, hipEventCreateWithFlags(&c->comm_event, hipEventDisableTiming));
@@ -168,7 +168,7 @@ static int rccl_allgather_host(cq_ctx* c, const void* send, void* recv, size_t b
   const size_t total = bytes * c->rccl_world;
   void *dev, *pin;
   int rc;
-  if ((rc = c->ensure_scratch(9, bytes + total + 512, &dev)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::CommGather, bytes + total + 512, &dev)) != CQ_OK) return rc;
   if ((rc = c->ensure_pinned_comm(bytes + total, &pin)) != CQ_OK) return rc;
   char* dsend = (char*)dev;
   char* drecv = dsend + ((bytes + 255) & ~(size_t)255);
@@ -339,7 +339,7 @@ int comm_rccl_selftest(cq_ctx* c) {
     total += (len[r] + 255) & ~(size_t)255;
   }
   void* dev;
-  if ((rc = c->ensure_scratch(8, total + 4096, &dev)) != CQ_OK) return rc;  // (slot 9 stages the all-gathers)
+  if ((rc = c->ensure_scratch(Scratch::EntryA, total + 4096, &dev)) != CQ_OK) return rc;
   std::vector<uint8_t> host(total, 0);
   for (size_t i = 0; i < len[R]; i++) host[off[R] + i] = (uint8_t)(i * 13 + R * 17 + 3);
   CQ_HIP(c, hipMemcpyAsync(dev, host.data(), total, hipMemcpyHostToDevice, c->stream));

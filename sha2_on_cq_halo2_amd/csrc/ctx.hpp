@@ -12,7 +12,36 @@
 
 namespace cq {
 int comm_rccl_wait(cq_ctx* c, hipStream_t stream, const char* what);  // comm.hip
-}
+
+// The device scratch buffers of a context, one per owner (cq_ctx::ensure_scratch).  A buffer grows and never shrinks, and
+// growing frees the old allocation: a pointer into a buffer is good only until the next larger request for the same one.
+// Beside each name: its users, and the rule that keeps any of them from taking it while another still holds it.
+enum class Scratch {
+  Ntt,          // domain.hip transforms on any stream but the side stream, for one launch
+  EntryA,       // a public entry point's own staging or temporaries, for that call only: capi.hip fft, capi_poly.hip HostStage
+                // input, capi_msm.hip (multiexp scalars, params set-up temp, validate flag), capi_g2.hip scalars, capi_cq.hip
+                // (table config, static table, pk create / validate / write temps), comm.hip self-test.  Nothing they call
+                // takes an entry buffer
+  EntryB,       // the second buffer of the same entry points (outputs, bases, pk permutation mapping); also g1_fft's twiddles:
+                // its callers (g1_to_lagrange, fk_table_quotients) run under entry points that hold neither entry buffer
+  MsmWork,      // capi_msm.hip: the workspace of one MSM launch
+  MsmSums,      // capi_msm.hip: window sums, from msm_multi_begin to its msm_multi_end (launches are never nested)
+  PolyTmp,      // poly.hip eval / kate, plonk.hip prefix_product partials, for one call each
+  ProverArena,  // create_proof_dev's arena, for the whole proof
+  ProverStage,  // create_proof_dev's resident receive staging or its legacy-lookup staging (never both: resident sharding
+                // requires no legacy lookups); capi_rounds.hip's stand-alone rounds, which a proof never calls
+  HostAdvice,   // create_proof_host_any's copy of the caller's advice columns, held for the whole proof: nothing else takes it
+  NttAux,       // domain.hip transforms while AuxFork has put `stream` on the side stream
+  CommGather,   // comm.hip rccl_allgather_host; 1 MiB of it is taken in comm_rccl_init
+  Count
+};
+
+// a grow-only allocation, device or pinned host memory
+struct GrowBuf {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+};
+}  // namespace cq
 
 struct cq_ctx {
   int device = 0;
@@ -20,11 +49,8 @@ struct cq_ctx {
   bool own_stream = false;
   std::string err;
   std::vector<std::unique_ptr<cq::NttTables>> ntt_cache;
-  static constexpr int NSCRATCH = 10;
-  void* scratch[NSCRATCH] = {};
-  size_t scratch_bytes[NSCRATCH] = {};
-  void* pinned = nullptr;  // small pinned host staging buffer
-  size_t pinned_bytes = 0;
+  cq::GrowBuf scratch[(int)cq::Scratch::Count];
+  cq::GrowBuf pinned;  // a proof's pinned host staging: the random polynomial's words, blinding rows (prover.hip)
   uint32_t msm_c = 0;  // 0 = automatic window size
   uint32_t msm_table_c = 0;  // caller's override of the window width of precomputed tables (cq_msm_set_table_window); 0 = by array length
   bool msm_precompute = true;  // build per-window tables for resident SRS arrays
@@ -98,38 +124,24 @@ struct cq_ctx {
     err = std::string(what) + ": " + hipGetErrorString(e);
     return CQ_ERR_HIP;
   }
-  // grow-only scratch slot
-  int ensure_scratch(int slot, size_t bytes, void** out) {
-    if (scratch_bytes[slot] < bytes) {
-      if (scratch[slot]) {
+  // grows `b` to at least max(bytes, min_bytes); the old allocation is freed once `stream` has drained
+  int grow(cq::GrowBuf& b, size_t bytes, size_t min_bytes, bool host, void** out) {
+    if (b.bytes < bytes) {
+      if (b.ptr) {
         hipStreamSynchronize(stream);
-        hipFree(scratch[slot]);
-        scratch[slot] = nullptr;
-        scratch_bytes[slot] = 0;
+        host ? hipHostFree(b.ptr) : hipFree(b.ptr);
+        b = {};
       }
-      size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-      hipError_t e = hipMalloc(&scratch[slot], want);
-      if (e != hipSuccess) return hip_fail(e, "hipMalloc(scratch)");
-      scratch_bytes[slot] = want;
+      const size_t want = bytes < min_bytes ? min_bytes : bytes;
+      const hipError_t e = host ? hipHostMalloc(&b.ptr, want, hipHostMallocDefault) : hipMalloc(&b.ptr, want);
+      if (e != hipSuccess) return hip_fail(e, host ? "hipHostMalloc" : "hipMalloc(scratch)");
+      b.bytes = want;
     }
-    *out = scratch[slot];
+    *out = b.ptr;
     return CQ_OK;
   }
-  int ensure_pinned(size_t bytes, void** out) {
-    if (pinned_bytes < bytes) {
-      if (pinned) {
-        hipStreamSynchronize(stream);
-        hipHostFree(pinned);
-        pinned = nullptr;
-        pinned_bytes = 0;
-      }
-      hipError_t e = hipHostMalloc(&pinned, bytes, hipHostMallocDefault);
-      if (e != hipSuccess) return hip_fail(e, "hipHostMalloc");
-      pinned_bytes = bytes;
-    }
-    *out = pinned;
-    return CQ_OK;
-  }
+  int ensure_scratch(cq::Scratch s, size_t bytes, void** out) { return grow(scratch[(int)s], bytes, 1u << 20, false, out); }
+  int ensure_pinned(size_t bytes, void** out) { return grow(pinned, bytes, 0, true, out); }
   // side stream for host->device uploads that should overlap kernels on `stream` (the DMA engine is otherwise
   // serialised behind whatever the main stream has queued); `copy_done` orders the main stream after an upload
   hipStream_t copy_stream = nullptr;
@@ -146,12 +158,11 @@ struct cq_ctx {
   // column sums, weighted sums) that leave most of the GPU idle; the prover uses that time for transforms whose
   // inputs are already fixed (prover.hip, AuxFork).  msm_run records `msm_tail_event` right after its accumulate
   // kernel; work on `aux_stream` starts there; `aux_done` orders the main stream after it.  While the prover has
-  // `stream` pointed at the side stream, NTTs take their scratch from `ntt_scratch_slot` (a slot of their own).
+  // `stream` pointed at the side stream, NTTs take their scratch from Scratch::NttAux (domain.hip).
   hipStream_t aux_stream = nullptr;
   hipEvent_t msm_tail_event = nullptr, aux_done = nullptr;
   uint64_t msm_tail_seq = 0;
   bool aux_pending = false;
-  int ntt_scratch_slot = 0;
   int ensure_aux_stream() {
     if (aux_stream) return CQ_OK;
     int least = 0, greatest = 0;
@@ -226,57 +237,18 @@ struct cq_ctx {
   }
   // a page of pinned memory for the scalars a proof reads back (error flags, b(0), z values): a device-to-host copy into
   // pageable memory is staged and blocks the host for ~25 us each, into pinned memory it is a plain asynchronous DMA
-  void* pinned_small = nullptr;
+  cq::GrowBuf pinned_small;
   static constexpr size_t PINNED_SMALL_BYTES = 16384;
-  int ensure_pinned_small(void** out) {
-    if (!pinned_small) {
-      hipError_t e = hipHostMalloc(&pinned_small, PINNED_SMALL_BYTES, hipHostMallocDefault);
-      if (e != hipSuccess) return hip_fail(e, "hipHostMalloc");
-    }
-    *out = pinned_small;
-    return CQ_OK;
-  }
+  int ensure_pinned_small(void** out) { return grow(pinned_small, PINNED_SMALL_BYTES, PINNED_SMALL_BYTES, true, out); }
   // RCCL communicator of the context (comm.hip; cq_ctx_comm_init_rccl) and the pinned staging of its small exchanges
   void* rccl_comm = nullptr;
   uint32_t rccl_rank = 0, rccl_world = 1;
   bool rccl_aborted = false;        // the communicator was given up after a failure (comm_rccl_abort)
   hipEvent_t comm_event = nullptr;  // polled by comm_rccl_wait
-  void* pinned_comm = nullptr;
-  size_t pinned_comm_bytes = 0;
-  int ensure_pinned_comm(size_t bytes, void** out) {
-    if (pinned_comm_bytes < bytes) {
-      if (pinned_comm) {
-        hipStreamSynchronize(stream);
-        hipHostFree(pinned_comm);
-        pinned_comm = nullptr;
-        pinned_comm_bytes = 0;
-      }
-      const size_t want = bytes < 65536 ? 65536 : bytes;
-      hipError_t e = hipHostMalloc(&pinned_comm, want, hipHostMallocDefault);
-      if (e != hipSuccess) return hip_fail(e, "hipHostMalloc");
-      pinned_comm_bytes = want;
-    }
-    *out = pinned_comm;
-    return CQ_OK;
-  }
-  void* pinned_msm = nullptr;  // MSM results (kept apart from `pinned`, which stages RNG words)
-  size_t pinned_msm_bytes = 0;
-  int ensure_pinned_msm(size_t bytes, void** out) {
-    if (pinned_msm_bytes < bytes) {
-      if (pinned_msm) {
-        hipStreamSynchronize(stream);
-        hipHostFree(pinned_msm);
-        pinned_msm = nullptr;
-        pinned_msm_bytes = 0;
-      }
-      size_t want = bytes < 65536 ? 65536 : bytes;
-      hipError_t e = hipHostMalloc(&pinned_msm, want, hipHostMallocDefault);
-      if (e != hipSuccess) return hip_fail(e, "hipHostMalloc");
-      pinned_msm_bytes = want;
-    }
-    *out = pinned_msm;
-    return CQ_OK;
-  }
+  cq::GrowBuf pinned_comm;
+  int ensure_pinned_comm(size_t bytes, void** out) { return grow(pinned_comm, bytes, 65536, true, out); }
+  cq::GrowBuf pinned_msm;  // MSM results (kept apart from `pinned`, which stages RNG words)
+  int ensure_pinned_msm(size_t bytes, void** out) { return grow(pinned_msm, bytes, 65536, true, out); }
   const cq::NttTables* tables_for(uint32_t log_n, const cq::Fr& omega, int* rc);
 };
 

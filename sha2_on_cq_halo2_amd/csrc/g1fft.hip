@@ -123,7 +123,7 @@ int g1_fft(cq_ctx* c, XYZZ* data, uint32_t log_n, const Fr& omega) {
   if (log_n == 0) return CQ_OK;
   void* tw;
   int rc;
-  if ((rc = c->ensure_scratch(2, (size_t)(n / 2) * 32 + 64, &tw)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryB, (size_t)(n / 2) * 32 + 64, &tw)) != CQ_OK) return rc;
   fr_powers_canonical_kernel<<<blocks_for(n / 2), 256, 0, c->stream>>>(omega, Fr::one(), n / 2, (uint64_t*)tw);
   g1_bitrev_kernel<<<blocks_for(n), 256, 0, c->stream>>>(data, log_n);
   for (uint32_t s = 0; s < log_n; s++)
@@ -142,7 +142,7 @@ int g1_to_lagrange(cq_ctx* c, const G1Affine* g, uint32_t k, G1Affine* out) {
   int rc = g1_fft(c, buf, k, w.inv());
   if (rc == CQ_OK) {
     void* sc;
-    if ((rc = c->ensure_scratch(2, 64, &sc)) == CQ_OK) {
+    if ((rc = c->ensure_scratch(Scratch::EntryB, 64, &sc)) == CQ_OK) {
       const Fr n_inv = Fr::from_u64(n).inv();
       fr_powers_canonical_kernel<<<1, 256, 0, c->stream>>>(Fr::one(), n_inv, 1, (uint64_t*)sc);
       g1_scale_kernel<<<(n + 63) / 64, 64, 0, c->stream>>>(buf, n, (const uint64_t*)sc, 0);

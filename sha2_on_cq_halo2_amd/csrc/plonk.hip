@@ -286,7 +286,7 @@ int prefix_product(cq_ctx* c, const Fr* in, Fr* out, uint32_t n, uint32_t batch)
   const uint32_t ntiles = (n + SCAN_TILE - 1) / SCAN_TILE;
   void* scr;
   int rc;
-  if ((rc = c->ensure_scratch(5, (size_t)batch * ntiles * sizeof(Fr), &scr)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::PolyTmp, (size_t)batch * ntiles * sizeof(Fr), &scr)) != CQ_OK) return rc;
   Fr* partial = (Fr*)scr;
   scan_tile_kernel<<<dim3(ntiles, batch), 256, 0, c->stream>>>(in, n, ntiles, partial);
   scan_spine_kernel<<<batch, 256, 0, c->stream>>>(partial, ntiles);

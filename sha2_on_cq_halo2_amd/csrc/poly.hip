@@ -489,7 +489,7 @@ int poly_eval_batch(cq_ctx* c, const Fr* const* p, const uint32_t* len, uint32_t
   const uint32_t nb0 = (maxlen + EVAL_TILE - 1) / EVAL_TILE;
   void* scr;
   int rc;
-  if ((rc = c->ensure_scratch(5, ((size_t)count * (nb0 + 8) * 2) * sizeof(Fr), &scr)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::PolyTmp, ((size_t)count * (nb0 + 8) * 2) * sizeof(Fr), &scr)) != CQ_OK) return rc;
   Fr* buf[2] = {(Fr*)scr, (Fr*)scr + (size_t)count * (nb0 + 8)};
   const uint32_t stride = nb0 + 8;
   Fr x = z;
@@ -564,7 +564,7 @@ int poly_kate_division(cq_ctx* c, const Fr* a, uint32_t n, const Fr& z, Fr* q) {
     while ((uint64_t)1024 * 256 * E < n) E <<= 1;  // at most 1024 blocks (one scan block for their carries)
     const uint32_t nblk = (n + 256 * E - 1) / (256 * E);
     const size_t elems = (size_t)nblk * 256 + 2 * (size_t)nblk + 256;
-    if ((rc = c->ensure_scratch(5, elems * sizeof(Fr), &scr)) != CQ_OK) return rc;
+    if ((rc = c->ensure_scratch(Scratch::PolyTmp, elems * sizeof(Fr), &scr)) != CQ_OK) return rc;
     Fr* tail = (Fr*)scr;
     Fr* total = tail + (size_t)nblk * 256;
     Fr* carry = total + nblk;
@@ -583,7 +583,7 @@ int poly_kate_division(cq_ctx* c, const Fr* a, uint32_t n, const Fr& z, Fr* q) {
     return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "kate launch failed");
   }
   const size_t elems = 4 * ((size_t)n / POLY_CHUNK + POLY_CHUNK) + 256;
-  if ((rc = c->ensure_scratch(5, elems * sizeof(Fr), &scr)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::PolyTmp, elems * sizeof(Fr), &scr)) != CQ_OK) return rc;
   rc = kate_rec(c, a, n, z, q, (Fr*)scr, elems);
   if (rc != CQ_OK) return rc;
   return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "kate launch failed");

@@ -222,7 +222,6 @@ int shard_any(const cq_pk* pk, bool flag, bool& out) {
 struct AuxFork {
   cq_ctx* c;
   hipStream_t main = nullptr;
-  int saved_slot = 0;
   bool active = false;
   explicit AuxFork(cq_ctx* c_) : c(c_) {}
   // `seq_before`: c->msm_tail_seq sampled before the MSMs were queued
@@ -230,9 +229,7 @@ struct AuxFork {
     if (c->msm_tail_seq == seq_before) CQ_HIP(c, hipEventRecord(c->msm_tail_event, c->stream));  // no launch: plain ordering
     CQ_HIP(c, hipStreamWaitEvent(c->aux_stream, c->msm_tail_event, 0));
     main = c->stream;
-    saved_slot = c->ntt_scratch_slot;
     c->stream = c->aux_stream;
-    c->ntt_scratch_slot = 8;
     active = true;
     return CQ_OK;
   }
@@ -245,7 +242,6 @@ struct AuxFork {
   }
   void restore() {
     c->stream = main;
-    c->ntt_scratch_slot = saved_slot;
     active = false;
   }
   ~AuxFork() {
@@ -486,12 +482,12 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
   const size_t res_stage_elems = (size_t)pk->shard_world * res_slice_max * (pk->cs_degree > 2 ? pk->cs_degree - 1 : 1) + res_slice_max + 64;
   {
     auto setup = [&]() -> int {
-      CQ_TRY(c->ensure_scratch(6, prover_arena_elems(pk) * sizeof(Fr), &arena_v));
+      CQ_TRY(c->ensure_scratch(Scratch::ProverArena, prover_arena_elems(pk) * sizeof(Fr), &arena_v));
       CQ_TRY(c->ensure_pinned_small(&small_v));
       CQ_TRY(c->ensure_pinned((size_t)64 * n + A * (n - u) * sizeof(Fr) + 64, &pin));
       CQ_TRY(c->ensure_aux_stream());
       CQ_TRY(c->ensure_copy_stream());
-      if (resident) CQ_TRY(c->ensure_scratch(7, res_stage_elems * sizeof(Fr), &res_stage_v));  // where received slices land
+      if (resident) CQ_TRY(c->ensure_scratch(Scratch::ProverStage, res_stage_elems * sizeof(Fr), &res_stage_v));  // where received slices land
       int trc = CQ_OK;
       if (!c->tables_for(dom->k, dom->omega_inv, &trc) || !c->tables_for(dom->extended_k, dom->extended_omega, &trc)) return trc;
       return CQ_OK;
@@ -831,11 +827,11 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
     // (lksort.hip), back to Montgomery form; one status read-back per lookup
     void* stage_v;
     const size_t slot = n * 4;  // u64 words of one array of 2^k canonical values
-    CQ_TRY(c->ensure_scratch(7, 3 * slot * sizeof(uint64_t) + lookup_permute_scratch_bytes(k) + 64, &stage_v));
+    CQ_TRY(c->ensure_scratch(Scratch::ProverStage, 3 * slot * sizeof(uint64_t) + lookup_permute_scratch_bytes(k) + 64, &stage_v));
     uint64_t* stage = (uint64_t*)stage_v;
     void* lk_scratch = stage + 3 * slot;
     uint32_t* lk_status = (uint32_t*)((char*)lk_scratch + lookup_permute_scratch_bytes(k));
-    uint32_t* lk_status_host = (uint32_t*)((char*)c->pinned_small + 16);  // beside the lookup error flag
+    uint32_t* lk_status_host = (uint32_t*)((char*)small_v + 16);  // beside the lookup error flag
     for (size_t l = 0; l < PL; l++) {
       const auto& lk = pk->legacy[l];
       CQ_TRY(lagrange_compress(pk->legacy_prog + lk.in_off, lk.width, theta, plk_buf(l, 0)));

@@ -171,6 +171,29 @@ def test_rccl_path_single_rank(ctx):
     wl.close()
 
 
+def test_host_advice_proof_with_resident_sharding():
+    """A host-advice proof stages the caller's columns on the device and holds them for the whole proof.  With resident
+    sharding at pairs=1, k=14 the receive staging is larger than that copy; the two used to share one scratch buffer, and
+    the first such proof on a fresh context grew it (freeing the advice) before the columns were read."""
+    from sha2_on_cq_halo2_amd import Context
+    from sha2_on_cq_halo2_amd.api import rccl_unique_id
+    from sha2_on_cq_halo2_amd.sha_circuit import ShaCqWorkload
+
+    ctx = Context(0)
+    wl = ShaCqWorkload(ctx, 14, pairs=1)
+    plain = wl.prove(seed=11)  # device advice: no staging buffer taken yet
+    host_cols = [c.download((wl.n, 4)) for c in wl.cols]
+    ctx.comm_init_rccl(0, 1, rccl_unique_id())
+    try:
+        wl.pk.set_sharding(0, 1, transport="rccl", resident=True)
+        assert wl.pk.create_proof(host_cols, seed=11) == plain
+    finally:
+        ctx.comm_destroy()
+        wl.pk.set_sharding(0, 1)
+    wl.close()
+    ctx.close()
+
+
 BIG_SHARD_WORKER = r'''
 import os, sys, hashlib
 sys.path.insert(0, %(root)r)
