@@ -485,6 +485,52 @@ typedef int (*cq_phase_fn)(void* user, uint32_t phase, const uint64_t* challenge
 int cq_create_proof_phases(cq_pk* pk, uint64_t* const* advice_dev, const uint64_t* const* instances,
                            const size_t* instance_lens, cq_phase_fn phase_fn, void* phase_user, cq_rng_next_u64 rng,
                            void* rng_state, uint8_t* proof, size_t proof_cap, size_t* proof_len);
+/* ---- dev.rs: MockProver::verify on the GPU ---------------------------------------------------------------------------
+ * cq_pk_check_witness checks the witness a caller is about to prove against the key, as `MockProver::verify` does
+ * (dev.rs:601-958), extended to static lookups (which MockProver ignores, dev.rs:345-350), and says WHICH constraint
+ * fails on WHICH row.  A finding is (kind, index, row, detail):
+ *   CQ_FAIL_GATE           VerifyFailure::ConstraintNotSatisfied (dev.rs:694-766): index = gate polynomial in cs.gates order
+ *                          (the order of cq_plonk.gate_programs), row = the row it was evaluated on.  Every polynomial is
+ *                          evaluated on every row 0 .. n-1, blinding rows included, rotations taken mod n.
+ *   CQ_FAIL_GATE_POISONED  VerifyFailure::ConstraintPoisoned (dev.rs:755): the polynomial reads an advice cell of a blinding
+ *                          row (rows >= usable_rows are poisoned, dev.rs:546-548; the caller's values there are ignored, as
+ *                          the prover ignores them) that nothing multiplies by zero.  Poison propagates as `Value` does
+ *                          (dev.rs:126-178): -P = P, P + x = P, P * 0 = 0, P * x = P, P scaled by 0 = 0.  Unlike the
+ *                          reference, these findings carry their row and are not de-duplicated.
+ *   CQ_FAIL_LOOKUP         VerifyFailure::Lookup (dev.rs:768-906): index = legacy lookup, row = a usable row whose tuple of
+ *                          input expressions equals the tuple of table expressions on no usable row.  Whole tuples are
+ *                          compared (no compression by a challenge); a poisoned entry equals a poisoned entry only
+ *                          (`Value` derives Eq, dev.rs:109).
+ *   CQ_FAIL_STATIC_LOOKUP  no counterpart in the reference: index = static lookup, row = usable input row, detail =
+ *                          0 "not in table" (static_lookup/prover.rs:141) | 1 "Vector lookup must be on the same table row"
+ *                          (:148) | 2 the input expression is poisoned on this row (the prover would look up a value it
+ *                          draws at random).  The table columns are tried in order and the first objection decides.
+ *   CQ_FAIL_PERMUTATION    VerifyFailure::Permutation (dev.rs:908-951): index = position in cs.permutation.columns, row:
+ *                          the cell's value differs from the value of the cell the permutation maps it to.  All n rows; a
+ *                          copy constraint can only name usable rows (dev.rs:457), so blinding-row cells map to themselves.
+ *                          The mapping is recovered from the key's sigma values delta^c' omega^r' (permutation/keygen.rs:
+ *                          151-208), so keys made by cq_pk_read_raw are checked like those of cq_pk_create.
+ * Fixed and instance cells are never poisoned; instance rows beyond instance_lens[c] are zero.
+ *
+ * advice: num_advice columns of 2^k elements, all phases (HOST pointers, or DEVICE pointers if advice_on_device != 0);
+ * instances / instance_lens as for cq_create_proof_instances; challenges: num_challenges x 4 limbs (HOST), the values the
+ * later-phase columns were synthesised with -- no transcript is squeezed; may be NULL when the circuit has none.
+ * Returns CQ_OK whenever the check ran: *total = the exact number of findings (it may exceed cap) and
+ * failures[0 .. min(cap, *total)) = the first ones in ascending (kind, index, row) order -- the same list on every run, for
+ * host or device advice.  cap = 0 with failures = NULL asks only whether the witness is satisfying.  A value missing from
+ * a table is a finding, never CQ_ERR_LOOKUP.  CQ_ERR_ARG: an instance column longer than usable_rows, missing instances,
+ * NULL challenges for a circuit that has some, a sharded key (cq_pk_set_sharding world > 1).
+ * Draws no randomness, writes nothing to the key, and a following cq_create_proof* gives the bytes it would have given
+ * without the call. */
+#define CQ_FAIL_GATE 1u
+#define CQ_FAIL_GATE_POISONED 2u
+#define CQ_FAIL_LOOKUP 3u
+#define CQ_FAIL_STATIC_LOOKUP 4u
+#define CQ_FAIL_PERMUTATION 5u
+typedef struct { uint32_t kind; uint32_t index; uint32_t row; uint32_t detail; } cq_witness_failure;
+int cq_pk_check_witness(cq_pk* pk, const uint64_t* const* advice, int advice_on_device, const uint64_t* const* instances,
+                        const size_t* instance_lens, const uint64_t* challenges, cq_witness_failure* failures, size_t cap,
+                        size_t* total);
 /* ---- the CQ sub-arguments on their own (for a host that keeps its own create_proof and swaps in only these) ---------
  * Shapes: L = lookups of `pk`, n = 2^k, N = table size, ext = 2^extended_k; lookups in cs.static_lookups order.
  *

@@ -9,4 +9,4 @@ the Rust side holds.
 """
 from ._lib import CqError, load, header_symbols  # noqa: F401
 from .api import (Context, DevBuf, EvaluationDomain, G2Srs, ParamsKZG, ProvingKey, StaticTable,  # noqa: F401
-                  TableConfig)
+                  TableConfig, WitnessError, WitnessFailure)

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import weakref
+from typing import NamedTuple
 
 import numpy as np
 
@@ -813,6 +814,80 @@ class ProvingKey(_Handle):
     def create_proof_dev(self, advice_ptrs, rng_words=None, seed=None, instances=None, opaque_rng=False) -> bytes:
         fn, st = self._rng(rng_words, seed, opaque_rng)
         return self._run(self.ctx.lib.cq_create_proof, list(advice_ptrs), fn, st, instances, on_device=True)
+
+
+    def check_witness(self, advice, instances=None, challenges=None, max_failures=64):
+        """`MockProver::verify` (dev.rs:601-958) on the GPU, static lookups included (cq_pk_check_witness): checks the
+        witness `create_proof*` would be given against the key and returns `(total, [WitnessFailure, ...])` -- the exact
+        number of findings and the first `max_failures` of them in ascending (kind, index, row) order.  `advice`: every
+        advice column of every phase, as host arrays (uint64[n, 4]) or as device pointers (ints / DevBufs); `instances`
+        as for create_proof; `challenges`: the user challenges the later phases were synthesised with (Python ints,
+        canonical, or uint64[4] Montgomery limbs each)."""
+        on_device = len(advice) > 0 and all(isinstance(a, (int, DevBuf)) for a in advice)
+        if on_device:
+            ptrs = [a.ptr if isinstance(a, DevBuf) else a for a in advice]
+        else:
+            cols = [np.ascontiguousarray(a, dtype=np.uint64) for a in advice]
+            assert all(c.shape == (1 << self.k, 4) for c in cols), "advice columns are uint64[2^k, 4]"
+            ptrs = [c.ctypes.data for c in cols]
+        assert len(ptrs) == self.num_advice
+        arr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        iptr = ilen = ch_ptr = None
+        if instances is not None:
+            icols = [_fr(i) if len(i) else np.zeros((0, 4), dtype=np.uint64) for i in instances]
+            iptr = (C.c_void_p * max(len(icols), 1))(*[c.ctypes.data for c in icols])
+            ilen = (C.c_size_t * max(len(icols), 1))(*[c.shape[0] for c in icols])
+        if challenges is not None and len(challenges):
+            ch = np.stack([fr_to_mont(int(v)) if np.ndim(v) == 0 else np.asarray(v, dtype=np.uint64).reshape(4) for v in challenges])
+            ch = np.ascontiguousarray(ch, dtype=np.uint64)
+            ch_ptr = ch.ctypes.data
+        cap = max(int(max_failures), 0)
+        out = np.zeros((max(cap, 1), 4), dtype=np.uint32)
+        total = C.c_size_t()
+        self.ctx._chk(self.ctx.lib.cq_pk_check_witness(self.h, arr, 1 if on_device else 0, iptr, ilen, ch_ptr,
+                                                       out.ctypes.data if cap else None, cap, C.byref(total)))
+        return total.value, [WitnessFailure(*(int(x) for x in row)) for row in out[: min(cap, total.value)]]
+
+    def assert_satisfied(self, advice, instances=None, challenges=None, max_failures=8):
+        """`MockProver::assert_satisfied` (dev.rs:960-990): raises `WitnessError` (a `CqError`) naming the first failures."""
+        total, fails = self.check_witness(advice, instances, challenges, max_failures)
+        if total:
+            raise WitnessError(total, fails)
+
+
+class WitnessFailure(NamedTuple):
+    """One finding of `ProvingKey.check_witness`: cq_witness_failure (kind = CQ_FAIL_*)."""
+
+    kind: int
+    index: int
+    row: int
+    detail: int = 0
+
+    def __str__(self):
+        if self.kind == FAIL_GATE:
+            return f"gate polynomial {self.index} is not satisfied on row {self.row}"
+        if self.kind == FAIL_GATE_POISONED:
+            return f"gate polynomial {self.index} is poisoned on row {self.row} (it reads a blinding-row advice cell)"
+        if self.kind == FAIL_LOOKUP:
+            return f"lookup {self.index}: the inputs of row {self.row} are not a row of the table"
+        if self.kind == FAIL_STATIC_LOOKUP:
+            why = ("the value is not in the table", "the values are on different table rows", "the input is poisoned")[min(self.detail, 2)]
+            return f"static lookup {self.index}, row {self.row}: {why}"
+        if self.kind == FAIL_PERMUTATION:
+            return f"permutation column {self.index}, row {self.row}: the cell differs from the one it is copied from"
+        return f"finding of kind {self.kind} (index {self.index}, row {self.row})"
+
+
+FAIL_GATE, FAIL_GATE_POISONED, FAIL_LOOKUP, FAIL_STATIC_LOOKUP, FAIL_PERMUTATION = 1, 2, 3, 4, 5  # CQ_FAIL_*
+
+
+class WitnessError(CqError):
+    """The witness does not satisfy the circuit: `total` findings, the first of them in `failures`."""
+
+    def __init__(self, total, failures):
+        more = f" (and {total - len(failures)} more)" if total > len(failures) else ""
+        super().__init__(0, f"witness not satisfied, {total} finding(s): " + "; ".join(str(f) for f in failures) + more)
+        self.total, self.failures = total, failures
 
 
 def _pk_shape(self):

@@ -33,6 +33,8 @@ enum class Scratch {
   HostAdvice,   // create_proof_host_any's copy of the caller's advice columns, held for the whole proof: nothing else takes it
   NttAux,       // domain.hip transforms while AuxFork has put `stream` on the side stream
   CommGather,   // comm.hip rccl_allgather_host; 1 MiB of it is taken in comm_rccl_init
+  Check,        // check.hip cq_pk_check_witness, for that call only: the staged witness, verdict bitmaps, hash slots,
+                // expression values, the compacted findings.  A public entry point that calls no other: nothing else takes it
   Count
 };
 

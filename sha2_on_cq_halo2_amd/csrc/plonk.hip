@@ -35,10 +35,16 @@ static __device__ __forceinline__ uint32_t rot_idx(uint32_t i, int32_t rot, uint
   return (uint32_t)((int64_t)i + (int64_t)rot * (int64_t)rot_scale) & (size - 1);
 }
 
-__global__ __launch_bounds__(256) void gate_eval_kernel(GateEvalArgs a, Fr* __restrict__ h) {
+// One interpreter loop, two forms (Args::check): the prover's (GateEvalArgs: values only, Horner fold into h) and the
+// witness checker's (GateCheckArgs: a poison bit per stack slot next to the value, a verdict per polynomial).  Every
+// poison statement sits under `if constexpr (CHECK)`: the prover's instantiation carries none of it.
+template <class Args>
+__global__ __launch_bounds__(256) void gate_eval_kernel(Args a, Fr* __restrict__ h) {
+  constexpr bool CHECK = Args::check;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.size) return;
   Fr stack[GATE_STACK];
+  [[maybe_unused]] uint32_t poison = 0;  // bit s: stack[s] is `Value::Poison` (dev.rs:109-124)
   Fr acc = Fr::zero();
   uint32_t pc = 0;
   for (uint32_t poly = 0; poly < a.num_polys; poly++) {
@@ -50,6 +56,7 @@ __global__ __launch_bounds__(256) void gate_eval_kernel(GateEvalArgs a, Fr* __re
       const uint32_t op = w & 0xffu, arg = w >> 8;
       switch (op) {
         case GATE_CONST:
+          if constexpr (CHECK) poison &= ~(1u << sp);
           stack[sp++] = ld(a.constants + arg);
           break;
         case GATE_ADVICE:
@@ -57,31 +64,61 @@ __global__ __launch_bounds__(256) void gate_eval_kernel(GateEvalArgs a, Fr* __re
         case GATE_INSTANCE: {
           const int32_t rot = (int32_t)a.prog[pc++];
           const Fr* base = op == GATE_ADVICE ? a.advice : (op == GATE_FIXED ? a.fixed : a.instance);
-          stack[sp++] = ld(base + (size_t)arg * a.stride + rot_idx(i, rot, a.rot_scale, a.size));
+          const uint32_t row = rot_idx(i, rot, a.rot_scale, a.size);
+          if constexpr (CHECK) {  // advice cells of the blinding rows are poisoned (dev.rs:546-548)
+            const uint32_t p = (op == GATE_ADVICE && row >= a.usable) ? 1u : 0u;
+            poison = (poison & ~(1u << sp)) | (p << sp);
+          }
+          stack[sp++] = ld(base + (size_t)arg * a.stride + row);
           break;
         }
         case GATE_CHALLENGE:
+          if constexpr (CHECK) poison &= ~(1u << sp);
           stack[sp++] = ld(a.challenges + arg);
           break;
-        case GATE_NEG:
+        case GATE_NEG:  // -P = P (dev.rs:126-135)
           stack[sp - 1] = stack[sp - 1].neg();
           break;
-        case GATE_ADD:
+        case GATE_ADD:  // P + x = P (dev.rs:137-147)
+          if constexpr (CHECK) poison |= ((poison >> (sp - 1)) & 1u) << (sp - 2);
           stack[sp - 2] = stack[sp - 2] + stack[sp - 1];
           sp--;
           break;
         case GATE_MUL:
+          if constexpr (CHECK) {  // P * 0 = 0, P * x = P, P * P = P (dev.rs:149-166); the value of 0 * anything is 0 already
+            const uint32_t pa = (poison >> (sp - 2)) & 1u, pb = (poison >> (sp - 1)) & 1u;
+            const bool za = !pa && stack[sp - 2].is_zero(), zb = !pb && stack[sp - 1].is_zero();
+            const uint32_t p = ((pa | pb) && !za && !zb) ? 1u : 0u;
+            poison = (poison & ~(1u << (sp - 2))) | (p << (sp - 2));
+          }
           stack[sp - 2] = stack[sp - 2] * stack[sp - 1];
           sp--;
           break;
-        default:  // GATE_SCALE
-          stack[sp - 1] = stack[sp - 1] * ld(a.constants + arg);
+        default: {  // GATE_SCALE; P scaled by 0 = 0 (dev.rs:168-178)
+          const Fr k = ld(a.constants + arg);
+          if constexpr (CHECK)
+            if (k.is_zero()) poison &= ~(1u << (sp - 1));
+          stack[sp - 1] = stack[sp - 1] * k;
           break;
+        }
       }
     }
-    acc = acc * a.y + stack[0];
+    if constexpr (CHECK) {
+      // the program is wave-uniform, so every live lane of the wave is here: one ballot writes 64 rows of the bitmap
+      const bool poisoned = poison & 1u;
+      const bool failed = !poisoned && !stack[0].is_zero();
+      const unsigned long long fb = __ballot(failed), pb = __ballot(poisoned);
+      if ((threadIdx.x & 63u) == 0) {
+        const size_t word = (size_t)poly * a.words + (i >> 6);
+        if (a.fail_bits) a.fail_bits[word] = fb;
+        a.poison_bits[word] = pb;
+      }
+      if (h) st(h + (size_t)poly * a.size + i, poisoned ? Fr::zero() : stack[0]);
+    } else {
+      acc = acc * a.y + stack[0];
+    }
   }
-  st(h + i, acc);
+  if constexpr (!CHECK) st(h + i, acc);
 }
 
 bool gate_program_check(const uint32_t* lens, const uint32_t* words, uint32_t num_polys, uint32_t num_constants,
@@ -137,8 +174,12 @@ bool gate_program_check(const uint32_t* lens, const uint32_t* words, uint32_t nu
 }
 
 int gate_eval(cq_ctx* c, const GateEvalArgs& a, Fr* h) {
-  gate_eval_kernel<<<blocks_for(a.size), 256, 0, c->stream>>>(a, h);
+  gate_eval_kernel<GateEvalArgs><<<blocks_for(a.size), 256, 0, c->stream>>>(a, h);
   return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "gate_eval launch failed");
+}
+int gate_check(cq_ctx* c, const GateCheckArgs& a, Fr* values) {
+  gate_eval_kernel<GateCheckArgs><<<blocks_for(a.size), 256, 0, c->stream>>>(a, values);
+  return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "gate_check launch failed");
 }
 
 // ---- permutation keygen --------------------------------------------------------------------------------

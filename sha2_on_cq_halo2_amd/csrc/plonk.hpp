@@ -39,6 +39,19 @@ struct GateEvalArgs {
   uint32_t size;             // domain size (power of two)
   uint32_t rot_scale;        // 2^(extended_k - k) on the coset, 1 on the Lagrange basis
   Fr y;
+  static constexpr bool check = false;
+};
+
+// The checking form of the interpreter (cq_pk_check_witness, check.hip): the same programs over the n rows of the
+// Lagrange basis (rot_scale = 1), every operand carrying the poison bit of MockProver's `Value` (dev.rs:109-178), and
+// per polynomial a verdict instead of the Horner fold.  Advice cells at rows >= usable are poisoned (dev.rs:546-548).
+// Bitmaps: bit (row & 63) of word [poly * words + (row >> 6)], words = (size + 63) / 64.
+struct GateCheckArgs : GateEvalArgs {
+  uint32_t usable;
+  uint32_t words;
+  unsigned long long* fail_bits;    // the polynomial ends real and non-zero; nullptr = not wanted
+  unsigned long long* poison_bits;  // the polynomial ends poisoned
+  static constexpr bool check = true;
 };
 
 struct PermProductArgs {
@@ -79,6 +92,8 @@ bool gate_program_check(const uint32_t* lens, const uint32_t* words, uint32_t nu
                         const char** why, size_t* total_words);
 
 int gate_eval(cq_ctx* c, const GateEvalArgs& a, Fr* h);  // h[i] = Horner_y(gate polynomials)(i)
+// verdict bitmaps of every polynomial; `values` != nullptr also keeps [poly * size + row] = its value (zero where poisoned)
+int gate_check(cq_ctx* c, const GateCheckArgs& a, Fr* values);
 int perm_sigma(cq_ctx* c, const uint32_t* mapping_dev, uint32_t ncols, uint32_t n, const Fr* omega_powers,
                const Fr* delta_powers_dev, Fr* out);
 int fr_powers(cq_ctx* c, const Fr& base, uint32_t n, Fr* out);  // out[i] = base^i
