@@ -173,6 +173,15 @@ int cq_msm_set_table_window(cq_ctx* ctx, uint32_t bits);
  * its longest MSM.  Introspection for callers and tests: results never depend on it. */
 int cq_msm_table_width_dev(cq_ctx* ctx, const uint64_t* bases_dev, size_t n, uint32_t preferred_bits, uint32_t* bits);
 
+/* Sums of base points by bucket -- the launch behind [b_0] and [p] of a proof's round 2, on its own (introspection for
+ * callers and tests).  `arrays` base arrays of n affine points each (device) share one index vector index_dev[n] (u32,
+ * device): out_dev[a * buckets + b] = the sum of bases_dev[a][i] over the i with index_dev[i] == b, for b < buckets <=
+ * 16384, as affine points in the reference's layout -- the identity for a bucket no i names; an index >= buckets names no
+ * bucket.  packed == 0: the arrays are in the reference's layout; != 0: in the library's packed form, as
+ * cq_pk_b_row_bases_dev returns them.  At most 32 arrays. */
+int cq_msm_bucket_sums_dev(cq_ctx* ctx, const uint64_t* const* bases_dev, size_t arrays, int packed, const uint32_t* index_dev, size_t n,
+                           size_t buckets, uint64_t* out_dev);
+
 /* eval_polynomial(poly, point)  arithmetic.rs:304-329 */
 int cq_eval_polynomial(cq_ctx* ctx, const uint64_t* poly, size_t n, const uint64_t point[4], uint64_t out[4]);
 int cq_eval_polynomial_dev(cq_ctx* ctx, const uint64_t* poly_dev, size_t n, const uint64_t point[4], uint64_t out[4]);
@@ -449,6 +458,10 @@ int cq_pk_set_opener(cq_pk* pk, int opener);
 int cq_pk_set_rng_fill(cq_pk* pk, cq_rng_fill_fn fill);
 void cq_pk_destroy(cq_pk* pk);
 uint32_t cq_pk_usable_rows(const cq_pk* pk);
+/* The key's per-row bases of [b_0] (which = 0) and [p] (which = 1): 2^k points in the library's packed form (device), so
+ * that [b_0] = sum_i b(w^i) * bases[i]; NULL when the key has none (no static lookups, or a table of more than 16383 rows).
+ * Introspection for tests (cq_msm_bucket_sums_dev takes them). */
+const uint64_t* cq_pk_b_row_bases_dev(const cq_pk* pk, int which);
 size_t cq_pk_proof_size(const cq_pk* pk);
 /* create_proof (plonk/prover.rs:51-779) with ProverGWC + Blake2bWrite<Challenge255>.
  * advice_dev: `num_advice` DEVICE pointers to 2^k field elements each; rows [0, usable_rows) are the

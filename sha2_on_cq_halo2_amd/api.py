@@ -958,6 +958,7 @@ def _pk_create_proof_batch(self, advice_ptr_lists, seeds, lanes: int = 0, opaque
 
 
 ProvingKey.create_proof_batch = _pk_create_proof_batch
+ProvingKey.b_row_bases = lambda self, which: self.ctx.lib.cq_pk_b_row_bases_dev(self.h, which)
 ProvingKey.cq_round1 = _pk_cq_round1
 ProvingKey.cq_round2 = _pk_cq_round2
 ProvingKey.cq_quotient = _pk_cq_quotient
@@ -1117,6 +1118,21 @@ def _ctx_msm_table_width(self, bases_ptr: int, n: int, preferred: int = 0) -> in
     return bits.value
 
 
+def _ctx_msm_bucket_sums(self, bases_ptrs, index: np.ndarray, buckets: int, packed: bool = False) -> np.ndarray:
+    """cq_msm_bucket_sums_dev: out[a, b] = the sum of the points bases_ptrs[a][i] with index[i] == b (affine, uint64[arrays,
+    buckets, 8]; the identity for an empty bucket).  `packed`: the arrays are ProvingKey.b_row_bases pointers."""
+    idx = self.to_device(np.ascontiguousarray(index, dtype=np.uint32))
+    out = self.alloc(len(bases_ptrs) * buckets * 64)
+    arr = (C.c_void_p * len(bases_ptrs))(*bases_ptrs)
+    try:
+        self._chk(self.lib.cq_msm_bucket_sums_dev(self.h, arr, len(bases_ptrs), 1 if packed else 0, idx.ptr, len(index), buckets, out.ptr))
+        return out.download((len(bases_ptrs), buckets, 8))
+    finally:
+        idx.close()
+        out.close()
+
+
+Context.msm_bucket_sums = _ctx_msm_bucket_sums
 Context.msm_table_width = _ctx_msm_table_width
 Context.set_hip_graphs = lambda self, on: self._chk(self.lib.cq_ctx_set_hip_graphs(self.h, 1 if on else 0))
 Context.comm_init_rccl = _ctx_comm_init_rccl

@@ -605,6 +605,16 @@ static int pk_create_impl(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq
   }
   if ((rc = pk_small_tables(pk)) != CQ_OK) return pk_abort(pk, rc);
   CQ_HIP(c, hipStreamSynchronize(c->stream));
+  // the per-row bases of [b_0] and [p] (cq.hpp): two G1 transforms, once per key
+  if (!pk->lookups.empty() && pk->b0_g1_bound && cfg->N + 1 <= ((size_t)1 << (MSM_TABLE_C - 1)) && n >= 2) {
+    const G1Affine* src[2] = {params->g, pk->b0_g1_bound};
+    for (int q = 0; q < 2; q++) {
+      if (hipMalloc(&pk->b_row_bases[q], n * sizeof(G1Affine)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(b row bases)"));
+      if ((rc = g1_to_lagrange_shifted(c, src[q], (uint32_t)(n - 1), 1, pk->k, pk->b_row_bases[q])) != CQ_OK) return pk_abort(pk, rc);
+      if (msm_bases29(c, pk->b_row_bases[q], (uint32_t)n, pk->b_row_bases[q]) != 0) return pk_abort(pk, c->fail(CQ_ERR_HIP, "b row bases"));
+    }
+    CQ_HIP(c, hipStreamSynchronize(c->stream));
+  }
   *out = guard.release();
   return CQ_OK;
 }
@@ -813,6 +823,8 @@ void cq_pk_destroy(cq_pk* pk) {
     (void)pk_shard_tables(pk);
   }
   for (auto& t : pk->held_tables) msm_release_table(pk->ctx, t.bases, t.n, t.c);
+  for (int q = 0; q < 2; q++)
+    if (pk->b_row_bases[q]) hipFree(pk->b_row_bases[q]);
   if (pk->own_b0 && pk->b0_g1_bound) {
     msm_unregister_tables(pk->ctx, pk->b0_g1_bound);
     hipFree(pk->b0_g1_bound);
@@ -831,6 +843,9 @@ void cq_pk_destroy(cq_pk* pk) {
 }
 
 uint32_t cq_pk_usable_rows(const cq_pk* pk) { return pk ? pk->u : 0; }
+const uint64_t* cq_pk_b_row_bases_dev(const cq_pk* pk, int which) {
+  return pk && (which == 0 || which == 1) ? (const uint64_t*)pk->b_row_bases[which] : nullptr;
+}
 
 size_t cq_pk_proof_size(const cq_pk* pk) {
   if (!pk) return 0;

@@ -293,6 +293,33 @@ int cq_msm_table_width_dev(cq_ctx* c, const uint64_t* bases_dev, size_t n, uint3
   return CQ_OK;
 }
 
+int cq_msm_bucket_sums_dev(cq_ctx* c, const uint64_t* const* bases_dev, size_t arrays, int packed, const uint32_t* index_dev, size_t n,
+                           size_t buckets, uint64_t* out_dev) {
+  if (!c || !bases_dev || !index_dev || !out_dev || !arrays || arrays > MSM_MAX_BATCH || !n || n > ((size_t)1 << 26) || !buckets ||
+      buckets > ((size_t)1 << (MSM_TABLE_C - 1)))
+    return CQ_ERR_ARG;
+  CQ_HIP(c, hipSetDevice(c->device));
+  void *sc, *conv = nullptr;
+  int rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryA, n * sizeof(Fr), &sc)) != CQ_OK) return rc;
+  if (!packed && (rc = c->ensure_scratch(Scratch::EntryB, arrays * n * sizeof(G1Affine), &conv)) != CQ_OK) return rc;
+  if (msm_index_scalars(c, index_dev, (uint32_t)n, (uint32_t)buckets, (Fr*)sc) != 0) return c->fail(CQ_ERR_HIP, "bucket sums: scalars");
+  std::vector<const Fr*> scal(arrays, (const Fr*)sc);
+  std::vector<const G1Affine*> bs(arrays);
+  for (size_t a = 0; a < arrays; a++) {
+    if (!bases_dev[a]) return CQ_ERR_ARG;
+    bs[a] = (const G1Affine*)bases_dev[a];
+    if (!packed) {
+      G1Affine* dst = (G1Affine*)conv + a * n;
+      if (msm_bases29(c, bs[a], (uint32_t)n, dst) != 0) return c->fail(CQ_ERR_HIP, "bucket sums: bases");
+      bs[a] = dst;
+    }
+  }
+  if (msm_bucket_sums(c, scal.data(), bs.data(), (uint32_t)n, (uint32_t)arrays, (uint32_t)buckets, (G1Affine*)out_dev) != 0)
+    return c->fail(CQ_ERR_HIP, "bucket-sum launch failed");
+  return c->wait(c->stream);
+}
+
 int cq_msm_set_window(cq_ctx* c, uint32_t bits) {
   if (!c || (bits != 0 && (bits < 2 || bits > 15))) return CQ_ERR_ARG;
   c->msm_c = bits;

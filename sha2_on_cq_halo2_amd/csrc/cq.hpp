@@ -26,6 +26,10 @@ constexpr uint32_t CQ_ROUND1_BATCH = 8;
 struct CqRound1Batch {
   CqRound1Args a[CQ_ROUND1_BATCH];
   uint32_t* m_counts[CQ_ROUND1_BATCH];
+  // optional, n elements per lookup: the table row j(i) every row looks up, as the scalar j(i) + 1 of a bucket-sum launch
+  // (msm_bucket_sums); the rows from u on, which carry beta alone in round 2, name the extra bucket `blind_bucket`
+  Fr* bucket[CQ_ROUND1_BATCH] = {};
+  uint32_t blind_bucket = 0, n = 0;
   uint32_t count;
 };
 struct CqThetaPowers {
@@ -53,6 +57,10 @@ struct CqAValuesBatch {
   const uint32_t* m[CQ_FOLD_BATCH];
   Fr* a[CQ_FOLD_BATCH];
   Fr* a_scaled[CQ_FOLD_BATCH];
+  // optional, N + 1 elements per lookup: the value b takes on the rows that look up table row i, 1 / (t_i + beta) -- zero
+  // where no row does -- and behind them beta^-1, its value on the blinding rows: the scalars over the per-row bucket sums
+  Fr* b_values[CQ_FOLD_BATCH] = {};
+  Fr beta_inv;
   uint32_t width[CQ_FOLD_BATCH];
   Fr theta_pow[CQ_MAX_WIDTH];
   uint32_t count;
@@ -138,6 +146,12 @@ struct cq_pk {
   cq_table_config* table_cfg;
   cq::G1Affine* b0_g1_bound = nullptr;  // n-1 points
   bool own_b0 = false;
+  // Per-ROW bases of b's two commitments, n points each in the accumulate kernel's packed form (built with the key when it
+  // has static lookups and the table fits a bucket set): [0] = g_to_lagrange of (identity, g[0 .. n-1)), [1] = the same of
+  // (identity, b0_g1_bound), so that  [b_0] = sum_i b(w^i) * b_row_bases[0][i]  and  [p] = sum_i b(w^i) * b_row_bases[1][i]
+  // -- coefficient 0 of b meets the identity, which is the division by X.  b takes one value per table row, so both are
+  // short MSMs over per-table-row sums of these bases (prover.hip, round 2).
+  cq::G1Affine* b_row_bases[2] = {nullptr, nullptr};
   cq::Fr* l_active_row = nullptr;       // extended coset
   // ---- general PLONK part (empty for a CQ-only circuit) ----
   uint32_t num_fixed = 0, num_instance = 0, cs_degree = 3;

@@ -24,7 +24,7 @@ enum class Scratch {
                 // takes an entry buffer
   EntryB,       // the second buffer of the same entry points (outputs, bases, pk permutation mapping); also g1_fft's twiddles:
                 // its callers (g1_to_lagrange, fk_table_quotients) run under entry points that hold neither entry buffer
-  MsmWork,      // capi_msm.hip: the workspace of one MSM launch
+  MsmWork,      // capi_msm.hip, msm.hip (msm_bucket_sums): the workspace of one MSM launch; launches follow one another on `stream`
   MsmSums,      // capi_msm.hip: window sums, from msm_multi_begin to its msm_multi_end (launches are never nested)
   PolyTmp,      // poly.hip eval / kate, plonk.hip prefix_product partials, for one call each
   ProverArena,  // create_proof_dev's arena, for the whole proof

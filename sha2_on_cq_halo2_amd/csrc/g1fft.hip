@@ -35,13 +35,14 @@ static __device__ __forceinline__ void ld_canon(const uint64_t* p, uint32_t* k) 
   k[0] = a.x; k[1] = a.y; k[2] = a.z; k[3] = a.w; k[4] = b.x; k[5] = b.y; k[6] = b.z; k[7] = b.w;
 }
 
-// affine (R = 2^256 form) -> packed XYZZ in the kernels' R' form; entries >= n_in are the identity (zero padding)
-__global__ void g1_from_affine_kernel(const G1Affine* __restrict__ in, uint32_t n_in, uint32_t n, XYZZ* __restrict__ out) {
+// affine (R = 2^256 form) -> packed XYZZ in the kernels' R' form: out[shift + j] = in[j] for j < n_in, every other entry
+// the identity (zero padding)
+__global__ void g1_from_affine_kernel(const G1Affine* __restrict__ in, uint32_t n_in, uint32_t shift, uint32_t n, XYZZ* __restrict__ out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   XYZZ29 v = XYZZ29::identity();
-  if (i < n_in) {
-    const Affine29 a = load_affine29(in + i, true);
+  if (i >= shift && i - shift < n_in) {
+    const Affine29 a = load_affine29(in + (i - shift), true);
     if (!a.is_identity()) v = {a.x, a.y, Fq29::one(), Fq29::one()};
   }
   store_xyzz29(out + i, v);
@@ -132,11 +133,15 @@ int g1_fft(cq_ctx* c, XYZZ* data, uint32_t log_n, const Fr& omega) {
 }
 
 // g_to_lagrange (arithmetic.rs:277-301): inverse FFT with omega^-1, every point times n^-1, normalised
-int g1_to_lagrange(cq_ctx* c, const G1Affine* g, uint32_t k, G1Affine* out) {
+int g1_to_lagrange(cq_ctx* c, const G1Affine* g, uint32_t k, G1Affine* out) { return g1_to_lagrange_shifted(c, g, 1u << k, 0, k, out); }
+
+// the same for the n-point array [identity x shift | g[0 .. n_in) | identity ...]: out[i] = (1/n) sum_j omega^(-i (j + shift)) g[j],
+// the base that evaluation i of a polynomial meets when its coefficient j + shift is committed over g[j]
+int g1_to_lagrange_shifted(cq_ctx* c, const G1Affine* g, uint32_t n_in, uint32_t shift, uint32_t k, G1Affine* out) {
   const uint32_t n = 1u << k;
   XYZZ* buf = nullptr;
   if (hipMalloc(&buf, (size_t)n * sizeof(XYZZ)) != hipSuccess) return c->fail(CQ_ERR_HIP, "hipMalloc(g_to_lagrange)");
-  g1_from_affine_kernel<<<blocks_for(n), 256, 0, c->stream>>>(g, n, n, buf);
+  g1_from_affine_kernel<<<blocks_for(n), 256, 0, c->stream>>>(g, n_in, shift, n, buf);
   Fr w = fr_from_raw(FR_ROOT_OF_UNITY_RAW);
   for (uint32_t i = k; i < FR_S; i++) w = w.sqr();
   int rc = g1_fft(c, buf, k, w.inv());
@@ -197,7 +202,7 @@ int fk_table_quotients(cq_ctx* c, const Fr* coeffs /* N, device */, const G1Affi
   const Fr w1 = w2.sqr();
   int rc;
   // FFT_2N of the powers [s^j] (zero-padded) over G1, and of the reversed coefficients over Fr
-  g1_from_affine_kernel<<<blocks_for(N2), 256, 0, c->stream>>>(srs, N, N2, S);
+  g1_from_affine_kernel<<<blocks_for(N2), 256, 0, c->stream>>>(srs, N, 0, N2, S);
   if ((rc = g1_fft(c, S, log_n + 1, w2)) != CQ_OK) { cleanup(); return rc; }
   fk_reverse_kernel<<<blocks_for(N2), 256, 0, c->stream>>>(coeffs, N, d);
   if ((rc = domain_fft(c, d, d, log_n + 1, w2, 1, N2, N2)) != CQ_OK) { cleanup(); return rc; }

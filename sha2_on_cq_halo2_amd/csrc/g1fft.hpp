@@ -9,6 +9,8 @@ namespace cq {
 int g1_fft(cq_ctx* c, XYZZ* data, uint32_t log_n, const Fr& omega);
 // g_to_lagrange (arithmetic.rs:277-301): affine in / affine out, device arrays of 2^k points
 int g1_to_lagrange(cq_ctx* c, const G1Affine* g, uint32_t k, G1Affine* out);
+// ... of the 2^k-point array that holds g[0 .. n_in) from position `shift` on and the identity elsewhere
+int g1_to_lagrange_shifted(cq_ctx* c, const G1Affine* g, uint32_t n_in, uint32_t shift, uint32_t k, G1Affine* out);
 // cached quotients of StaticTableValues::new (static_lookup.rs:108-119) in O(N log N) group operations
 int fk_table_quotients(cq_ctx* c, const Fr* coeffs, const G1Affine* srs, uint32_t log_n, G1Affine* qs_out);
 }  // namespace cq

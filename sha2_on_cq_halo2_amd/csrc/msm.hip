@@ -865,6 +865,56 @@ int msm_precompute_tables(cq_ctx* ctx, const G1Affine* bases, uint32_t n, uint32
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// (no __restrict__: out may be bases -- every lane loads its point before it stores it)
+__global__ __launch_bounds__(256) void msm_bases29_kernel(const G1Affine* bases, G1Affine* out, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Affine29 p = load_affine29(bases + i, true);
+  store_affine29(out + i, p);
+}
+int msm_bases29(cq_ctx* ctx, const G1Affine* bases, uint32_t n, G1Affine* out) {
+  msm_bases29_kernel<<<(n + 255) / 256, 256, 0, ctx->stream>>>(bases, out, n);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+__global__ __launch_bounds__(256) void msm_index_scalars_kernel(const uint32_t* __restrict__ index, uint32_t n, uint32_t count, Fr* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t j = index[i];
+  out[i] = j < count ? Fr::from_u64(j + 1) : Fr::zero();
+}
+int msm_index_scalars(cq_ctx* ctx, const uint32_t* index, uint32_t n, uint32_t count, Fr* out) {
+  msm_index_scalars_kernel<<<(n + 255) / 256, 256, 0, ctx->stream>>>(index, n, count, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- bucket-sum launches (msm_bucket_sums): the first `count` buckets of every MSM as affine points ------------------
+// A launch whose scalars are small non-negative integers d_i = j(i) + 1 < 2^(c-1) has one entry per scalar, in window 0, and
+// bucket j ends up holding sum_{i : j(i) = j} base[i]: the launch stops there and hands the bucket sums out in the callers'
+// R = 2^256 affine layout (one inversion per bucket, all independent), ready to be the bases of a later MSM.  A bucket
+// without entries was never written (msm_rowcol_kernel) and stands for the identity.
+__global__ __launch_bounds__(256) void msm_buckets_affine_kernel(const XYZZ* __restrict__ buckets, const uint32_t* __restrict__ t1, uint32_t B,
+                                                                 uint32_t count, G1Affine* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, m = blockIdx.y;
+  if (i >= count) return;
+  const size_t g = (size_t)m * B + i;
+  G1Affine r = G1Affine::identity();
+  if (t1[g]) {
+    const XYZZ29 v = load_xyzz29(buckets + g);
+    if (!v.is_identity()) {
+      const Fq x = v.x.reduced().to_mont256(), y = v.y.to_mont256(), zz = v.zz.to_mont256(), zzz = v.zzz.to_mont256();
+      const Fq iv = (zz * zzz).inv();
+      r.x = x * (iv * zzz);
+      r.y = y * (iv * zz);
+    }
+  }
+  G1Affine* o = out + (size_t)m * count + i;
+  uint32_t w[8];
+  for (int k = 0; k < 8; k++) w[k] = r.x.v.l[k];
+  st8(&o->x, w);
+  for (int k = 0; k < 8; k++) w[k] = r.y.v.l[k];
+  st8(&o->y, w);
+}
+
 // ---- 5. reduction: sum_{b=1..M} b * B_b per bucket set ---------------------------------------------------
 // Every dependent EC addition costs a lone wave ~9 us whatever the number of busy lanes, so the reduction is shaped
 // for depth, not work.  Buckets are read as a rows x cols matrix (b = cols * hi + lo + 1, cols = min(M, 128)):
@@ -1123,7 +1173,7 @@ MsmLayout::MsmLayout(uint32_t n_, uint32_t c_, uint32_t batch_, bool pre_) : n(n
 
 int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* const* bases_host_ptrs, const size_t* lens,
             uint32_t n, uint32_t c, uint32_t batch, bool pre, const size_t* table_strides, void* workspace,
-            G1Jac* window_sums_dev) {
+            G1Jac* window_sums_dev, G1Affine* raw_out, uint32_t raw_count) {
   hipStream_t s = ctx->stream;
   MsmLayout L(n, c, batch, pre);
   if (pre && (n > (1u << 26) || L.W > 32)) return -4;
@@ -1272,7 +1322,8 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
   return 0;
   };
   // everything the captured kernels' arguments are made of
-  std::vector<uint64_t> sig{(uint64_t)(uintptr_t)workspace, (uint64_t)(uintptr_t)window_sums_dev, n, c, batch, pre ? 1u : 0u, s1};
+  std::vector<uint64_t> sig{(uint64_t)(uintptr_t)workspace, (uint64_t)(uintptr_t)window_sums_dev, n, c, batch, pre ? 1u : 0u, s1,
+                            (uint64_t)(uintptr_t)raw_out, raw_count};
   for (uint32_t i = 0; i < batch; i++) {
     sig.push_back((uint64_t)(uintptr_t)scalars_host_ptrs[i]);
     sig.push_back((uint64_t)(uintptr_t)bases_host_ptrs[i]);
@@ -1317,6 +1368,10 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
     else if (q == 2) msm_combine_level_kernel<2><<<cs_blocks + wv_blocks, 256, 0, s>>>(part[(k - 1) & 1], t_prev, off_prev, t_cur, off_cur, Bt, cs_blocks, part[k & 1], buckets);
     else msm_combine_level_kernel<1><<<cs_blocks + wv_blocks, 256, 0, s>>>(part[(k - 1) & 1], t_prev, off_prev, t_cur, off_cur, Bt, cs_blocks, part[k & 1], buckets);
   }
+  if (raw_out) {  // a bucket-sum launch ends here: no weighted sum over the buckets
+    msm_buckets_affine_kernel<<<dim3((raw_count + 255) / 256, batch), 256, 0, s>>>(buckets, tk, L.B, raw_count, raw_out);
+    return 0;
+  }
   const uint32_t sets = batch * L.Wb;
   // (few sets: the launch waits for chains of dependent additions, and four lanes per addition shorten them; many sets: the
   // SIMDs are busy, and one lane per addition is half the instructions.)
@@ -1336,6 +1391,27 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
   };
   if (ctx->run_graph(sig, 1, tail) != 0) return -1;
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// (The layout is the generic one of a c = 15 table launch: sized for 17 entries per scalar where this launch has one.  That
+// costs address space in a grow-only buffer the round-2 launch outgrows anyway at every size in use; a shape it cannot
+// hold -- msm_run's 2^32 entry bound, the 32 GiB cap of msm_multi_begin -- is refused here and the prover keeps the
+// coefficient path.)
+bool msm_bucket_sums_fit(uint32_t n, uint32_t batch) {
+  if (!batch || batch > MSM_MAX_BATCH || !n || n > (1u << 26)) return false;
+  MsmLayout L(n, MSM_TABLE_C, batch, true);
+  return (uint64_t)batch * L.W * n <= 0xfffffff0ull && L.tmax[0] <= 0xfffffff0ull && L.total <= ((size_t)32 << 30);
+}
+
+int msm_bucket_sums(cq_ctx* ctx, const Fr* const* scalars, const G1Affine* const* bases29, uint32_t n, uint32_t batch, uint32_t count,
+                    G1Affine* out) {
+  const uint32_t c = MSM_TABLE_C;  // the two-pass sort's native width; every digit is below 2^(c-1), hence non-negative
+  if (!count || count > (1u << (c - 1)) || !msm_bucket_sums_fit(n, batch)) return -2;
+  MsmLayout L(n, c, batch, true);
+  void* ws;
+  if (ctx->ensure_scratch(Scratch::MsmWork, L.total, &ws) != 0) return -1;
+  const std::vector<size_t> lens(batch, n), strides(batch, n);  // (window 0 only: the stride is never multiplied by anything but 0)
+  return msm_run(ctx, scalars, bases29, lens.data(), n, c, batch, true, strides.data(), ws, nullptr, out, count);
 }
 
 // cols * V + U from the bit-plane sums of msm_weighted_kernel: V = sum_t 2^t R_t, U = sum_t 2^t C_t + C_total.
@@ -1377,6 +1453,17 @@ G1Jac msm_fold_sets(const G1Jac* pairs, uint32_t Wb, uint32_t M, uint32_t cols) 
 
 G1Jac msm_fold_windows(const G1Jac* pairs, uint32_t W, uint32_t c, uint32_t cols) {
   G1Jac acc = G1Jac::identity();
+  if (c >= 2 && cols == (1u << (c - 1))) {
+    // one row of buckets (c <= 8): the row planes are empty, and the Horner over the c - 1 column planes is the low end of
+    // the window's own c doublings -- c doublings and c additions per window instead of c + 13 and 15
+    for (int w = (int)W - 1; w >= 0; w--) {
+      const G1Jac* pl = pairs + (size_t)MSM_SET_POINTS * w;
+      acc = jac_dbl(acc);
+      for (int t = (int)c - 2; t >= 0; t--) acc = jac_add(jac_dbl(acc), pl[7 + t]);
+      acc = jac_add(acc, pl[14]);
+    }
+    return acc;
+  }
   for (int w = (int)W - 1; w >= 0; w--) {
     for (uint32_t j = 0; j < c; j++) acc = jac_dbl(acc);
     acc = jac_add(acc, msm_set_value(pairs + (size_t)MSM_SET_POINTS * w, cols));

@@ -82,7 +82,20 @@ uint32_t msm_window_bits(uint32_t n);
 // (msm_precompute_tables); then there is ONE bucket set per MSM.
 // lens[j] <= n: per-MSM lengths (one launch may mix lengths; n is the maximum)
 int msm_run(cq_ctx* ctx, const Fr* const* scalars, const G1Affine* const* bases, const size_t* lens, uint32_t n, uint32_t c,
-            uint32_t batch, bool pre, const size_t* table_strides, void* workspace, G1Jac* window_sums_dev);
+            uint32_t batch, bool pre, const size_t* table_strides, void* workspace, G1Jac* window_sums_dev,
+            G1Affine* raw_out = nullptr, uint32_t raw_count = 0);
+// Bucket sums instead of an MSM's value: scalars[j][i] is a small integer d in [0, count] (Montgomery form, as ever), and
+// out[j][b] = sum of bases29[j][i] over the i with d = b + 1, for b < count <= 2^14 -- affine, the callers' R = 2^256 layout,
+// the identity for a bucket nobody names.  One table-mode launch on ctx->stream (sort, accumulate, combine levels; MSMs over
+// the same scalar array share their lists); bases29: n points each in the accumulate kernel's own form (msm_bases29).
+int msm_bucket_sums(cq_ctx* ctx, const Fr* const* scalars, const G1Affine* const* bases29, uint32_t n, uint32_t batch, uint32_t count,
+                    G1Affine* out);
+// out[i] = bases[i] in the accumulate kernel's packed R' form (window 0 of a table); out == bases converts in place
+int msm_bases29(cq_ctx* ctx, const G1Affine* bases, uint32_t n, G1Affine* out);
+// out[i] = the scalar index[i] + 1 of a bucket-sum launch, zero (no bucket) for an index >= count
+int msm_index_scalars(cq_ctx* ctx, const uint32_t* index, uint32_t n, uint32_t count, Fr* out);
+// can msm_bucket_sums plan a launch of this shape (entry counts below 2^32, workspace within the launches' cap)?
+bool msm_bucket_sums_fit(uint32_t n, uint32_t batch);
 int msm_precompute_tables(cq_ctx* ctx, const G1Affine* bases, uint32_t n, uint32_t c, G1Affine* table);
 // Host: value of one bucket set from its MSM_SET_POINTS points; sum_w 2^(c*w) * (value of set w) over W consecutive sets.
 G1Jac msm_set_value(const G1Jac* planes, uint32_t cols);

@@ -299,6 +299,10 @@ struct Buffers {
   Fr *adv, *adv_coeff, *inst_lag, *inst_coeff, *f_lag, *f_coeff, *bpoly, *random_poly, *z, *mv, *cosets, *adv_cosets, *inst_cosets,
       *z_cosets, *lk_inputs, *plk, *plk_cosets, *h_ext, *h_coeff, *gwc_batch, *gwc_wit, *shplonk, *t_comp, *den, *a_val, *m_fr, *a_scaled;
   Fr* challenges;  // user challenges (Expression::Challenge), uploaded as the phases complete
+  // b's commitments from per-table-row sums (round 2): the N + 1 values b takes, per lookup; the bucket sums -- per lookup
+  // two arrays of N + 1 affine points (64 B = 2 Fr each) -- that a launch before theta leaves there
+  Fr* b_values;
+  G1Affine* b_sums;
   Fr *tails, *gather;  // blinding rows of a phase's advice columns (staging); scalars on their way to the host
   uint64_t* rng_dev;
   uint32_t *m_counts, *err_dev;
@@ -361,6 +365,9 @@ void carve(const cq_pk* pk, Arena& ar, Buffers& b) {
   b.a_val = ar.take(L * N);
   b.m_fr = ar.take(L * N);
   b.a_scaled = ar.take(wsum * N);
+  // (an even element count: the 64-byte points behind it stay 64-byte aligned)
+  b.b_values = ar.take(pk->b_row_bases[0] ? (L * (N + 1) + 1) & ~(size_t)1 : 0);
+  b.b_sums = (G1Affine*)ar.take(pk->b_row_bases[0] ? 2 * 2 * L * (N + 1) : 0);
   b.challenges = ar.take(pk->challenge_phase.size() + 8);
   b.tails = ar.take(A * (pk->bf + 1) + 8);
   b.gather = ar.take(GATHER_MAX);
@@ -635,6 +642,13 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
   std::vector<std::array<const Fr*, CQ_MAX_WIDTH>> lk_input(L);
   volatile uint32_t* herr = (volatile uint32_t*)small_v;             // lookup error flag
   Fr* small_fr = (Fr*)((char*)small_v + 64);                         // scalars read back (b(0), z values)
+  // [b_0] and [p] of every lookup as MSMs of N + 1 terms over per-table-row sums of the key's per-row bases (cq.hpp:
+  // b_row_bases) instead of n - 1 terms over the SRS: b takes one value per table row looked up and one on the blinding
+  // rows.  Which rows share a value is known from the witness alone, so the sums are formed where m is counted, ahead of
+  // theta and beta.  Sharded keys commit slices of b's coefficients by point range and keep that path.
+  // A launch the MSM engine cannot plan (entry bound, workspace cap) leaves the coefficient path too.
+  const bool b_by_rows = L > 0 && !pk->sharded() && pk->b_row_bases[0] != nullptr &&
+                         msm_bucket_sums_fit((uint32_t)n, (uint32_t)std::min<size_t>(2 * L, MSM_MAX_BATCH));
   auto count_multiplicities = [&]() -> int {
     if (!L) return CQ_OK;
     CQ_HIP(c, hipMemsetAsync(m_counts_, 0, (L * N + 16) * sizeof(uint32_t), s));
@@ -674,6 +688,9 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
         ra.slots[j] = lk.tables[j]->slots;
         ra.nslots[j] = lk.tables[j]->nslots;
       }
+      r1b.bucket[r1b.count] = b_by_rows ? bpoly + l * n : nullptr;  // (b's own buffer is free until round 2 writes it)
+      r1b.n = b_by_rows ? (uint32_t)n : 0;
+      r1b.blind_bucket = (uint32_t)N;
       r1b.m_counts[r1b.count++] = m_counts_ + l * N;
       if (r1b.count == CQ_ROUND1_BATCH || l + 1 == L) {  // the lookups of a proof share launches
         CQ_TRY(cq_round1(c, r1b, u, err_dev_));
@@ -681,6 +698,14 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       }
     }
     CQ_TRY(cq_m_to_fr(c, m_counts_, (uint32_t)(L * N), B.m_fr));  // the L vectors are adjacent
+    for (size_t l0 = 0; b_by_rows && l0 < L; l0 += MSM_MAX_BATCH / 2) {
+      std::vector<const Fr*> sc;
+      std::vector<const G1Affine*> bs;
+      for (size_t l = l0; l < std::min(L, l0 + MSM_MAX_BATCH / 2); l++)
+        for (int q = 0; q < 2; q++) { sc.push_back(bpoly + l * n); bs.push_back(pk->b_row_bases[q]); }
+      if (msm_bucket_sums(c, sc.data(), bs.data(), (uint32_t)n, (uint32_t)sc.size(), (uint32_t)(N + 1), B.b_sums + 2 * l0 * (N + 1)) != 0)
+        return c->fail(CQ_ERR_HIP, "bucket-sum launch failed");
+    }
     *herr = 0;
     CQ_HIP(c, hipMemcpyAsync((void*)herr, err_dev_, 4, hipMemcpyDeviceToHost, s));  // read after the next synchronisation
     return CQ_OK;
@@ -1056,6 +1081,7 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
     for (size_t l0 = 0; l0 < L; l0 += CQ_FOLD_BATCH) {  // a_i = m_i / (t_i + beta) and its theta-scaled copies for q_a (:247-256)
       CqAValuesBatch ab;
       ab.count = (uint32_t)std::min<size_t>(CQ_FOLD_BATCH, L - l0);
+      ab.beta_inv = beta_inv;
       for (uint32_t j = 0; j < CQ_MAX_WIDTH; j++) ab.theta_pow[j] = theta_pow[j];
       for (uint32_t q = 0; q < ab.count; q++) {
         const size_t l = l0 + q;
@@ -1064,6 +1090,7 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
         ab.m[q] = m_counts + l * N;
         ab.a[q] = a_val + l * N;
         ab.a_scaled[q] = a_scaled + woff * N;
+        ab.b_values[q] = b_by_rows ? B.b_values + l * (N + 1) : nullptr;
         woff += ab.width[q];
       }
       CQ_TRY(cq_a_values_batch(c, ab, (uint32_t)N));
@@ -1128,19 +1155,30 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       std::vector<const Fr*> sc;
       std::vector<const G1Affine*> bs;
       std::vector<size_t> ln;
-      for (size_t st = 0; st < S; st++) { sc.push_back(B.z + st * n); bs.push_back(pk->params->g_lagrange); ln.push_back(n); }
-      for (size_t l = 0; l < PL; l++) { sc.push_back(plk_buf(l, 4)); bs.push_back(pk->params->g_lagrange); ln.push_back(n); }
+      // (b_by_rows: the 2 L short MSMs over this proof's bucket sums -- plain mode, no tables -- go first as one launch of
+      // their own, so that the table-mode MSMs behind them still share one; `at[i]`: where result i of the transcript's
+      // order sits in the launch order)
+      std::vector<size_t> at;
+      for (size_t l = 0; b_by_rows && l < L; l++)
+        for (size_t q = 0; q < 2; q++) { sc.push_back(B.b_values + l * (N + 1)); bs.push_back(B.b_sums + (2 * l + q) * (N + 1)); ln.push_back(N + 1); }
+      for (size_t st = 0; st < S; st++) { at.push_back(sc.size()); sc.push_back(B.z + st * n); bs.push_back(pk->params->g_lagrange); ln.push_back(n); }
+      for (size_t l = 0; l < PL; l++) { at.push_back(sc.size()); sc.push_back(plk_buf(l, 4)); bs.push_back(pk->params->g_lagrange); ln.push_back(n); }
       woff = 0;
       for (size_t l = 0; l < L; l++) {
         const uint32_t w = (uint32_t)pk->lookups[l].cols.size();
-        sc.push_back(a_val + l * N); bs.push_back(pk->table_cfg->g1_lagrange); ln.push_back(N);             // a
-        sc.push_back(a_scaled + woff * N); bs.push_back(pk->qs_concat[l]); ln.push_back((size_t)w * N);      // q_a
-        sc.push_back(a_val + l * N); bs.push_back(pk->table_cfg->g_lagrange_opening_at_0); ln.push_back(N);  // a0
-        sc.push_back(bpoly + l * n + 1); bs.push_back(pk->params->g); ln.push_back(n - 1);                   // b0 (:310)
-        sc.push_back(bpoly + l * n + 1); bs.push_back(pk->b0_g1_bound); ln.push_back(n - 1);                 // p (:299)
+        at.push_back(sc.size()); sc.push_back(a_val + l * N); bs.push_back(pk->table_cfg->g1_lagrange); ln.push_back(N);             // a
+        at.push_back(sc.size()); sc.push_back(a_scaled + woff * N); bs.push_back(pk->qs_concat[l]); ln.push_back((size_t)w * N);      // q_a
+        at.push_back(sc.size()); sc.push_back(a_val + l * N); bs.push_back(pk->table_cfg->g_lagrange_opening_at_0); ln.push_back(N);  // a0
+        if (b_by_rows) {
+          at.push_back(2 * l);      // b0 (:310)
+          at.push_back(2 * l + 1);  // p (:299)
+        } else {
+          at.push_back(sc.size()); sc.push_back(bpoly + l * n + 1); bs.push_back(pk->params->g); ln.push_back(n - 1);     // b0
+          at.push_back(sc.size()); sc.push_back(bpoly + l * n + 1); bs.push_back(pk->b0_g1_bound); ln.push_back(n - 1);   // p
+        }
         woff += w;
       }
-      if (!random_late) { sc.push_back(random_poly); bs.push_back(pk->params->g); ln.push_back(n); }
+      if (!random_late) { at.push_back(sc.size()); sc.push_back(random_poly); bs.push_back(pk->params->g); ln.push_back(n); }
       Commit r2cm;
       const uint64_t seq = c->msm_tail_seq;
       CQ_TRY(r2cm.begin(pk, sc, bs, ln));
@@ -1159,7 +1197,11 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       }
       if (random_late) CQ_TRY(finish_random_poly());  // queued behind the launch above
       mark("round 2 queued");
-      CQ_TRY(r2cm.end(r2));
+      {
+        std::vector<G1Affine> in_launch_order;
+        CQ_TRY(r2cm.end(in_launch_order));
+        for (size_t i : at) r2.push_back(in_launch_order[i]);
+      }
       mark("round 2 commitments on the host");
       if (random_late) {
         std::vector<G1Affine> rc;
