@@ -229,6 +229,35 @@ int cq_fixed_base_mul_dev(cq_ctx* ctx, const uint64_t* scalars_dev, size_t n, ui
  * 4 + 128 n byte G1 part. */
 int cq_params_read_raw(cq_ctx* ctx, const uint8_t* buf, size_t len, int checked, cq_params** out);
 int cq_params_write_raw(cq_params* params, uint8_t* buf, size_t cap, size_t* written);
+/* SerdeFormat (helpers.rs:8-20), the `format` argument of the readers and writers below. */
+#define CQ_SERDE_PROCESSED 0           /* compressed points, canonical scalars: the portable format, half the size */
+#define CQ_SERDE_RAW_BYTES 1           /* raw Montgomery limbs, every element validated on read */
+#define CQ_SERDE_RAW_BYTES_UNCHECKED 2 /* raw Montgomery limbs, no checks */
+/* `CurveAffine::from_bytes` (derive/curve.rs:603-627) for a device array: n x 32 B compressed points (little-endian
+ * canonical x, the parity of the canonical y in bit 7 of byte 31, 32 zero bytes = identity) -> n affine points in the raw
+ * layout.  One square root in Fq per point, a^((q+1)/4), on the GPU.  An encoding is invalid when x >= q, when x^3 + 3 is
+ * not a square, or when x = 0 carries the sign bit: CQ_ERR_ARG, *first_bad (may be NULL) = the LOWEST invalid index, and
+ * cq_last_error names it; the output array is then unspecified.  Buffers 16-byte aligned.  Unlike most `_dev` entry points
+ * this one returns after the stream has drained (it reads the verdict back). */
+int cq_g1_decompress_dev(cq_ctx* ctx, const uint8_t* bytes_dev, size_t n, uint64_t* out_affine_dev, size_t* first_bad);
+/* `CurveAffine::to_bytes` (derive/curve.rs:635-646): n raw affine points -> n x 32 B, asynchronous on the context's stream. */
+int cq_g1_compress_dev(cq_ctx* ctx, const uint64_t* affine_dev, size_t n, uint8_t* bytes_dev);
+/* `SerdePrimeField::read` / `write` with SerdeFormat::Processed (helpers.rs:68-91), i.e. `Fr::from_repr` / `to_repr`: n x 32 B
+ * canonical little-endian scalars <-> Montgomery limbs; `out_dev` may be `bytes_dev` (in place).  from_repr rejects values
+ * >= r exactly as cq_g1_decompress_dev rejects points (CQ_ERR_ARG, *first_bad, waits for the stream); to_repr is asynchronous. */
+int cq_fr_from_repr_dev(cq_ctx* ctx, const uint8_t* bytes_dev, size_t n, uint64_t* out_dev, size_t* first_bad);
+int cq_fr_to_repr_dev(cq_ctx* ctx, const uint64_t* in_dev, size_t n, uint8_t* bytes_dev);
+/* ParamsKZG::read_custom / write_custom in any SerdeFormat (commitment.rs:366-459).  The raw formats are
+ * cq_params_read_raw (checked / unchecked) and cq_params_write_raw.  CQ_SERDE_PROCESSED:
+ *   k:u32 LE | n x 32 B g | n x 32 B g_lagrange | [64 B g2 | 64 B s_g2]
+ * read: the compressed bytes are staged in device scratch and decompressed on the GPU straight into the resident arrays
+ * (the reference decompresses in parallel for the same reason, commitment.rs:394-426); an invalid point is CQ_ERR_ARG and
+ * cq_last_error names the array and the index.  As in the raw reader the G2 tail (2 x 64 B compressed here) is ignored on
+ * read and not emitted on write: the caller appends its own.  cq_params_serialized_size: the bytes cq_params_write emits
+ * (4 + 64 n processed, 4 + 128 n raw; 0 for an unknown format). */
+int cq_params_read(cq_ctx* ctx, const uint8_t* buf, size_t len, int format, cq_params** out);
+int cq_params_write(cq_params* params, int format, uint8_t* buf, size_t cap, size_t* written);
+size_t cq_params_serialized_size(const cq_params* params, int format);
 /* g_to_lagrange(g, k) (arithmetic.rs:277-301): the Lagrange-basis SRS from the monomial one by an inverse FFT
  * over G1 (device arrays of 2^k affine points). */
 int cq_g_to_lagrange_dev(cq_ctx* ctx, const uint64_t* g_dev, uint32_t k, uint64_t* g_lagrange_dev);
@@ -409,7 +438,8 @@ int cq_pk_create(cq_ctx* ctx, cq_params* params, const cq_circuit* circuit, cq_t
  *     polynomials starts with its count:u32 BE (helpers.rs:129-140).
  * cq_pk_read_raw = cq_pk_create with those polynomials uploaded straight into HBM instead of recomputed (cosets
  * included: no NTT runs); `circuit` gives the shape (its plonk->fixed / perm_mapping are not read), `num_selectors`
- * the number of selector bit vectors to skip, `checked` != 0 validates every element (RawBytes).  The Rust reader
+ * the number of selector bit vectors to skip, `checked` != 0 validates every element the key keeps (RawBytes; l0 / l_last of a
+ * CQ-only key and the commitments are skipped unread).  The Rust reader
  * leaves static tables / b0_g1_bound empty (:396-401, "FIXME"); here they are passed as for cq_pk_create.
  * cq_pk_write_raw emits the same stream (`selector_bits` is copied through: the prover does not keep selectors). */
 int cq_pk_read_raw(cq_ctx* ctx, cq_params* params, const cq_circuit* circuit, cq_table_config* cfg,
@@ -417,6 +447,17 @@ int cq_pk_read_raw(cq_ctx* ctx, cq_params* params, const cq_circuit* circuit, cq
                    int checked, cq_pk** out);
 size_t cq_pk_raw_size(const cq_pk* pk, uint32_t num_selectors);
 int cq_pk_write_raw(cq_pk* pk, const uint8_t* selector_bits, uint32_t num_selectors, uint8_t* buf, size_t cap, size_t* written);
+/* ProvingKey::read / ProvingKey::write in any SerdeFormat (plonk.rs:349-403): the arguments of the raw trio plus `format`.
+ * The raw formats behave as cq_pk_read_raw (checked / unchecked) / cq_pk_write_raw.  CQ_SERDE_PROCESSED is the stream
+ * documented above with 32-byte compressed fixed and permutation commitments and 32-byte canonical little-endian scalars in
+ * every polynomial; counts, lengths and selector bits are unchanged.  read: the scalars are converted on the GPU where they
+ * land and nothing is recomputed (no NTT runs, as for raw); the commitments are decompressed only to validate them.  A scalar
+ * >= r anywhere in the stream (sections the prover does not keep included) or an invalid commitment is CQ_ERR_ARG, and cq_last_error names the polynomial (in stream order, l0 = 0) and the
+ * element, or the commitment (fixed ones first).  StaticTableValues are not part of the stream (plonk.rs:396-401). */
+int cq_pk_read(cq_ctx* ctx, cq_params* params, const cq_circuit* circuit, cq_table_config* cfg, const uint64_t* b0_g1_bound,
+               int b0_on_device, const uint8_t* buf, size_t len, uint32_t num_selectors, int format, cq_pk** out);
+size_t cq_pk_serialized_size(const cq_pk* pk, int format, uint32_t num_selectors);
+int cq_pk_write(cq_pk* pk, int format, const uint8_t* selector_bits, uint32_t num_selectors, uint8_t* buf, size_t cap, size_t* written);
 /* Shards every commitment of cq_create_proof across `world` ranks by point range: rank r
  * multiplies the slice shard(len, r, world) of each (scalars, bases) pair, the 96-byte Jacobian partials of a round are
  * all-gathered and summed locally (EC addition is not an RCCL reduction op), so every rank derives the same
@@ -629,6 +670,7 @@ void cq_opaque_rng_fill(void* state, uint64_t* dst, size_t count);
 #define CQ_PROF_NTT_PASS 2       /* ntt_pass_kernel: one radix-2^deg Stockham pass */
 #define CQ_PROF_MSM_ENTRIES 3    /* no timing: `calls` = (point, non-zero digit) pairs = mixed additions executed by
                                   * msm_accumulate_kernel since the last read */
+#define CQ_PROF_G1_DECOMPRESS 4  /* g1_decompress_kernel: point decompression of the Processed readers */
 int cq_profile_enable(cq_ctx* ctx, int on);
 int cq_profile_read(cq_ctx* ctx, int id, double* total_ms, uint64_t* calls);
 

@@ -271,6 +271,7 @@ class ParamsKZG:
 PROF_MSM_ACCUMULATE = 1
 PROF_NTT_PASS = 2
 PROF_MSM_ENTRIES = 3
+PROF_G1_DECOMPRESS = 4
 
 
 def _ctx_profile_enable(self, on: bool = True):
@@ -666,7 +667,7 @@ class ProvingKey(_Handle):
 
     def __init__(self, ctx: Context, params: ParamsKZG, k: int, num_advice: int, lookups, table_cfg: TableConfig,
                  b0_g1_bound, vk_repr: np.ndarray, cs=None, fixed=None, permutation=None, raw: bytes = None,
-                 num_selectors: int = 0, checked: bool = True):
+                 num_selectors: int = 0, checked: bool = None, format: int = None):
         self.ctx, self.params, self.k = ctx, params, k
         self.cs = cs
         if cs is not None:
@@ -702,7 +703,14 @@ class ProvingKey(_Handle):
         cfg_h = table_cfg.h if table_cfg is not None else None
         if raw is None:
             ctx._chk(ctx.lib.cq_pk_create(ctx.h, params.h, C.byref(cs_), cfg_h, b0_ptr, on_dev, C.byref(h)))
-        else:  # `ProvingKey::read(reader, RawBytes | RawBytesUnchecked)` (plonk.rs:379-403)
+        elif format is not None:  # `ProvingKey::read(reader, format)` in any SerdeFormat (ProvingKey.read)
+            if checked is not None:
+                raise CqError(-1, "ProvingKey: give `format` or `checked`, not both")
+            rb = np.frombuffer(raw, dtype=np.uint8)
+            ctx._chk(ctx.lib.cq_pk_read(ctx.h, params.h, C.byref(cs_), cfg_h, b0_ptr, on_dev, rb.ctypes.data, rb.shape[0],
+                                        num_selectors, format, C.byref(h)))
+        else:  # `ProvingKey::read(reader, RawBytes | RawBytesUnchecked)` (plonk.rs:379-403); checked: default True
+            checked = True if checked is None else checked
             rb = np.frombuffer(raw, dtype=np.uint8)
             ctx._chk(ctx.lib.cq_pk_read_raw(ctx.h, params.h, C.byref(cs_), cfg_h, b0_ptr, on_dev, rb.ctypes.data, rb.shape[0],
                                             num_selectors, 1 if checked else 0, C.byref(h)))
@@ -1046,6 +1054,101 @@ def _params_write_raw(self) -> bytes:
 
 ParamsKZG.read_raw = classmethod(_params_read_raw)
 ParamsKZG.write_raw = _params_write_raw
+
+# `SerdeFormat` (helpers.rs:8-20): the values of CQ_SERDE_* in include/cq_halo2.h
+SERDE_PROCESSED, SERDE_RAW_BYTES, SERDE_RAW_BYTES_UNCHECKED = 0, 1, 2
+
+
+def _params_read(cls, ctx: Context, data: bytes, format: int = SERDE_PROCESSED) -> "ParamsKZG":
+    """`ParamsKZG::read_custom(reader, format)` (kzg/commitment.rs:383-459); Processed points are decompressed on the GPU."""
+    self = cls.__new__(cls)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    h = C.c_void_p()
+    ctx._chk(ctx.lib.cq_params_read(ctx.h, buf.ctypes.data, buf.shape[0], format, C.byref(h)))
+    self.ctx = ctx
+    self.k = int.from_bytes(data[:4], "little")
+    self.n = 1 << self.k
+    self.h = h
+    ctx._children.add(self)
+    return self
+
+
+def _params_write(self, format: int = SERDE_PROCESSED) -> bytes:
+    """G1 part of `ParamsKZG::write_custom(writer, format)` (kzg/commitment.rs:366-379)."""
+    size = self.ctx.lib.cq_params_serialized_size(self.h, format)
+    buf = np.zeros(max(size, 1), dtype=np.uint8)
+    w = C.c_size_t()
+    self.ctx._chk(self.ctx.lib.cq_params_write(self.h, format, buf.ctypes.data, size, C.byref(w)))
+    return buf[: w.value].tobytes()
+
+
+ParamsKZG.read = classmethod(_params_read)
+ParamsKZG.write = _params_write
+
+
+def _ctx_checked_conversion(self, fn, src: DevBuf, n: int, dst: DevBuf):
+    bad = C.c_size_t()
+    rc = fn(self.h, src.ptr, n, dst.ptr, C.byref(bad))
+    if rc != 0:
+        e = CqError(rc, self.lib.cq_last_error(self.h).decode())
+        e.first_bad = bad.value if rc == -1 else None
+        raise e
+
+
+def _ctx_g1_decompress(self, src: DevBuf, n: int, dst: DevBuf):
+    """`CurveAffine::from_bytes` (derive/curve.rs:603-627) over a device array: n x 32 B -> n raw affine points.  An invalid
+    encoding raises CqError whose `first_bad` is the lowest invalid index."""
+    _ctx_checked_conversion(self, self.lib.cq_g1_decompress_dev, src, n, dst)
+
+
+def _ctx_g1_compress(self, src: DevBuf, n: int, dst: DevBuf):
+    """`CurveAffine::to_bytes` (derive/curve.rs:635-646) over a device array: n raw affine points -> n x 32 B."""
+    self._chk(self.lib.cq_g1_compress_dev(self.h, src.ptr, n, dst.ptr))
+
+
+def _ctx_fr_from_repr(self, src: DevBuf, n: int, dst: DevBuf):
+    """`Fr::from_repr` (helpers.rs:68-79) over a device array: n x 32 B canonical little-endian -> Montgomery limbs (dst may be
+    src).  A value >= r raises CqError whose `first_bad` is the lowest such index."""
+    _ctx_checked_conversion(self, self.lib.cq_fr_from_repr_dev, src, n, dst)
+
+
+def _ctx_fr_to_repr(self, src: DevBuf, n: int, dst: DevBuf):
+    """`Fr::to_repr` (helpers.rs:81-91) over a device array."""
+    self._chk(self.lib.cq_fr_to_repr_dev(self.h, src.ptr, n, dst.ptr))
+
+
+Context.g1_decompress = _ctx_g1_decompress
+Context.g1_compress = _ctx_g1_compress
+Context.fr_from_repr = _ctx_fr_from_repr
+Context.fr_to_repr = _ctx_fr_to_repr
+
+
+def _pk_read(cls, ctx: Context, params: ParamsKZG, k: int, num_advice: int, lookups, table_cfg, b0_g1_bound, vk_repr, data: bytes,
+             format: int = SERDE_PROCESSED, cs=None, num_selectors: int = 0) -> "ProvingKey":
+    """`ProvingKey::read(reader, format)` (plonk.rs:379-403): the constructor's arguments (the circuit's shape) plus the
+    serialized key and its format."""
+    return cls(ctx, params, k, num_advice, lookups, table_cfg, b0_g1_bound, vk_repr, cs=cs, raw=data, num_selectors=num_selectors,
+               format=format)
+
+
+def _pk_write(self, format: int = SERDE_PROCESSED, selector_bits: bytes = b"", num_selectors: int = 0) -> bytes:
+    """`ProvingKey::write(writer, format)` (plonk.rs:349-362)."""
+    size = self.ctx.lib.cq_pk_serialized_size(self.h, format, num_selectors)
+    buf = np.zeros(max(size, 1), dtype=np.uint8)
+    sel = np.frombuffer(selector_bits, dtype=np.uint8) if num_selectors else None
+    w = C.c_size_t()
+    self.ctx._chk(self.ctx.lib.cq_pk_write(self.h, format, sel.ctypes.data if sel is not None else None, num_selectors,
+                                           buf.ctypes.data, size, C.byref(w)))
+    return buf[: w.value].tobytes()
+
+
+def _pk_serialized_size(self, format: int = SERDE_PROCESSED, num_selectors: int = 0) -> int:
+    return self.ctx.lib.cq_pk_serialized_size(self.h, format, num_selectors)
+
+
+ProvingKey.read = classmethod(_pk_read)
+ProvingKey.write = _pk_write
+ProvingKey.serialized_size = _pk_serialized_size
 
 SHA_ROT0, SHA_ROT1, SHA_MAJ, SHA_CH = 0, 1, 2, 3
 

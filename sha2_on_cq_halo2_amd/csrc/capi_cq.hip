@@ -15,6 +15,7 @@
 #include "setup.hpp"
 #include "msm.hpp"
 #include "comm.hpp"
+#include "serde.hpp"
 
 using namespace cq;
 
@@ -276,7 +277,8 @@ static int pk_small_tables(cq_pk* pk) {
 }
 
 static int pk_create_impl(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq_table_config* cfg, const uint64_t* b0_g1_bound,
-                          int b0_on_device, const uint8_t* raw, size_t raw_len, uint32_t num_selectors, int checked, cq_pk** out) {
+                          int b0_on_device, const uint8_t* raw, size_t raw_len, uint32_t num_selectors, int checked, bool processed,
+                          cq_pk** out) {
   if (!c || !params || !cs || !out) return CQ_ERR_ARG;
   if (cs->num_lookups && (!cfg || !b0_g1_bound)) return c->fail(CQ_ERR_ARG, "pk: static lookups need a table config and b0_g1_bound");
   if (cs->k != params->k) return c->fail(CQ_ERR_ARG, "pk: circuit k differs from params k");
@@ -441,8 +443,17 @@ static int pk_create_impl(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq
   // extended domain for cs.degree(): 3 for permutation / static lookups (static_lookup.rs:181-190), more with gates
   if ((rc = domain_create(c, pk->cs_degree, pk->k, &pk->domain)) != CQ_OK) return pk_abort(pk, rc);
   const size_t ext = pk->domain->ext();
+  // SerdeFormat::Processed: verdict words of the device conversions, [0] the commitments, [1 + j] polynomial j of the stream
+  const size_t cells = 4 + 3 * ((size_t)pk->num_fixed + pk->perm_columns.size());
   void* tmp;
-  if ((rc = c->ensure_scratch(Scratch::EntryA, n * sizeof(Fr), &tmp)) != CQ_OK) return pk_abort(pk, rc);
+  if ((rc = c->ensure_scratch(Scratch::EntryA, std::max(n * sizeof(Fr), 2 * cells * sizeof(uint32_t)), &tmp)) != CQ_OK) return pk_abort(pk, rc);
+  // The cells live in `tmp` from the reset below to the read-back after the last section.  That holds because nothing in
+  // between asks for a larger EntryA (growing a scratch buffer frees it): the raw paths use `tmp` for nothing else, the
+  // sections stage through EntryB, and the checked-raw branch, which takes EntryA for its flag, excludes the Processed one.
+  uint32_t* count_dev = (uint32_t*)tmp;
+  uint32_t* first_dev = count_dev + cells;
+  if (raw && processed && (rc = serde_verdict_reset(c, count_dev, first_dev, cells)) != CQ_OK) return pk_abort(pk, rc);
+  size_t poly_index = 0;
   // l_active_row = 1 - (l_last + l_blind) on the extended coset (keygen.rs:344-373); by linearity it is
   // the coset extension of the indicator of the usable rows
   if (hipMalloc(&pk->l_active_row, ext * sizeof(Fr)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(l_active_row)"));
@@ -455,9 +466,18 @@ static int pk_create_impl(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq
     const uint32_t len = rd.be32();
     const uint8_t* src = rd.take((size_t)len * sizeof(Fr));
     if (!rd.ok || len != expect) return c->fail(CQ_ERR_ARG, "pk: serialized polynomial has the wrong length");
+    const size_t j = poly_index++;
     if (dst) {
       CQ_HIP(c, hipMemcpyAsync(dst, src, (size_t)len * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+      if (processed)  // canonical scalars: converted where they landed (helpers.rs:68-79)
+        return fr_from_repr(c, (const uint8_t*)dst, len, dst, count_dev + 1 + j, first_dev + 1 + j);
       to_check.push_back({dst, len});
+    } else if (processed && len) {  // a section the prover does not keep (l0 / l_last of a CQ-only key): validated in scratch
+      void* stage;
+      int r2 = c->ensure_scratch(Scratch::EntryB, (size_t)len * sizeof(Fr), &stage);
+      if (r2 != CQ_OK) return r2;
+      CQ_HIP(c, hipMemcpyAsync(stage, src, (size_t)len * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+      return fr_from_repr(c, (const uint8_t*)stage, len, (Fr*)stage, count_dev + 1 + j, first_dev + 1 + j);
     }
     return CQ_OK;
   };
@@ -474,8 +494,17 @@ static int pk_create_impl(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq
     rd.left = raw_len;
     const uint32_t rk = rd.be32(), nfix = rd.be32();
     const size_t nperm = pk->perm_columns.size();
-    rd.take((size_t)nfix * sizeof(G1Affine) + nperm * sizeof(G1Affine) + (size_t)num_selectors * ((n + 7) / 8));
+    const size_t ncm = (size_t)nfix + nperm, cm_bytes = ncm * (processed ? 32 : sizeof(G1Affine));
+    const uint8_t* cm = rd.take(cm_bytes);
+    rd.take((size_t)num_selectors * ((n + 7) / 8));
     if (!rd.ok || rk != pk->k || nfix != pk->num_fixed) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: serialized key does not match the circuit"));
+    if (processed && ncm) {  // compressed commitments: decompressed to validate them (`C::read`, plonk.rs:120-127), then dropped
+      void* stage;
+      if ((rc = c->ensure_scratch(Scratch::EntryB, cm_bytes + ncm * sizeof(G1Affine), &stage)) != CQ_OK) return pk_abort(pk, rc);
+      CQ_HIP(c, hipMemcpyAsync(stage, cm, cm_bytes, hipMemcpyHostToDevice, c->stream));
+      if ((rc = g1_decompress(c, (const uint8_t*)stage, (uint32_t)ncm, (G1Affine*)((uint8_t*)stage + cm_bytes), count_dev, first_dev)) != CQ_OK)
+        return pk_abort(pk, rc);
+    }
   }
   if (raw) {
     // l0, l_last, l_active_row (keygen.rs:338-373) come first; a CQ-only prover reads only the last
@@ -573,7 +602,18 @@ static int pk_create_impl(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq
       return pk_abort(pk, rc);
   }
   if (raw && rd.left != 0) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: trailing bytes after the serialized key"));
-  if (raw && checked) {  // SerdeFormat::RawBytes: every field element below the modulus (helpers.rs:62-79)
+  if (raw && processed) {  // SerdeFormat::Processed: the verdicts of the conversions above
+    std::vector<uint32_t> verdict(2 * cells);
+    CQ_HIP(c, hipMemcpyAsync(verdict.data(), count_dev, 2 * cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    CQ_HIP(c, hipStreamSynchronize(c->stream));
+    if (verdict[0])
+      return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: invalid point encoding at commitment " + std::to_string(verdict[cells]) +
+                                                  " (fixed commitments first, then permutation commitments)"));
+    for (size_t j = 1; j < cells; j++)
+      if (verdict[j])
+        return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: field element not below the modulus at polynomial " + std::to_string(j - 1) + " element " +
+                                                    std::to_string(verdict[cells + j]) + " (polynomials in stream order, l0 = 0)"));
+  } else if (raw && checked) {  // SerdeFormat::RawBytes: every field element below the modulus (helpers.rs:62-79)
     void* flag;
     if ((rc = c->ensure_scratch(Scratch::EntryA, 64, &flag)) != CQ_OK) return pk_abort(pk, rc);
     CQ_HIP(c, hipMemsetAsync(flag, 0, 4, c->stream));
@@ -621,30 +661,49 @@ static int pk_create_impl(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq
 
 int cq_pk_create(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq_table_config* cfg, const uint64_t* b0_g1_bound,
                  int b0_on_device, cq_pk** out) {
-  return pk_create_impl(c, params, cs, cfg, b0_g1_bound, b0_on_device, nullptr, 0, 0, 0, out);
+  return pk_create_impl(c, params, cs, cfg, b0_g1_bound, b0_on_device, nullptr, 0, 0, 0, false, out);
 }
 
 int cq_pk_read_raw(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq_table_config* cfg, const uint64_t* b0_g1_bound,
                    int b0_on_device, const uint8_t* buf, size_t len, uint32_t num_selectors, int checked, cq_pk** out) {
   if (!buf) return CQ_ERR_ARG;
-  return pk_create_impl(c, params, cs, cfg, b0_g1_bound, b0_on_device, buf, len, num_selectors, checked, out);
+  return pk_create_impl(c, params, cs, cfg, b0_g1_bound, b0_on_device, buf, len, num_selectors, checked, false, out);
 }
 
-size_t cq_pk_raw_size(const cq_pk* pk, uint32_t num_selectors) {
+// ProvingKey::read in any SerdeFormat (plonk.rs:379-403)
+int cq_pk_read(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq_table_config* cfg, const uint64_t* b0_g1_bound, int b0_on_device,
+               const uint8_t* buf, size_t len, uint32_t num_selectors, int format, cq_pk** out) {
+  if (!buf) return CQ_ERR_ARG;
+  if (format != CQ_SERDE_PROCESSED && format != CQ_SERDE_RAW_BYTES && format != CQ_SERDE_RAW_BYTES_UNCHECKED)
+    return c ? c->fail(CQ_ERR_ARG, "pk: unknown serde format") : CQ_ERR_ARG;
+  return pk_create_impl(c, params, cs, cfg, b0_g1_bound, b0_on_device, buf, len, num_selectors, format == CQ_SERDE_RAW_BYTES,
+                        format == CQ_SERDE_PROCESSED, out);
+}
+
+static size_t pk_stream_size(const cq_pk* pk, uint32_t num_selectors, size_t point_bytes) {
   if (!pk) return 0;
   const size_t n = (size_t)1 << pk->k, ext = pk->domain->ext(), F = pk->num_fixed, PC = pk->perm_columns.size();
   const size_t poly_n = 4 + n * sizeof(Fr), poly_e = 4 + ext * sizeof(Fr);
-  return 8 + (F + PC) * sizeof(G1Affine) + (size_t)num_selectors * ((n + 7) / 8) + 3 * poly_e + 3 * 4 + F * (2 * poly_n + poly_e) + 3 * 4 +
+  return 8 + (F + PC) * point_bytes + (size_t)num_selectors * ((n + 7) / 8) + 3 * poly_e + 3 * 4 + F * (2 * poly_n + poly_e) + 3 * 4 +
          PC * (2 * poly_n + poly_e);
 }
+size_t cq_pk_raw_size(const cq_pk* pk, uint32_t num_selectors) { return pk_stream_size(pk, num_selectors, sizeof(G1Affine)); }
+// a canonical scalar is as long as a raw one: the formats differ by the commitments alone
+size_t cq_pk_serialized_size(const cq_pk* pk, int format, uint32_t num_selectors) {
+  if (format == CQ_SERDE_PROCESSED) return pk_stream_size(pk, num_selectors, 32);
+  if (format == CQ_SERDE_RAW_BYTES || format == CQ_SERDE_RAW_BYTES_UNCHECKED) return pk_stream_size(pk, num_selectors, sizeof(G1Affine));
+  return 0;
+}
 
-// ProvingKey::write, SerdeFormat::RawBytes (plonk.rs:349-362)
-int cq_pk_write_raw(cq_pk* pk, const uint8_t* selector_bits, uint32_t num_selectors, uint8_t* buf, size_t cap, size_t* written) {
+// ProvingKey::write (plonk.rs:349-362); processed: compressed commitments, canonical scalars (converted into the second
+// entry buffer, one polynomial at a time, and copied out from there)
+static int pk_write_impl(cq_pk* pk, bool processed, const uint8_t* selector_bits, uint32_t num_selectors, uint8_t* buf, size_t cap,
+                         size_t* written) {
   if (!pk || !buf || !written || (num_selectors && !selector_bits)) return CQ_ERR_ARG;
   cq_ctx* c = pk->ctx;
   CQ_HIP(c, hipSetDevice(c->device));
   const size_t n = (size_t)1 << pk->k, ext = pk->domain->ext(), F = pk->num_fixed, PC = pk->perm_columns.size();
-  const size_t total = cq_pk_raw_size(pk, num_selectors);
+  const size_t total = pk_stream_size(pk, num_selectors, processed ? 32 : sizeof(G1Affine));
   if (cap < total) return c->fail(CQ_ERR_ARG, "pk: output buffer too small");
   uint8_t* o = buf;
   // VerifyingKey::write (:92-113): k, fixed commitments, permutation commitments, packed selector bits
@@ -653,13 +712,31 @@ int cq_pk_write_raw(cq_pk* pk, const uint8_t* selector_bits, uint32_t num_select
   std::vector<uint64_t> cm((F + PC) * 8 + 8);
   int rc = cq_pk_vk_commitments(pk, cm.data(), cm.data() + F * 8);
   if (rc != CQ_OK) return rc;
-  memcpy(o, cm.data(), (F + PC) * sizeof(G1Affine));
-  o += (F + PC) * sizeof(G1Affine);
+  void* stage = nullptr;  // processed only
+  if (processed) {
+    if ((rc = c->ensure_scratch(Scratch::EntryB, std::max(ext * sizeof(Fr), (F + PC) * (sizeof(G1Affine) + 32)), &stage)) != CQ_OK) return rc;
+    if (F + PC) {
+      uint8_t* packed = (uint8_t*)stage + (F + PC) * sizeof(G1Affine);
+      CQ_HIP(c, hipMemcpyAsync(stage, cm.data(), (F + PC) * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
+      if ((rc = g1_compress(c, (const G1Affine*)stage, (uint32_t)(F + PC), packed)) != CQ_OK) return rc;
+      CQ_HIP(c, hipMemcpyAsync(o, packed, (F + PC) * 32, hipMemcpyDeviceToHost, c->stream));
+      CQ_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    o += (F + PC) * 32;
+  } else {
+    memcpy(o, cm.data(), (F + PC) * sizeof(G1Affine));
+    o += (F + PC) * sizeof(G1Affine);
+  }
   const size_t sel_bytes = (size_t)num_selectors * ((n + 7) / 8);
   if (sel_bytes) memcpy(o, selector_bits, sel_bytes);
   o += sel_bytes;
   auto write_poly = [&](const Fr* src, size_t len) -> int {
     put_be32(o, (uint32_t)len);
+    if (processed) {  // (stream order: the next conversion waits for this copy)
+      int r2 = fr_to_repr(c, src, (uint32_t)len, (uint8_t*)stage);
+      if (r2 != CQ_OK) return r2;
+      src = (const Fr*)stage;
+    }
     CQ_HIP(c, hipMemcpyAsync(o, src, len * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
     o += len * sizeof(Fr);
     return CQ_OK;
@@ -692,6 +769,16 @@ int cq_pk_write_raw(cq_pk* pk, const uint8_t* selector_bits, uint32_t num_select
   CQ_HIP(c, hipStreamSynchronize(c->stream));
   *written = (size_t)(o - buf);
   return *written == total ? CQ_OK : c->fail(CQ_ERR_INTERNAL, "pk: serialized size mismatch");
+}
+
+int cq_pk_write_raw(cq_pk* pk, const uint8_t* selector_bits, uint32_t num_selectors, uint8_t* buf, size_t cap, size_t* written) {
+  return pk_write_impl(pk, false, selector_bits, num_selectors, buf, cap, written);
+}
+
+int cq_pk_write(cq_pk* pk, int format, const uint8_t* selector_bits, uint32_t num_selectors, uint8_t* buf, size_t cap, size_t* written) {
+  if (format != CQ_SERDE_PROCESSED && format != CQ_SERDE_RAW_BYTES && format != CQ_SERDE_RAW_BYTES_UNCHECKED)
+    return pk ? pk->ctx->fail(CQ_ERR_ARG, "pk: unknown serde format") : CQ_ERR_ARG;
+  return pk_write_impl(pk, format == CQ_SERDE_PROCESSED, selector_bits, num_selectors, buf, cap, written);
 }
 
 int cq_pk_set_opener(cq_pk* pk, int opener) {

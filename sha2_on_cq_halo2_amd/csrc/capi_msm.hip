@@ -2,12 +2,14 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 #include "ctx.hpp"
 #include "msm.hpp"
 #include "g1fft.hpp"
 #include "setup.hpp"
 #include "cq.hpp"
+#include "serde.hpp"
 
 using namespace cq;
 
@@ -450,6 +452,84 @@ int cq_params_read_raw(cq_ctx* c, const uint8_t* buf, size_t len, int checked, c
     if ((rc2 = msm_register_tables(c, p->g_lagrange, p->n)) != CQ_OK) return rc2;
   }
   *out = guard.release();
+  return CQ_OK;
+}
+
+/* ParamsKZG::read_custom with SerdeFormat::Processed (kzg/commitment.rs:383-459):
+ * k:u32 LE | n x 32 B g | n x 32 B g_lagrange | [2 x 64 B compressed g2, s_g2: ignored] -- the compressed bytes are staged
+ * in the entry scratch and decompressed straight into the resident arrays */
+static int params_read_processed(cq_ctx* c, const uint8_t* buf, size_t len, cq_params** out) {
+  if (!c || !buf || !out || len < 4) return CQ_ERR_ARG;
+  uint32_t k;
+  memcpy(&k, buf, 4);
+  if (k > FR_S) return c->fail(CQ_ERR_ARG, "params: k out of range");
+  const size_t n = (size_t)1 << k, half = n * 32;
+  if (len < 4 + 2 * half) return c->fail(CQ_ERR_ARG, "params: buffer too short");
+  CQ_HIP(c, hipSetDevice(c->device));
+  *out = nullptr;
+  cq_params* p = params_new(c, k);
+  ParamsGuard guard(p);
+  if (hipMalloc(&p->g, n * sizeof(G1Affine)) != hipSuccess || hipMalloc(&p->g_lagrange, n * sizeof(G1Affine)) != hipSuccess)
+    return c->fail(CQ_ERR_HIP, "hipMalloc(params)");
+  void *stage, *cells;
+  int rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryB, 2 * half, &stage)) != CQ_OK) return rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryA, 64, &cells)) != CQ_OK) return rc;
+  uint32_t* count_dev = (uint32_t*)cells;  // [0], [1]: g, g_lagrange
+  uint32_t* first_dev = count_dev + 2;
+  if ((rc = serde_verdict_reset(c, count_dev, first_dev, 2)) != CQ_OK) return rc;
+  CQ_HIP(c, hipMemcpyAsync(stage, buf + 4, 2 * half, hipMemcpyHostToDevice, c->stream));
+  if ((rc = g1_decompress(c, (const uint8_t*)stage, (uint32_t)n, p->g, count_dev, first_dev)) != CQ_OK) return rc;
+  if ((rc = g1_decompress(c, (const uint8_t*)stage + half, (uint32_t)n, p->g_lagrange, count_dev + 1, first_dev + 1)) != CQ_OK) return rc;
+  uint32_t verdict[4] = {0, 0, 0, 0};
+  CQ_HIP(c, hipMemcpyAsync(verdict, cells, sizeof(verdict), hipMemcpyDeviceToHost, c->stream));
+  CQ_HIP(c, hipStreamSynchronize(c->stream));
+  for (int a = 0; a < 2; a++)
+    if (verdict[a])
+      return c->fail(CQ_ERR_ARG, std::string("params: invalid point encoding at ") + (a ? "g_lagrange[" : "g[") + std::to_string(verdict[2 + a]) +
+                                     "] (" + std::to_string(verdict[a]) + " invalid in that array)");
+  if (c->msm_precompute) {
+    if ((rc = msm_register_tables(c, p->g, p->n)) != CQ_OK) return rc;
+    if ((rc = msm_register_tables(c, p->g_lagrange, p->n)) != CQ_OK) return rc;
+  }
+  *out = guard.release();
+  return CQ_OK;
+}
+
+int cq_params_read(cq_ctx* c, const uint8_t* buf, size_t len, int format, cq_params** out) {
+  switch (format) {
+    case CQ_SERDE_PROCESSED: return params_read_processed(c, buf, len, out);
+    case CQ_SERDE_RAW_BYTES: return cq_params_read_raw(c, buf, len, 1, out);
+    case CQ_SERDE_RAW_BYTES_UNCHECKED: return cq_params_read_raw(c, buf, len, 0, out);
+  }
+  return c ? c->fail(CQ_ERR_ARG, "params: unknown serde format") : CQ_ERR_ARG;
+}
+
+size_t cq_params_serialized_size(const cq_params* p, int format) {
+  if (!p) return 0;
+  if (format == CQ_SERDE_PROCESSED) return 4 + 2 * p->n * 32;
+  if (format == CQ_SERDE_RAW_BYTES || format == CQ_SERDE_RAW_BYTES_UNCHECKED) return 4 + 2 * p->n * sizeof(G1Affine);
+  return 0;
+}
+
+/* G1 part of ParamsKZG::write_custom (commitment.rs:366-379); Processed: points compressed on the GPU into the entry scratch */
+int cq_params_write(cq_params* p, int format, uint8_t* buf, size_t cap, size_t* written) {
+  if (!p || !buf || !written) return CQ_ERR_ARG;
+  cq_ctx* c = p->ctx;
+  if (format == CQ_SERDE_RAW_BYTES || format == CQ_SERDE_RAW_BYTES_UNCHECKED) return cq_params_write_raw(p, buf, cap, written);
+  if (format != CQ_SERDE_PROCESSED) return c->fail(CQ_ERR_ARG, "params: unknown serde format");
+  const size_t half = p->n * 32;
+  if (cap < 4 + 2 * half) return c->fail(CQ_ERR_ARG, "params: output buffer too small");
+  CQ_HIP(c, hipSetDevice(c->device));
+  void* stage;
+  int rc;
+  if ((rc = c->ensure_scratch(Scratch::EntryB, 2 * half, &stage)) != CQ_OK) return rc;
+  if ((rc = g1_compress(c, p->g, (uint32_t)p->n, (uint8_t*)stage)) != CQ_OK) return rc;
+  if ((rc = g1_compress(c, p->g_lagrange, (uint32_t)p->n, (uint8_t*)stage + half)) != CQ_OK) return rc;
+  memcpy(buf, &p->k, 4);
+  CQ_HIP(c, hipMemcpyAsync(buf + 4, stage, 2 * half, hipMemcpyDeviceToHost, c->stream));
+  CQ_HIP(c, hipStreamSynchronize(c->stream));
+  *written = 4 + 2 * half;
   return CQ_OK;
 }
 
