@@ -35,7 +35,7 @@ static __device__ __forceinline__ void st(Fr* p, const Fr& r) {
 // of the tile -- so a wave's load is 64 consecutive elements (2 KB) instead of 64 runs 256 bytes apart, which the
 // address path served at a fraction of the rate (k = 18: 122 -> ~50 us for the 19 polynomials of a proof) -- runs Horner
 // over them with x^256, multiplies by x^t (composed from x^(2^i) by the bits of t) and the 256 lane values are then just
-// ADDED in an 8-level LDS tree.  p(x) = S(x^2048) over the block sums S, so the host applies the kernel again until one
+// ADDED in an 8-level LDS tree.  p(x) = S(x^EVAL_TILE) over the block sums S, so the host applies the kernel again until one
 // value per polynomial is left (2 levels at n = 2^18).  blockIdx.y selects the polynomial: all evaluations of a proof at
 // one point go in one launch.
 __global__ __launch_bounds__(256) void block_eval_kernel(EvalBatchArgs args, uint32_t level_stride_in,

@@ -2,6 +2,7 @@
 the permutation argument over several product sets, optionally next to a static lookup).  Proof BYTES must
 equal the oracle's for the same key, witness, public inputs and RNG stream; larger proofs (several scan
 tiles, extended domain 4n) are checked with the acceptance verifier."""
+import functools
 import os
 
 import numpy as np
@@ -70,6 +71,29 @@ def test_plonk_proof_bytes_match_oracle_k11(ctx, opener):
     assert proof == tr.proof
 
 
+@functools.lru_cache(maxsize=1)
+def _legacy_env_k11(flags):
+    """Oracle key and SRS of one k = 11 fixture, shared by the cases that differ in the opener only (never modified)."""
+    return oracle_env(11, fast=True, **{f: True for f in flags})
+
+
+@pytest.mark.parametrize("kw,opener", [(dict(plookup=True), "gwc"), (dict(plookup=True, with_lookup=True, degree5=True), "gwc"),
+                                       (dict(plookup=True, with_lookup=True, degree5=True), "shplonk")],
+                         ids=["plookup-gwc", "plookup+cq+deg5-gwc", "plookup+cq+deg5-shplonk"])
+def test_plonk_legacy_lookup_proof_bytes_match_oracle_k11(ctx, kw, opener):
+    """The legacy lookup beyond one scan tile, byte for byte (n = 2048): its grand product is scanned IN PLACE over two
+    tiles -- the smallest size at which that scan applies a tile prefix other than one -- and the permute stage sorts
+    exactly one LDS tile instead of one small block; alone, and next to a static lookup and a degree-5 gate."""
+    k = 11
+    fx = _legacy_env_k11(tuple(sorted(kw)))
+    gpk, _ = _backend_pk(ctx, fx, k, fx["s"], b0=fx["pk"].b0_g1_bound if fx["tables"] else None)
+    gpk.set_opener(opener)
+    tr = CP.create_proof(fx["params"], fx["pk"], fx["advice"], B.Xoshiro256ss(37), msm=c_msm, instances=fx["instances"], opener=opener)
+    proof = gpk.create_proof(_advice_cols(fx, 1 << k), seed=37, instances=[B.to_mont_limbs(i) for i in fx["instances"]])
+    assert len(proof) == gpk.proof_size == len(tr.proof)
+    assert proof == tr.proof
+
+
 def test_plonk_api_shape_proof_bytes(ctx):
     """halo2_proofs/tests/plonk_api.rs `MyCircuit`, legacy lookup included: 6 chained product sets at degree 4."""
     k = 5
@@ -109,11 +133,13 @@ def test_plonk_instance_too_large_and_missing(ctx):
         gpk.create_proof(cols, seed=1)
 
 
-@pytest.mark.parametrize("k,kw", [(11, dict(degree5=True)), (12, dict(with_lookup=True)), (10, dict(lookup_expr=True))],
-                         ids=["k11-deg5", "k12-lookup", "k10-lookup-expr"])
+@pytest.mark.parametrize("k,kw", [(11, dict(degree5=True)), (12, dict(with_lookup=True)), (10, dict(lookup_expr=True)),
+                                  (12, dict(plookup=True))],
+                         ids=["k11-deg5", "k12-lookup", "k10-lookup-expr", "k12-plookup"])
 def test_plonk_large_proof_verifies(ctx, k, kw):
     """Beyond the sizes the Python prover reaches: several scan tiles per product set, batched multi-point
-    openings; the proof must satisfy every verifier equation, and a broken copy constraint must not."""
+    openings; the proof must satisfy every verifier equation, and a broken copy constraint must not.  k12-plookup:
+    the legacy lookup's in-place product scan over 4 tiles, after a sort with one merge phase beyond the LDS tile."""
     n = 1 << k
     fx = chain_circuit(k, **kw)
     s = B.fr_random(B.Xoshiro256ss(k))
@@ -196,6 +222,27 @@ def test_legacy_lookup_failure_is_an_error(ctx):
     assert e.value.code == -4
     with pytest.raises(ValueError):
         CP.create_proof(fx["params"], fx["pk"], adv, B.Xoshiro256ss(1), instances=fx["instances"])
+
+
+def test_legacy_lookup_failure_is_an_error_k12(ctx):
+    """The same through the streaming sort (n = 4096: one merge phase beyond the LDS tile), the offending input in the
+    upper half of the rows."""
+    from sha2_on_cq_halo2_amd import CqError
+
+    k = 12
+    n = 1 << k
+    fx = chain_circuit(k, plookup=True)
+    gpk, _ = _backend_pk(ctx, fx, k, B.fr_random(B.Xoshiro256ss(k)))
+    inst = [B.to_mont_limbs(i) for i in fx["instances"]]
+    adv = [list(c) for c in fx["advice"]]
+    row = 3000
+    assert fx["fixed"][-3][row] == 1 and adv[3][row] != 4  # a selected row: the lookup reads (p, 2 p + 1) there
+    adv[3][row] = 4  # (4, 9) is not in the table
+    cols = [B.to_mont_limbs(list(c) + [0] * (n - len(c))) for c in adv]
+    with pytest.raises(CqError) as e:
+        gpk.create_proof(cols, seed=1, instances=inst)
+    assert e.value.code == -4
+    assert len(gpk.create_proof(_advice_cols(fx, n), seed=1, instances=inst)) == gpk.proof_size  # the key itself is fine
 
 
 @pytest.mark.parametrize("k,usable,distinct", [(3, 2, 2), (5, 26, 7), (10, 1018, 50), (11, 2042, 2042), (12, 4090, 300),

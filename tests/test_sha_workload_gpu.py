@@ -167,23 +167,25 @@ def test_large_k_proof_is_accepted_and_deterministic(ctx, k):
         wl.close()
 
 
-@pytest.mark.parametrize("k", [10, 14])
-def test_sha_plonk_workload_proof_is_accepted(ctx, k):
-    """SHA-shaped circuit with a custom gate (rotation), a selector and copy constraints around the lookups
-    (`ShaPlonkWorkload`): the proof satisfies the restated verifier; a broken copy does not."""
+def _sha_plonk_verifier(wl, seed, legacy=False):
+    """`ShaPlonkWorkload`'s constraint system restated for the oracle's verifier (gates "recompose" and "shift", the
+    permutation over (w, w2), the static lookups; legacy: the fixed table column and the lookup of advice column 0 in
+    it, registered after the gates as sha_circuit.py does) -> verify(proof)."""
     from oracle import plonk as PL
-    from sha2_on_cq_halo2_amd.sha_circuit import ShaPlonkWorkload
 
-    seed = 0x5348413243515F
-    wl = ShaPlonkWorkload(ctx, k, seed=seed)
+    k = wl.k
     s = (seed * 0x9E3779B97F4A7C15 + 12345) % B.R_MOD
     N = wl.cfg.size
     A = 2 * wl.pairs
     w, w2 = A, A + 1
     gates = [PL.mul(PL.fix(0), PL.sub(PL.add(PL.adv(0), PL.scale(PL.adv(2), 1 << 16)), PL.adv(w))),
              PL.mul(PL.fix(0), PL.sub(PL.adv(w2), PL.adv(w, 1)))]
-    circ = CP.CqCircuit(k, A + 2, [[(2 * p, "dense"), (2 * p + 1, "spread")] for p in range(wl.pairs)], 1, 0, gates,
-                        [(PL.ADVICE, w), (PL.ADVICE, w2)])
+    lookups = [[(2 * p, "dense"), (2 * p + 1, "spread")] for p in range(wl.pairs)]
+    circ = CP.CqCircuit(k, A + 2, lookups, 1, 0, gates, [(PL.ADVICE, w), (PL.ADVICE, w2)])
+    if legacy:
+        queries = {PL.ADVICE: circ.advice_queries(), PL.FIXED: [(0, 0), (1, 0)], PL.INSTANCE: []}
+        circ = CP.CqCircuit(k, A + 2, lookups, 2, 0, gates, [(PL.ADVICE, w), (PL.ADVICE, w2)], queries,
+                            [([PL.adv(0)], [PL.fix(1)])])
     assert circ.advice_queries() == wl.cs.advice_queries and circ.fixed_queries() == wl.cs.fixed_queries
     tv = {"dense": list(range(N)), "spread": [_spread(i) for i in range(N)]}
     fcm, pcm = wl.pk.vk_commitments()
@@ -192,11 +194,66 @@ def test_sha_plonk_workload_proof_is_accepted(ctx, k):
         return CV.verify_proof(pr, circ, 0xC0FFEE + k, s, tv, N, 1 << k, fixed_commitments=B.points_from_mont_limbs(fcm),
                                perm_commitments=B.points_from_mont_limbs(pcm))
 
+    return verify
+
+
+@pytest.mark.parametrize("k", [10, 14])
+def test_sha_plonk_workload_proof_is_accepted(ctx, k):
+    """SHA-shaped circuit with a custom gate (rotation), a selector and copy constraints around the lookups
+    (`ShaPlonkWorkload`): the proof satisfies the restated verifier; a broken copy does not."""
+    from sha2_on_cq_halo2_amd.sha_circuit import ShaPlonkWorkload
+
+    seed = 0x5348413243515F
+    wl = ShaPlonkWorkload(ctx, k, seed=seed)
+    verify = _sha_plonk_verifier(wl, seed)
     proof = wl.prove(seed=4)
     assert len(proof) == wl.pk.proof_size and verify(proof)
     # w2[7] no longer equals w[8]: the `shift` gate and the copy constraint both fail
     n = 1 << k
+    w2 = 2 * wl.pairs + 1
     col = wl.cols[w2].download((n, 4))
     col[7] = B.to_mont_limbs([12345])[0]
     wl.cols[w2].upload(col)
     assert not verify(wl.prove(seed=4))
+
+
+@pytest.mark.parametrize("k,legacy", [(19, False), (19, True), (20, False)], ids=["k19-static", "k19-static+legacy", "k20-static"])
+def test_sha_plonk_workload_reaches_the_later_spine_passes(ctx, k, legacy):
+    """k = 19 is the smallest size at which the grand products' scan has more than 256 tiles (512), so its spine carries
+    a running product from one pass of 256 tile products into the next -- for the permutation's two product sets and,
+    with the legacy lookup, for the in-place scan of its product as well.  With two passes the carry is used once, as
+    the first pass's total; k = 20 (1024 tiles, four passes) is the smallest size at which a carry that is not
+    accumulated over the passes (`carry = total`) gives another result than the right one, which two passes cannot
+    tell apart.  A wrong or dropped carry makes z wrong from row 2^18 on, the quotient then does not divide, and the
+    verifier rejects with overwhelming probability.  Byte parity is not available at these sizes: the Python oracle
+    prover does not reach k = 19, and the C restatement proves CQ circuits only.  So: the witness checker -- an
+    independent statement that the witness is valid -- reports nothing, the proof is accepted by the restated verifier
+    and identical for identical (key, witness, seed); and a copy broken in the last 2^18 rows, which only the last pass
+    reaches, is named by the checker and makes the verifier reject."""
+    from sha2_on_cq_halo2_amd.api import fr_to_mont
+    from sha2_on_cq_halo2_amd.sha_circuit import ShaPlonkWorkload
+
+    seed = 0x5348413243515F
+    cls = type("ShaPlonkLegacy", (ShaPlonkWorkload,), dict(legacy_lookup=True)) if legacy else ShaPlonkWorkload
+    wl = cls(ctx, k, seed=seed)
+    try:
+        ptrs = [c.ptr for c in wl.cols]
+        assert wl.pk.check_witness(ptrs) == (0, [])
+        wl.pk.assert_satisfied(ptrs)
+        verify = _sha_plonk_verifier(wl, seed, legacy)
+        proof = wl.prove(seed=4)
+        assert len(proof) == wl.pk.proof_size
+        assert verify(proof)
+        assert wl.prove(seed=4) == proof
+        # w2[r] no longer equals w[r + 1]: the `shift` gate fails on row r, and so does the copy (w2, r) == (w, r + 1)
+        r = (1 << k) - (1 << 18) + 1024 + 77
+        assert (1 << 18) + 1024 <= r and r + 1 < wl.rows
+        w2 = 2 * wl.pairs + 1
+        v = np.ascontiguousarray(fr_to_mont(12345), dtype=np.uint64)
+        ctx._chk(ctx.lib.cq_dev_upload(ctx.h, wl.cols[w2].ptr + 32 * r, v.ctypes.data, 32))
+        total, fails = wl.pk.check_witness(ptrs)
+        print("check_witness:", total, fails)
+        assert (total, [tuple(f) for f in fails]) == (3, [(1, 1, r, 0), (5, 0, r + 1, 0), (5, 1, r, 0)])
+        assert not verify(wl.prove(seed=4))
+    finally:
+        wl.close()
