@@ -226,7 +226,7 @@ int cq_fixed_base_mul_dev(cq_ctx* ctx, const uint64_t* scalars_dev, size_t n, ui
 /* ParamsKZG::read_custom / write_custom in the RawBytes layouts (commitment.rs:366-459):
  * k:u32 LE | n x 64 B g | n x 64 B g_lagrange | 128 B g2 | 128 B s_g2.  read: `checked` != 0 validates
  * every point (SerdeFormat::RawBytes), 0 = RawBytesUnchecked; the G2 tail is ignored.  write: emits the
- * 4 + 128 n byte G1 part. */
+ * 4 + 128 n byte G1 part.  cq_params_read_full / cq_params_write_full handle the complete stream. */
 int cq_params_read_raw(cq_ctx* ctx, const uint8_t* buf, size_t len, int checked, cq_params** out);
 int cq_params_write_raw(cq_params* params, uint8_t* buf, size_t cap, size_t* written);
 /* SerdeFormat (helpers.rs:8-20), the `format` argument of the readers and writers below. */
@@ -253,11 +253,45 @@ int cq_fr_to_repr_dev(cq_ctx* ctx, const uint64_t* in_dev, size_t n, uint8_t* by
  * read: the compressed bytes are staged in device scratch and decompressed on the GPU straight into the resident arrays
  * (the reference decompresses in parallel for the same reason, commitment.rs:394-426); an invalid point is CQ_ERR_ARG and
  * cq_last_error names the array and the index.  As in the raw reader the G2 tail (2 x 64 B compressed here) is ignored on
- * read and not emitted on write: the caller appends its own.  cq_params_serialized_size: the bytes cq_params_write emits
- * (4 + 64 n processed, 4 + 128 n raw; 0 for an unknown format). */
+ * read and not emitted on write, and the params hold none afterwards: cq_params_read_full / cq_params_write_full below are
+ * the forms with the tail.  cq_params_serialized_size: the bytes cq_params_write emits (4 + 64 n processed, 4 + 128 n raw;
+ * 0 for an unknown format). */
 int cq_params_read(cq_ctx* ctx, const uint8_t* buf, size_t len, int format, cq_params** out);
 int cq_params_write(cq_params* params, int format, uint8_t* buf, size_t cap, size_t* written);
 size_t cq_params_serialized_size(const cq_params* params, int format);
+/* `GroupEncoding::from_bytes` for G2Affine (derive/curve.rs:603-627, instantiated at bn256/curve.rs:37-48 with compressed
+ * size 64) for a device array: n x 64 B compressed points -> n affine points in the raw layout (x.c0 | x.c1 | y.c0 | y.c1,
+ * 16 Montgomery limbs, R = 2^256: `SerdeObject`, derive/curve.rs:649-700).  The encoding is `Fq2::to_bytes` of x
+ * (bn256/fq2.rs:134-155: canonical little-endian c0, then c1) with bit 7 of byte 63 set to the parity of the canonical
+ * y.c0; 64 zero bytes are the identity.  y = (x^3 + 3/(9+i)).sqrt(), negated when the sign bit differs from the parity
+ * of the root's canonical c0 -- `Fq2::sqrt` is Algorithm 9 of eprint 2012/685 (fq2.rs:344-398); the GPU computes the
+ * same decoded y with two exponentiations in Fq (csrc/sqrt2_29.hpp), including the one case where the algorithm's choice of
+ * root shows: a root with c0 == 0 has parity 0 whichever it is, so from_bytes(to_bytes(P)) is P or -P for such a point
+ * depending on the algorithm alone, and that is reproduced.  No subgroup check (the reference has none).  Invalid: c0 >= q,
+ * c1 >= q after the sign bit is masked, or x^3 + b' not a square -- which includes x = 0 with the sign bit, b' being a
+ * non-square.  Contract otherwise as cq_g1_decompress_dev: CQ_ERR_ARG, *first_bad (may be NULL) = the LOWEST invalid index,
+ * cq_last_error names it and the number of invalid points; 16-byte aligned buffers; returns after the stream has drained;
+ * n == 0 is CQ_OK. */
+int cq_g2_decompress_dev(cq_ctx* ctx, const uint8_t* bytes_dev, size_t n, uint64_t* out_affine_dev, size_t* first_bad);
+/* `GroupEncoding::to_bytes` for G2Affine (derive/curve.rs:635-646): n raw affine points -> n x 64 B, asynchronous. */
+int cq_g2_compress_dev(cq_ctx* ctx, const uint64_t* affine_dev, size_t n, uint8_t* bytes_dev);
+/* ParamsKZG's g2 and s_g2 (commitment.rs:31-39), 16 limbs each in the raw layout, kept in host memory.
+ * cq_params_setup_from_toxic_waste stores generator and [s]_2 (commitment.rs:265-266), cq_params_read_full what the stream
+ * holds, cq_params_downsize carries them over (commitment.rs:480-492); cq_params_create, cq_params_read and
+ * cq_params_read_raw produce params without them.  cq_params_set_g2 stores the caller's two points as given (no check);
+ * cq_params_g2 returns CQ_ERR_ARG when the params hold none. */
+int cq_params_set_g2(cq_params* params, const uint64_t g2[16], const uint64_t s_g2[16]);
+int cq_params_g2(const cq_params* params, uint64_t g2[16], uint64_t s_g2[16]);
+/* The complete stream of ParamsKZG::read_custom / write_custom (commitment.rs:366-459) in any CQ_SERDE_* format:
+ *   k:u32 LE | n g | n g_lagrange | g2 | s_g2        4 + 64 n + 128 bytes processed, 4 + 128 n + 256 raw
+ * read_full: the G1 part as cq_params_read; then the two G2 points are decompressed on the GPU (CQ_SERDE_PROCESSED),
+ * validated there -- coordinates below q, on the twist or the identity -- (CQ_SERDE_RAW_BYTES) or copied
+ * (CQ_SERDE_RAW_BYTES_UNCHECKED).  An invalid tail point is CQ_ERR_ARG and cq_last_error names `g2` or `s_g2`; so is a
+ * buffer shorter than the full size.  write_full: the bytes of cq_params_write followed by the tail; CQ_ERR_ARG when the
+ * params hold no tail.  cq_params_serialized_size_full: the bytes write_full emits (0 for NULL or an unknown format). */
+int cq_params_read_full(cq_ctx* ctx, const uint8_t* buf, size_t len, int format, cq_params** out);
+int cq_params_write_full(cq_params* params, int format, uint8_t* buf, size_t cap, size_t* written);
+size_t cq_params_serialized_size_full(const cq_params* params, int format);
 /* g_to_lagrange(g, k) (arithmetic.rs:277-301): the Lagrange-basis SRS from the monomial one by an inverse FFT
  * over G1 (device arrays of 2^k affine points). */
 int cq_g_to_lagrange_dev(cq_ctx* ctx, const uint64_t* g_dev, uint32_t k, uint64_t* g_lagrange_dev);
@@ -312,6 +346,16 @@ int cq_g2_srs_download(cq_g2_srs* srs, uint64_t* points);
 size_t cq_g2_srs_len(const cq_g2_srs* srs);
 const uint64_t* cq_g2_srs_dev(const cq_g2_srs* srs);
 void cq_g2_srs_destroy(cq_g2_srs* srs);
+/* The G2 powers as a byte stream.  TableSRS has no serialisation in the reference; the stream is what
+ * `for p in srs.g2() { p.write(w, format) }` produces (`SerdeCurveAffine::write`, helpers.rs): `count` points back to back,
+ * no header, 64 B each processed / 128 B raw; the count comes from `len`, which must be a multiple of the point size.
+ * read: the bytes are staged in device scratch (in chunks) and converted on the GPU -- CQ_SERDE_PROCESSED decompresses as
+ * cq_g2_decompress_dev, CQ_SERDE_RAW_BYTES checks every point as cq_g2_srs_create(checked) does but on the GPU,
+ * CQ_SERDE_RAW_BYTES_UNCHECKED is one copy.  An invalid point is CQ_ERR_ARG and cq_last_error names its index in the whole
+ * array.  write: CQ_ERR_ARG when `cap` is too small.  cq_g2_srs_serialized_size: 0 for NULL or an unknown format. */
+int cq_g2_srs_read(cq_ctx* ctx, const uint8_t* buf, size_t len, int format, cq_g2_srs** out);
+int cq_g2_srs_write(cq_g2_srs* srs, int format, uint8_t* buf, size_t cap, size_t* written);
+size_t cq_g2_srs_serialized_size(const cq_g2_srs* srs, int format);
 /* StaticTableValues::commit(srs_g2, srs_g1_len, circuit_n)  static_lookup.rs:128-157: the StaticCommittedTable that
  * keygen_vk stores in vk.static_table_mapping (plonk/keygen.rs:261-265), as three affine G2 points (16 limbs each):
  *   t          = best_multiexp(iNTT(values in ascending canonical order), srs_g2[..N])  -- the reference interpolates
@@ -671,6 +715,7 @@ void cq_opaque_rng_fill(void* state, uint64_t* dst, size_t count);
 #define CQ_PROF_MSM_ENTRIES 3    /* no timing: `calls` = (point, non-zero digit) pairs = mixed additions executed by
                                   * msm_accumulate_kernel since the last read */
 #define CQ_PROF_G1_DECOMPRESS 4  /* g1_decompress_kernel: point decompression of the Processed readers */
+#define CQ_PROF_G2_DECOMPRESS 5  /* g2_decompress_kernel: G2 point decompression (params tail, G2 SRS) */
 int cq_profile_enable(cq_ctx* ctx, int on);
 int cq_profile_read(cq_ctx* ctx, int id, double* total_ms, uint64_t* calls);
 

@@ -200,7 +200,8 @@ Context.set_msm_window = _ctx_set_msm_window
 
 
 class ParamsKZG:
-    """`ParamsKZG<Bn256>` G1 part (poly/kzg/commitment.rs:31-39), SRS resident on the GPU."""
+    """`ParamsKZG<Bn256>` (poly/kzg/commitment.rs:31-39): the G1 SRS resident on the GPU; g2 / s_g2 when the params were set up
+    from toxic waste, read with `read_full` or given them with `set_g2`."""
 
     @classmethod
     def setup_from_toxic_waste(cls, ctx: Context, k: int, s: np.ndarray) -> "ParamsKZG":
@@ -272,6 +273,7 @@ PROF_MSM_ACCUMULATE = 1
 PROF_NTT_PASS = 2
 PROF_MSM_ENTRIES = 3
 PROF_G1_DECOMPRESS = 4
+PROF_G2_DECOMPRESS = 5
 
 
 def _ctx_profile_enable(self, on: bool = True):
@@ -1086,6 +1088,77 @@ ParamsKZG.read = classmethod(_params_read)
 ParamsKZG.write = _params_write
 
 
+def _params_read_full(cls, ctx: Context, data: bytes, format: int = SERDE_PROCESSED) -> "ParamsKZG":
+    """`ParamsKZG::read_custom(reader, format)` (kzg/commitment.rs:383-459), the complete stream: g2 and s_g2 are decompressed
+    (Processed) or validated (RawBytes) on the GPU and kept."""
+    self = cls.__new__(cls)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    h = C.c_void_p()
+    ctx._chk(ctx.lib.cq_params_read_full(ctx.h, buf.ctypes.data, buf.shape[0], format, C.byref(h)))
+    self.ctx = ctx
+    self.k = int.from_bytes(data[:4], "little")
+    self.n = 1 << self.k
+    self.h = h
+    ctx._children.add(self)
+    return self
+
+
+def _params_write_full(self, format: int = SERDE_PROCESSED) -> bytes:
+    """`ParamsKZG::write_custom(writer, format)` (kzg/commitment.rs:366-379), the complete stream; raises when no g2 / s_g2
+    is held."""
+    size = self.ctx.lib.cq_params_serialized_size_full(self.h, format)
+    buf = np.zeros(max(size, 1), dtype=np.uint8)
+    w = C.c_size_t()
+    self.ctx._chk(self.ctx.lib.cq_params_write_full(self.h, format, buf.ctypes.data, size, C.byref(w)))
+    return buf[: w.value].tobytes()
+
+
+def _params_tail(self):
+    g2, s_g2 = np.zeros(16, dtype=np.uint64), np.zeros(16, dtype=np.uint64)
+    self.ctx._chk(self.ctx.lib.cq_params_g2(self.h, g2.ctypes.data, s_g2.ctypes.data))
+    return g2, s_g2
+
+
+def _params_set_g2(self, g2: np.ndarray, s_g2: np.ndarray):
+    """stores `g2` and `s_g2` (uint64[16] each, raw layout) as given"""
+    a = np.ascontiguousarray(g2, dtype=np.uint64).reshape(16)
+    b = np.ascontiguousarray(s_g2, dtype=np.uint64).reshape(16)
+    self.ctx._chk(self.ctx.lib.cq_params_set_g2(self.h, a.ctypes.data, b.ctypes.data))
+
+
+ParamsKZG.read_full = classmethod(_params_read_full)
+ParamsKZG.write_full = _params_write_full
+ParamsKZG.set_g2 = _params_set_g2
+# `ParamsKZG::g2()` / `s_g2()` (commitment.rs:351-358) as uint64[16]; CqError when the params hold none
+ParamsKZG.g2 = property(lambda self: _params_tail(self)[0])
+ParamsKZG.s_g2 = property(lambda self: _params_tail(self)[1])
+
+
+def _g2srs_read(cls, ctx: Context, data: bytes, format: int = SERDE_PROCESSED) -> "G2Srs":
+    """The G2 powers from the bytes `for p in srs.g2() { p.write(w, format) }` produces: points back to back, no header.
+    Processed points are decompressed, RawBytes points validated, on the GPU; an invalid point is named by its index."""
+    self = cls.__new__(cls)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    h = C.c_void_p()
+    ctx._chk(ctx.lib.cq_g2_srs_read(ctx.h, buf.ctypes.data if buf.shape[0] else None, buf.shape[0], format, C.byref(h)))
+    self.ctx, self.h = ctx, h
+    self.count = ctx.lib.cq_g2_srs_len(h)
+    ctx._children.add(self)
+    return self
+
+
+def _g2srs_write(self, format: int = SERDE_PROCESSED) -> bytes:
+    size = self.ctx.lib.cq_g2_srs_serialized_size(self.h, format)
+    buf = np.zeros(max(size, 1), dtype=np.uint8)
+    w = C.c_size_t()
+    self.ctx._chk(self.ctx.lib.cq_g2_srs_write(self.h, format, buf.ctypes.data, size, C.byref(w)))
+    return buf[: w.value].tobytes()
+
+
+G2Srs.read = classmethod(_g2srs_read)
+G2Srs.write = _g2srs_write
+
+
 def _ctx_checked_conversion(self, fn, src: DevBuf, n: int, dst: DevBuf):
     bad = C.c_size_t()
     rc = fn(self.h, src.ptr, n, dst.ptr, C.byref(bad))
@@ -1117,6 +1190,19 @@ def _ctx_fr_to_repr(self, src: DevBuf, n: int, dst: DevBuf):
     self._chk(self.lib.cq_fr_to_repr_dev(self.h, src.ptr, n, dst.ptr))
 
 
+def _ctx_g2_decompress(self, src: DevBuf, n: int, dst: DevBuf):
+    """`GroupEncoding::from_bytes` for G2Affine (derive/curve.rs:603-627) over a device array: n x 64 B -> n raw affine points
+    (uint64[16] each).  An invalid encoding raises CqError whose `first_bad` is the lowest invalid index."""
+    _ctx_checked_conversion(self, self.lib.cq_g2_decompress_dev, src, n, dst)
+
+
+def _ctx_g2_compress(self, src: DevBuf, n: int, dst: DevBuf):
+    """`GroupEncoding::to_bytes` for G2Affine (derive/curve.rs:635-646) over a device array: n raw affine points -> n x 64 B."""
+    self._chk(self.lib.cq_g2_compress_dev(self.h, src.ptr, n, dst.ptr))
+
+
+Context.g2_decompress = _ctx_g2_decompress
+Context.g2_compress = _ctx_g2_compress
 Context.g1_decompress = _ctx_g1_decompress
 Context.g1_compress = _ctx_g1_compress
 Context.fr_from_repr = _ctx_fr_from_repr

@@ -1,12 +1,15 @@
 // C ABI: G2 multiexp, the G2 SRS of the table setup and StaticTableValues::commit (the verifying key's
 // StaticCommittedTable, plonk/static_lookup.rs:128-157).
+#include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 #include "cq.hpp"
 #include "ctx.hpp"
 #include "msm_g2.hpp"
 #include "plonk.hpp"
 #include "poly.hpp"
+#include "serde.hpp"
 
 using namespace cq;
 
@@ -167,6 +170,97 @@ int cq_g2_srs_download(cq_g2_srs* s, uint64_t* points) {
 }
 
 size_t cq_g2_srs_len(const cq_g2_srs* s) { return s ? s->count : 0; }
+
+// ---- the G2 SRS as a byte stream: `count` points back to back, `SerdeCurveAffine::write` each (helpers.rs) ------------------
+static size_t g2_srs_point_size(int format) {
+  if (format == CQ_SERDE_PROCESSED) return 64;
+  if (format == CQ_SERDE_RAW_BYTES || format == CQ_SERDE_RAW_BYTES_UNCHECKED) return sizeof(G2Affine);
+  return 0;
+}
+// points converted per staging of compressed bytes: 64 MiB of entry scratch at most
+static constexpr size_t G2_SRS_CHUNK = (size_t)1 << 20;
+
+size_t cq_g2_srs_serialized_size(const cq_g2_srs* s, int format) { return s ? s->count * g2_srs_point_size(format) : 0; }
+
+int cq_g2_srs_read(cq_ctx* c, const uint8_t* buf, size_t len, int format, cq_g2_srs** out) {
+  if (!c || !out || (len && !buf)) return CQ_ERR_ARG;
+  *out = nullptr;
+  const size_t psz = g2_srs_point_size(format);
+  if (!psz) return c->fail(CQ_ERR_ARG, "g2 srs: unknown serde format");
+  if (len % psz) return c->fail(CQ_ERR_ARG, "g2 srs: stream length is not a multiple of the point size");
+  const size_t count = len / psz;
+  if (count > ((size_t)1 << 30)) return c->fail(CQ_ERR_ARG, "g2 srs: too many points");
+  CQ_HIP(c, hipSetDevice(c->device));
+  cq_g2_srs* s;
+  int rc = g2_srs_alloc(c, count, &s);
+  if (rc != CQ_OK) return rc;
+  struct Guard {
+    cq_g2_srs* s;
+    ~Guard() {
+      if (s) cq_g2_srs_destroy(s);
+    }
+  } guard{s};
+  if (count == 0) {
+    guard.s = nullptr;
+    *out = s;
+    return CQ_OK;
+  }
+  if (format != CQ_SERDE_PROCESSED) CQ_HIP(c, hipMemcpyAsync(s->pts, buf, len, hipMemcpyHostToDevice, c->stream));
+  if (format != CQ_SERDE_RAW_BYTES_UNCHECKED) {
+    void* cells;
+    if ((rc = c->ensure_scratch(Scratch::EntryA, 64, &cells)) != CQ_OK) return rc;
+    uint32_t* count_dev = (uint32_t*)cells;
+    uint32_t* first_dev = count_dev + 1;
+    if ((rc = serde_verdict_reset(c, count_dev, first_dev, 1)) != CQ_OK) return rc;
+    if (format == CQ_SERDE_PROCESSED) {
+      // chunk by chunk through one staging buffer (copies and kernels follow one another on the stream); the kernel reports
+      // indices in the whole array
+      void* stage;
+      if ((rc = c->ensure_scratch(Scratch::EntryB, std::min(count, G2_SRS_CHUNK) * 64, &stage)) != CQ_OK) return rc;
+      for (size_t off = 0; off < count; off += G2_SRS_CHUNK) {
+        const size_t m = std::min(G2_SRS_CHUNK, count - off);
+        CQ_HIP(c, hipMemcpyAsync(stage, buf + off * 64, m * 64, hipMemcpyHostToDevice, c->stream));
+        if ((rc = g2_decompress(c, (const uint8_t*)stage, (uint32_t)m, (uint32_t)off, s->pts + off, count_dev, first_dev)) != CQ_OK) return rc;
+      }
+    } else if ((rc = g2_validate(c, s->pts, (uint32_t)count, 0, count_dev, first_dev)) != CQ_OK) {
+      return rc;
+    }
+    uint32_t verdict[2] = {0, 0};
+    CQ_HIP(c, hipMemcpyAsync(verdict, cells, sizeof(verdict), hipMemcpyDeviceToHost, c->stream));
+    CQ_HIP(c, hipStreamSynchronize(c->stream));
+    if (verdict[0])
+      return c->fail(CQ_ERR_ARG, std::string("g2 srs: invalid point ") + (format == CQ_SERDE_PROCESSED ? "encoding" : "(coordinate not below the modulus or not on the twist)") +
+                                     " at index " + std::to_string(verdict[1]) + " (" + std::to_string(verdict[0]) + " invalid in all)");
+  }
+  CQ_HIP(c, hipStreamSynchronize(c->stream));
+  guard.s = nullptr;
+  *out = s;
+  return CQ_OK;
+}
+
+int cq_g2_srs_write(cq_g2_srs* s, int format, uint8_t* buf, size_t cap, size_t* written) {
+  if (!s || !written || (s->count && !buf)) return CQ_ERR_ARG;
+  cq_ctx* c = s->ctx;
+  const size_t psz = g2_srs_point_size(format);
+  if (!psz) return c->fail(CQ_ERR_ARG, "g2 srs: unknown serde format");
+  if (cap < s->count * psz) return c->fail(CQ_ERR_ARG, "g2 srs: output buffer too small");
+  CQ_HIP(c, hipSetDevice(c->device));
+  if (format != CQ_SERDE_PROCESSED) {
+    CQ_HIP(c, hipMemcpyAsync(buf, s->pts, s->count * psz, hipMemcpyDeviceToHost, c->stream));
+  } else if (s->count) {
+    void* stage;
+    int rc;
+    if ((rc = c->ensure_scratch(Scratch::EntryB, std::min(s->count, G2_SRS_CHUNK) * 64, &stage)) != CQ_OK) return rc;
+    for (size_t off = 0; off < s->count; off += G2_SRS_CHUNK) {
+      const size_t m = std::min(G2_SRS_CHUNK, s->count - off);
+      if ((rc = g2_compress(c, s->pts + off, (uint32_t)m, (uint8_t*)stage)) != CQ_OK) return rc;
+      CQ_HIP(c, hipMemcpyAsync(buf + off * 64, stage, m * 64, hipMemcpyDeviceToHost, c->stream));
+    }
+  }
+  CQ_HIP(c, hipStreamSynchronize(c->stream));
+  *written = s->count * psz;
+  return CQ_OK;
+}
 
 const uint64_t* cq_g2_srs_dev(const cq_g2_srs* s) { return s ? (const uint64_t*)s->pts : nullptr; }
 

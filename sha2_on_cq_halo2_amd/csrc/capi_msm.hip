@@ -10,6 +10,7 @@
 #include "setup.hpp"
 #include "cq.hpp"
 #include "serde.hpp"
+#include "msm_g2.hpp"
 
 using namespace cq;
 
@@ -404,6 +405,16 @@ int cq_params_setup_from_toxic_waste(cq_ctx* c, uint32_t k, const uint64_t s[4],
     if ((rc = msm_register_tables(c, p->g_lagrange, p->n)) != CQ_OK) return rc;
   }
   CQ_HIP(c, hipStreamSynchronize(c->stream));
+  // g2 = generator, s_g2 = [s]_2 (commitment.rs:265-266): the first two G2 powers
+  void* two;
+  if ((rc = c->ensure_scratch(Scratch::EntryB, 2 * sizeof(G2Affine), &two)) != CQ_OK) return rc;
+  if ((rc = g2_srs_powers(c, Fr::from_limbs64(s), 2, (G2Affine*)two)) != CQ_OK) return rc;
+  uint64_t tail[32];
+  CQ_HIP(c, hipMemcpyAsync(tail, two, sizeof(tail), hipMemcpyDeviceToHost, c->stream));
+  CQ_HIP(c, hipStreamSynchronize(c->stream));
+  memcpy(p->g2, tail, sizeof(p->g2));
+  memcpy(p->s_g2, tail + 16, sizeof(p->s_g2));
+  p->has_g2 = true;
   *out = guard.release();
   return CQ_OK;
 }
@@ -416,7 +427,7 @@ int cq_fixed_base_mul_dev(cq_ctx* c, const uint64_t* scalars_dev, size_t n, uint
 }
 
 /* ParamsKZG::read_custom with RawBytes / RawBytesUnchecked (kzg/commitment.rs:383-459):
- * k:u32 LE | n x 64 B g | n x 64 B g_lagrange | [128 B g2 | 128 B s_g2, ignored] -- straight into HBM */
+ * k:u32 LE | n x 64 B g | n x 64 B g_lagrange | [128 B g2 | 128 B s_g2, ignored here: cq_params_read_full] -- straight into HBM */
 int cq_params_read_raw(cq_ctx* c, const uint8_t* buf, size_t len, int checked, cq_params** out) {
   if (!c || !buf || !out || len < 4) return CQ_ERR_ARG;
   uint32_t k;
@@ -456,7 +467,7 @@ int cq_params_read_raw(cq_ctx* c, const uint8_t* buf, size_t len, int checked, c
 }
 
 /* ParamsKZG::read_custom with SerdeFormat::Processed (kzg/commitment.rs:383-459):
- * k:u32 LE | n x 32 B g | n x 32 B g_lagrange | [2 x 64 B compressed g2, s_g2: ignored] -- the compressed bytes are staged
+ * k:u32 LE | n x 32 B g | n x 32 B g_lagrange | [2 x 64 B compressed g2, s_g2: ignored here, cq_params_read_full] -- the compressed bytes are staged
  * in the entry scratch and decompressed straight into the resident arrays */
 static int params_read_processed(cq_ctx* c, const uint8_t* buf, size_t len, cq_params** out) {
   if (!c || !buf || !out || len < 4) return CQ_ERR_ARG;
@@ -533,6 +544,114 @@ int cq_params_write(cq_params* p, int format, uint8_t* buf, size_t cap, size_t* 
   return CQ_OK;
 }
 
+// ---- g2 / s_g2 and the complete ParamsKZG stream ------------------------------------------------------------------------
+int cq_params_set_g2(cq_params* p, const uint64_t g2[16], const uint64_t s_g2[16]) {
+  if (!p || !g2 || !s_g2) return CQ_ERR_ARG;
+  memcpy(p->g2, g2, sizeof(p->g2));
+  memcpy(p->s_g2, s_g2, sizeof(p->s_g2));
+  p->has_g2 = true;
+  return CQ_OK;
+}
+
+int cq_params_g2(const cq_params* p, uint64_t g2[16], uint64_t s_g2[16]) {
+  if (!p || !g2 || !s_g2) return CQ_ERR_ARG;
+  if (!p->has_g2) return p->ctx->fail(CQ_ERR_ARG, "params: no g2 / s_g2 held (read_full, set_g2 or setup_from_toxic_waste provide them)");
+  memcpy(g2, p->g2, sizeof(p->g2));
+  memcpy(s_g2, p->s_g2, sizeof(p->s_g2));
+  return CQ_OK;
+}
+
+static size_t g2_point_size(int format) {
+  if (format == CQ_SERDE_PROCESSED) return 64;
+  if (format == CQ_SERDE_RAW_BYTES || format == CQ_SERDE_RAW_BYTES_UNCHECKED) return sizeof(G2Affine);
+  return 0;
+}
+
+size_t cq_params_serialized_size_full(const cq_params* p, int format) {
+  const size_t g1 = cq_params_serialized_size(p, format);
+  return g1 ? g1 + 2 * g2_point_size(format) : 0;
+}
+
+/* ParamsKZG::read_custom (commitment.rs:383-459), tail included: the G1 part by cq_params_read, then g2 | s_g2 staged in the
+ * entry scratch and decompressed / validated by the G2 kernels of serde.hip */
+int cq_params_read_full(cq_ctx* c, const uint8_t* buf, size_t len, int format, cq_params** out) {
+  if (!c || !buf || !out || len < 4) return CQ_ERR_ARG;
+  const size_t psz = g2_point_size(format);
+  if (!psz) return c->fail(CQ_ERR_ARG, "params: unknown serde format");
+  uint32_t k;
+  memcpy(&k, buf, 4);
+  if (k > FR_S) return c->fail(CQ_ERR_ARG, "params: k out of range");
+  const size_t g1 = 4 + 2 * ((size_t)1 << k) * (psz / 2);
+  if (len < g1 + 2 * psz) return c->fail(CQ_ERR_ARG, "params: buffer too short for the full stream (g2 | s_g2 missing)");
+  *out = nullptr;
+  cq_params* p = nullptr;
+  int rc = cq_params_read(c, buf, len, format, &p);
+  if (rc != CQ_OK) return rc;
+  ParamsGuard guard(p);
+  const uint8_t* tail = buf + g1;
+  if (format == CQ_SERDE_RAW_BYTES_UNCHECKED) {
+    memcpy(p->g2, tail, sizeof(p->g2));
+    memcpy(p->s_g2, tail + sizeof(G2Affine), sizeof(p->s_g2));
+  } else {
+    void *stage, *cells;
+    if ((rc = c->ensure_scratch(Scratch::EntryB, 2 * 64 + 2 * sizeof(G2Affine), &stage)) != CQ_OK) return rc;
+    if ((rc = c->ensure_scratch(Scratch::EntryA, 64, &cells)) != CQ_OK) return rc;
+    uint32_t* count_dev = (uint32_t*)cells;
+    uint32_t* first_dev = count_dev + 1;
+    G2Affine* pts = (G2Affine*)((uint8_t*)stage + 2 * 64);
+    if ((rc = serde_verdict_reset(c, count_dev, first_dev, 1)) != CQ_OK) return rc;
+    if (format == CQ_SERDE_PROCESSED) {
+      CQ_HIP(c, hipMemcpyAsync(stage, tail, 2 * 64, hipMemcpyHostToDevice, c->stream));
+      if ((rc = g2_decompress(c, (const uint8_t*)stage, 2, 0, pts, count_dev, first_dev)) != CQ_OK) return rc;
+    } else {
+      CQ_HIP(c, hipMemcpyAsync(pts, tail, 2 * sizeof(G2Affine), hipMemcpyHostToDevice, c->stream));
+      if ((rc = g2_validate(c, pts, 2, 0, count_dev, first_dev)) != CQ_OK) return rc;
+    }
+    uint32_t verdict[2] = {0, 0};
+    uint64_t both[32];
+    CQ_HIP(c, hipMemcpyAsync(verdict, cells, sizeof(verdict), hipMemcpyDeviceToHost, c->stream));
+    CQ_HIP(c, hipMemcpyAsync(both, pts, sizeof(both), hipMemcpyDeviceToHost, c->stream));
+    CQ_HIP(c, hipStreamSynchronize(c->stream));
+    if (verdict[0])
+      return c->fail(CQ_ERR_ARG, std::string("params: invalid point encoding at ") + (verdict[1] ? "s_g2" : "g2") + " (" +
+                                     std::to_string(verdict[0]) + " of the two G2 points invalid)");
+    memcpy(p->g2, both, sizeof(p->g2));
+    memcpy(p->s_g2, both + 16, sizeof(p->s_g2));
+  }
+  p->has_g2 = true;
+  *out = guard.release();
+  return CQ_OK;
+}
+
+/* ParamsKZG::write_custom (commitment.rs:366-379), tail included */
+int cq_params_write_full(cq_params* p, int format, uint8_t* buf, size_t cap, size_t* written) {
+  if (!p || !buf || !written) return CQ_ERR_ARG;
+  cq_ctx* c = p->ctx;
+  const size_t psz = g2_point_size(format);
+  if (!psz) return c->fail(CQ_ERR_ARG, "params: unknown serde format");
+  if (!p->has_g2) return c->fail(CQ_ERR_ARG, "params: no g2 / s_g2 held, the full stream cannot be written");
+  const size_t g1 = cq_params_serialized_size(p, format);
+  if (cap < g1 + 2 * psz) return c->fail(CQ_ERR_ARG, "params: output buffer too small");
+  size_t w = 0;
+  int rc = cq_params_write(p, format, buf, cap, &w);
+  if (rc != CQ_OK) return rc;
+  if (format == CQ_SERDE_PROCESSED) {
+    void* stage;
+    if ((rc = c->ensure_scratch(Scratch::EntryB, 2 * 64 + 2 * sizeof(G2Affine), &stage)) != CQ_OK) return rc;
+    G2Affine* pts = (G2Affine*)((uint8_t*)stage + 2 * 64);
+    CQ_HIP(c, hipMemcpyAsync(pts, p->g2, sizeof(p->g2), hipMemcpyHostToDevice, c->stream));
+    CQ_HIP(c, hipMemcpyAsync(pts + 1, p->s_g2, sizeof(p->s_g2), hipMemcpyHostToDevice, c->stream));
+    if ((rc = g2_compress(c, pts, 2, (uint8_t*)stage)) != CQ_OK) return rc;
+    CQ_HIP(c, hipMemcpyAsync(buf + w, stage, 2 * 64, hipMemcpyDeviceToHost, c->stream));
+    CQ_HIP(c, hipStreamSynchronize(c->stream));
+  } else {
+    memcpy(buf + w, p->g2, sizeof(p->g2));
+    memcpy(buf + w + sizeof(G2Affine), p->s_g2, sizeof(p->s_g2));
+  }
+  *written = w + 2 * psz;
+  return CQ_OK;
+}
+
 int cq_g_to_lagrange_dev(cq_ctx* c, const uint64_t* g_dev, uint32_t k, uint64_t* g_lagrange_dev) {
   if (!c || !g_dev || !g_lagrange_dev || k > 26) return CQ_ERR_ARG;
   CQ_HIP(c, hipSetDevice(c->device));
@@ -557,12 +676,15 @@ int cq_params_downsize(cq_params* p, uint32_t k, cq_params** out) {
     if ((rc = msm_register_tables(c, q->g, q->n)) != CQ_OK) return rc;
     if ((rc = msm_register_tables(c, q->g_lagrange, q->n)) != CQ_OK) return rc;
   }
+  q->has_g2 = p->has_g2;  // downsize shortens g and g_lagrange in place: g2 and s_g2 stay (commitment.rs:480-492)
+  memcpy(q->g2, p->g2, sizeof(q->g2));
+  memcpy(q->s_g2, p->s_g2, sizeof(q->s_g2));
   *out = guard.release();
   return CQ_OK;
 }
 
-/* G1 part of ParamsKZG::write_custom(RawBytes) (commitment.rs:366-379): 4 + 128 n bytes; the caller
- * appends its g2 / s_g2. */
+/* G1 part of ParamsKZG::write_custom(RawBytes) (commitment.rs:366-379): 4 + 128 n bytes; cq_params_write_full
+ * appends g2 / s_g2. */
 int cq_params_write_raw(cq_params* p, uint8_t* buf, size_t cap, size_t* written) {
   if (!p || !buf || !written) return CQ_ERR_ARG;
   cq_ctx* c = p->ctx;

@@ -97,7 +97,7 @@ inline void shard_range(size_t n, uint32_t rank, uint32_t world, size_t& lo, siz
 }
 }  // namespace cq
 
-// ParamsKZG G1 part (poly/kzg/commitment.rs:31-39), SRS resident in HBM
+// ParamsKZG (poly/kzg/commitment.rs:31-39): the G1 SRS resident in HBM, g2 / s_g2 (when held) in host memory
 struct cq_params {
   cq_ctx* ctx;
   uint32_t k;
@@ -106,6 +106,8 @@ struct cq_params {
   cq::G1Affine* g_lagrange;  // [L_i(s)]_1
   uint32_t key_users = 0;    // proving keys built on this object (a sharded key drops the whole-array tables only when alone)
   bool owner_released = false;  // cq_params_destroy was called while keys still used the object: the last key frees it
+  bool has_g2 = false;          // g2 / s_g2 below are set (setup_from_toxic_waste, read_full, set_g2, downsize of such params)
+  uint64_t g2[16] = {}, s_g2[16] = {};  // raw layout: x.c0 | x.c1 | y.c0 | y.c1, Montgomery limbs
 };
 
 // StaticTableConfig (plonk/static_lookup.rs:47-66): Lagrange SRS of the table-sized domain

@@ -21,9 +21,10 @@ enum class Scratch {
   EntryA,       // a public entry point's own staging or temporaries, for that call only: capi.hip fft, capi_poly.hip HostStage
                 // input, capi_msm.hip (multiexp scalars, params set-up temp, validate flag), capi_g2.hip scalars, capi_cq.hip
                 // (table config, static table, pk create / validate / write temps), comm.hip self-test, the verdict words of
-                // the Processed conversions (serde.hip entry points, params / pk readers).  Nothing they call takes an entry buffer
+                // the Processed conversions (serde.hip entry points, params / pk / G2 SRS readers).  Nothing they call takes an entry buffer
   EntryB,       // the second buffer of the same entry points (outputs, bases, pk permutation mapping, the staged compressed
-                // bytes of the Processed params / pk readers and writers); also g1_fft's twiddles: its callers (g1_to_lagrange,
+                // bytes of the Processed params / pk / G2 SRS readers and writers, the two G2 points of a params set-up or full
+                // stream); also g1_fft's twiddles: its callers (g1_to_lagrange,
                 // fk_table_quotients) run under entry points that hold neither entry buffer
   MsmWork,      // capi_msm.hip, msm.hip (msm_bucket_sums): the workspace of one MSM launch; launches follow one another on `stream`
   MsmSums,      // capi_msm.hip: window sums, from msm_multi_begin to its msm_multi_end (launches are never nested)

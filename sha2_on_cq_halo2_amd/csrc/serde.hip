@@ -1,11 +1,12 @@
-// SerdeFormat::Processed on the device: point decompression / compression (derive/curve.rs:603-646) and the canonical
-// scalar encodings (helpers.rs:68-91), with their C entry points.  The params and proving-key readers built on them live
-// next to their raw twins (capi_msm.hip, capi_cq.hip).
+// SerdeFormat::Processed on the device: point decompression / compression (derive/curve.rs:603-646) for G1 and G2 and the
+// canonical scalar encodings (helpers.rs:68-91), with their C entry points.  The params, proving-key and G2 SRS readers
+// built on them live next to their raw twins (capi_msm.hip, capi_cq.hip, capi_g2.hip).
 #include <cstdint>
 #include <string>
 #include "ctx.hpp"
 #include "serde.hpp"
 #include "sqrt29.hpp"
+#include "sqrt2_29.hpp"
 
 namespace cq {
 namespace {
@@ -47,6 +48,43 @@ constexpr SerdeConsts make_serde_consts() {
   return c;
 }
 constexpr SerdeConsts SERDE_CONSTS = make_serde_consts();
+
+// v 2^e mod q for a canonical v in 29-bit limbs, by repeated doubling
+constexpr void shl_mod_q29(const uint32_t* v, int e, uint32_t* out) {
+  uint32_t t[9] = {};
+  for (int i = 0; i < 9; i++) t[i] = v[i];
+  for (int s = 0; s < e; s++) {
+    uint32_t d[9] = {};
+    add_mod_q29(t, t, d);
+    for (int i = 0; i < 9; i++) t[i] = d[i];
+  }
+  for (int i = 0; i < 9; i++) out[i] = t[i];
+}
+// four 64-bit words (little-endian) -> nine 29-bit limbs
+constexpr void limbs29_of_words64(const uint64_t* w, uint32_t* out) {
+  for (int i = 0; i < 9; i++) {
+    const int bit = 29 * i, k = bit >> 6, sh = bit & 63;
+    uint64_t x = w[k] >> sh;
+    if (sh > 35 && k + 1 < 4) x |= w[k + 1] << (64 - sh);
+    out[i] = (uint32_t)(x & 0x1fffffffu);
+  }
+}
+// the twist's b' = 3 / (9 + i) (bn256/curve.rs:85-98, canonical words) in the R' = 2^261 Montgomery form
+struct Serde2Consts {
+  uint32_t b0[9], b1[9];
+};
+constexpr Serde2Consts make_serde2_consts() {
+  constexpr uint64_t B0[4] = {0x3267e6dc24a138e5ull, 0xb5b4c5e559dbefa3ull, 0x81be18991be06ac3ull, 0x2b149d40ceb8aaaeull};
+  constexpr uint64_t B1[4] = {0xe4a2bd0685c315d2ull, 0xa74fa084e52d1852ull, 0xcd2cafadeed8fdf4ull, 0x009713b03af0fed4ull};
+  Serde2Consts c{};
+  uint32_t t[9] = {};
+  limbs29_of_words64(B0, t);
+  shl_mod_q29(t, 261, c.b0);
+  limbs29_of_words64(B1, t);
+  shl_mod_q29(t, 261, c.b1);
+  return c;
+}
+constexpr Serde2Consts SERDE2_CONSTS = make_serde2_consts();
 
 __device__ __forceinline__ void ld8(const void* p, uint32_t* w) {
   const uint4* q = reinterpret_cast<const uint4*>(p);
@@ -163,6 +201,101 @@ __global__ void __launch_bounds__(256) fr_to_repr_kernel(const Fr* in, uint32_t 
   st8(out + (size_t)i * 32, w.l);
 }
 
+// ---- G2 ---------------------------------------------------------------------------------------------------------------
+// `GroupEncoding::from_bytes` for G2Affine (derive/curve.rs:603-627, compressed size 64; `Fq2::from_bytes`, fq2.rs:134-146):
+// canonical x.c0 | x.c1 little-endian, bit 7 of byte 63 the parity of the canonical y.c0, 64 zero bytes the identity; no
+// subgroup check.  One point per lane: about 670 dependent Fq products (sqrt2_29.hpp: 651; x to limb form and back 4, x^3 6,
+// y to memory form 2).  Invalid: a component >= q, x^3 + b' not a square -- which covers x = 0 with the sign bit, b' being
+// a non-square.  Reported indices are base + i: a caller converting an array in chunks gets indices in the whole array.
+__global__ void __launch_bounds__(256) g2_decompress_kernel(const uint8_t* __restrict__ in, uint32_t n, uint32_t base, G2Affine* __restrict__ out,
+                                                            uint32_t* __restrict__ count, uint32_t* __restrict__ first) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t w0[8], w1[8];
+  ld8(in + (size_t)i * 64, w0);
+  ld8(in + (size_t)i * 64 + 32, w1);
+  const uint32_t ysign = w1[7] >> 31;  // bit 7 of byte 63
+  w1[7] &= 0x7fffffffu;
+  if (!below_modulus<FqP>(w0) || !below_modulus<FqP>(w1)) {  // `Fq::from_bytes` fails on a non-canonical component
+    report(base + i, count, first);
+    return;
+  }
+  uint32_t any = 0;
+  CQ_UNROLL for (int k = 0; k < 8; k++) any |= w0[k] | w1[k];
+  uint32_t o[8];
+  if (any == 0 && ysign == 0) {  // the identity: (0, 0, 0, 0) in the raw layout
+    CQ_UNROLL for (int k = 0; k < 8; k++) o[k] = 0;
+    st8(&out[i].x.c0, o);
+    st8(&out[i].x.c1, o);
+    st8(&out[i].y.c0, o);
+    st8(&out[i].y.c1, o);
+    return;
+  }
+  Fq29 r2;
+  Fq2_29 b;
+  CQ_UNROLL for (int k = 0; k < 9; k++) {
+    r2.a[k] = SERDE_CONSTS.r2[k];     // < q, normalised
+    b.c0.a[k] = SERDE2_CONSTS.b0[k];  // b' R' mod q per component: < q, normalised
+    b.c1.a[k] = SERDE2_CONSTS.b1[k];
+  }
+  Fq2_29 x;
+  x.c0 = Fq29::mul(Fq29::unpack(w0), r2);  // canonical memory word < q, normalised: 1 * 1 <= 128  ->  x.c0 R' < 2 q, normalised
+  x.c1 = Fq29::mul(Fq29::unpack(w1), r2);
+  // x leaves now (an invalid point's output is unspecified): nothing of it stays live across the two chains
+  st8(&out[i].x.c0, x.c0.to_mont256().v.l);  // < 2 q <= 64 q
+  st8(&out[i].x.c1, x.c1.to_mont256().v.l);
+  const Fq2_29 x2 = x.sqr<2>();               // Ka = 2 <= 5  ->  < 2 q
+  const Fq2_29 x3 = Fq2_29::mul<2>(x2, x);    // Ka Kb = 4 <= 64  ->  < 2 q
+  const Fq2_29 rhs = x3 + b;                  // limb-wise: < 3 q per component, limbs < 2^30
+  Fq2_29 y;
+  if (!fq2_decoded_y29(rhs, ysign, y)) {      // operand < 8 q with limbs < 2^30: x^3 + b' is not a square
+    report(base + i, count, first);
+    return;
+  }
+  st8(&out[i].y.c0, y.c0.to_mont256().v.l);   // <= 2 q <= 64 q, normalised  ->  canonical R = 2^256 word
+  st8(&out[i].y.c1, y.c1.to_mont256().v.l);
+}
+
+// `GroupEncoding::to_bytes` for G2Affine (derive/curve.rs:635-646; `Fq2::to_bytes`, fq2.rs:148-155)
+__global__ void __launch_bounds__(256) g2_compress_kernel(const G2Affine* __restrict__ in, uint32_t n, uint8_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Fq x0, x1, y0, y1;
+  ld8(&in[i].x.c0, x0.v.l);
+  ld8(&in[i].x.c1, x1.v.l);
+  ld8(&in[i].y.c0, y0.v.l);
+  ld8(&in[i].y.c1, y1.v.l);
+  uint32_t o0[8], o1[8];
+  if (x0.is_zero() && x1.is_zero() && y0.is_zero() && y1.is_zero()) {
+    CQ_UNROLL for (int k = 0; k < 8; k++) o0[k] = o1[k] = 0;
+  } else {
+    const U256 c0 = x0.to_canonical(), c1 = x1.to_canonical(), yc = y0.to_canonical();
+    CQ_UNROLL for (int k = 0; k < 8; k++) {
+      o0[k] = c0.l[k];
+      o1[k] = c1.l[k];
+    }
+    o1[7] |= (yc.l[0] & 1u) << 31;
+  }
+  st8(out + (size_t)i * 64, o0);
+  st8(out + (size_t)i * 64 + 32, o1);
+}
+
+// SerdeFormat::RawBytes for G2Affine (`SerdeObject::from_raw_bytes`, derive/curve.rs:649-700): every coordinate below q and
+// the point on the twist, or the identity.  `b` = 3 / (9 + i) in the memory form.
+__global__ void __launch_bounds__(256) g2_validate_kernel(const G2Affine* __restrict__ pts, uint32_t n, uint32_t base, Fq2 b,
+                                                          uint32_t* __restrict__ count, uint32_t* __restrict__ first) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Fq2 x, y;
+  ld8(&pts[i].x.c0, x.c0.v.l);
+  ld8(&pts[i].x.c1, x.c1.v.l);
+  ld8(&pts[i].y.c0, y.c0.v.l);
+  ld8(&pts[i].y.c1, y.c1.v.l);
+  bool ok = below_modulus<FqP>(x.c0.v.l) && below_modulus<FqP>(x.c1.v.l) && below_modulus<FqP>(y.c0.v.l) && below_modulus<FqP>(y.c1.v.l);
+  if (ok && !(x.is_zero() && y.is_zero())) ok = y.sqr() == x.sqr() * x + b;
+  if (!ok) report(base + i, count, first);
+}
+
 inline uint32_t blocks_for(uint32_t n) { return (n + 255) / 256; }
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
@@ -202,6 +335,29 @@ int fr_to_repr(cq_ctx* c, const Fr* in, uint32_t n, uint8_t* out) {
   if (!aligned16(in) || !aligned16(out)) return c->fail(CQ_ERR_ARG, "fr_to_repr: buffers must be 16-byte aligned");
   fr_to_repr_kernel<<<blocks_for(n), 256, 0, c->stream>>>(in, n, out);
   return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "fr_to_repr launch failed");
+}
+
+int g2_decompress(cq_ctx* c, const uint8_t* in, uint32_t n, uint32_t base, G2Affine* out, uint32_t* count_dev, uint32_t* first_dev) {
+  if (!n) return CQ_OK;
+  if (!aligned16(in) || !aligned16(out)) return c->fail(CQ_ERR_ARG, "g2_decompress: buffers must be 16-byte aligned");
+  hipEvent_t pe = c->prof_begin(CQ_PROF_G2_DECOMPRESS);
+  g2_decompress_kernel<<<blocks_for(n), 256, 0, c->stream>>>(in, n, base, out, count_dev, first_dev);
+  c->prof_end(pe);
+  return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "g2_decompress launch failed");
+}
+
+int g2_compress(cq_ctx* c, const G2Affine* in, uint32_t n, uint8_t* out) {
+  if (!n) return CQ_OK;
+  if (!aligned16(in) || !aligned16(out)) return c->fail(CQ_ERR_ARG, "g2_compress: buffers must be 16-byte aligned");
+  g2_compress_kernel<<<blocks_for(n), 256, 0, c->stream>>>(in, n, out);
+  return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "g2_compress launch failed");
+}
+
+int g2_validate(cq_ctx* c, const G2Affine* pts, uint32_t n, uint32_t base, uint32_t* count_dev, uint32_t* first_dev) {
+  if (!n) return CQ_OK;
+  if (!aligned16(pts)) return c->fail(CQ_ERR_ARG, "g2_validate: buffer must be 16-byte aligned");
+  g2_validate_kernel<<<blocks_for(n), 256, 0, c->stream>>>(pts, n, base, g2_b(), count_dev, first_dev);
+  return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "g2_validate launch failed");
 }
 
 }  // namespace cq
@@ -245,6 +401,20 @@ int cq_g1_compress_dev(cq_ctx* c, const uint64_t* affine_dev, size_t n, uint8_t*
   if (!c || (n && (!affine_dev || !bytes_dev)) || n > 0x7fffffffull) return CQ_ERR_ARG;
   CQ_HIP(c, hipSetDevice(c->device));
   return g1_compress(c, (const G1Affine*)affine_dev, (uint32_t)n, bytes_dev);
+}
+
+int cq_g2_decompress_dev(cq_ctx* c, const uint8_t* bytes_dev, size_t n, uint64_t* out_affine_dev, size_t* first_bad) {
+  if (!c || (n && (!bytes_dev || !out_affine_dev)) || n > 0x7fffffffull) return CQ_ERR_ARG;
+  CQ_HIP(c, hipSetDevice(c->device));
+  return checked_conversion(c, "g2 decompress", first_bad, [&](uint32_t* count_dev, uint32_t* first_dev) {
+    return g2_decompress(c, bytes_dev, (uint32_t)n, 0, (G2Affine*)out_affine_dev, count_dev, first_dev);
+  });
+}
+
+int cq_g2_compress_dev(cq_ctx* c, const uint64_t* affine_dev, size_t n, uint8_t* bytes_dev) {
+  if (!c || (n && (!affine_dev || !bytes_dev)) || n > 0x7fffffffull) return CQ_ERR_ARG;
+  CQ_HIP(c, hipSetDevice(c->device));
+  return g2_compress(c, (const G2Affine*)affine_dev, (uint32_t)n, bytes_dev);
 }
 
 int cq_fr_from_repr_dev(cq_ctx* c, const uint8_t* bytes_dev, size_t n, uint64_t* out_dev, size_t* first_bad) {

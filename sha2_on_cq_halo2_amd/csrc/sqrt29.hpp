@@ -7,7 +7,8 @@
 // The digit is wave-uniform (it depends on the loop counter alone), and the entry is chosen by compares over the table's
 // registers (sqrt_pick) -- never by indexing a private array at run time, which would put the table into scratch memory.
 // W = 4 and BN254's q: 14 products for the table, then 248 squarings and 56 products for the 62 digits below the top one
-// (six of them are zero) -- 318 products.
+// (six of them are zero) -- 318 products.  The chain takes its exponent as a template parameter (pow_window29): sqrt2_29.hpp
+// runs it with (p - 3) / 4 as well, which has the same digit counts.
 //
 // Compiles for the device and, with __device__ / __forceinline__ defined away, with a host compiler
 // (tests/host/sqrt29_check.cpp); `Trace` sees every intermediate value there and is a no-op in kernels.
@@ -16,7 +17,7 @@
 
 namespace cq {
 
-// (p + 1) / 4 as eight 32-bit words
+// an exponent below 2^256 as eight 32-bit words
 struct SqrtExp {
   uint32_t w[8];
 };
@@ -36,6 +37,25 @@ constexpr SqrtExp make_sqrt_exp() {
 }
 template <class P>
 inline constexpr SqrtExp SQRT_EXP = make_sqrt_exp<P>();
+// (p - 3) / 4 = (p + 1) / 4 - 1: a^((p - 3) / 4) is 1 / sqrt(a) up to sign (sqrt2_29.hpp)
+template <class P>
+constexpr SqrtExp make_inv_sqrt_exp() {
+  SqrtExp e = make_sqrt_exp<P>();
+  for (int i = 0; i < 8; i++)
+    if (e.w[i]-- != 0) break;  // borrow out of a zero word
+  return e;
+}
+template <class P>
+inline constexpr SqrtExp INV_SQRT_EXP = make_inv_sqrt_exp<P>();
+// The chain's exponent is a type: `word(i)` is a literal once the loops over i are unrolled.
+template <class P>
+struct ExpSqrt {  // (p + 1) / 4
+  static constexpr uint32_t word(int i) { return SQRT_EXP<P>.w[i]; }
+};
+template <class P>
+struct ExpInvSqrt {  // (p - 3) / 4
+  static constexpr uint32_t word(int i) { return INV_SQRT_EXP<P>.w[i]; }
+};
 
 struct SqrtNoTrace {
   template <class F>
@@ -44,13 +64,13 @@ struct SqrtNoTrace {
   __device__ __forceinline__ void difference(const F&) const {}  // the root check's y^2 + 8 p - a, claimed < 10 p, normalised
 };
 
-// bits [W j, W j + W) of (p + 1) / 4; j is wave-uniform (a loop counter), the words are literals after unrolling
-template <class P, int W>
+// bits [W j, W j + W) of the exponent E; j is wave-uniform (a loop counter), the words are literals after unrolling
+template <class E, int W>
 __device__ __forceinline__ uint32_t sqrt_exp_digit(int j) {
   static_assert(32 % W == 0, "a digit must not straddle two words");
   const int word = (W * j) >> 5, sh = (W * j) & 31;
   uint32_t e = 0;
-  CQ_UNROLL for (int i = 0; i < 8; i++) e = (word == i) ? SQRT_EXP<P>.w[i] : e;
+  CQ_UNROLL for (int i = 0; i < 8; i++) e = (word == i) ? E::word(i) : e;
   return (e >> sh) & ((1u << W) - 1);
 }
 
@@ -68,13 +88,13 @@ __device__ __forceinline__ Fp29<P> sqrt_pick(const Fp29<P>* T, uint32_t d) {
   return t;
 }
 
-// a^((p + 1) / 4) in the R' = 2^261 Montgomery form the operand is in.
+// a^E for a compile-time exponent E < 2^254 (ExpSqrt<P>, ExpInvSqrt<P>), in the R' = 2^261 Montgomery form the operand is in.
 //   a: value < 8 p, limbs < 2^30 (a limb-wise sum of up to two normalised values, e.g. x^3 + b).
 //   result: normalised, < 2 p.
-template <class P, int W = 4, class Trace = SqrtNoTrace>
-__device__ __forceinline__ Fp29<P> sqrt_candidate29(const Fp29<P>& a, Trace&& tr = Trace()) {
+template <class P, class E, int W = 4, class Trace = SqrtNoTrace>
+__device__ __forceinline__ Fp29<P> pow_window29(const Fp29<P>& a, Trace&& tr = Trace()) {
   using F = Fp29<P>;
-  constexpr int DIGITS = (254 + W - 1) / W;  // (p + 1) / 4 < 2^252 for p < 2^254; leading zero digits are skipped below
+  constexpr int DIGITS = (254 + W - 1) / W;  // E < 2^254; leading zero digits are skipped below
   F T[1 << W];
   T[1] = a;            // < 8 p, limbs < 2^30
   T[2] = a.sqr();      // 8 * 8 = 64 <= 121, limbs < 2^30  ->  < 2 p, normalised
@@ -86,8 +106,8 @@ __device__ __forceinline__ Fp29<P> sqrt_candidate29(const Fp29<P>& a, Trace&& tr
   });
   // the top non-zero digit starts the chain (no squarings of 1)
   int j = DIGITS - 1;
-  while (j > 0 && sqrt_exp_digit<P, W>(j) == 0) j--;
-  F acc = sqrt_pick<P, W>(T, sqrt_exp_digit<P, W>(j));  // a itself (< 8 p, limbs < 2^30) or a table power (< 2 p)
+  while (j > 0 && sqrt_exp_digit<E, W>(j) == 0) j--;
+  F acc = sqrt_pick<P, W>(T, sqrt_exp_digit<E, W>(j));  // a itself (< 8 p, limbs < 2^30) or a table power (< 2 p)
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll 1
 #endif
@@ -96,13 +116,19 @@ __device__ __forceinline__ Fp29<P> sqrt_candidate29(const Fp29<P>& a, Trace&& tr
       acc = acc.sqr();  // 8 * 8 = 64 <= 121 the first time (limbs < 2^30), 2 * 2 = 4 after it  ->  < 2 p, normalised
       tr(acc);
     }
-    const uint32_t d = sqrt_exp_digit<P, W>(j);
+    const uint32_t d = sqrt_exp_digit<E, W>(j);
     if (d) {  // wave-uniform
       acc = F::mul(acc, sqrt_pick<P, W>(T, d));  // 2 * 8 = 16 <= 128, limbs < 2^29 and < 2^30  ->  < 2 p, normalised
       tr(acc);
     }
   }
   return acc;
+}
+
+// a^((p + 1) / 4), the candidate square root: operand and result as for pow_window29
+template <class P, int W = 4, class Trace = SqrtNoTrace>
+__device__ __forceinline__ Fp29<P> sqrt_candidate29(const Fp29<P>& a, Trace&& tr = Trace()) {
+  return pow_window29<P, ExpSqrt<P>, W>(a, tr);
 }
 
 // y^2 == a (mod p)?   y: normalised, < 2 p (a result of sqrt_candidate29); a: value < 8 p, limbs < 2^30 (its operand).
