@@ -34,7 +34,8 @@ static uint32_t pick_c(cq_ctx* c, uint32_t n) {
 // Runs `count` MSMs (each with its own base array and length); results to host Jacobians.
 // Base arrays registered with cq_msm_precompute use their per-window tables (one bucket set per MSM,
 // no window folding on the host) and may share a launch whatever their lengths; plain MSMs are
-// grouped by equal length.
+// grouped by equal length, and a group of at most MSM_SHORT_MAX terms takes the one-kernel short path (msm_short_run)
+// unless the caller fixed the window width of the generic pipeline (cq_msm_set_window).
 int msm_multi_begin(cq_ctx* c, const Fr* const* scalars, const G1Affine* const* bases, const size_t* lens, size_t count,
                     MsmPending& pend) {
   pend.launches.clear();
@@ -76,7 +77,8 @@ int msm_multi_begin(cq_ctx* c, const Fr* const* scalars, const G1Affine* const* 
       nmax = std::max(nmax, (uint32_t)l);
       batch++;
     }
-    const uint32_t cb = pre ? t0->c : pick_c(c, nmax);
+    ln.short_path = !pre && !c->msm_c && nmax <= MSM_SHORT_MAX;
+    const uint32_t cb = pre ? t0->c : ln.short_path ? MSM_SHORT_C : pick_c(c, nmax);
     // keep the workspace below ~32 GiB (of 288)
     while (batch > 1 && MsmLayout(nmax, cb, batch, pre).total > ((size_t)32 << 30)) batch = (batch + 1) / 2;
     ln.batch = batch;
@@ -103,6 +105,13 @@ int msm_multi_begin(cq_ctx* c, const Fr* const* scalars, const G1Affine* const* 
   pend.slots = slots;
   for (auto& ln : pend.launches) {
     if (ln.empty) continue;
+    if (ln.short_path) {  // same result layout as a plain launch of 8-bit windows: 32 one-row bucket sets per MSM
+      void* ws;
+      if ((rc = c->ensure_scratch(Scratch::MsmWork, msm_short_workspace(ln.nmax, ln.batch), &ws)) != CQ_OK) return rc;
+      if (msm_short_run(c, scalars + ln.first, bases + ln.first, ln.nmax, ln.batch, ws, (G1Jac*)wsums + ln.slot) != 0)
+        return c->fail(CQ_ERR_HIP, "msm launch failed");
+      continue;
+    }
     MsmLayout L(ln.nmax, ln.c, ln.batch, ln.pre);
     std::vector<const G1Affine*> bp(ln.batch);
     std::vector<size_t> strides(ln.batch, 0);

@@ -55,6 +55,18 @@ constexpr uint32_t MSM_COMBINE_WAVE_BLOCKS = 2048;  // blocks of the combine lev
 constexpr uint32_t MSM_MAX_BATCH = 32;  // MSMs per launch
 constexpr uint32_t MSM_SET_POINTS = 15; // points a bucket set leaves for the host: 7 + 7 bit-plane sums and a total (msm_set_value)
 
+// Short plain-mode MSMs (msm_short_run): signed 8-bit windows, one workgroup per (MSM, window).  MSM_SHORT_LIMIT is what the
+// kernel is built for (the longest table of the prover's b_by_rows path; a sorted entry has 15 bits of term index, and a term
+// takes a byte of LDS); MSM_SHORT_MAX is the cut-over
+// of msm_multi_begin, measured against the generic pipeline at batch 8 (profiles/r09_short_msm_ab.txt).
+constexpr uint32_t MSM_SHORT_C = 8, MSM_SHORT_W = 32;
+constexpr uint32_t MSM_SHORT_LIMIT = 1u << 14;
+#ifndef CQ_MSM_SHORT_MAX
+#define CQ_MSM_SHORT_MAX 16384
+#endif
+constexpr uint32_t MSM_SHORT_MAX = CQ_MSM_SHORT_MAX;
+static_assert(MSM_SHORT_MAX <= MSM_SHORT_LIMIT && MSM_SHORT_MAX >= 4097, "the cut-over covers N + 1 = 4097 and fits the kernel");
+
 struct MsmPtrs {
   const void* p[MSM_MAX_BATCH];
 };
@@ -84,6 +96,12 @@ uint32_t msm_window_bits(uint32_t n);
 int msm_run(cq_ctx* ctx, const Fr* const* scalars, const G1Affine* const* bases, const size_t* lens, uint32_t n, uint32_t c,
             uint32_t batch, bool pre, const size_t* table_strides, void* workspace, G1Jac* window_sums_dev,
             G1Affine* raw_out = nullptr, uint32_t raw_count = 0);
+// `batch` plain-mode MSMs of n <= MSM_SHORT_LIMIT terms each in ONE kernel on ctx->stream; window_sums_dev as for msm_run with
+// c = MSM_SHORT_C (MSM_SHORT_W one-row bucket sets per MSM: the column planes and the total of every set are written);
+// workspace: msm_short_workspace(n, batch) bytes
+size_t msm_short_workspace(uint32_t n, uint32_t batch);
+int msm_short_run(cq_ctx* ctx, const Fr* const* scalars, const G1Affine* const* bases, uint32_t n, uint32_t batch, void* workspace,
+                  G1Jac* window_sums_dev);
 // Bucket sums instead of an MSM's value: scalars[j][i] is a small integer d in [0, count] (Montgomery form, as ever), and
 // out[j][b] = sum of bases29[j][i] over the i with d = b + 1, for b < count <= 2^14 -- affine, the callers' R = 2^256 layout,
 // the identity for a bucket nobody names.  One table-mode launch on ctx->stream (sort, accumulate, combine levels; MSMs over
@@ -120,6 +138,7 @@ struct MsmPending {
     size_t first = 0, slot = 0;
     uint32_t batch = 0, c = 0, nmax = 0, W = 0, Wb = 0, M = 0, cols = 0;
     bool pre = false, empty = false;
+    bool short_path = false;  // msm_short_run: the result has a plain launch's layout (c = 8), msm_multi_end folds it the same way
   };
   std::vector<Launch> launches;
   void* host = nullptr;

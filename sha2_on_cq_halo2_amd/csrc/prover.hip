@@ -1156,7 +1156,7 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       std::vector<const G1Affine*> bs;
       std::vector<size_t> ln;
       // (b_by_rows: the 2 L short MSMs over this proof's bucket sums -- plain mode, no tables -- go first as one launch of
-      // their own, so that the table-mode MSMs behind them still share one; `at[i]`: where result i of the transcript's
+      // their own (a single kernel, msm_short_run), so that the table-mode MSMs behind them still share one; `at[i]`: where result i of the transcript's
       // order sits in the launch order)
       std::vector<size_t> at;
       for (size_t l = 0; b_by_rows && l < L; l++)
