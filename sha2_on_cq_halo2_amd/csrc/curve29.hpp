@@ -191,6 +191,18 @@ static __device__ __forceinline__ XYZZ29 xyzz29_shfl_down(const XYZZ29& a, int d
   }
   return r;
 }
+// acc of the lane at pos = 0 += the acc of the WIDTH - 1 lanes above it: a shuffle tree over groups of WIDTH adjacent lanes.
+// EVERY lane of the wave executes the shuffles; the lanes that add are the `live` ones with a partner inside their group
+// (pos + delta >= WIDTH reads the next group's lanes, or the lane itself at the wave's end: a point added to itself is
+// the doubling path).  One level at a time (unroll 1) keeps the callers inside their register budgets.
+template <uint32_t WIDTH>
+static __device__ __forceinline__ void xyzz29_tree_sum(XYZZ29& acc, uint32_t pos, bool live = true) {
+#pragma unroll 1
+  for (uint32_t delta = WIDTH / 2; delta >= 1; delta >>= 1) {
+    const XYZZ29 o = xyzz29_shfl_down(acc, (int)delta);
+    if (live && pos + delta < WIDTH) xyzz29_add(acc, o);
+  }
+}
 
 // ---- one addition by FOUR lanes ----------------------------------------------------------------------------------
 // The tails of an MSM launch (row / column sums, bit-plane trees) are chains of dependent general additions on a handful
@@ -230,6 +242,10 @@ static __device__ __forceinline__ Fq29 select29(bool c, const Fq29& a, const Fq2
   CQ_UNROLL for (int k = 0; k < 9; k++) r.a[k] = c ? a.a[k] : b.a[k];
   return r;
 }
+// a quad's point in every lane
+static __device__ __forceinline__ XYZZ29 quad_to_xyzz29(const Fq29& F) {
+  return {quad_perm<0, 0, 0, 0>(F), quad_perm<1, 1, 1, 1>(F), quad_perm<2, 2, 2, 2>(F), quad_perm<3, 3, 3, 3>(F)};
+}
 // F: this quad's point, G: the other point, both one coordinate per lane (x | y | zz | zzz).  Returns F + G in that form.
 static __device__ __forceinline__ Fq29 quad_add(const Fq29& F, const Fq29& G) {
   const uint32_t role = threadIdx.x & 3u;
@@ -264,13 +280,60 @@ static __device__ __forceinline__ Fq29 quad_add(const Fq29& F, const Fq29& G) {
   Fq29 R = role == 0 ? X3all : role == 1 ? Y3 : role == 2 ? T3 : T4;
   const bool needs_slow = same_x && !id1 && !id2;
   if (__any(needs_slow)) {  // doubling or cancellation somewhere in the wave: the plain formulas on the gathered points
-    XYZZ29 a = {quad_perm<0, 0, 0, 0>(F), quad_perm<1, 1, 1, 1>(F), quad_perm<2, 2, 2, 2>(F), quad_perm<3, 3, 3, 3>(F)};
-    const XYZZ29 b = {quad_perm<0, 0, 0, 0>(G), quad_perm<1, 1, 1, 1>(G), quad_perm<2, 2, 2, 2>(G), quad_perm<3, 3, 3, 3>(G)};
+    XYZZ29 a = quad_to_xyzz29(F);
+    const XYZZ29 b = quad_to_xyzz29(G);
     xyzz29_add(a, b);
     const Fq29 S = role == 0 ? a.x : role == 1 ? a.y : role == 2 ? a.zz : a.zzz;
     R = select29(needs_slow, S, R);
   }
   return select29(id2, F, select29(id1, G, R));
+}
+
+// ---- sums by quads: lane r of a quad (threadIdx.x & 3) holds coordinate r, in memory 32 bytes of the packed XYZZ ----
+static __device__ __forceinline__ Fq29 quad_load(const XYZZ* p, uint32_t role) {
+  uint32_t w[8];
+  ld8(reinterpret_cast<const char*>(p) + 32 * role, w);
+  return Fq29::unpack(w);
+}
+static __device__ __forceinline__ Fq29 quad_shfl_xor(const Fq29& a, int lanes) {
+  Fq29 r;
+  CQ_UNROLL for (int k = 0; k < 9; k++) r.a[k] = __shfl_xor(a.a[k], lanes, 64);
+  return r;
+}
+// XOR butterfly over the from_d / 2 quads a wave's data sits in (from_d = 32: all sixteen): every one of them ends with
+// their sum.  All lanes of the wave take part (the permutes and shuffles need them); one addition at a time (unroll 1).
+static __device__ __forceinline__ Fq29 quad_wave_sum(Fq29 F, int from_d) {
+#pragma unroll 1
+  for (int d = from_d; d >= 4; d >>= 1) F = quad_add(F, quad_shfl_xor(F, d));
+  return F;
+}
+// The sum of the 64 quads of a 256-thread block, in the first four quads of wave 0: the butterfly per wave, the four
+// waves' sums through LDS, two more levels.  Called by the whole block; the other waves get their own wave's sum back and
+// have nothing left to do.
+static __device__ __forceinline__ Fq29 quad_block_sum(Fq29 F, uint32_t (*xs)[4][9]) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, role = threadIdx.x & 3u;
+  F = quad_wave_sum(F, 32);
+  if (lane < 4) {
+    CQ_UNROLL for (int k = 0; k < 9; k++) xs[wave][role][k] = F.a[k];
+  }
+  __syncthreads();
+  if (wave != 0) return F;
+  F = Fq29::zero();
+  if (lane < 16) {
+    CQ_UNROLL for (int k = 0; k < 9; k++) F.a[k] = xs[lane >> 2][role][k];
+  }
+  return quad_wave_sum(F, 8);
+}
+// the wave's first quad writes its point in packed form: x below 2^256 needs the reduction (8 p > 2^256), the other
+// coordinates are below 4 p.  (Every lane reduces: the store alone is conditional.)
+static __device__ __forceinline__ void quad_store(XYZZ* p, const Fq29& F) {
+  const uint32_t role = threadIdx.x & 3u;
+  const Fq29 red = F.reduced();
+  if ((threadIdx.x & 63u) < 4) {
+    uint32_t w[8];
+    (role == 0 ? red : F).pack(w);
+    st8(reinterpret_cast<char*>(p) + 32 * role, w);
+  }
 }
 
 }  // namespace cq

@@ -31,6 +31,9 @@
 //   6. host      : table mode returns one Jacobian point per MSM; plain mode W window sums per MSM, folded by a
 //                  Horner over windows (c doublings each) on the host.
 // Plain-mode MSMs of at most MSM_SHORT_MAX terms skip all of that: msm_short_kernel, one workgroup per (MSM, 8-bit window).
+// What several kernels share exists once: the LDS sort of the bucket and refinement passes is part_count / part_tile_place
+// below, named by a policy (BucketBins<PB>, RefineBins); the shuffle tree of the lane sums is xyzz29_tree_sum<WIDTH> and the
+// four-lane sums are quad_load / quad_wave_sum / quad_block_sum / quad_store / quad_to_xyzz29, next to quad_add in curve29.hpp.
 #include <algorithm>
 #include <cstdlib>
 #include "msm.hpp"
@@ -169,6 +172,8 @@ __global__ __launch_bounds__(256) void msm_digits_kernel(const Fr* const* __rest
 //   e. bucket_place : after the plan: per tile of 4096 entries of a partition, LDS histogram, one device atomic
 //                     per non-empty bucket to reserve the tile's run inside the bucket's list, entries written
 //                     there (runs of ~32 entries).  PART_SPLIT workgroups share a partition tile by tile.
+// d and e are part_count and part_tile_place with the BucketBins policy; the refinement pass of the wide windows (c > 17)
+// is the same two bodies with RefineBins.
 #ifndef CQ_PART_CHUNK_THREADS
 #define CQ_PART_CHUNK_THREADS 256
 #endif
@@ -285,9 +290,6 @@ static __device__ __forceinline__ void wave0_scan(const uint32_t* __restrict__ h
     run += v[k];
   }
 }
-static __device__ __forceinline__ void wave0_scan128(const uint32_t* __restrict__ hist, uint32_t* __restrict__ start) {
-  wave0_scan<128>(hist, start);
-}
 
 // One scalar per lane; the chunk's entries are sorted by partition in LDS first, so that the write-out is a linear
 // copy of runs (~34 entries = 272 B per partition) instead of one uncoalesced 8-byte store per entry (which kept the
@@ -360,21 +362,148 @@ __global__ __launch_bounds__(PSC_THREADS) void msm_part_scatter_kernel(const Fr*
   }
 }
 
-// partition pid = msm * npart + p owns the flat buckets [pid << PART_BITS, (pid + 1) << PART_BITS)
-// (PB: bits of the bucket inside a partition, 7 or 8)
+// ---- one LDS sort for the bucket passes and the refinement passes ------------------------------------------------
+// Both levels below the partition pass count the entries of a partition per BIN and then place them, tile by tile, as
+// per-bin runs.  A policy says what differs:
+//   Low          the incoming low part of an entry (what the pass before left of its bucket);
+//   CELLS, rlog  the LDS histogram: a bin owns 1 << rlog adjacent cells, an entry counts in cell (bin << rlog) | rep;
+//   bins_log     the pass's 1 << bins_log bins per partition: bin b of partition pid is entry (pid << bins_log) + b of
+//                the arrays the runs are reserved against;
+//   bin(low), emit(dst, payload, low)   an entry's bin, and what leaves the tile.
+// Bucket passes: partition pid = msm * npart + p owns the flat buckets [pid << PB, (pid + 1) << PB) (PB: bits of the bucket
+// inside a partition, 7 or 8); the bin is the bucket, one cell each, and the payload alone goes into the bucket's list.
+template <uint32_t PB>
+struct BucketBins {
+  using Low = uint8_t;
+  static constexpr uint32_t CELLS = 1u << PB, bins_log = PB, rlog = 0, rep = 0;
+  uint32_t* sorted;
+  __device__ __forceinline__ uint32_t bin(uint32_t low) const { return low; }
+  __device__ __forceinline__ void emit(uint32_t dst, uint32_t pay, uint32_t) const { sorted[dst] = pay; }
+};
+// Wide windows (c > 17, 2^(c-1) buckets per MSM): the first pass still cuts an MSM into 128 partitions -- now of
+// 2^(c-8) buckets -- and a REFINEMENT pass of the same shape as the bucket passes splits every such partition into
+// its 2^(c-15) final partitions of 128 buckets, which the bucket passes then finish.  The few bins of a partition are
+// spread over 128 histogram cells (bin, thread mod R) so that the LDS atomics of a wave do not pile up on 2..32
+// addresses; cells of one bin are adjacent, so the LDS-sorted tile is still a sequence of per-bin runs.  The payload and
+// the remaining 7 bits leave the tile.
+struct RefineBins {
+  using Low = uint16_t;
+  static constexpr uint32_t CELLS = PART_BUCKETS;
+  uint32_t bins_log, rlog, rep;
+  uint32_t* pay2;
+  uint8_t* low2;
+  __device__ __forceinline__ RefineBins(uint32_t bins_log_, uint32_t* pay2_ = nullptr, uint8_t* low2_ = nullptr)
+      : bins_log(bins_log_), rlog(PART_BITS - bins_log_), rep(threadIdx.x & ((1u << rlog) - 1u)), pay2(pay2_), low2(low2_) {}
+  __device__ __forceinline__ uint32_t bin(uint32_t low) const { return low >> PART_BITS; }
+  __device__ __forceinline__ void emit(uint32_t dst, uint32_t pay, uint32_t low) const {
+    pay2[dst] = pay;
+    low2[dst] = (uint8_t)(low & (PART_BUCKETS - 1));
+  }
+};
+template <class P>
+static __device__ __forceinline__ uint32_t bin_count(const P& p, const uint32_t* hist, uint32_t bin) {
+  uint32_t sum = 0;
+  for (uint32_t r = 0; r < (1u << p.rlog); r++) sum += hist[(bin << p.rlog) + r];
+  return sum;
+}
+
+// LDS histogram of the partition's entries (gridDim.y workgroups share it), one device atomic per non-empty bin
+template <class P>
+static __device__ __forceinline__ void part_count(const P& p, const typename P::Low* __restrict__ low, const uint32_t* __restrict__ poff,
+                                                  uint32_t* __restrict__ bin_sizes) {
+  __shared__ uint32_t hist[P::CELLS];
+  const uint32_t pid = blockIdx.x, t = threadIdx.x;
+  const uint32_t lo = poff[pid], hi = poff[pid + 1];
+  if (lo + blockIdx.y * PART_THREADS >= hi) return;  // block-uniform
+  if (t < P::CELLS) hist[t] = 0;
+  __syncthreads();
+  for (uint32_t e = lo + blockIdx.y * PART_THREADS + t; e < hi; e += gridDim.y * PART_THREADS)
+    atomicAdd(&hist[(p.bin(low[e]) << p.rlog) | p.rep], 1u);
+  __syncthreads();
+  if (t < (1u << p.bins_log)) {
+    const uint32_t h = bin_count(p, hist, t);
+    if (h) atomicAdd(&bin_sizes[(pid << p.bins_log) + t], h);
+  }
+}
+
+// A tile's entries are sorted by bin in LDS, then copied out run by run (bucket passes: ~32 entries = one 128-byte line
+// per bucket and tile): LDS histogram, scan, one device atomic per non-empty bin to reserve the tile's run behind
+// bin_start + what bin_cursor holds, placement in LDS, linear copy.  gridDim.y workgroups share a partition tile by tile.
+template <class P>
+static __device__ __forceinline__ void part_tile_place(const P& p, const uint32_t* __restrict__ pay, const typename P::Low* __restrict__ low,
+                                                       const uint32_t* __restrict__ poff, const uint32_t* __restrict__ bin_start,
+                                                       uint32_t* __restrict__ bin_cursor) {
+  constexpr uint32_t NC = P::CELLS;
+  __shared__ uint32_t hist[NC], lstart[NC], base[NC];
+  __shared__ uint32_t spay[PART_TILE];
+  __shared__ typename P::Low slow[PART_TILE];
+  const uint32_t pid = blockIdx.x, t = threadIdx.x;
+  const uint32_t lo = poff[pid], hi = poff[pid + 1];
+  const uint32_t ntiles = (hi - lo + PART_TILE - 1) / PART_TILE;
+  for (uint32_t tile = blockIdx.y; tile < ntiles; tile += gridDim.y) {  // block-uniform trip count
+    const uint32_t tlo = lo + tile * PART_TILE, thi = min(hi, tlo + PART_TILE);
+    if (t < NC) hist[t] = 0;
+    __syncthreads();
+    uint2 ent[PART_PER_LANE];
+#pragma unroll
+    for (uint32_t k = 0; k < PART_PER_LANE; k++) {
+      const uint32_t e = tlo + k * PART_THREADS + t;
+      if (e < thi) {
+        ent[k] = make_uint2(pay[e], low[e]);
+        atomicAdd(&hist[(p.bin(ent[k].y) << p.rlog) | p.rep], 1u);
+      }
+    }
+    __syncthreads();
+    wave0_scan<NC>(hist, lstart);
+    if (t < (1u << p.bins_log)) {  // the tile's run inside bin (pid, t)
+      const uint32_t h = bin_count(p, hist, t), g = (pid << p.bins_log) + t;
+      base[t] = h ? bin_start[g] + atomicAdd(&bin_cursor[g], h) : 0u;
+    }
+    __syncthreads();
+    if (t < NC) hist[t] = 0;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < PART_PER_LANE; k++) {
+      const uint32_t e = tlo + k * PART_THREADS + t;
+      if (e < thi) {
+        const uint32_t cell = (p.bin(ent[k].y) << p.rlog) | p.rep;
+        const uint32_t lp = lstart[cell] + atomicAdd(&hist[cell], 1u);
+        spay[lp] = ent[k].x;
+        slow[lp] = (typename P::Low)ent[k].y;
+      }
+    }
+    __syncthreads();
+    for (uint32_t j = t; j < thi - tlo; j += PART_THREADS) {
+      const uint32_t l = slow[j], b = p.bin(l);
+      p.emit(base[b] + (j - lstart[b << p.rlog]), spay[j], l);
+    }
+    __syncthreads();
+  }
+}
+
 template <uint32_t PB>
 __global__ __launch_bounds__(PART_THREADS) void msm_bucket_count_kernel(const uint8_t* __restrict__ part_low, const uint32_t* __restrict__ poff,
                                                                         uint32_t* __restrict__ counts) {
   CQ_CRITICAL_WAVES();
-  __shared__ uint32_t hist[1u << PB];
-  const uint32_t pid = blockIdx.x, t = threadIdx.x;
-  const uint32_t lo = poff[pid], hi = poff[pid + 1];
-  if (lo + blockIdx.y * PART_THREADS >= hi) return;  // block-uniform
-  if (t < (1u << PB)) hist[t] = 0;
-  __syncthreads();
-  for (uint32_t e = lo + blockIdx.y * PART_THREADS + t; e < hi; e += gridDim.y * PART_THREADS) atomicAdd(&hist[part_low[e]], 1u);
-  __syncthreads();
-  if (t < (1u << PB) && hist[t]) atomicAdd(&counts[(pid << PB) + t], hist[t]);
+  part_count(BucketBins<PB>{nullptr}, part_low, poff, counts);
+}
+template <uint32_t PB>
+__global__ __launch_bounds__(PART_THREADS) void msm_bucket_place_kernel(const uint32_t* __restrict__ part_pay, const uint8_t* __restrict__ part_low,
+                                                                        const uint32_t* __restrict__ poff,
+                                                                        const uint32_t* __restrict__ off0, uint32_t* __restrict__ cursor,
+                                                                        uint32_t* __restrict__ sorted) {
+  CQ_CRITICAL_WAVES();
+  part_tile_place(BucketBins<PB>{sorted}, part_pay, part_low, poff, off0, cursor);
+}
+__global__ __launch_bounds__(PART_THREADS) void msm_refine_count_kernel(const uint16_t* __restrict__ low1, const uint32_t* __restrict__ poff1,
+                                                                        uint32_t bins_log, uint32_t* __restrict__ psize2) {
+  part_count(RefineBins(bins_log), low1, poff1, psize2);
+}
+__global__ __launch_bounds__(PART_THREADS) void msm_refine_place_kernel(const uint32_t* __restrict__ pay1, const uint16_t* __restrict__ low1,
+                                                                        const uint32_t* __restrict__ poff1, uint32_t bins_log,
+                                                                        const uint32_t* __restrict__ poff2, uint32_t* __restrict__ cursor2,
+                                                                        uint32_t* __restrict__ pay2, uint8_t* __restrict__ low2) {
+  part_tile_place(RefineBins(bins_log, pay2, low2), pay1, low1, poff1, poff2, cursor2);
 }
 
 // an MSM that accumulates from another one's lists (same scalar vector) takes a copy of its bucket counts
@@ -383,143 +512,6 @@ __global__ __launch_bounds__(256) void msm_alias_counts_kernel(uint32_t* __restr
   const uint32_t m = blockIdx.y, src = (uint32_t)list_src[m];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (src != m && i < B) counts[(size_t)m * B + i] = counts[(size_t)src * B + i];
-}
-
-// Same idea one level down: a tile's entries are sorted by bucket in LDS, then copied out run by run (~32 entries =
-// one 128-byte line per bucket and tile).
-template <uint32_t PB>
-__global__ __launch_bounds__(PART_THREADS) void msm_bucket_place_kernel(const uint32_t* __restrict__ part_pay, const uint8_t* __restrict__ part_low,
-                                                                        const uint32_t* __restrict__ poff,
-                                                                        const uint32_t* __restrict__ off0, uint32_t* __restrict__ cursor,
-                                                                        uint32_t* __restrict__ sorted) {
-  CQ_CRITICAL_WAVES();
-  constexpr uint32_t NB = 1u << PB;
-  __shared__ uint32_t hist[NB], lstart[NB], base[NB];
-  __shared__ uint32_t spay[PART_TILE];
-  __shared__ uint8_t sbkt[PART_TILE];
-  const uint32_t pid = blockIdx.x, t = threadIdx.x;
-  const uint32_t lo = poff[pid], hi = poff[pid + 1];
-  const uint32_t ntiles = (hi - lo + PART_TILE - 1) / PART_TILE;
-  for (uint32_t tile = blockIdx.y; tile < ntiles; tile += gridDim.y) {  // block-uniform trip count
-    const uint32_t tlo = lo + tile * PART_TILE, thi = min(hi, tlo + PART_TILE);
-    if (t < NB) hist[t] = 0;
-    __syncthreads();
-    uint2 ent[PART_PER_LANE];
-#pragma unroll
-    for (uint32_t k = 0; k < PART_PER_LANE; k++) {
-      const uint32_t e = tlo + k * PART_THREADS + t;
-      if (e < thi) {
-        ent[k] = make_uint2(part_pay[e], part_low[e]);
-        atomicAdd(&hist[ent[k].y], 1u);
-      }
-    }
-    __syncthreads();
-    wave0_scan<NB>(hist, lstart);
-    if (t < NB) {
-      const uint32_t h = hist[t], g = (pid << PB) + t;
-      base[t] = h ? off0[g] + atomicAdd(&cursor[g], h) : 0u;
-    }
-    __syncthreads();
-    if (t < NB) hist[t] = 0;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t k = 0; k < PART_PER_LANE; k++) {
-      const uint32_t e = tlo + k * PART_THREADS + t;
-      if (e < thi) {
-        const uint32_t b = ent[k].y;
-        const uint32_t lp = lstart[b] + atomicAdd(&hist[b], 1u);
-        spay[lp] = ent[k].x;
-        sbkt[lp] = (uint8_t)b;
-      }
-    }
-    __syncthreads();
-    for (uint32_t j = t; j < thi - tlo; j += PART_THREADS) {
-      const uint32_t b = sbkt[j];
-      sorted[base[b] + (j - lstart[b])] = spay[j];
-    }
-    __syncthreads();
-  }
-}
-
-// Wide windows (c > 17, 2^(c-1) buckets per MSM): the first pass still cuts an MSM into 128 partitions -- now of
-// 2^(c-8) buckets -- and a REFINEMENT pass of the same shape as the two kernels above splits every such partition into
-// its 2^(c-15) final partitions of 128 buckets, which the kernels above then finish.  The few bins of a partition are
-// spread over 128 histogram cells (bin, thread mod R) so that the LDS atomics of a wave do not pile up on 2..32
-// addresses; cells of one bin are adjacent, so the LDS-sorted tile is still a sequence of per-bin runs.
-__global__ __launch_bounds__(PART_THREADS) void msm_refine_count_kernel(const uint16_t* __restrict__ low1, const uint32_t* __restrict__ poff1,
-                                                                        uint32_t bins_log, uint32_t* __restrict__ psize2) {
-  __shared__ uint32_t hist[PART_BUCKETS];
-  const uint32_t cp = blockIdx.x, t = threadIdx.x;
-  const uint32_t lo = poff1[cp], hi = poff1[cp + 1];
-  if (lo + blockIdx.y * PART_THREADS >= hi) return;  // block-uniform
-  const uint32_t rlog = PART_BITS - bins_log, rep = t & ((1u << rlog) - 1u);
-  if (t < PART_BUCKETS) hist[t] = 0;
-  __syncthreads();
-  for (uint32_t e = lo + blockIdx.y * PART_THREADS + t; e < hi; e += gridDim.y * PART_THREADS)
-    atomicAdd(&hist[((uint32_t)(low1[e] >> PART_BITS) << rlog) | rep], 1u);
-  __syncthreads();
-  if (t < (1u << bins_log)) {
-    uint32_t sum = 0;
-    for (uint32_t r = 0; r < (1u << rlog); r++) sum += hist[(t << rlog) + r];
-    if (sum) atomicAdd(&psize2[(cp << bins_log) + t], sum);
-  }
-}
-
-__global__ __launch_bounds__(PART_THREADS) void msm_refine_place_kernel(const uint32_t* __restrict__ pay1, const uint16_t* __restrict__ low1,
-                                                                        const uint32_t* __restrict__ poff1, uint32_t bins_log,
-                                                                        const uint32_t* __restrict__ poff2, uint32_t* __restrict__ cursor2,
-                                                                        uint32_t* __restrict__ pay2, uint8_t* __restrict__ low2) {
-  __shared__ uint32_t hist[PART_BUCKETS], lstart[PART_BUCKETS], base[PART_BUCKETS];
-  __shared__ uint32_t spay[PART_TILE];
-  __shared__ uint16_t slow[PART_TILE];
-  const uint32_t cp = blockIdx.x, t = threadIdx.x;
-  const uint32_t lo = poff1[cp], hi = poff1[cp + 1];
-  const uint32_t ntiles = (hi - lo + PART_TILE - 1) / PART_TILE;
-  const uint32_t bins = 1u << bins_log, rlog = PART_BITS - bins_log, rep = t & ((1u << rlog) - 1u);
-  for (uint32_t tile = blockIdx.y; tile < ntiles; tile += gridDim.y) {  // block-uniform trip count
-    const uint32_t tlo = lo + tile * PART_TILE, thi = min(hi, tlo + PART_TILE);
-    if (t < PART_BUCKETS) hist[t] = 0;
-    __syncthreads();
-    uint2 ent[PART_PER_LANE];
-#pragma unroll
-    for (uint32_t k = 0; k < PART_PER_LANE; k++) {
-      const uint32_t e = tlo + k * PART_THREADS + t;
-      if (e < thi) {
-        ent[k] = make_uint2(pay1[e], low1[e]);
-        atomicAdd(&hist[((ent[k].y >> PART_BITS) << rlog) | rep], 1u);
-      }
-    }
-    __syncthreads();
-    wave0_scan128(hist, lstart);
-    __syncthreads();
-    if (t < bins) {  // the tile's run inside final partition (cp, t)
-      const uint32_t first = lstart[t << rlog];
-      const uint32_t end = t + 1 < bins ? lstart[(t + 1) << rlog] : lstart[PART_BUCKETS - 1] + hist[PART_BUCKETS - 1];
-      const uint32_t f = (cp << bins_log) + t;
-      base[t] = end > first ? poff2[f] + atomicAdd(&cursor2[f], end - first) : 0u;
-    }
-    __syncthreads();
-    if (t < PART_BUCKETS) hist[t] = 0;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t k = 0; k < PART_PER_LANE; k++) {
-      const uint32_t e = tlo + k * PART_THREADS + t;
-      if (e < thi) {
-        const uint32_t cell = ((ent[k].y >> PART_BITS) << rlog) | rep;
-        const uint32_t lp = lstart[cell] + atomicAdd(&hist[cell], 1u);
-        spay[lp] = ent[k].x;
-        slow[lp] = (uint16_t)ent[k].y;
-      }
-    }
-    __syncthreads();
-    for (uint32_t j = t; j < thi - tlo; j += PART_THREADS) {
-      const uint32_t l = slow[j], bin = l >> PART_BITS;
-      const uint32_t dst = base[bin] + (j - lstart[bin << rlog]);
-      pay2[dst] = spay[j];
-      low2[dst] = (uint8_t)(l & (PART_BUCKETS - 1));
-    }
-    __syncthreads();
-  }
 }
 
 // ---- 2. plan: exclusive scans over the flat bucket array -----------------------------------------
@@ -768,11 +760,7 @@ __global__ __launch_bounds__(256, 3) void msm_combine_level_kernel(
         xyzz29_add(acc, cur);
       }
     }
-#pragma unroll 1
-    for (int delta = Q / 2; delta >= 1; delta >>= 1) {
-      XYZZ29 o = xyzz29_shfl_down(acc, delta);  // all lanes take part in the shuffle
-      if (mine && sub + delta < Q) xyzz29_add(acc, o);
-    }
+    xyzz29_tree_sum<Q>(acc, sub, mine);
     if (mine && sub == 0) store_xyzz29(buckets + g, acc);
     return;
   }
@@ -795,32 +783,17 @@ __global__ __launch_bounds__(256, 3) void msm_combine_level_kernel(
   // launch then waits for.  Quad q sums the partial sums lo + q, lo + q + 16, .. (lane r of the quad their coordinate r),
   // an XOR butterfly over the quads that hold data folds them: <= 4 + 4 additions of ~2.4 us instead of 1 + 6 of ~5 us.
   const uint32_t role = lane & 3u, quad = lane >> 2, len = hi - lo;
-  auto load_coord = [&](uint32_t e) {
-    uint32_t w[8];
-    ld8(reinterpret_cast<const char*>(prev + e) + 32 * role, w);
-    return Fq29::unpack(w);
-  };
   Fq29 F = Fq29::zero();
-  if (quad < len) F = load_coord(lo + quad);
+  if (quad < len) F = quad_load(prev + lo + quad, role);
 #pragma unroll 1
   for (uint32_t e = quad + 16; e < ((len + 15u) & ~15u); e += 16) {  // (the same trip count for every quad: the permutes need all lanes)
     Fq29 G = Fq29::zero();
-    if (e < len) G = load_coord(lo + e);
+    if (e < len) G = quad_load(prev + lo + e, role);
     F = quad_add(F, G);
   }
   const uint32_t nq = len < 16 ? len : 16;  // quads holding data
-#pragma unroll 1
-  for (int d = nq > 8 ? 32 : nq > 4 ? 16 : nq > 2 ? 8 : nq > 1 ? 4 : 0; d >= 4; d >>= 1) {
-    Fq29 o;
-    CQ_UNROLL for (int k = 0; k < 9; k++) o.a[k] = __shfl_xor(F.a[k], d, 64);
-    F = quad_add(F, o);
-  }
-  const Fq29 red = F.reduced();  // packed form: x below 2^256
-  if (lane < 4) {
-    uint32_t w[8];
-    (role == 0 ? red : F).pack(w);
-    st8(reinterpret_cast<char*>(t_cur[g] == 1 ? buckets + g : partial + j) + 32 * role, w);
-  }
+  F = quad_wave_sum(F, nq > 8 ? 32 : nq > 4 ? 16 : nq > 2 ? 8 : nq > 1 ? 4 : 0);
+  quad_store(t_cur[g] == 1 ? buckets + g : partial + j, F);
   }
 }
 
@@ -950,11 +923,7 @@ __global__ __launch_bounds__(64) void msm_rowcol_kernel(const XYZZ* __restrict__
     for (uint32_t hi = seg * per; hi < min(rows, (seg + 1) * per); hi++)
       if (Tk[(size_t)hi * cols + lo]) xyzz29_add(acc, load_xyzz29(Bk + (size_t)hi * cols + lo));
   }
-#pragma unroll 1
-  for (int delta = SEG / 2; delta >= 1; delta >>= 1) {
-    XYZZ29 o = xyzz29_shfl_down(acc, delta);  // lanes seg + delta >= SEG read the next line's lanes: not used
-    if (seg + delta < SEG) xyzz29_add(acc, o);
-  }
+  xyzz29_tree_sum<SEG>(acc, seg);
   if (seg == 0 && q < rows + cols) store_xyzz29(sums + (size_t)set * (rows + cols) + q, acc);
 }
 
@@ -983,11 +952,7 @@ __global__ __launch_bounds__(64) void msm_weighted_kernel(const XYZZ* __restrict
     if (lane < count) v = load_xyzz29(X + lane);
     if (lane + 64 < count) xyzz29_add(v, load_xyzz29(X + lane + 64));
   }
-#pragma unroll 1
-  for (int delta = 32; delta >= 1; delta >>= 1) {
-    XYZZ29 o = xyzz29_shfl_down(v, delta);
-    if ((int)lane < delta) xyzz29_add(v, o);  // the lanes that still matter (the others would add a point to itself: the doubling path)
-  }
+  xyzz29_tree_sum<64>(v, lane);
   if (lane == 0) out[(size_t)set * MSM_SET_POINTS + plane] = xyzz29_to_jac(v);
 }
 
@@ -999,7 +964,7 @@ __global__ __launch_bounds__(256) void msm_rowcol_quad_kernel(const XYZZ* __rest
   CQ_CRITICAL_WAVES();
   __shared__ uint32_t xs[4][4][9];
   const uint32_t set = blockIdx.y, q = blockIdx.x;  // line: row q or column q - rows
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, role = threadIdx.x & 3u, quad = threadIdx.x >> 2;
+  const uint32_t wave = threadIdx.x >> 6, role = threadIdx.x & 3u, quad = threadIdx.x >> 2;
   const XYZZ* Bk = buckets + (size_t)set * M;
   const uint32_t* Tk = t1 + (size_t)set * M;
   const bool is_row = q < rows;
@@ -1008,41 +973,14 @@ __global__ __launch_bounds__(256) void msm_rowcol_quad_kernel(const XYZZ* __rest
     Fq29 r = Fq29::zero();
     if (e < len) {
       const size_t idx = is_row ? (size_t)q * cols + e : (size_t)e * cols + (q - rows);
-      if (Tk[idx]) {
-        uint32_t w[8];
-        ld8(reinterpret_cast<const char*>(Bk + idx) + 32 * role, w);
-        r = Fq29::unpack(w);
-      }
+      if (Tk[idx]) r = quad_load(Bk + idx, role);
     }
     return r;
   };
   const Fq29 F0 = load_coord(quad), G0 = load_coord(quad + 64);
-  Fq29 F = quad_add(F0, G0);
-  auto other = [&](const Fq29& a, int lanes) {
-    Fq29 r;
-    CQ_UNROLL for (int k = 0; k < 9; k++) r.a[k] = __shfl_xor(a.a[k], lanes, 64);
-    return r;
-  };
-#pragma unroll 1
-  for (int d = 32; d >= 4; d >>= 1) F = quad_add(F, other(F, d));
-  if (lane < 4) {
-    CQ_UNROLL for (int k = 0; k < 9; k++) xs[wave][role][k] = F.a[k];
-  }
-  __syncthreads();
+  const Fq29 F = quad_block_sum(quad_add(F0, G0), xs);
   if (wave != 0) return;
-  F = Fq29::zero();
-  if (lane < 16) {
-    CQ_UNROLL for (int k = 0; k < 9; k++) F.a[k] = xs[lane >> 2][role][k];
-  }
-#pragma unroll 1
-  for (int d = 8; d >= 4; d >>= 1) F = quad_add(F, other(F, d));
-  // packed form: x below 2^256 needs the reduction (8 p > 2^256); the other coordinates are below 4 p
-  const Fq29 red = F.reduced();
-  if (lane < 4) {
-    uint32_t w[8];
-    (role == 0 ? red : F).pack(w);
-    st8(reinterpret_cast<char*>(sums + (size_t)set * (rows + cols) + q) + 32 * role, w);
-  }
+  quad_store(sums + (size_t)set * (rows + cols) + q, F);
 }
 
 // The same bit-plane sums with FOUR lanes per addition (quad_add, curve29.hpp), for launches of a few bucket sets -- the
@@ -1059,41 +997,20 @@ __global__ __launch_bounds__(256) void msm_weighted_quad_kernel(const XYZZ* __re
   const uint32_t which = plane >= 7 ? 1u : 0u;
   const XYZZ* X = sums + (size_t)set * (rows + cols) + (which ? rows : 0);
   const uint32_t count = which ? cols : rows;
-  auto load_coord = [&](uint32_t j) {  // coordinate `role` of X[j]: 32 bytes of the packed form
-    uint32_t w[8];
-    ld8(reinterpret_cast<const char*>(X + j) + 32 * role, w);
-    return Fq29::unpack(w);
-  };
   Fq29 F = Fq29::zero();
   if (plane < 14) {
     const uint32_t t = plane - 7 * which;
     const uint32_t j = ((quad >> t) << (t + 1)) | (1u << t) | (quad & ((1u << t) - 1u));  // quad-th index with bit t set
-    if (j < count) F = load_coord(j);
+    if (j < count) F = quad_load(X + j, role);
   } else {
-    if (quad < count) F = load_coord(quad);
+    if (quad < count) F = quad_load(X + quad, role);
     Fq29 G = Fq29::zero();
-    if (quad + 64 < count) G = load_coord(quad + 64);
+    if (quad + 64 < count) G = quad_load(X + quad + 64, role);
     F = quad_add(F, G);
   }
-  auto other = [&](const Fq29& a, int lanes) {
-    Fq29 r;
-    CQ_UNROLL for (int k = 0; k < 9; k++) r.a[k] = __shfl_xor(a.a[k], lanes, 64);
-    return r;
-  };
-#pragma unroll 1
-  for (int d = 32; d >= 4; d >>= 1) F = quad_add(F, other(F, d));  // 16 quads of the wave -> every quad holds their sum
-  if (lane < 4) {
-    CQ_UNROLL for (int k = 0; k < 9; k++) xs[wave][role][k] = F.a[k];
-  }
-  __syncthreads();
+  F = quad_block_sum(F, xs);
   if (wave != 0) return;
-  F = Fq29::zero();
-  if (lane < 16) {
-    CQ_UNROLL for (int k = 0; k < 9; k++) F.a[k] = xs[lane >> 2][role][k];
-  }
-#pragma unroll 1
-  for (int d = 8; d >= 4; d >>= 1) F = quad_add(F, other(F, d));
-  const XYZZ29 v = {quad_perm<0, 0, 0, 0>(F), quad_perm<1, 1, 1, 1>(F), quad_perm<2, 2, 2, 2>(F), quad_perm<3, 3, 3, 3>(F)};
+  const XYZZ29 v = quad_to_xyzz29(F);
   if (lane == 0) out[(size_t)set * MSM_SET_POINTS + plane] = xyzz29_to_jac(v);
 }
 
@@ -1188,7 +1105,7 @@ __global__ __launch_bounds__(SHORT_THREADS) void msm_short_kernel(MsmPtrs sc, Ms
     (void)short_rank(hist, byte != 128u, key_of(byte) & 127u, lane);
   }
   __syncthreads();
-  wave0_scan128(hist, bstart);
+  wave0_scan<SHORT_BUCKETS>(hist, bstart);
   __syncthreads();
   if (t == 0) bstart[SHORT_BUCKETS] = bstart[SHORT_BUCKETS - 1] + hist[SHORT_BUCKETS - 1];
 #pragma unroll 1
@@ -1272,11 +1189,8 @@ __global__ __launch_bounds__(SHORT_THREADS) void msm_short_kernel(MsmPtrs sc, Ms
 #pragma unroll 1
       for (uint32_t j = sub; j < parts; j += 2) xyzz29_add(acc, load_xyzz29(slots + tlo + j + b));
     }
-    const XYZZ29 o = xyzz29_shfl_down(acc, 1);  // all lanes take part in the shuffle
-    if (own && sub == 0) {
-      xyzz29_add(acc, o);
-      store_xyzz29(bk + b, acc);
-    }
+    xyzz29_tree_sum<2>(acc, sub, own);
+    if (own && sub == 0) store_xyzz29(bk + b, acc);
   }
   {
     uint32_t nlong = 0;
@@ -1290,11 +1204,7 @@ __global__ __launch_bounds__(SHORT_THREADS) void msm_short_kernel(MsmPtrs sc, Ms
       XYZZ29 acc = XYZZ29::identity();
 #pragma unroll 1
       for (uint32_t j = lane; j < parts; j += 64) xyzz29_add(acc, load_xyzz29(slots + tlo + j + b));
-#pragma unroll 1
-      for (int delta = 32; delta >= 1; delta >>= 1) {
-        const XYZZ29 o = xyzz29_shfl_down(acc, delta);
-        if ((int)lane < delta) xyzz29_add(acc, o);
-      }
+      xyzz29_tree_sum<64>(acc, lane);
       if (lane == 0) store_xyzz29(bk + b, acc);
     }
   }
@@ -1302,16 +1212,6 @@ __global__ __launch_bounds__(SHORT_THREADS) void msm_short_kernel(MsmPtrs sc, Ms
 
   // ---- 3. bit planes of d - 1 and the total, sixteen quads per wave (lane r of a quad: coordinate r) ----
   const uint32_t role = t & 3u, quad = lane >> 2;
-  auto load_coord = [&](uint32_t j) {
-    uint32_t wd[8];
-    ld8(reinterpret_cast<const char*>(bk + j) + 32 * role, wd);
-    return Fq29::unpack(wd);
-  };
-  auto other = [&](const Fq29& a, int lanes) {
-    Fq29 r;
-    CQ_UNROLL for (int k = 0; k < 9; k++) r.a[k] = __shfl_xor(a.a[k], lanes, 64);
-    return r;
-  };
   G1Jac* o = out + ((size_t)m * MSM_SHORT_W + w) * MSM_SET_POINTS;
   Fq29 first = Fq29::zero();
 #pragma unroll 1
@@ -1320,15 +1220,14 @@ __global__ __launch_bounds__(SHORT_THREADS) void msm_short_kernel(MsmPtrs sc, Ms
     const uint32_t tb = rep == 0 ? wave : wave < 3 ? wave + 4 : 3u;
     const uint32_t bit = rep == 1 && wave == 3 ? 0u : 1u << tb;
     auto index = [&](uint32_t j) { return ((j >> tb) << (tb + 1)) | bit | (j & ((1u << tb) - 1u)); };
-    Fq29 F = load_coord(index(quad));
+    Fq29 F = quad_load(bk + index(quad), role);
 #pragma unroll 1
-    for (uint32_t k = 1; k < 4; k++) F = quad_add(F, load_coord(index(quad + 16 * k)));
-#pragma unroll 1
-    for (int d = 32; d >= 4; d >>= 1) F = quad_add(F, other(F, d));  // every quad ends with the wave's sum
+    for (uint32_t k = 1; k < 4; k++) F = quad_add(F, quad_load(bk + index(quad + 16 * k), role));
+    F = quad_wave_sum(F, 32);
     if (rep == 0) first = F;
     else if (wave == 3) F = quad_add(first, F);  // plane 3 + its complement: the total
     const uint32_t slot = rep == 0 ? 7 + wave : wave < 3 ? 11 + wave : MSM_SET_POINTS - 1;
-    const XYZZ29 v = {quad_perm<0, 0, 0, 0>(F), quad_perm<1, 1, 1, 1>(F), quad_perm<2, 2, 2, 2>(F), quad_perm<3, 3, 3, 3>(F)};
+    const XYZZ29 v = quad_to_xyzz29(F);
     if (lane == 0) o[slot] = xyzz29_to_jac(v);
   }
 }
@@ -1424,6 +1323,24 @@ MsmLayout::MsmLayout(uint32_t n_, uint32_t c_, uint32_t batch_, bool pre_) : n(n
   total = o;
 }
 
+// the partition pass of a table-mode launch: histogram, scan (which also settles the launch's s1), scatter
+struct PartPass1 {
+  hipStream_t s;
+  dim3 hgrid, sgrid;
+  const Fr* const* scalars;
+  const uint64_t *lens, *list_src;
+  uint32_t c, W, npart, per_lane, batch, s1, P;
+  uint32_t *psize /* [P] sizes, [P] cursors */, *poff, *s1_dev, *part_pay;
+  void* part_low;
+};
+template <uint32_t CW, uint32_t NW, typename LowT>
+static void launch_part_pass1(const PartPass1& a) {
+  msm_part_hist_kernel<CW, NW><<<a.hgrid, DIGITS_LDS_THREADS, 0, a.s>>>(a.scalars, a.lens, a.c, a.W, a.npart, a.per_lane, a.psize);
+  msm_part_scan_kernel<<<1, 1024, 0, a.s>>>(a.psize, a.P, a.poff, a.list_src, a.batch, a.npart, a.s1, a.s1_dev);
+  msm_part_scatter_kernel<CW, NW, LowT><<<a.sgrid, PSC_THREADS, 0, a.s>>>(a.scalars, a.lens, a.c, a.W, a.npart, a.poff, a.psize + a.P, a.part_pay,
+                                                                          (LowT*)a.part_low);
+}
+
 int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* const* bases_host_ptrs, const size_t* lens,
             uint32_t n, uint32_t c, uint32_t batch, bool pre, const size_t* table_strides, void* workspace,
             G1Jac* window_sums_dev, G1Affine* raw_out, uint32_t raw_count) {
@@ -1509,30 +1426,22 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
     void* part_low = part_pay + (L.mid ? 2 * E : E);
     uint32_t* poff = (uint32_t*)(ws + L.off_poff);
     uint32_t* cursor = (uint32_t*)(ws + L.off_cursor);
-    uint32_t* psize = (uint32_t*)(ws + L.off_psize);
-    uint32_t* pcursor = psize + P;
+    uint32_t* psize = (uint32_t*)(ws + L.off_psize);  // P sizes, then the P cursors of the scatter
     // scalars per lane of the partition histogram: few in a small launch (more workgroups in flight: the kernel is
     // latency-bound there), DIGITS_LDS_PER_LANE in a large one (fewer device atomics: 128 per workgroup)
     const uint32_t per_lane = (uint64_t)n * batch <= (1u << 21) ? 2u : DIGITS_LDS_PER_LANE;
     const uint32_t hist_chunk = DIGITS_LDS_THREADS * per_lane;
     const dim3 hgrid((n + hist_chunk - 1) / hist_chunk, batch), sgrid((n + PSC_THREADS - 1) / PSC_THREADS, batch);
     // window width and count as compile-time constants for the table widths in use (see msm_part_hist_kernel)
-#define CQ_PART_PASS1(CW, NW, LOWT)                                                                                               \
-  do {                                                                                                                            \
-    msm_part_hist_kernel<CW, NW><<<hgrid, DIGITS_LDS_THREADS, 0, s>>>(d_scalars, d_lens, c, W, L.npart, per_lane, psize);          \
-    msm_part_scan_kernel<<<1, 1024, 0, s>>>(psize, P, poff, d_src, batch, L.npart, s1, s1_dev);                                  \
-    msm_part_scatter_kernel<CW, NW, LOWT><<<sgrid, PSC_THREADS, 0, s>>>(d_scalars, d_lens, c, W, L.npart, poff, pcursor, part_pay, \
-                                                                        (LOWT*)part_low);                                         \
-  } while (0)
-    if (c == 15 && W == 17) CQ_PART_PASS1(15, 17, uint8_t);
-    else if (c == 16 && W == 16) CQ_PART_PASS1(16, 16, uint8_t);
-    else if (c == 17 && W == 15) CQ_PART_PASS1(17, 15, uint8_t);
-    else if (c == 18 && W == 15) CQ_PART_PASS1(18, 15, uint16_t);
-    else if (c == 19 && W == 14) CQ_PART_PASS1(19, 14, uint16_t);
-    else if (c == 20 && W == 13) CQ_PART_PASS1(20, 13, uint16_t);
-    else if (L.mid) CQ_PART_PASS1(0, 0, uint16_t);
-    else CQ_PART_PASS1(0, 0, uint8_t);
-#undef CQ_PART_PASS1
+    const PartPass1 pp{s, hgrid, sgrid, d_scalars, d_lens, d_src, c, W, L.npart, per_lane, batch, s1, P, psize, poff, s1_dev, part_pay, part_low};
+    if (c == 15 && W == 17) launch_part_pass1<15, 17, uint8_t>(pp);
+    else if (c == 16 && W == 16) launch_part_pass1<16, 16, uint8_t>(pp);
+    else if (c == 17 && W == 15) launch_part_pass1<17, 15, uint8_t>(pp);
+    else if (c == 18 && W == 15) launch_part_pass1<18, 15, uint16_t>(pp);
+    else if (c == 19 && W == 14) launch_part_pass1<19, 14, uint16_t>(pp);
+    else if (c == 20 && W == 13) launch_part_pass1<20, 13, uint16_t>(pp);
+    else if (L.mid) launch_part_pass1<0, 0, uint16_t>(pp);
+    else launch_part_pass1<0, 0, uint8_t>(pp);
     // workgroups per partition in the bucket passes: PART_SPLIT when partitions hold many tiles, one when they hold one
     auto split_for = [&](uint32_t parts) {
       const uint64_t tiles = (uint64_t)W * n * batch / ((uint64_t)parts * PART_TILE) + 1;
@@ -1617,9 +1526,12 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
     // (CQ_MSM_COMBINE_WAVE_BLOCKS: tests shrink the cap so that small launches stride too)
     static const uint32_t wave_cap = getenv("CQ_MSM_COMBINE_WAVE_BLOCKS") ? (uint32_t)std::max(1, atoi(getenv("CQ_MSM_COMBINE_WAVE_BLOCKS"))) : MSM_COMBINE_WAVE_BLOCKS;
     const uint32_t wv_blocks = (uint32_t)std::min<uint64_t>((L.tmax[k] + 3) / 4, wave_cap);
-    if (q == 4) msm_combine_level_kernel<4><<<cs_blocks + wv_blocks, 256, 0, s>>>(part[(k - 1) & 1], t_prev, off_prev, t_cur, off_cur, Bt, cs_blocks, part[k & 1], buckets);
-    else if (q == 2) msm_combine_level_kernel<2><<<cs_blocks + wv_blocks, 256, 0, s>>>(part[(k - 1) & 1], t_prev, off_prev, t_cur, off_cur, Bt, cs_blocks, part[k & 1], buckets);
-    else msm_combine_level_kernel<1><<<cs_blocks + wv_blocks, 256, 0, s>>>(part[(k - 1) & 1], t_prev, off_prev, t_cur, off_cur, Bt, cs_blocks, part[k & 1], buckets);
+    auto combine = [&](auto kernel) {
+      kernel<<<cs_blocks + wv_blocks, 256, 0, s>>>(part[(k - 1) & 1], t_prev, off_prev, t_cur, off_cur, Bt, cs_blocks, part[k & 1], buckets);
+    };
+    if (q == 4) combine(msm_combine_level_kernel<4>);
+    else if (q == 2) combine(msm_combine_level_kernel<2>);
+    else combine(msm_combine_level_kernel<1>);
   }
   if (raw_out) {  // a bucket-sum launch ends here: no weighted sum over the buckets
     msm_buckets_affine_kernel<<<dim3((raw_count + 255) / 256, batch), 256, 0, s>>>(buckets, tk, L.B, raw_count, raw_out);

@@ -46,6 +46,7 @@ TABLE = [
     (C1, "r.x = Fq29::mul(r.x, f);", "mul", [(W, L29), (1, L29)], 2),                                    # load_affine29, mont256
     (C1, "r.y = Fq29::mul(r.y, f);", "mul", [(W, L29), (1, L29)], 2),
     (C1, "const Fq29 xr = v.x.reduced();", "reduced", _n(8), 2),                                           # store_xyzz29
+    (C1, "const Fq29 red = F.reduced();", "reduced", _n(8), 2),                                            # quad_store (lane 0: x)
     (C1, "const Fq29 v = u.sqr();                      // 16", "sqr", [(4, L30)], 2),                       # dbl_affine, u = y + y
     (C1, "const Fq29 w = u * v;                        // 8", "mul", [(4, L30), (2, L29)], 2),
     (C1, "const Fq29 s = a.x * v;", "mul", _n(2, 2), 2),

@@ -401,7 +401,11 @@ def test_srs_objects_destroyed_before_their_key():
 def test_quad_add_matches_lane_serial_addition(tmp_path):
     """The four-lane addition of the launch tails (curve29.hpp quad_add; msm_rowcol_quad_kernel, msm_weighted_quad_kernel)
     against xyzz29_add on every kind of operand pair: general, either or both the identity, equal points (doubling),
-    opposite points (cancellation).  Built from tools/micro/quad_add_test.hip with hipcc on the GPU box."""
+    opposite points (cancellation).  The same program checks the sums built on it and on xyzz29_add -- quad_wave_sum,
+    quad_block_sum, quad_store then load_xyzz29, xyzz29_tree_sum<2 / 4 / 16 / 32 / 64> -- against a lane-serial xyzz29_add chain
+    over the same 1, 2, 3, 5, 16, 17, 64 and 128 terms (distinct points; identities in some slots; one point in every slot: a
+    doubling at every tree level; opposite pairs), equal after normalising to affine: one launch per (terms, mix).
+    Built from tools/micro/quad_add_test.hip with hipcc on the GPU box."""
     import shutil
     import subprocess
 
@@ -415,6 +419,8 @@ def test_quad_add_matches_lane_serial_addition(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr[-1000:]
     assert r.stdout.count("0 of 64 lanes disagree") == 6, r.stdout
+    sums = [l for l in r.stdout.splitlines() if l.startswith("sums n")]
+    assert len(sums) == 8 * 4 and all(l.endswith("results, 0 disagree") for l in sums), r.stdout
 
 
 def test_combine_wave_half_strides_over_more_slots_than_waves():
