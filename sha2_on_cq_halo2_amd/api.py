@@ -166,6 +166,17 @@ def _ctx_permute_expression_pair(self, k: int, input_values: np.ndarray, table_v
     return oa.download((usable, 4), np.uint64), ot.download((usable, 4), np.uint64)
 
 
+def _ctx_g_to_lagrange(self, points: np.ndarray, k: int) -> np.ndarray:
+    """`g_to_lagrange(g_projective, k)` (arithmetic.rs:277-301) on the device: 2^k affine points in, the Lagrange-basis
+    points out (uint64[2^k, 8]).  Any points, the identity (0, 0) included; nothing is validated."""
+    g = _g1(points)
+    if g.shape[0] != 1 << k:
+        raise CqError(-1, "g_to_lagrange: len != 1 << k")
+    dg, out = self.to_device(g), self.alloc(g.shape[0] * 64)
+    self._chk(self.lib.cq_g_to_lagrange_dev(self.h, dg.ptr, k, out.ptr))
+    return out.download((g.shape[0], 8), np.uint64)
+
+
 def _g2(a) -> np.ndarray:
     a = np.ascontiguousarray(a, dtype=np.uint64)
     assert a.ndim == 2 and a.shape[1] == 16, "expected uint64[n,16] G2 affine points"
@@ -193,6 +204,7 @@ Context.best_multiexp_g2 = _ctx_best_multiexp_g2
 Context.best_multiexp_g2_dev = _ctx_best_multiexp_g2_dev
 Context.set_msm_table_window = _ctx_set_msm_table_window
 Context.permute_expression_pair = _ctx_permute_expression_pair
+Context.g_to_lagrange = _ctx_g_to_lagrange
 Context.best_multiexp = _ctx_best_multiexp
 Context.best_multiexp_dev = _ctx_best_multiexp_dev
 Context.msm_batch_dev = _ctx_msm_batch_dev

@@ -277,6 +277,70 @@ def test_permute_expression_pair_matches_oracle(ctx, k, usable, distinct):
             assert e.value.code == -4
 
 
+def _join_limbs(l):
+    return l[0] | (l[1] << 64) | (l[2] << 128) | (l[3] << 192)
+
+
+def _limb_decided_keys(count):
+    """`count` distinct canonical values whose order is decided in every 64-bit limb: a shared random base with exactly
+    one limb L in 0..3 varied (40 small deltas per limb: the limbs above L are equal, the ones below too), and
+    adversarial pairs x < y in which limb L (1, 2, 3) orders one way and EVERY lower limb the other way.  The pairs come
+    first, then the single-limb values round-robin over the limbs, so that a short prefix still holds every kind."""
+    rng = B.Xoshiro256ss(0x11b5)
+    rs = np.random.RandomState(64)
+    top = P >> 192
+    base = [rng.next_u64() >> 1 for _ in range(3)] + [rng.next_u64() % (top - 1024)]  # limb 3 stays below the modulus' top limb
+    out = []
+    for L in (1, 2, 3):
+        for i in range(2):
+            hi = base[L] + 300 + 2 * i
+            x = [(1 << 64) - 1 - i] * L + [hi] + base[L + 1:]
+            y = [i] * L + [hi + 1] + base[L + 1:]
+            assert _join_limbs(x) < _join_limbs(y) and all(x[l] > y[l] for l in range(L))
+            out += [_join_limbs(x), _join_limbs(y)]
+    per_limb = []
+    for L in range(4):
+        deltas = rs.choice(np.arange(1, 200), size=40, replace=False)
+        per_limb.append([_join_limbs(base[:L] + [base[L] + int(d)] + base[L + 1:]) for d in deltas])
+    for group in zip(*per_limb):
+        out += list(group)
+    assert len(set(out)) == len(out) == 172 and all(v < P for v in out)
+    return out[:count]
+
+
+@pytest.mark.parametrize("k,usable", [(5, 26), (11, 2042), (13, 8186)])
+def test_permute_expression_pair_keys_decided_in_every_limb(ctx, k, usable):
+    """The sort's 256-bit comparison (`key_less`, csrc/lksort.hip) on keys that differ in exactly one limb, for every limb,
+    and on pairs where a higher limb and all lower limbs disagree in direction -- the one-block kernel (k = 5), one LDS
+    tile (k = 11), streaming steps plus LDS merges (k = 13) -- against the oracle's restatement, value for value."""
+    from oracle import plonk as OP
+    from sha2_on_cq_halo2_amd import CqError
+
+    values = _limb_decided_keys(min(usable, 172))
+    if usable == 26:  # every kind is in the short prefix: adversarial pairs for three limbs, single-limb values for four
+        assert len(values) == 26
+    rs = np.random.RandomState(k)
+    table = [values[i % len(values)] for i in range(usable)]  # every value at least once, padded with repeats
+    table = [table[i] for i in rs.permutation(usable)]
+    n, bf = 1 << k, (1 << k) - usable - 1
+    inputs = {"draws": [values[int(i)] for i in rs.randint(0, len(values), size=usable)],
+              "one value": [values[len(values) // 2]] * usable}
+    for what, inp in inputs.items():
+        exp_in, exp_tab = OP.permute_expression_pair(n, bf, inp, table, B.Xoshiro256ss(1))
+        got_in, got_tab = ctx.permute_expression_pair(k, B.to_mont_limbs(inp), B.to_mont_limbs(table))
+        assert np.array_equal(got_in, B.to_mont_limbs(exp_in[:usable])), what
+        assert np.array_equal(got_tab, B.to_mont_limbs(exp_tab[:usable])), what
+    # an absent value that differs from a present one only in limb 1
+    present = values[6]
+    absent = present ^ (1 << (64 + 40))
+    assert absent not in values and absent < P and (absent ^ present) >> 64 < (1 << 64) and (absent ^ present) & ((1 << 64) - 1) == 0
+    bad = list(inputs["draws"])
+    bad[usable // 3] = absent
+    with pytest.raises(CqError) as e:
+        ctx.permute_expression_pair(k, B.to_mont_limbs(bad), B.to_mont_limbs(table))
+    assert e.value.code == -4
+
+
 def test_permute_expression_pair_edge_cases(ctx):
     """Empty and one-row inputs, a usable range equal to the whole domain, and argument errors."""
     from oracle import plonk as OP
