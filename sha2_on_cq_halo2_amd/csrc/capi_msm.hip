@@ -311,12 +311,10 @@ int cq_msm_bucket_sums_dev(cq_ctx* c, const uint64_t* const* bases_dev, size_t a
       buckets > ((size_t)1 << (MSM_TABLE_C - 1)))
     return CQ_ERR_ARG;
   CQ_HIP(c, hipSetDevice(c->device));
-  void *sc, *conv = nullptr;
+  void* conv = nullptr;
   int rc;
-  if ((rc = c->ensure_scratch(Scratch::EntryA, n * sizeof(Fr), &sc)) != CQ_OK) return rc;
   if (!packed && (rc = c->ensure_scratch(Scratch::EntryB, arrays * n * sizeof(G1Affine), &conv)) != CQ_OK) return rc;
-  if (msm_index_scalars(c, index_dev, (uint32_t)n, (uint32_t)buckets, (Fr*)sc) != 0) return c->fail(CQ_ERR_HIP, "bucket sums: scalars");
-  std::vector<const Fr*> scal(arrays, (const Fr*)sc);
+  std::vector<const uint32_t*> idx(arrays, index_dev);
   std::vector<const G1Affine*> bs(arrays);
   for (size_t a = 0; a < arrays; a++) {
     if (!bases_dev[a]) return CQ_ERR_ARG;
@@ -327,7 +325,7 @@ int cq_msm_bucket_sums_dev(cq_ctx* c, const uint64_t* const* bases_dev, size_t a
       bs[a] = dst;
     }
   }
-  if (msm_bucket_sums(c, scal.data(), bs.data(), (uint32_t)n, (uint32_t)arrays, (uint32_t)buckets, (G1Affine*)out_dev) != 0)
+  if (msm_bucket_sums(c, idx.data(), bs.data(), (uint32_t)n, (uint32_t)arrays, (uint32_t)buckets, (G1Affine*)out_dev) != 0)
     return c->fail(CQ_ERR_HIP, "bucket-sum launch failed");
   return c->wait(c->stream);
 }

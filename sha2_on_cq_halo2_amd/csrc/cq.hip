@@ -39,7 +39,7 @@ constexpr uint32_t R1_ROWS = 4;
 __global__ __launch_bounds__(256) void cq_round1_kernel(CqRound1Batch batch, uint32_t u, uint32_t* __restrict__ err) {
   const CqRound1Args& a = batch.a[blockIdx.y];
   uint32_t* __restrict__ m_counts = batch.m_counts[blockIdx.y];
-  Fr* __restrict__ bucket = batch.bucket[blockIdx.y];
+  uint32_t* __restrict__ bucket = batch.bucket[blockIdx.y];
   uint32_t found[R1_ROWS];
 #pragma unroll
   for (uint32_t r = 0; r < R1_ROWS; r++) {  // independent probe chains, in flight together
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void cq_round1_kernel(CqRound1Batch batch, uin
       idx = ix;
     }
     found[r] = bad ? EMPTY : idx;
-    if (bucket && row < batch.n) st(bucket + row, row >= u ? Fr::from_u64(batch.blind_bucket + 1) : bad ? Fr::zero() : Fr::from_u64(idx + 1));
+    if (bucket && row < batch.n) bucket[row] = row >= u ? batch.blind_bucket : bad ? EMPTY : idx;
   }
   uint32_t held = EMPTY, held_cnt = 0;
 #pragma unroll
@@ -230,7 +230,7 @@ int cq_table_build_index(cq_ctx* c, const Fr* values, uint32_t N, uint32_t** slo
 }
 
 int cq_round1(cq_ctx* c, const CqRound1Batch& b, uint32_t u, uint32_t* err_dev) {
-  const uint32_t rows = b.n > u ? b.n : u;  // with bucket scalars the grid covers the blinding rows too
+  const uint32_t rows = b.n > u ? b.n : u;  // with bucket indices the grid covers the blinding rows too
   if (u && b.count) cq_round1_kernel<<<dim3((rows + 256 * R1_ROWS - 1) / (256 * R1_ROWS), b.count), 256, 0, c->stream>>>(b, u, err_dev);
   return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "cq_round1 launch failed");
 }

@@ -26,9 +26,10 @@ constexpr uint32_t CQ_ROUND1_BATCH = 8;
 struct CqRound1Batch {
   CqRound1Args a[CQ_ROUND1_BATCH];
   uint32_t* m_counts[CQ_ROUND1_BATCH];
-  // optional, n elements per lookup: the table row j(i) every row looks up, as the scalar j(i) + 1 of a bucket-sum launch
-  // (msm_bucket_sums); the rows from u on, which carry beta alone in round 2, name the extra bucket `blind_bucket`
-  Fr* bucket[CQ_ROUND1_BATCH] = {};
+  // optional, n elements per lookup: the table row j(i) every row looks up, as the index of a bucket-sum launch
+  // (msm_bucket_sums); the rows from u on, which carry beta alone in round 2, name the extra bucket `blind_bucket`, and a row
+  // whose value is not in the table names none (0xFFFFFFFF)
+  uint32_t* bucket[CQ_ROUND1_BATCH] = {};
   uint32_t blind_bucket = 0, n = 0;
   uint32_t count;
 };

@@ -31,6 +31,7 @@
 //   6. host      : table mode returns one Jacobian point per MSM; plain mode W window sums per MSM, folded by a
 //                  Horner over windows (c doublings each) on the host.
 // Plain-mode MSMs of at most MSM_SHORT_MAX terms skip all of that: msm_short_kernel, one workgroup per (MSM, 8-bit window).
+// Bucket-sum launches (msm_bucket_sums) are given bucket numbers instead of scalars: steps 1 and 2 are the index front's two kernels.
 // What several kernels share exists once: the LDS sort of the bucket and refinement passes is part_count / part_tile_place
 // below, named by a policy (BucketBins<PB>, RefineBins); the shuffle tree of the lane sums is xyzz29_tree_sum<WIDTH> and the
 // four-lane sums are quad_load / quad_wave_sum / quad_block_sum / quad_store / quad_to_xyzz29, next to quad_add in curve29.hpp.
@@ -514,6 +515,181 @@ __global__ __launch_bounds__(256) void msm_alias_counts_kernel(uint32_t* __restr
   if (src != m && i < B) counts[(size_t)m * B + i] = counts[(size_t)src * B + i];
 }
 
+// ---- index front (bucket-sum launches): the "scalars" are bucket numbers already ---------------------------------------
+// index[i] = b < count puts row i into bucket b of its MSM, any other value nowhere: one entry per row at most, window 0,
+// no sign -- the payload is the row number.  Nothing has to be reduced, cut into digits or routed through partitions: one
+// kernel counts, one places behind the plan's list starts.  Both work on tiles of INDEX_TILE rows per workgroup and keep the
+// tile's buckets in a small LDS hash table (open addressing, INDEX_SLOTS = 2 x INDEX_TILE slots: a tile names at most
+// INDEX_TILE buckets, so a probe always ends at its own key or at a free slot), whatever `count` is.  What reaches L2 is one
+// device atomic per (tile, bucket named in it): a witness whose padded rows all look up one table row costs that bucket one
+// atomic per tile -- 128 per list at k = 18 -- where an atomic per wave would be 4 096 of ~15 ns each.  The LDS atomics are
+// thinned the same way: lanes of a wave that share a bucket send one.
+constexpr uint32_t INDEX_THREADS = 256, INDEX_PER_LANE = 8, INDEX_TILE = INDEX_THREADS * INDEX_PER_LANE;
+constexpr uint32_t INDEX_SLOTS = 2 * INDEX_TILE, INDEX_NONE = 0xffffffffu;
+constexpr uint32_t INDEX_RANK_BITS = 12;  // a placed entry: slot << INDEX_RANK_BITS | rank inside the tile's run
+static_assert(INDEX_TILE <= (1u << INDEX_RANK_BITS) && INDEX_SLOTS <= (1u << (31 - INDEX_RANK_BITS)), "slot and rank share a word");
+
+// the slot of bucket b in the tile's table, claimed on first sight
+static __device__ __forceinline__ uint32_t index_slot(uint32_t* keys, uint32_t b) {
+  uint32_t s = (b * 0x9e3779b1u) >> 20 & (INDEX_SLOTS - 1);
+  for (uint32_t probe = 0; probe < INDEX_SLOTS; probe++) {  // (ends long before: at most INDEX_TILE slots are ever taken)
+    const uint32_t prev = atomicCAS(&keys[s], INDEX_NONE, b);
+    if (prev == INDEX_NONE || prev == b) break;
+    s = (s + 1) & (INDEX_SLOTS - 1);
+  }
+  return s;
+}
+
+// counts[m * B + b] += the rows of the tile on bucket b.  A lane folds the equal neighbours among its INDEX_PER_LANE rows
+// (strided, so loads stay coalesced) into a running (bucket, count) pair as cq_round1_kernel does; the pair it ends with is
+// summed across the lanes that share it before it goes to LDS.  totals[m]: the list's entries; the workgroup that finishes
+// last settles the launch's sub-list length from them exactly as msm_part_scan_kernel does for the generic front.
+__global__ __launch_bounds__(INDEX_THREADS) void msm_index_count_kernel(const uint32_t* const* __restrict__ index, const uint64_t* __restrict__ lens,
+                                                                        const uint64_t* __restrict__ list_src, uint32_t batch, uint32_t B,
+                                                                        uint32_t count, uint32_t* __restrict__ counts, uint32_t* totals /* [batch] */,
+                                                                        uint32_t* ticket, uint32_t s1_host, uint32_t* __restrict__ s1_out) {
+  CQ_CRITICAL_WAVES();
+  __shared__ uint32_t keys[INDEX_SLOTS], cnt[INDEX_SLOTS];
+  __shared__ uint32_t tile_total;
+  const uint32_t m = blockIdx.y, t = threadIdx.x, lane = t & 63;
+  const uint32_t len = (uint32_t)lens[m];  // 0 for an MSM that reads another one's lists
+  const uint32_t base = blockIdx.x * INDEX_TILE;
+  if (base < len) {  // block-uniform
+    for (uint32_t s = t; s < INDEX_SLOTS; s += INDEX_THREADS) {
+      keys[s] = INDEX_NONE;
+      cnt[s] = 0;
+    }
+    if (t == 0) tile_total = 0;
+    __syncthreads();
+    const uint32_t* __restrict__ idx = index[m];
+    uint32_t bk[INDEX_PER_LANE];
+#pragma unroll
+    for (uint32_t k = 0; k < INDEX_PER_LANE; k++) {
+      const uint32_t i = base + k * INDEX_THREADS + t;
+      bk[k] = i < len ? idx[i] : INDEX_NONE;
+    }
+    uint32_t held = INDEX_NONE, held_cnt = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < INDEX_PER_LANE; k++) {
+      if (bk[k] >= count) continue;
+      if (bk[k] == held) {
+        held_cnt++;
+      } else {
+        if (held_cnt) atomicAdd(&cnt[index_slot(keys, held)], held_cnt);
+        held = bk[k];
+        held_cnt = 1;
+      }
+    }
+    bool pending = held_cnt != 0;
+#pragma unroll 1
+    for (int round = 0; round < 2 && __ballot(pending); round++) {
+      const int leader = __ffsll((long long)__ballot(pending)) - 1;
+      const uint32_t lb = __shfl(held, leader, 64);
+      const bool mine = pending && held == lb;
+      uint32_t c = mine ? held_cnt : 0u;
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+      if ((int)lane == leader) atomicAdd(&cnt[index_slot(keys, lb)], c);
+      if (mine) pending = false;
+    }
+    if (pending) atomicAdd(&cnt[index_slot(keys, held)], held_cnt);
+    __syncthreads();
+    uint32_t sum = 0;
+    for (uint32_t s = t; s < INDEX_SLOTS; s += INDEX_THREADS) {
+      const uint32_t h = cnt[s];
+      if (h) atomicAdd(&counts[(size_t)m * B + keys[s]], h);
+      sum += h;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == 0 && sum) atomicAdd(&tile_total, sum);
+    __syncthreads();
+    if (t == 0 && tile_total) atomicAdd(&totals[m], tile_total);
+  }
+  if (t) return;
+  __threadfence();
+  if (atomicAdd(ticket, 1u) != gridDim.x * gridDim.y - 1) return;
+  __threadfence();
+  uint64_t entries = 0;
+  for (uint32_t q = 0; q < batch; q++) entries += atomicAdd(&totals[(uint32_t)list_src[q]], 0u);
+  const uint32_t s1 = msm_small_launch_s1(entries);  // (the host's value stands for a launch that is not small)
+  *s1_out = entries < (uint64_t)MSM_S1 * MSM_SMALL_LANES && s1 < s1_host ? s1 : s1_host;
+}
+
+// sorted[off0[m * B + b] + rank] = i for every row i of the tile on bucket b.  The rank inside the tile comes from LDS --
+// lanes of a wave that share the bucket of the first (then the second) pending lane are ranked from one ballot and send one
+// atomic, as in msm_digits_kernel; the rest send their own -- and the tile's run inside the bucket's list is reserved with
+// one device atomic on `cursor` per bucket the tile names.  Lanes ranked together write consecutive words.
+__global__ __launch_bounds__(INDEX_THREADS) void msm_index_place_kernel(const uint32_t* const* __restrict__ index, const uint64_t* __restrict__ lens,
+                                                                        uint32_t B, uint32_t count, const uint32_t* __restrict__ off0,
+                                                                        uint32_t* __restrict__ cursor, uint32_t* __restrict__ sorted) {
+  CQ_CRITICAL_WAVES();
+  __shared__ uint32_t keys[INDEX_SLOTS], run[INDEX_SLOTS];  // run: the tile's entries on the slot's bucket, then where they go
+  const uint32_t m = blockIdx.y, t = threadIdx.x, lane = t & 63;
+  const uint32_t len = (uint32_t)lens[m];
+  const uint32_t base = blockIdx.x * INDEX_TILE;
+  if (base >= len) return;  // block-uniform
+  for (uint32_t s = t; s < INDEX_SLOTS; s += INDEX_THREADS) {
+    keys[s] = INDEX_NONE;
+    run[s] = 0;
+  }
+  __syncthreads();
+  const uint32_t* __restrict__ idx = index[m];
+  uint32_t bk[INDEX_PER_LANE], where[INDEX_PER_LANE];
+#pragma unroll
+  for (uint32_t k = 0; k < INDEX_PER_LANE; k++) {
+    const uint32_t i = base + k * INDEX_THREADS + t;
+    bk[k] = i < len ? idx[i] : INDEX_NONE;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < INDEX_PER_LANE; k++) {
+    const bool act = bk[k] < count;
+    bool pending = act, issue = act;
+    uint32_t add = 1, lead = 64, below = 0;
+#pragma unroll
+    for (int round = 0; round < 2; round++) {
+      const unsigned long long pend = __ballot(pending);
+      if (pend) {  // wave-uniform
+        const int leader = __ffsll((long long)pend) - 1;
+        const uint32_t lb = __shfl(bk[k], leader, 64);
+        const bool mine = pending && bk[k] == lb;
+        const unsigned long long grp = __ballot(mine);
+        if (mine) {
+          lead = (uint32_t)leader;
+          below = __popcll(grp & ((1ull << lane) - 1ull));
+          add = __popcll(grp);
+          issue = (int)lane == leader;
+          pending = false;
+        }
+      }
+    }
+    uint32_t slot = 0, first = 0;
+    if (issue) {
+      slot = index_slot(keys, bk[k]);
+      first = atomicAdd(&run[slot], add);
+    }
+    const uint32_t lslot = __shfl(slot, lead & 63, 64), lfirst = __shfl(first, lead & 63, 64);  // every lane takes part
+    if (lead < 64) {
+      slot = lslot;
+      first = lfirst + below;
+    }
+    where[k] = act ? (slot << INDEX_RANK_BITS) | first : INDEX_NONE;
+  }
+  __syncthreads();
+  for (uint32_t s = t; s < INDEX_SLOTS; s += INDEX_THREADS) {
+    const uint32_t h = run[s];
+    if (h) {
+      const size_t g = (size_t)m * B + keys[s];
+      run[s] = off0[g] + atomicAdd(&cursor[g], h);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t k = 0; k < INDEX_PER_LANE; k++)
+    if (where[k] != INDEX_NONE)
+      sorted[run[where[k] >> INDEX_RANK_BITS] + (where[k] & ((1u << INDEX_RANK_BITS) - 1u))] = base + k * INDEX_THREADS + t;
+}
+
 // ---- 2. plan: exclusive scans over the flat bucket array -----------------------------------------
 // Sequence 0 is the histogram itself (-> list start of every bucket); sequence k >= 1 is the
 // number of level-k sub-lists of every bucket: t1 = ceil(cnt/S1); t_k = ceil(t_{k-1}/S2) while t_{k-1} > MSM_SHORT_MIN,
@@ -850,19 +1026,9 @@ int msm_bases29(cq_ctx* ctx, const G1Affine* bases, uint32_t n, G1Affine* out) {
   msm_bases29_kernel<<<(n + 255) / 256, 256, 0, ctx->stream>>>(bases, out, n);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-__global__ __launch_bounds__(256) void msm_index_scalars_kernel(const uint32_t* __restrict__ index, uint32_t n, uint32_t count, Fr* __restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t j = index[i];
-  out[i] = j < count ? Fr::from_u64(j + 1) : Fr::zero();
-}
-int msm_index_scalars(cq_ctx* ctx, const uint32_t* index, uint32_t n, uint32_t count, Fr* out) {
-  msm_index_scalars_kernel<<<(n + 255) / 256, 256, 0, ctx->stream>>>(index, n, count, out);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 
 // ---- bucket-sum launches (msm_bucket_sums): the first `count` buckets of every MSM as affine points ------------------
-// A launch whose scalars are small non-negative integers d_i = j(i) + 1 < 2^(c-1) has one entry per scalar, in window 0, and
+// A launch that is given the bucket j(i) of every point i (the index front) has one entry per point at most, in window 0, and
 // bucket j ends up holding sum_{i : j(i) = j} base[i]: the launch stops there and hands the bucket sums out in the callers'
 // R = 2^256 affine layout (one inversion per bucket, all independent), ready to be the bases of a later MSM.  A bucket
 // without entries was never written (msm_rowcol_kernel) and stands for the identity.
@@ -1343,9 +1509,13 @@ static void launch_part_pass1(const PartPass1& a) {
 
 int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* const* bases_host_ptrs, const size_t* lens,
             uint32_t n, uint32_t c, uint32_t batch, bool pre, const size_t* table_strides, void* workspace,
-            G1Jac* window_sums_dev, G1Affine* raw_out, uint32_t raw_count) {
+            G1Jac* window_sums_dev, G1Affine* raw_out, uint32_t raw_count, const uint32_t* const* index_host_ptrs) {
   hipStream_t s = ctx->stream;
   MsmLayout L(n, c, batch, pre);
+  // index mode (msm_bucket_sums): index_host_ptrs[i] stands where scalars_host_ptrs[i] does, and names buckets directly
+  const bool by_index = index_host_ptrs != nullptr;
+  if (by_index && (!L.part_sort || L.Wb != 1 || !raw_out || raw_count > L.B)) return -2;
+  auto list_ptr = [&](uint32_t i) -> const void* { return by_index ? (const void*)index_host_ptrs[i] : (const void*)scalars_host_ptrs[i]; };
   if (pre && (n > (1u << 26) || L.W > 32)) return -4;
   if (L.tmax[0] > 0xfffffff0ull || (uint64_t)batch * L.W * n > 0xfffffff0ull) return -3;
   char* ws = (char*)workspace;
@@ -1372,14 +1542,14 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
   uint32_t alias[MSM_MAX_BATCH];
   bool any_alias = false;
   for (uint32_t i = 0; i < MSM_MAX_BATCH; i++) {
-    sp.p[i] = i < batch ? (const void*)scalars_host_ptrs[i] : nullptr;
+    sp.p[i] = i < batch ? list_ptr(i) : nullptr;
     bp.p[i] = i < batch ? (const void*)bases_host_ptrs[i] : nullptr;
     stv.s[i] = (i < batch && pre) ? (uint64_t)table_strides[i] : 0;
     lnv.s[i] = i < batch ? (uint64_t)lens[i] : 0;
     alias[i] = i;
     if (i < batch && L.part_sort)
       for (uint32_t j = 0; j < i; j++)
-        if (alias[j] == j && scalars_host_ptrs[j] == scalars_host_ptrs[i] && lens[j] == lens[i] && lens[i]) {
+        if (alias[j] == j && list_ptr(j) == list_ptr(i) && lens[j] == lens[i] && lens[i]) {
           alias[i] = j;
           lnv.s[i] = 0;
           any_alias = true;
@@ -1417,7 +1587,19 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
     const uint32_t blocks = (uint32_t)std::min<size_t>((quads + 255) / 256, 1024);
     msm_set_ptrs_kernel<<<std::max(blocks, 1u), 256, 0, s>>>(sp, bp, stv, lnv, srcv, (const void**)d_scalars, batch, (uint4*)counts, quads);
   }
-  if (L.part_sort) {
+  if (by_index) {
+    // count -> plan -> place over the rows of every list source (see "index front"); the region of the partition sizes,
+    // cleared with the counts, holds the lists' totals and the count kernel's ticket
+    uint32_t* cursor = (uint32_t*)(ws + L.off_cursor);
+    uint32_t* totals = (uint32_t*)(ws + L.off_psize);
+    const dim3 grid((n + INDEX_TILE - 1) / INDEX_TILE, batch);
+    const uint32_t* const* d_index = (const uint32_t* const*)d_scalars;
+    msm_index_count_kernel<<<grid, INDEX_THREADS, 0, s>>>(d_index, d_lens, d_src, batch, L.B, raw_count, counts, totals, totals + batch, s1, s1_dev);
+    if (any_alias) msm_alias_counts_kernel<<<dim3((L.B + 255) / 256, batch), 256, 0, s>>>(counts, d_src, L.B);
+    msm_scan_reduce_kernel<<<L.nblk, 256, 0, s>>>(counts, Bt, L.nseq, s1, s1_dev, blocksums, ticket);
+    msm_scan_apply_kernel<<<L.nblk, 256, 0, s>>>(counts, Bt, L.nseq, s1, s1_dev, blocksums, off, tk);
+    msm_index_place_kernel<<<grid, INDEX_THREADS, 0, s>>>(d_index, d_lens, L.B, raw_count, off0, cursor, sorted);
+  } else if (L.part_sort) {
     const uint32_t P = batch * L.npart;
     const uint64_t E = (uint64_t)batch * W * n;
     uint32_t* part_pay = (uint32_t*)(ws + L.off_ranks);
@@ -1484,10 +1666,10 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
   return 0;
   };
   // everything the captured kernels' arguments are made of
-  std::vector<uint64_t> sig{(uint64_t)(uintptr_t)workspace, (uint64_t)(uintptr_t)window_sums_dev, n, c, batch, pre ? 1u : 0u, s1,
+  std::vector<uint64_t> sig{(uint64_t)(uintptr_t)workspace, (uint64_t)(uintptr_t)window_sums_dev, n, c, batch, (pre ? 1u : 0u) | (by_index ? 2u : 0u), s1,
                             (uint64_t)(uintptr_t)raw_out, raw_count};
   for (uint32_t i = 0; i < batch; i++) {
-    sig.push_back((uint64_t)(uintptr_t)scalars_host_ptrs[i]);
+    sig.push_back((uint64_t)(uintptr_t)list_ptr(i));
     sig.push_back((uint64_t)(uintptr_t)bases_host_ptrs[i]);
     sig.push_back((uint64_t)lens[i]);
     sig.push_back(pre ? (uint64_t)table_strides[i] : 0);
@@ -1568,15 +1750,15 @@ bool msm_bucket_sums_fit(uint32_t n, uint32_t batch) {
   return (uint64_t)batch * L.W * n <= 0xfffffff0ull && L.tmax[0] <= 0xfffffff0ull && L.total <= ((size_t)32 << 30);
 }
 
-int msm_bucket_sums(cq_ctx* ctx, const Fr* const* scalars, const G1Affine* const* bases29, uint32_t n, uint32_t batch, uint32_t count,
+int msm_bucket_sums(cq_ctx* ctx, const uint32_t* const* index, const G1Affine* const* bases29, uint32_t n, uint32_t batch, uint32_t count,
                     G1Affine* out) {
-  const uint32_t c = MSM_TABLE_C;  // the two-pass sort's native width; every digit is below 2^(c-1), hence non-negative
+  const uint32_t c = MSM_TABLE_C;  // one bucket set of 2^(c-1) buckets per MSM, the layout of a table launch
   if (!count || count > (1u << (c - 1)) || !msm_bucket_sums_fit(n, batch)) return -2;
   MsmLayout L(n, c, batch, true);
   void* ws;
   if (ctx->ensure_scratch(Scratch::MsmWork, L.total, &ws) != 0) return -1;
   const std::vector<size_t> lens(batch, n), strides(batch, n);  // (window 0 only: the stride is never multiplied by anything but 0)
-  return msm_run(ctx, scalars, bases29, lens.data(), n, c, batch, true, strides.data(), ws, nullptr, out, count);
+  return msm_run(ctx, nullptr, bases29, lens.data(), n, c, batch, true, strides.data(), ws, nullptr, out, count, index);
 }
 
 // cols * V + U from the bit-plane sums of msm_weighted_kernel: V = sum_t 2^t R_t, U = sum_t 2^t C_t + C_total.

@@ -90,28 +90,28 @@ uint32_t msm_window_bits(uint32_t n);
 // Enqueues the whole pipeline on ctx->stream.
 // `scalars` / `bases`: HOST arrays of `batch` device pointers; window_sums_dev receives MSM_SET_POINTS points per
 // bucket set -- bit-plane sums the host folds into the set's value (msm_set_value; cols = MsmLayout::cols).
+// `index` (msm_bucket_sums only; `scalars` is then unused): bucket numbers instead of scalars, one entry per point.
 // `pre`: every bases[j] points to a precomputed table [W][table_stride] with table[w][i] = 2^(c*w)*base[i]
 // (msm_precompute_tables); then there is ONE bucket set per MSM.
 // lens[j] <= n: per-MSM lengths (one launch may mix lengths; n is the maximum)
 int msm_run(cq_ctx* ctx, const Fr* const* scalars, const G1Affine* const* bases, const size_t* lens, uint32_t n, uint32_t c,
             uint32_t batch, bool pre, const size_t* table_strides, void* workspace, G1Jac* window_sums_dev,
-            G1Affine* raw_out = nullptr, uint32_t raw_count = 0);
+            G1Affine* raw_out = nullptr, uint32_t raw_count = 0, const uint32_t* const* index = nullptr);
 // `batch` plain-mode MSMs of n <= MSM_SHORT_LIMIT terms each in ONE kernel on ctx->stream; window_sums_dev as for msm_run with
 // c = MSM_SHORT_C (MSM_SHORT_W one-row bucket sets per MSM: the column planes and the total of every set are written);
 // workspace: msm_short_workspace(n, batch) bytes
 size_t msm_short_workspace(uint32_t n, uint32_t batch);
 int msm_short_run(cq_ctx* ctx, const Fr* const* scalars, const G1Affine* const* bases, uint32_t n, uint32_t batch, void* workspace,
                   G1Jac* window_sums_dev);
-// Bucket sums instead of an MSM's value: scalars[j][i] is a small integer d in [0, count] (Montgomery form, as ever), and
-// out[j][b] = sum of bases29[j][i] over the i with d = b + 1, for b < count <= 2^14 -- affine, the callers' R = 2^256 layout,
-// the identity for a bucket nobody names.  One table-mode launch on ctx->stream (sort, accumulate, combine levels; MSMs over
-// the same scalar array share their lists); bases29: n points each in the accumulate kernel's own form (msm_bases29).
-int msm_bucket_sums(cq_ctx* ctx, const Fr* const* scalars, const G1Affine* const* bases29, uint32_t n, uint32_t batch, uint32_t count,
+// Bucket sums instead of an MSM's value: index[j][i] = b < count puts bases29[j][i] into bucket b, any other value
+// (0xFFFFFFFF included) nowhere, and out[j][b] = the sum of bucket b, for b < count <= 2^14 -- affine, the callers' R = 2^256
+// layout, the identity for a bucket nobody names.  One launch on ctx->stream in a table launch's layout (index front,
+// accumulate, combine levels; MSMs with the same index array share their lists); bases29: n points each in the accumulate
+// kernel's own form (msm_bases29).
+int msm_bucket_sums(cq_ctx* ctx, const uint32_t* const* index, const G1Affine* const* bases29, uint32_t n, uint32_t batch, uint32_t count,
                     G1Affine* out);
 // out[i] = bases[i] in the accumulate kernel's packed R' form (window 0 of a table); out == bases converts in place
 int msm_bases29(cq_ctx* ctx, const G1Affine* bases, uint32_t n, G1Affine* out);
-// out[i] = the scalar index[i] + 1 of a bucket-sum launch, zero (no bucket) for an index >= count
-int msm_index_scalars(cq_ctx* ctx, const uint32_t* index, uint32_t n, uint32_t count, Fr* out);
 // can msm_bucket_sums plan a launch of this shape (entry counts below 2^32, workspace within the launches' cap)?
 bool msm_bucket_sums_fit(uint32_t n, uint32_t batch);
 int msm_precompute_tables(cq_ctx* ctx, const G1Affine* bases, uint32_t n, uint32_t c, G1Affine* table);

@@ -688,7 +688,7 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
         ra.slots[j] = lk.tables[j]->slots;
         ra.nslots[j] = lk.tables[j]->nslots;
       }
-      r1b.bucket[r1b.count] = b_by_rows ? bpoly + l * n : nullptr;  // (b's own buffer is free until round 2 writes it)
+      r1b.bucket[r1b.count] = b_by_rows ? (uint32_t*)(bpoly + l * n) : nullptr;  // (b's own buffer is free until round 2 writes it)
       r1b.n = b_by_rows ? (uint32_t)n : 0;
       r1b.blind_bucket = (uint32_t)N;
       r1b.m_counts[r1b.count++] = m_counts_ + l * N;
@@ -699,10 +699,10 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
     }
     CQ_TRY(cq_m_to_fr(c, m_counts_, (uint32_t)(L * N), B.m_fr));  // the L vectors are adjacent
     for (size_t l0 = 0; b_by_rows && l0 < L; l0 += MSM_MAX_BATCH / 2) {
-      std::vector<const Fr*> sc;
+      std::vector<const uint32_t*> sc;
       std::vector<const G1Affine*> bs;
       for (size_t l = l0; l < std::min(L, l0 + MSM_MAX_BATCH / 2); l++)
-        for (int q = 0; q < 2; q++) { sc.push_back(bpoly + l * n); bs.push_back(pk->b_row_bases[q]); }
+        for (int q = 0; q < 2; q++) { sc.push_back((const uint32_t*)(bpoly + l * n)); bs.push_back(pk->b_row_bases[q]); }
       if (msm_bucket_sums(c, sc.data(), bs.data(), (uint32_t)n, (uint32_t)sc.size(), (uint32_t)(N + 1), B.b_sums + 2 * l0 * (N + 1)) != 0)
         return c->fail(CQ_ERR_HIP, "bucket-sum launch failed");
     }
