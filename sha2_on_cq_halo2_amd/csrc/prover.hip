@@ -297,7 +297,7 @@ struct Arena {
 };
 struct Buffers {
   Fr *adv, *adv_coeff, *inst_lag, *inst_coeff, *f_lag, *f_coeff, *bpoly, *random_poly, *z, *mv, *cosets, *adv_cosets, *inst_cosets,
-      *z_cosets, *lk_inputs, *plk, *plk_cosets, *h_ext, *h_coeff, *gwc_batch, *gwc_wit, *shplonk, *t_comp, *den, *a_val, *m_fr, *a_scaled;
+      *z_cosets, *lk_inputs, *plk, *plk_cosets, *h_ext, *h_coeff, *gwc_batch, *gwc_wit, *shplonk, *den, *a_val, *m_fr, *a_scaled;
   Fr* challenges;  // user challenges (Expression::Challenge), uploaded as the phases complete
   // b's commitments from per-table-row sums (round 2): the N + 1 values b takes, per lookup; the bucket sums -- per lookup
   // two arrays of N + 1 affine points (64 B = 2 Fr each) -- that a launch before theta leaves there
@@ -361,7 +361,6 @@ void carve(const cq_pk* pk, Arena& ar, Buffers& b) {
   b.gwc_batch = ar.take(shplonk ? 0 : npts * n);
   b.gwc_wit = ar.take(shplonk ? 0 : npts * n);
   b.shplonk = ar.take(shplonk ? 5 * n + 64 * 8 : 0);  // h, two division buffers, h_x, l_x, low-degree remainders
-  b.t_comp = ar.take(0);             // (the compressed table is folded inside cq_round2_prep since round 3)
   b.a_val = ar.take(L * N);
   b.m_fr = ar.take(L * N);
   b.a_scaled = ar.take(wsum * N);
@@ -420,37 +419,126 @@ int eval_many(cq_ctx* c, const std::vector<const Fr*>& ps, const std::vector<uin
   return CQ_OK;
 }
 
-}  // namespace
+// One opening query.  Every polynomial opened by the proof is listed in the order ProverGWC receives the queries; h is
+// opened but its value is derived (vanishing/prover.rs:131-153).
+struct Query {
+  const Fr* p;
+  uint32_t len;
+  int32_t rot;
+  int h_piece;  // -1, or the index of an h piece (folded into one query with coefficient xn^i)
+  Fr eval;
+};
 
-size_t prover_arena_elems(const cq_pk* pk) {
-  Arena ar{nullptr};
-  Buffers b;
-  carve(pk, ar, b);
-  return ar.used + 1024;
+// lagrange_interpolate (arithmetic.rs:425-478) of a commitment's evaluations over its set's points
+std::vector<Fr> lagrange_interpolate(const std::vector<Fr>& pts, const std::vector<Fr>& evals) {
+  const size_t m = pts.size();
+  if (m == 1) return std::vector<Fr>{evals[0]};
+  std::vector<Fr> fin(m, Fr::zero());
+  for (size_t j = 0; j < m; j++) {
+    std::vector<Fr> tmp{Fr::one()};
+    for (size_t kk = 0; kk < m; kk++) {
+      if (kk == j) continue;
+      const Fr denom = (pts[j] - pts[kk]).inv();
+      std::vector<Fr> nxt(tmp.size() + 1, Fr::zero());
+      for (size_t i = 0; i <= tmp.size(); i++) {
+        const Fr a_ = i < tmp.size() ? tmp[i] : Fr::zero();
+        const Fr b_ = i > 0 ? tmp[i - 1] : Fr::zero();
+        nxt[i] = a_ * (Fr::zero() - denom * pts[kk]) + b_ * denom;
+      }
+      tmp.swap(nxt);
+    }
+    for (size_t i = 0; i < m; i++) fin[i] = fin[i] + tmp[i] * evals[j];
+  }
+  return fin;
+}
+Fr eval_small(const std::vector<Fr>& poly, const Fr& at) {
+  Fr acc = Fr::zero();
+  for (size_t i = poly.size(); i-- > 0;) acc = acc * at + poly[i];
+  return acc;
 }
 
-int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_t* const* instances,
-                     const size_t* instance_lens, cq_phase_fn phase_fn, void* phase_user, cq_rng_next_u64 rng_next,
-                     void* rng_state, std::vector<uint8_t>& proof_out) {
-  cq_ctx* c = pk->ctx;
-  cq_domain* dom = pk->domain;
+// The vanishing argument's random polynomial (vanishing/prover.rs:51-55: n field elements = 8n words, then one
+// blind) is the bulk of the RNG stream -- 2^21 words at k = 18, 2^25 (268 MB) at k = 22, more host time than the
+// GPU needs for the advice and round-1 commitments together.  Every draw that precedes it in stream order is made
+// up front by the main thread; the words themselves are drawn by a helper thread, chunk by chunk, each chunk
+// uploaded on the side stream as soon as it is drawn, while the main thread runs rounds 0 and 1.  The main thread
+// does not touch the RNG again before it has joined the helper (just before round 2 commits the polynomial).
+struct RandomPolyDrawer {
+  std::thread th;
+  bool running = false;
+  std::atomic<bool> done{false};
+  std::atomic<uint32_t> chunks_done{0};
+  uint32_t chunks_total = 1;
+  std::chrono::steady_clock::time_point t_start;
+  hipError_t err = hipSuccess;
+  // estimated time to completion in microseconds (from the progress so far); 0 when done
+  double remaining_us() const {
+    if (done.load()) return 0.0;
+    const double el = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count();
+    const uint32_t d = chunks_done.load();
+    return d ? el * (double)(chunks_total - d + 1) / d : 1e9;  // +1: the last upload's event
+  }
+  void start(cq_ctx* c, Rng* rng, uint64_t* pin, uint64_t* dev, size_t words) {
+    const size_t chunk = std::max<size_t>(words / 4, (size_t)1 << 18);  // each drawn by up to eight threads, uploaded while the next is drawn
+    chunks_total = (uint32_t)((words + chunk - 1) / chunk);
+    t_start = std::chrono::steady_clock::now();
+    auto work = [=]() {
+      hipError_t e = hipSetDevice(c->device);
+      for (size_t off = 0; off < words && e == hipSuccess; off += chunk) {
+        const size_t cnt = std::min(chunk, words - off);
+        rng->fill(pin + off, cnt);
+        e = hipMemcpyAsync(dev + off, pin + off, cnt * sizeof(uint64_t), hipMemcpyHostToDevice, c->copy_stream);
+        chunks_done.fetch_add(1);
+      }
+      (void)rng->fr();  // random_blind
+      if (e == hipSuccess) e = hipEventRecord(c->copy_done, c->copy_stream);
+      err = e;
+      done.store(true);
+    };
+    try {
+      th = std::thread(work);
+      running = true;
+    } catch (...) {  // no thread to be had: draw here (nothing may unwind across the C ABI)
+      work();
+    }
+  }
+  int join() {
+    if (running) {
+      th.join();
+      running = false;
+    }
+    return err == hipSuccess ? 0 : -1;
+  }
+  ~RandomPolyDrawer() {
+    if (running) th.join();
+  }
+};
+
+// One proof.  `create_proof_dev` calls the stages below in the reference's order (plonk/prover.rs).  The members are what
+// crosses a stage boundary -- what one stage leaves behind for a later one; everything else is a local of its stage.
+struct ProofRun {
+  cq_pk* const pk;
+  cq_ctx* const c = pk->ctx;
+  cq_domain* const dom = pk->domain;
+  const hipStream_t s = c->stream;
   const uint32_t k = pk->k;
   const size_t n = (size_t)1 << k, ext = dom->ext();
   const uint32_t bf = pk->bf, u = pk->u;
   const size_t L = pk->lookups.size(), A = pk->num_advice, I = pk->num_instance;
   const size_t N = pk->table_cfg ? pk->table_cfg->N : 0;
   const size_t S = pk->perm_sets(), PC = pk->perm_columns.size(), chunk_len = pk->cs_degree - 2;
+  const size_t PL = pk->legacy.size(), NC = pk->challenge_phase.size(), pieces = dom->quotient_poly_degree;
   const bool general = pk->general();
-  const size_t PL = pk->legacy.size();
-  hipStream_t s = c->stream;
-  Rng rng{rng_next, rng_state, pk->rng_fill, &c->pool()};
-  Transcript tr;
-  // CQ_TRACE_HOST=1: microseconds since the start of the proof at the host's milestones, on stderr (development aid)
-  static const bool trace_host = getenv("CQ_TRACE_HOST") != nullptr;
-  const auto t_start = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    if (trace_host) fprintf(stderr, "[cq host] %8.1f us  %s\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count(), what);
-  };
+  // [m] is committed in the advice launch (see count_multiplicities); the advice polynomials get a buffer of their own
+  const bool early_m = L > 0 && pk->num_phases == 1 && pk->challenge_phase.empty();
+  const bool early_adv = early_advice_polys(pk);
+  // [b_0] and [p] of every lookup as MSMs of N + 1 terms over per-table-row sums of the key's per-row bases (cq.hpp:
+  // b_row_bases) instead of n - 1 terms over the SRS: b takes one value per table row looked up and one on the blinding
+  // rows.  Which rows share a value is known from the witness alone, so the sums are formed where m is counted, ahead of
+  // theta and beta.  Sharded keys commit slices of b's coefficients by point range and keep that path.
+  // A launch the MSM engine cannot plan (entry bound, workspace cap) leaves the coefficient path too.
+  const bool b_by_rows = L > 0 && !pk->sharded() && pk->b_row_bases[0] != nullptr &&
+                         msm_bucket_sums_fit((uint32_t)n, (uint32_t)std::min<size_t>(2 * L, MSM_MAX_BATCH));
 
   // Resident column sharding (cq_pk_set_resident_sharding; DESIGN.md, multi-GPU): for the CQ-shaped circuits of the
   // BASELINE configs -- advice columns, static lookups on plain advice inputs, one phase, ProverGWC -- a transformed
@@ -459,75 +547,86 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
   // departs from the replicated flow; every rank still derives the same transcript.
   bool resident = shard_resident_enabled(pk) && !general && PL == 0 && pk->num_phases == 1 && pk->challenge_phase.empty() && I == 0 &&
                   L > 0 && pk->opener == CQ_OPENER_GWC && n >= (size_t)64 * pk->shard_world;
-  for (size_t l = 0; l < L && resident; l++)
-    for (int64_t pj : pk->lookups[l].prog) resident = resident && pj < 0;
   const uint32_t SW = pk->shard_world, me = pk->shard_rank;
   size_t lk_lo = 0, lk_hi = L, adv_lo = 0, adv_hi = A;  // the lookups / advice columns this rank owns
-  if (resident) {
-    shard_range(L, me, SW, lk_lo, lk_hi);
-    shard_range(A, me, SW, adv_lo, adv_hi);
+  size_t lk_cnt = L;
+  // resident: staging for the slices a rank receives -- per exchange at most one slice from every rank (or every owner
+  // and piece), plus the rank's own range of the opening's batch polynomial with its two edge elements
+  const size_t res_slice_max = (n + pk->shard_world - 1) / pk->shard_world + 1;
+  const size_t res_stage_elems = (size_t)pk->shard_world * res_slice_max * (pk->cs_degree > 2 ? pk->cs_degree - 1 : 1) + res_slice_max + 64;
+  void* res_stage_v = nullptr;
+
+  Rng rng;
+  Transcript tr;
+  Buffers B;
+  // pinned staging: `pin` holds the random polynomial's words and the advice blinding rows; `small_v` the lookup error
+  // flag (`herr`), the legacy permute's status words and the scalars read back (`small_fr`: b(0), z values)
+  void *pin = nullptr, *small_v = nullptr;
+  volatile uint32_t* herr = nullptr;
+  Fr* small_fr = nullptr;
+  const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+
+  // blinding rows drawn ahead of their stages (advice_phase): permutation products, legacy permuted columns / products
+  std::vector<Fr> z_tails = std::vector<Fr>(S * bf), plk_tails = std::vector<Fr>(PL * 2 * (bf + 1)), plkz_tails = std::vector<Fr>(PL * bf);
+  // round 0 / 1: where each lookup input lives (Lagrange basis), the commitments later rounds and the f fold reuse
+  std::vector<std::array<const Fr*, CQ_MAX_WIDTH>> lk_input = std::vector<std::array<const Fr*, CQ_MAX_WIDTH>>(L);
+  std::vector<G1Affine> m_commitments = std::vector<G1Affine>(L, G1Affine::identity());
+  std::vector<G1Affine> advice_commitments = std::vector<G1Affine>(A, G1Affine::identity());
+  std::vector<Fr> user_challenges = std::vector<Fr>(NC, Fr::zero());
+  Fr* adv_poly = nullptr;     // where the advice polynomials (coefficient form) live
+  bool adv_is_coeff = false;  // the advice columns have been transformed (on the side stream, by whichever round came first)
+  // challenges, squeezed by create_proof_dev between the stages
+  Fr theta, beta, gamma, beta_inv, y, x, xn;
+  Fr theta_pow[CQ_MAX_WIDTH];  // powers of theta for the folds of this proof (theta^0 .. theta^(CQ_MAX_WIDTH - 1))
+  // round 2 -> evaluations / the vanishing argument
+  std::vector<Fr> a_at_zero = std::vector<Fr>(L);
+  G1Affine random_cm = G1Affine::identity();
+  // evaluate_and_write -> the openers: the queries, the h pieces among them, the distinct rotations in first-seen order,
+  // and (resident) the owner of each query with this rank's point range of a length-n vector
+  std::vector<Query> qs;
+  std::vector<size_t> q_h;
+  std::vector<int32_t> rots;
+  std::vector<int> qowner;
+  size_t my_lo = 0, my_hi = n;
+  RandomPolyDrawer drawer;  // last member: joined (destroyed) before anything its thread reads goes away
+
+  ProofRun(cq_pk* pk_, cq_rng_next_u64 rng_next, void* rng_state) : pk(pk_), rng{rng_next, rng_state, pk_->rng_fill, &pk_->ctx->pool()} {
+    for (size_t l = 0; l < L && resident; l++)
+      for (int64_t pj : pk->lookups[l].prog) resident = resident && pj < 0;
+    if (resident) {
+      shard_range(L, me, SW, lk_lo, lk_hi);
+      shard_range(A, me, SW, adv_lo, adv_hi);
+    }
+    lk_cnt = lk_hi - lk_lo;
   }
-  auto owner_of = [&](size_t item, size_t count) -> uint32_t {
+
+  // CQ_TRACE_HOST=1: microseconds since the start of the proof at the host's milestones, on stderr (development aid)
+  void mark(const char* what) const {
+    static const bool trace_host = getenv("CQ_TRACE_HOST") != nullptr;
+    if (trace_host) fprintf(stderr, "[cq host] %8.1f us  %s\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count(), what);
+  }
+  uint32_t owner_of(size_t item, size_t count) const {
     for (uint32_t r = 0; r < SW; r++) {
       size_t lo, hi;
       shard_range(count, r, SW, lo, hi);
       if (item >= lo && item < hi) return r;
     }
     return 0;
-  };
-  const size_t lk_cnt = lk_hi - lk_lo;
-
-  // ---- set-up that can fail on this rank alone (allocations: arena, pinned staging, streams, twiddle tables) comes first,
-  //      and a sharded proof agrees on its outcome before anything else is exchanged: a rank that cannot start says so in
-  //      a one-word all-gather and every rank returns an error, instead of the others waiting in the first collective of a
-  //      proof one of them never joins.  (A failure later on one rank alone -- the MSM workspace, a HIP error -- aborts that
-  //      rank's communicator, and its peers' waits time out: capi_cq.hip, comm.hip.)
-  void *arena_v = nullptr, *small_v = nullptr, *pin = nullptr, *res_stage_v = nullptr;
-  // resident: staging for the slices a rank receives -- per exchange at most one slice from every rank (or every owner
-  // and piece), plus the rank's own range of the opening's batch polynomial with its two edge elements
-  const size_t res_slice_max = (n + pk->shard_world - 1) / pk->shard_world + 1;
-  const size_t res_stage_elems = (size_t)pk->shard_world * res_slice_max * (pk->cs_degree > 2 ? pk->cs_degree - 1 : 1) + res_slice_max + 64;
-  {
-    auto setup = [&]() -> int {
-      CQ_TRY(c->ensure_scratch(Scratch::ProverArena, prover_arena_elems(pk) * sizeof(Fr), &arena_v));
-      CQ_TRY(c->ensure_pinned_small(&small_v));
-      CQ_TRY(c->ensure_pinned((size_t)64 * n + A * (n - u) * sizeof(Fr) + 64, &pin));
-      CQ_TRY(c->ensure_aux_stream());
-      CQ_TRY(c->ensure_copy_stream());
-      if (resident) CQ_TRY(c->ensure_scratch(Scratch::ProverStage, res_stage_elems * sizeof(Fr), &res_stage_v));  // where received slices land
-      int trc = CQ_OK;
-      if (!c->tables_for(dom->k, dom->omega_inv, &trc) || !c->tables_for(dom->extended_k, dom->extended_omega, &trc)) return trc;
-      return CQ_OK;
-    };
-    const int setup_rc = getenv("CQ_TEST_FAIL_SETUP") && atoi(getenv("CQ_TEST_FAIL_SETUP")) == (int)pk->shard_rank + 1
-                             ? c->fail(CQ_ERR_HIP, "set-up failure injected by CQ_TEST_FAIL_SETUP") : setup();
-    if (pk->sharded()) {
-      bool any = false;
-      const std::string mine = c->err;
-      CQ_TRY(shard_any(pk, setup_rc != CQ_OK, any));
-      if (any) return setup_rc != CQ_OK ? c->fail(setup_rc, mine) : c->fail(CQ_ERR_INTERNAL, "sharded proof: another rank could not set up its proof (allocation failure there)");
-    } else if (setup_rc != CQ_OK) {
-      return setup_rc;
-    }
   }
-  Arena ar{(Fr*)arena_v};
-  Buffers B;
-  carve(pk, ar, B);
-  Fr *adv = B.adv, *f_lag = B.f_lag, *f_coeff = B.f_coeff, *bpoly = B.bpoly, *random_poly = B.random_poly, *cosets = B.cosets,
-     *h_ext = B.h_ext, *h_coeff = B.h_coeff, *den = B.den, *a_val = B.a_val, *m_fr = B.m_fr,
-     *a_scaled = B.a_scaled;
-  uint64_t* rng_dev = B.rng_dev;
-  uint32_t* m_counts = B.m_counts;
-  const bool early_adv = early_advice_polys(pk);
-  Fr* const adv_poly = early_adv ? B.adv_coeff : adv;  // where the advice polynomials (coefficient form) live
-  bool adv_is_coeff = false;
+  uint32_t phase_of(size_t a) const { return pk->advice_phase.empty() ? 0u : pk->advice_phase[a]; }
+  Fr* plk_buf(size_t l, int which) const { return B.plk + (l * 5 + which) * n; }  // 0 A, 1 S, 2 a', 3 s', 4 z
+  Fr point_of(int32_t rot) const { return rot >= 0 ? x * dom->omega.pow_u64((uint64_t)rot) : x * dom->omega_inv.pow_u64((uint64_t)(-(int64_t)rot)); }  // rotate_omega (domain.rs:414-424)
+  size_t add_query(const Fr* p, size_t len, int32_t rot) {
+    qs.push_back({p, (uint32_t)len, rot, -1, Fr::zero()});
+    return qs.size() - 1;
+  }
 
   // Column sharding (cq_pk_set_column_sharding): a batch of independent column transforms is split
   // between the ranks by owner -- contiguous ranges of columns, cq::shard_range -- and every rank's output columns are
   // broadcast from their owner on the stream the transform ran on (one grouped RCCL launch).  Transforms chained on the
   // same batch (coefficients, then the coset of the same columns) read what their own rank wrote, so they need not
   // wait for the exchange.  Unsharded, or with fewer than two columns: the plain call.
-  auto sharded_transform = [&](bool to_extended, const Fr* in, Fr* out, uint32_t batch) -> int {
+  int sharded_transform(bool to_extended, const Fr* in, Fr* out, uint32_t batch) {
     const size_t in_stride = n, out_stride = to_extended ? ext : n;
     auto run = [&](size_t first, size_t count) -> int {
       if (!count) return CQ_OK;
@@ -544,114 +643,47 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       if (hi > lo) parts.push_back({out + lo * out_stride, (hi - lo) * out_stride * sizeof(Fr), r});
     }
     return shard_bcast_parts(pk, parts.data(), parts.size(), c->stream);
-  };
-  auto lagrange_to_coeff_cols = [&](const Fr* in, Fr* out, size_t batch) { return sharded_transform(false, in, out, (uint32_t)batch); };
-  auto coeff_to_extended_cols = [&](const Fr* in, Fr* out, size_t batch) { return sharded_transform(true, in, out, (uint32_t)batch); };
-
-  // side stream: drain whatever an aborted proof may have left there (its NTTs find their twiddle tables built: set-up above)
-  if (c->aux_pending) {
-    CQ_HIP(c, hipStreamSynchronize(c->aux_stream));
-    c->aux_pending = false;
   }
+  int lagrange_to_coeff_cols(const Fr* in, Fr* out, size_t batch) { return sharded_transform(false, in, out, (uint32_t)batch); }
+  int coeff_to_extended_cols(const Fr* in, Fr* out, size_t batch) { return sharded_transform(true, in, out, (uint32_t)batch); }
 
-  // prover.rs:85 -- vk.hash_into(transcript)
-  tr.common_scalar(pk->vk_repr);
-
-  // ---- instance columns (prover.rs:100-131), absorbed as scalars in phase 0 (:305-312) ---------------
-  if (I) {
-    CQ_HIP(c, hipMemsetAsync(B.inst_lag, 0, I * n * sizeof(Fr), s));
-    for (size_t i = 0; i < I; i++) {
-      if (instance_lens[i] > u) return c->fail(CQ_ERR_ARG, "Error::InstanceTooLarge");  // :108-110
-      if (instance_lens[i])
-        CQ_HIP(c, hipMemcpyAsync(B.inst_lag + i * n, instances[i], instance_lens[i] * sizeof(Fr), hipMemcpyHostToDevice, s));
-    }
-    CQ_TRY(domain_lagrange_to_coeff(dom, B.inst_lag, B.inst_coeff, (uint32_t)I, n, n));
-    for (size_t i = 0; i < I; i++)
-      for (size_t r = 0; r < instance_lens[i]; r++) tr.common_scalar(Fr::from_limbs64(instances[i] + 4 * r));
-  }
-
-  std::vector<Fr> z_tails(S * bf), plk_tails(PL * 2 * (bf + 1)), plkz_tails(PL * bf);
-  // The vanishing argument's random polynomial (vanishing/prover.rs:51-55: n field elements = 8n words, then one
-  // blind) is the bulk of the RNG stream -- 2^21 words at k = 18, 2^25 (268 MB) at k = 22, more host time than the
-  // GPU needs for the advice and round-1 commitments together.  Every draw that precedes it in stream order is made
-  // up front by the main thread; the words themselves are drawn by a helper thread, chunk by chunk, each chunk
-  // uploaded on the side stream as soon as it is drawn, while the main thread runs rounds 0 and 1.  The main thread
-  // does not touch the RNG again before it has joined the helper (just before round 2 commits the polynomial).
-  struct RandomPolyDrawer {
-    std::thread th;
-    bool running = false;
-    std::atomic<bool> done{false};
-    std::atomic<uint32_t> chunks_done{0};
-    uint32_t chunks_total = 1;
-    std::chrono::steady_clock::time_point t_start;
-    hipError_t err = hipSuccess;
-    // estimated time to completion in microseconds (from the progress so far); 0 when done
-    double remaining_us() const {
-      if (done.load()) return 0.0;
-      const double el = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count();
-      const uint32_t d = chunks_done.load();
-      return d ? el * (double)(chunks_total - d + 1) / d : 1e9;  // +1: the last upload's event
-    }
-    void start(cq_ctx* c, Rng* rng, uint64_t* pin, uint64_t* dev, size_t words) {
-      const size_t chunk = std::max<size_t>(words / 4, (size_t)1 << 18);  // each drawn by up to eight threads, uploaded while the next is drawn
-      chunks_total = (uint32_t)((words + chunk - 1) / chunk);
-      t_start = std::chrono::steady_clock::now();
-      auto work = [=]() {
-        hipError_t e = hipSetDevice(c->device);
-        for (size_t off = 0; off < words && e == hipSuccess; off += chunk) {
-          const size_t cnt = std::min(chunk, words - off);
-          rng->fill(pin + off, cnt);
-          e = hipMemcpyAsync(dev + off, pin + off, cnt * sizeof(uint64_t), hipMemcpyHostToDevice, c->copy_stream);
-          chunks_done.fetch_add(1);
-        }
-        (void)rng->fr();  // random_blind
-        if (e == hipSuccess) e = hipEventRecord(c->copy_done, c->copy_stream);
-        err = e;
-        done.store(true);
-      };
-      try {
-        th = std::thread(work);
-        running = true;
-      } catch (...) {  // no thread to be had: draw here (nothing may unwind across the C ABI)
-        work();
-      }
-    }
-    int join() {
-      if (running) {
-        th.join();
-        running = false;
-      }
-      return err == hipSuccess ? 0 : -1;
-    }
-    ~RandomPolyDrawer() {
-      if (running) th.join();
-    }
-  } drawer;
   // joins the helper, orders the main stream after the uploads, words -> field elements
-  auto finish_random_poly = [&]() -> int {
+  int finish_random_poly() {
     if (drawer.join() != 0) return c->fail(CQ_ERR_HIP, "random polynomial upload failed");
     CQ_HIP(c, hipStreamWaitEvent(s, c->copy_done, 0));
-    return poly_from_u512(c, rng_dev, (uint32_t)n, random_poly);
-  };
+    return poly_from_u512(c, B.rng_dev, (uint32_t)n, B.random_poly);
+  }
+
+  // `evaluate(expr, n, 1, fixed, advice, instance)`: gate_eval's arguments for `num_polys` expressions over the Lagrange
+  // basis, folded with `fold` (static_lookup/prover.rs:91-107, lookup/prover.rs:98-117)
+  GateEvalArgs lagrange_eval_args(const uint32_t* prog, uint32_t num_polys, const Fr& fold) const {
+    GateEvalArgs ga;
+    ga.prog = prog;
+    ga.num_polys = num_polys;
+    ga.constants = pk->constants;
+    ga.challenges = B.challenges;
+    ga.advice = B.adv;
+    ga.fixed = pk->fixed_values;
+    ga.instance = B.inst_lag;
+    ga.stride = n;
+    ga.size = (uint32_t)n;
+    ga.rot_scale = 1;
+    ga.y = fold;
+    return ga;
+  }
+  // `evaluate(expr, n, 1, ..)` of every expression, folded with theta (lookup/prover.rs:98-117)
+  int lagrange_compress(const uint32_t* prog, uint32_t width, const Fr& chal, Fr* dst) {
+    return gate_eval(c, lagrange_eval_args(prog, width, chal), dst);
+  }
+
   // ---- CQ round 1, the part that does not depend on theta (static_lookup/prover.rs:91-107, 122-160): the lookup
   //      inputs on the Lagrange basis and the multiplicities m.  With a single phase and no user challenge the witness
   //      alone determines them, so they are computed right after the advice columns are in place and [m] is committed
   //      in the advice launch -- the round then has no launch of its own (unless it has legacy lookups or an f that is
   //      not a linear combination of advice columns).  The points are WRITTEN where the reference writes them.
-  uint32_t *m_counts_ = B.m_counts, *err_dev_ = B.err_dev;
-  std::vector<std::array<const Fr*, CQ_MAX_WIDTH>> lk_input(L);
-  volatile uint32_t* herr = (volatile uint32_t*)small_v;             // lookup error flag
-  Fr* small_fr = (Fr*)((char*)small_v + 64);                         // scalars read back (b(0), z values)
-  // [b_0] and [p] of every lookup as MSMs of N + 1 terms over per-table-row sums of the key's per-row bases (cq.hpp:
-  // b_row_bases) instead of n - 1 terms over the SRS: b takes one value per table row looked up and one on the blinding
-  // rows.  Which rows share a value is known from the witness alone, so the sums are formed where m is counted, ahead of
-  // theta and beta.  Sharded keys commit slices of b's coefficients by point range and keep that path.
-  // A launch the MSM engine cannot plan (entry bound, workspace cap) leaves the coefficient path too.
-  const bool b_by_rows = L > 0 && !pk->sharded() && pk->b_row_bases[0] != nullptr &&
-                         msm_bucket_sums_fit((uint32_t)n, (uint32_t)std::min<size_t>(2 * L, MSM_MAX_BATCH));
-  auto count_multiplicities = [&]() -> int {
+  int count_multiplicities() {
     if (!L) return CQ_OK;
-    CQ_HIP(c, hipMemsetAsync(m_counts_, 0, (L * N + 16) * sizeof(uint32_t), s));
+    CQ_HIP(c, hipMemsetAsync(B.m_counts, 0, (L * N + 16) * sizeof(uint32_t), s));
     size_t input_slot = 0;
     CqRound1Batch r1b;
     r1b.count = 0;
@@ -664,20 +696,8 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
           lk_input[l][j] = B.adv + (size_t)lk.cols[j] * n;
           continue;
         }
-        GateEvalArgs ga;
-        ga.prog = pk->lookup_prog + lk.prog[j];
-        ga.num_polys = 1;
-        ga.constants = pk->constants;
-        ga.challenges = B.challenges;
-        ga.advice = B.adv;
-        ga.fixed = pk->fixed_values;
-        ga.instance = B.inst_lag;
-        ga.stride = n;
-        ga.size = (uint32_t)n;
-        ga.rot_scale = 1;
-        ga.y = Fr::zero();
         Fr* dst = B.lk_inputs + input_slot * n;
-        CQ_TRY(gate_eval(c, ga, dst));
+        CQ_TRY(gate_eval(c, lagrange_eval_args(pk->lookup_prog + lk.prog[j], 1, Fr::zero()), dst));
         lk_input[l][j] = dst;
       }
       CqRound1Args& ra = r1b.a[r1b.count];
@@ -688,44 +708,94 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
         ra.slots[j] = lk.tables[j]->slots;
         ra.nslots[j] = lk.tables[j]->nslots;
       }
-      r1b.bucket[r1b.count] = b_by_rows ? (uint32_t*)(bpoly + l * n) : nullptr;  // (b's own buffer is free until round 2 writes it)
+      r1b.bucket[r1b.count] = b_by_rows ? (uint32_t*)(B.bpoly + l * n) : nullptr;  // (b's own buffer is free until round 2 writes it)
       r1b.n = b_by_rows ? (uint32_t)n : 0;
       r1b.blind_bucket = (uint32_t)N;
-      r1b.m_counts[r1b.count++] = m_counts_ + l * N;
+      r1b.m_counts[r1b.count++] = B.m_counts + l * N;
       if (r1b.count == CQ_ROUND1_BATCH || l + 1 == L) {  // the lookups of a proof share launches
-        CQ_TRY(cq_round1(c, r1b, u, err_dev_));
+        CQ_TRY(cq::cq_round1(c, r1b, u, B.err_dev));
         r1b.count = 0;
       }
     }
-    CQ_TRY(cq_m_to_fr(c, m_counts_, (uint32_t)(L * N), B.m_fr));  // the L vectors are adjacent
+    CQ_TRY(cq_m_to_fr(c, B.m_counts, (uint32_t)(L * N), B.m_fr));  // the L vectors are adjacent
     for (size_t l0 = 0; b_by_rows && l0 < L; l0 += MSM_MAX_BATCH / 2) {
       std::vector<const uint32_t*> sc;
       std::vector<const G1Affine*> bs;
       for (size_t l = l0; l < std::min(L, l0 + MSM_MAX_BATCH / 2); l++)
-        for (int q = 0; q < 2; q++) { sc.push_back((const uint32_t*)(bpoly + l * n)); bs.push_back(pk->b_row_bases[q]); }
+        for (int q = 0; q < 2; q++) { sc.push_back((const uint32_t*)(B.bpoly + l * n)); bs.push_back(pk->b_row_bases[q]); }
       if (msm_bucket_sums(c, sc.data(), bs.data(), (uint32_t)n, (uint32_t)sc.size(), (uint32_t)(N + 1), B.b_sums + 2 * l0 * (N + 1)) != 0)
         return c->fail(CQ_ERR_HIP, "bucket-sum launch failed");
     }
     *herr = 0;
-    CQ_HIP(c, hipMemcpyAsync((void*)herr, err_dev_, 4, hipMemcpyDeviceToHost, s));  // read after the next synchronisation
+    CQ_HIP(c, hipMemcpyAsync((void*)herr, B.err_dev, 4, hipMemcpyDeviceToHost, s));  // read after the next synchronisation
     return CQ_OK;
-  };
-  auto lookup_error = [&]() -> int {
+  }
+  int lookup_error() {
     if (*herr == 1) return c->fail(CQ_ERR_LOOKUP, "witness value not in table");
     if (*herr == 2) return c->fail(CQ_ERR_LOOKUP, "Vector lookup must be on the same table row");
     return CQ_OK;
-  };
-  const bool early_m = L > 0 && pk->num_phases == 1 && pk->challenge_phase.empty();
-  std::vector<G1Affine> m_commitments(L, G1Affine::identity());
+  }
+
+  // ---- set-up that can fail on this rank alone (allocations: arena, pinned staging, streams, twiddle tables) comes first,
+  //      and a sharded proof agrees on its outcome before anything else is exchanged: a rank that cannot start says so in
+  //      a one-word all-gather and every rank returns an error, instead of the others waiting in the first collective of a
+  //      proof one of them never joins.  (A failure later on one rank alone -- the MSM workspace, a HIP error -- aborts that
+  //      rank's communicator, and its peers' waits time out: capi_cq.hip, comm.hip.)
+  int setup() {
+    void* arena_v = nullptr;
+    auto allocate = [&]() -> int {
+      CQ_TRY(c->ensure_scratch(Scratch::ProverArena, prover_arena_elems(pk) * sizeof(Fr), &arena_v));
+      CQ_TRY(c->ensure_pinned_small(&small_v));
+      CQ_TRY(c->ensure_pinned((size_t)64 * n + A * (n - u) * sizeof(Fr) + 64, &pin));
+      CQ_TRY(c->ensure_aux_stream());
+      CQ_TRY(c->ensure_copy_stream());
+      if (resident) CQ_TRY(c->ensure_scratch(Scratch::ProverStage, res_stage_elems * sizeof(Fr), &res_stage_v));  // where received slices land
+      int trc = CQ_OK;
+      if (!c->tables_for(dom->k, dom->omega_inv, &trc) || !c->tables_for(dom->extended_k, dom->extended_omega, &trc)) return trc;
+      return CQ_OK;
+    };
+    const int setup_rc = getenv("CQ_TEST_FAIL_SETUP") && atoi(getenv("CQ_TEST_FAIL_SETUP")) == (int)pk->shard_rank + 1
+                             ? c->fail(CQ_ERR_HIP, "set-up failure injected by CQ_TEST_FAIL_SETUP") : allocate();
+    if (pk->sharded()) {
+      bool any = false;
+      const std::string mine = c->err;
+      CQ_TRY(shard_any(pk, setup_rc != CQ_OK, any));
+      if (any) return setup_rc != CQ_OK ? c->fail(setup_rc, mine) : c->fail(CQ_ERR_INTERNAL, "sharded proof: another rank could not set up its proof (allocation failure there)");
+    } else if (setup_rc != CQ_OK) {
+      return setup_rc;
+    }
+    Arena ar{(Fr*)arena_v};
+    carve(pk, ar, B);
+    adv_poly = early_adv ? B.adv_coeff : B.adv;
+    herr = (volatile uint32_t*)small_v;
+    small_fr = (Fr*)((char*)small_v + 64);
+    // side stream: drain whatever an aborted proof may have left there (its NTTs find their twiddle tables built: set-up above)
+    if (c->aux_pending) {
+      CQ_HIP(c, hipStreamSynchronize(c->aux_stream));
+      c->aux_pending = false;
+    }
+    return CQ_OK;
+  }
+
+  // ---- instance columns (prover.rs:100-131), absorbed as scalars in phase 0 (:305-312) ---------------
+  int absorb_instances(const uint64_t* const* instances, const size_t* instance_lens) {
+    if (!I) return CQ_OK;
+    CQ_HIP(c, hipMemsetAsync(B.inst_lag, 0, I * n * sizeof(Fr), s));
+    for (size_t i = 0; i < I; i++) {
+      if (instance_lens[i] > u) return c->fail(CQ_ERR_ARG, "Error::InstanceTooLarge");  // :108-110
+      if (instance_lens[i])
+        CQ_HIP(c, hipMemcpyAsync(B.inst_lag + i * n, instances[i], instance_lens[i] * sizeof(Fr), hipMemcpyHostToDevice, s));
+    }
+    CQ_TRY(domain_lagrange_to_coeff(dom, B.inst_lag, B.inst_coeff, (uint32_t)I, n, n));
+    for (size_t i = 0; i < I; i++)
+      for (size_t r = 0; r < instance_lens[i]; r++) tr.common_scalar(Fr::from_limbs64(instances[i] + 4 * r));
+    return CQ_OK;
+  }
 
   // ---- advice, phase by phase (`next_phase`, prover.rs:299-391; the synthesis loop :436-463): copy the phase's
   //      columns in, blind rows u..n (:346-350), one unused blind per column (:352-355), commit, squeeze the phase's
   //      challenges ----------------------------------------------------------------------------------------------
-  const size_t NC = pk->challenge_phase.size();
-  std::vector<Fr> user_challenges(NC, Fr::zero());
-  std::vector<G1Affine> advice_commitments(A, G1Affine::identity());
-  auto phase_of = [&](size_t a) -> uint32_t { return pk->advice_phase.empty() ? 0u : pk->advice_phase[a]; };
-  for (uint32_t phase = 0; phase < pk->num_phases; phase++) {
+  int advice_phase(uint32_t phase, const uint64_t* const* advice_dev, cq_phase_fn phase_fn, void* phase_user) {
     const bool last_phase = phase + 1 == pk->num_phases;
     std::vector<size_t> cols;
     for (size_t a = 0; a < A; a++)
@@ -754,7 +824,7 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       fa.count = (uint32_t)std::min<size_t>(ADVICE_FILL_MAX, AC - off);
       for (uint32_t j = 0; j < fa.count; j++) {
         fa.src[j] = (const Fr*)advice_dev[cols[off + j]];
-        fa.dst[j] = adv + cols[off + j] * n;
+        fa.dst[j] = B.adv + cols[off + j] * n;
       }
       CQ_TRY(poly_advice_fill(c, fa, B.tails + off * (n - u), (uint32_t)n, u));
     }
@@ -762,7 +832,7 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
     std::vector<const Fr*> sc(AC);
     std::vector<const G1Affine*> bs(AC, pk->params->g_lagrange);
     std::vector<size_t> ln(AC, n);
-    for (size_t j = 0; j < AC; j++) sc[j] = adv + cols[j] * n;
+    for (size_t j = 0; j < AC; j++) sc[j] = B.adv + cols[j] * n;
     if (early_m) {  // m_cm (:167-172, as a dense MSM over the table SRS) rides along
       CQ_TRY(count_multiplicities());
       for (size_t l = 0; l < L; l++) { sc.push_back(B.m_fr + l * N); bs.push_back(pk->table_cfg->g1_lagrange); ln.push_back(N); }
@@ -777,36 +847,36 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       AuxFork fork(c);
       CQ_TRY(fork.begin(seq_adv));
       if (resident) {
-        if (adv_hi > adv_lo) CQ_TRY(domain_lagrange_to_coeff(dom, adv + adv_lo * n, adv_poly + adv_lo * n, (uint32_t)(adv_hi - adv_lo), n, n));
+        if (adv_hi > adv_lo) CQ_TRY(domain_lagrange_to_coeff(dom, B.adv + adv_lo * n, adv_poly + adv_lo * n, (uint32_t)(adv_hi - adv_lo), n, n));
       } else {
-        CQ_TRY(lagrange_to_coeff_cols(adv, adv_poly, A));
+        CQ_TRY(lagrange_to_coeff_cols(B.adv, adv_poly, A));
       }
       CQ_TRY(fork.end());
       adv_is_coeff = true;
     }
     if (last_phase) {
-    // The next draws from the RNG are, per permutation set, `bf` blinding rows of z and one blind
-    // (permutation/prover.rs:169-175), then the vanishing argument's n coefficients + 1 blind
-    // (vanishing/prover.rs:51-55): the CQ rounds in between draw nothing, so taking them now keeps the
-    // stream order, overlaps the host-side draws with the advice MSMs, and lets the random
-    // polynomial's commitment ride along with round 2's launch.
-    // legacy lookups, commit_permuted (lookup/prover.rs:491-494, 133-145): bf+1 rows of a', bf+1 rows of s', two blinds
-    for (size_t l = 0; l < PL; l++) {
-      for (uint32_t r = 0; r < 2 * (bf + 1); r++) plk_tails[l * 2 * (bf + 1) + r] = rng.fr();
-      (void)rng.fr();
-      (void)rng.fr();
-    }
-    for (size_t st = 0; st < S; st++) {
-      for (uint32_t r = 0; r < bf; r++) z_tails[st * bf + r] = rng.fr();
-      (void)rng.fr();  // permutation_product_blind
-    }
-    // legacy lookups, commit_product (:237, 283): bf rows of z, one blind
-    for (size_t l = 0; l < PL; l++) {
-      for (uint32_t r = 0; r < bf; r++) plkz_tails[l * bf + r] = rng.fr();
-      (void)rng.fr();
-    }
-    // the random polynomial's words: drawn and uploaded by the helper thread from here on (see RandomPolyDrawer)
-    drawer.start(c, &rng, (uint64_t*)pin, rng_dev, 8 * n);
+      // The next draws from the RNG are, per permutation set, `bf` blinding rows of z and one blind
+      // (permutation/prover.rs:169-175), then the vanishing argument's n coefficients + 1 blind
+      // (vanishing/prover.rs:51-55): the CQ rounds in between draw nothing, so taking them now keeps the
+      // stream order, overlaps the host-side draws with the advice MSMs, and lets the random
+      // polynomial's commitment ride along with round 2's launch.
+      // legacy lookups, commit_permuted (lookup/prover.rs:491-494, 133-145): bf+1 rows of a', bf+1 rows of s', two blinds
+      for (size_t l = 0; l < PL; l++) {
+        for (uint32_t r = 0; r < 2 * (bf + 1); r++) plk_tails[l * 2 * (bf + 1) + r] = rng.fr();
+        (void)rng.fr();
+        (void)rng.fr();
+      }
+      for (size_t st = 0; st < S; st++) {
+        for (uint32_t r = 0; r < bf; r++) z_tails[st * bf + r] = rng.fr();
+        (void)rng.fr();  // permutation_product_blind
+      }
+      // legacy lookups, commit_product (:237, 283): bf rows of z, one blind
+      for (size_t l = 0; l < PL; l++) {
+        for (uint32_t r = 0; r < bf; r++) plkz_tails[l * bf + r] = rng.fr();
+        (void)rng.fr();
+      }
+      // the random polynomial's words: drawn and uploaded by the helper thread from here on (see RandomPolyDrawer)
+      drawer.start(c, &rng, (uint64_t*)pin, B.rng_dev, 8 * n);
     }
     // batch_normalize (:363-366), write (:370-374)
     mark("advice launch queued");
@@ -825,29 +895,17 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
     }
     for (size_t i = 0; i < NC; i++)  // :383-389
       if (pk->challenge_phase[i] == phase) user_challenges[i] = tr.squeeze();
+    return CQ_OK;
   }
-  if (NC) CQ_HIP(c, hipMemcpyAsync(B.challenges, user_challenges.data(), NC * sizeof(Fr), hipMemcpyHostToDevice, s));
-  const Fr theta = tr.squeeze();  // :472
-  mark("theta");
+  int advice_phases(const uint64_t* const* advice_dev, cq_phase_fn phase_fn, void* phase_user) {
+    for (uint32_t phase = 0; phase < pk->num_phases; phase++) CQ_TRY(advice_phase(phase, advice_dev, phase_fn, phase_user));
+    if (NC) CQ_HIP(c, hipMemcpyAsync(B.challenges, user_challenges.data(), NC * sizeof(Fr), hipMemcpyHostToDevice, s));
+    return CQ_OK;
+  }
 
   // ---- legacy lookups: commit_permuted (lookup/prover.rs:57-160) ---------------------------------------------
-  auto plk_buf = [&](size_t l, int which) { return B.plk + (l * 5 + which) * n; };  // 0 A, 1 S, 2 a', 3 s', 4 z
-  auto lagrange_compress = [&](const uint32_t* prog, uint32_t width, const Fr& chal, Fr* dst) {
-    GateEvalArgs ga;  // `evaluate(expr, n, 1, ..)` of every expression, folded with theta (:98-117)
-    ga.prog = prog;
-    ga.num_polys = width;
-    ga.constants = pk->constants;
-    ga.challenges = B.challenges;
-    ga.advice = adv;
-    ga.fixed = pk->fixed_values;
-    ga.instance = B.inst_lag;
-    ga.stride = n;
-    ga.size = (uint32_t)n;
-    ga.rot_scale = 1;
-    ga.y = chal;
-    return gate_eval(c, ga, dst);
-  };
-  if (PL) {
+  int legacy_commit_permuted() {
+    if (!PL) return CQ_OK;
     // permute_expression_pair (lookup/prover.rs:400-502) on the device: canonical values, sorted and matched there
     // (lksort.hip), back to Montgomery form; one status read-back per lookup
     void* stage_v;
@@ -873,126 +931,125 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       if (lk_status_host[0] != 0 || lk_status_host[1] != lk_status_host[2])
         return c->fail(CQ_ERR_LOOKUP, "lookup input not in table (Error::ConstraintSystemFailure)");
     }
+    return CQ_OK;
   }
 
   // ---- CQ round 1 (static_lookup/prover.rs:51-183) ------------------------------------------------
-  if (L && !early_m) {
-    CQ_TRY(count_multiplicities());
-    CQ_TRY(c->wait(s));
-    CQ_TRY(lookup_error());
-  }
-  // powers of theta for the folds of this proof (theta^0 .. theta^(CQ_MAX_WIDTH - 1))
-  Fr theta_pow[CQ_MAX_WIDTH];
-  theta_pow[0] = Fr::one();
-  for (uint32_t j = 1; j < CQ_MAX_WIDTH; j++) theta_pow[j] = theta_pow[j - 1] * theta;
-  for (size_t l0 = 0; l0 < L; l0 += CQ_FOLD_BATCH) {
-    // f = sum_j theta^(w-1-j) * e_j   (:108-116, Horner with the first expression first), the lookups of a proof per launch
-    CqFoldBatch fb;
-    fb.count = (uint32_t)std::min<size_t>(CQ_FOLD_BATCH, L - l0);
-    for (uint32_t j = 0; j < CQ_MAX_WIDTH; j++) fb.theta_pow[j] = theta_pow[j];
-    for (uint32_t q = 0; q < fb.count; q++) {
-      const size_t l = l0 + q;
-      const uint32_t w = (uint32_t)pk->lookups[l].cols.size();
-      fb.width[q] = w;
-      for (uint32_t j = 0; j < w; j++) fb.src[q][j] = lk_input[l][j];
-      // resident: f_l exists on the owner of lookup l only
-      fb.out[q] = (resident && (l < lk_lo || l >= lk_hi)) ? nullptr : f_lag + l * n;
+  int cq_round1() {
+    if (L && !early_m) {
+      CQ_TRY(count_multiplicities());
+      CQ_TRY(c->wait(s));
+      CQ_TRY(lookup_error());
     }
-    CQ_TRY(cq_fold_inputs(c, fb, (uint32_t)n));
-  }
-  if (L || PL) {
-    // permuted input / table of every legacy lookup (lookup/prover.rs:136-151), then f_cm (:165) and, unless it went
-    // out with the advice launch, m_cm (:167-172): one launch
-    std::vector<const Fr*> sc;
-    std::vector<const G1Affine*> bs;
-    std::vector<size_t> ln;
-    for (size_t l = 0; l < PL; l++)
-      for (int which = 2; which <= 3; which++) { sc.push_back(plk_buf(l, which)); bs.push_back(pk->params->g_lagrange); ln.push_back(n); }
-    // f_cm: when every input of a lookup is a plain advice column, f = sum_j theta^(w-1-j) e_j over whole columns
-    // (blinding rows included), so [f] = sum_j theta^(w-1-j) [e_j] -- w - 1 scalar multiplications of commitments
-    // round 0 already produced, done by host threads, instead of an n-term MSM.
-    std::vector<int> f_linear(L, 0);
-    std::vector<G1Jac> f_host(L);
-    for (size_t l = 0; l < L; l++) {
-      f_linear[l] = 1;
-      for (int64_t pj : pk->lookups[l].prog) f_linear[l] &= pj < 0;
+    theta_pow[0] = Fr::one();
+    for (uint32_t j = 1; j < CQ_MAX_WIDTH; j++) theta_pow[j] = theta_pow[j - 1] * theta;
+    for (size_t l0 = 0; l0 < L; l0 += CQ_FOLD_BATCH) {
+      // f = sum_j theta^(w-1-j) * e_j   (:108-116, Horner with the first expression first), the lookups of a proof per launch
+      CqFoldBatch fb;
+      fb.count = (uint32_t)std::min<size_t>(CQ_FOLD_BATCH, L - l0);
+      for (uint32_t j = 0; j < CQ_MAX_WIDTH; j++) fb.theta_pow[j] = theta_pow[j];
+      for (uint32_t q = 0; q < fb.count; q++) {
+        const size_t l = l0 + q;
+        const uint32_t w = (uint32_t)pk->lookups[l].cols.size();
+        fb.width[q] = w;
+        for (uint32_t j = 0; j < w; j++) fb.src[q][j] = lk_input[l][j];
+        // resident: f_l exists on the owner of lookup l only
+        fb.out[q] = (resident && (l < lk_lo || l >= lk_hi)) ? nullptr : B.f_lag + l * n;
+      }
+      CQ_TRY(cq_fold_inputs(c, fb, (uint32_t)n));
     }
-    std::vector<size_t> f_slot(L, 0);
-    for (size_t l = 0; l < L; l++)
-      if (!f_linear[l]) { f_slot[l] = sc.size(); sc.push_back(f_lag + l * n); bs.push_back(pk->params->g_lagrange); ln.push_back(n); }
-    const size_t m_first = sc.size();
-    if (!early_m)
-      for (size_t l = 0; l < L; l++) { sc.push_back(m_fr + l * N); bs.push_back(pk->table_cfg->g1_lagrange); ln.push_back(N); }
-    std::vector<G1Affine> cm;
-    Commit r1;
-    const uint64_t seq = c->msm_tail_seq;
-    if (!sc.empty()) CQ_TRY(r1.begin(pk, sc, bs, ln));
-    // (on the context's worker threads: the main thread goes on queueing the work that needs theta only)
-    std::vector<size_t> f_lin;
-    for (size_t l = 0; l < L; l++)
-      if (f_linear[l]) f_lin.push_back(l);
-    struct PoolJoin {  // an error path must not leave workers with references into this frame
-      HostPool& pool;
-      HostPool::Ticket t;
-      ~PoolJoin() { pool.wait(t); }
-    } f_job{c->pool(), nullptr};
-    f_job.t = c->pool().submit(f_lin.size(), [&](size_t i) {
-      const size_t l = f_lin[i];
-      const auto& lcols = pk->lookups[l].cols;
-      G1Jac acc = jac_from_affine(advice_commitments[lcols[0]]);
-      for (size_t j = 1; j < lcols.size(); j++) acc = jac_add(host_scalar_mul(acc, theta), jac_from_affine(advice_commitments[lcols[j]]));
-      f_host[l] = acc;
-    });
-    {
-      // on the side stream (under the launch's tail when there is one): f -> coefficients (:326-334) and onto the
-      // extended coset (evaluation.rs:533-548 reads it), the instance cosets -- none of them depends on beta / gamma
-      AuxFork fork(c);
-      CQ_TRY(fork.begin(seq));
-      if (resident) {
-        // resident: the owner transforms its lookups' f and its advice columns; nobody else ever reads them
-        if (lk_cnt) {
-          CQ_TRY(domain_lagrange_to_coeff(dom, f_lag + lk_lo * n, f_coeff + lk_lo * n, (uint32_t)lk_cnt, n, n));
-          CQ_TRY(domain_coeff_to_extended(dom, f_coeff + lk_lo * n, cosets + (L + lk_lo) * ext, (uint32_t)lk_cnt, n, ext));
+    if (L || PL) {
+      // permuted input / table of every legacy lookup (lookup/prover.rs:136-151), then f_cm (:165) and, unless it went
+      // out with the advice launch, m_cm (:167-172): one launch
+      std::vector<const Fr*> sc;
+      std::vector<const G1Affine*> bs;
+      std::vector<size_t> ln;
+      for (size_t l = 0; l < PL; l++)
+        for (int which = 2; which <= 3; which++) { sc.push_back(plk_buf(l, which)); bs.push_back(pk->params->g_lagrange); ln.push_back(n); }
+      // f_cm: when every input of a lookup is a plain advice column, f = sum_j theta^(w-1-j) e_j over whole columns
+      // (blinding rows included), so [f] = sum_j theta^(w-1-j) [e_j] -- w - 1 scalar multiplications of commitments
+      // round 0 already produced, done by host threads, instead of an n-term MSM.
+      std::vector<int> f_linear(L, 0);
+      std::vector<G1Jac> f_host(L);
+      for (size_t l = 0; l < L; l++) {
+        f_linear[l] = 1;
+        for (int64_t pj : pk->lookups[l].prog) f_linear[l] &= pj < 0;
+      }
+      std::vector<size_t> f_slot(L, 0);
+      for (size_t l = 0; l < L; l++)
+        if (!f_linear[l]) { f_slot[l] = sc.size(); sc.push_back(B.f_lag + l * n); bs.push_back(pk->params->g_lagrange); ln.push_back(n); }
+      const size_t m_first = sc.size();
+      if (!early_m)
+        for (size_t l = 0; l < L; l++) { sc.push_back(B.m_fr + l * N); bs.push_back(pk->table_cfg->g1_lagrange); ln.push_back(N); }
+      std::vector<G1Affine> cm;
+      Commit r1;
+      const uint64_t seq = c->msm_tail_seq;
+      if (!sc.empty()) CQ_TRY(r1.begin(pk, sc, bs, ln));
+      // (on the context's worker threads: the main thread goes on queueing the work that needs theta only)
+      std::vector<size_t> f_lin;
+      for (size_t l = 0; l < L; l++)
+        if (f_linear[l]) f_lin.push_back(l);
+      struct PoolJoin {  // an error path must not leave workers with references into this frame
+        HostPool& pool;
+        HostPool::Ticket t;
+        ~PoolJoin() { pool.wait(t); }
+      } f_job{c->pool(), nullptr};
+      f_job.t = c->pool().submit(f_lin.size(), [&](size_t i) {
+        const size_t l = f_lin[i];
+        const auto& lcols = pk->lookups[l].cols;
+        G1Jac acc = jac_from_affine(advice_commitments[lcols[0]]);
+        for (size_t j = 1; j < lcols.size(); j++) acc = jac_add(host_scalar_mul(acc, theta), jac_from_affine(advice_commitments[lcols[j]]));
+        f_host[l] = acc;
+      });
+      {
+        // on the side stream (under the launch's tail when there is one): f -> coefficients (:326-334) and onto the
+        // extended coset (evaluation.rs:533-548 reads it), the instance cosets -- none of them depends on beta / gamma
+        AuxFork fork(c);
+        CQ_TRY(fork.begin(seq));
+        if (resident) {
+          // resident: the owner transforms its lookups' f and its advice columns; nobody else ever reads them
+          if (lk_cnt) {
+            CQ_TRY(domain_lagrange_to_coeff(dom, B.f_lag + lk_lo * n, B.f_coeff + lk_lo * n, (uint32_t)lk_cnt, n, n));
+            CQ_TRY(domain_coeff_to_extended(dom, B.f_coeff + lk_lo * n, B.cosets + (L + lk_lo) * ext, (uint32_t)lk_cnt, n, ext));
+          }
+          if (!adv_is_coeff && adv_hi > adv_lo) CQ_TRY(domain_lagrange_to_coeff(dom, B.adv + adv_lo * n, B.adv + adv_lo * n, (uint32_t)(adv_hi - adv_lo), n, n));
+          adv_is_coeff = true;
+        } else {
+          if (L) {
+            CQ_TRY(lagrange_to_coeff_cols(B.f_lag, B.f_coeff, L));
+            CQ_TRY(coeff_to_extended_cols(B.f_coeff, B.cosets + L * ext, L));
+          }
+          if (general && I) CQ_TRY(coeff_to_extended_cols(B.inst_coeff, B.inst_cosets, I));
+          if (A && S == 0 && !adv_is_coeff) {
+            // advice -> coefficients (prover.rs:587-603), in place: without a permutation argument nothing reads the
+            // Lagrange values after round 1, and the round-2 inversions leave room for it
+            CQ_TRY(lagrange_to_coeff_cols(B.adv, B.adv, A));
+            adv_is_coeff = true;
+          }
         }
-        if (!adv_is_coeff && adv_hi > adv_lo) CQ_TRY(domain_lagrange_to_coeff(dom, adv + adv_lo * n, adv + adv_lo * n, (uint32_t)(adv_hi - adv_lo), n, n));
-        adv_is_coeff = true;
-      } else {
-      if (L) {
-        CQ_TRY(lagrange_to_coeff_cols(f_lag, f_coeff, L));
-        CQ_TRY(coeff_to_extended_cols(f_coeff, cosets + L * ext, L));
+        CQ_TRY(fork.end());
       }
-      if (general && I) CQ_TRY(coeff_to_extended_cols(B.inst_coeff, B.inst_cosets, I));
-      if (A && S == 0 && !adv_is_coeff) {
-        // advice -> coefficients (prover.rs:587-603), in place: without a permutation argument nothing reads the
-        // Lagrange values after round 1, and the round-2 inversions leave room for it
-        CQ_TRY(lagrange_to_coeff_cols(adv, adv, A));
-        adv_is_coeff = true;
+      if (!sc.empty()) CQ_TRY(r1.end(cm));
+      c->pool().wait(f_job.t);
+      for (size_t q = 0; q < 2 * PL; q++)
+        if (!tr.write_point(cm[q])) return c->fail(CQ_ERR_TRANSCRIPT, "permuted lookup commitment is the identity");
+      for (size_t l = 0; l < L; l++) {
+        const G1Affine f_cm = f_linear[l] ? jac_to_affine(f_host[l]) : cm[f_slot[l]];
+        if (!tr.write_point(f_cm)) return c->fail(CQ_ERR_TRANSCRIPT, "f commitment is the identity");
+        if (!tr.write_point(early_m ? m_commitments[l] : cm[m_first + l])) return c->fail(CQ_ERR_TRANSCRIPT, "m commitment is the identity");
       }
-      }
-      CQ_TRY(fork.end());
     }
-    if (!sc.empty()) CQ_TRY(r1.end(cm));
-    c->pool().wait(f_job.t);
-    for (size_t q = 0; q < 2 * PL; q++)
-      if (!tr.write_point(cm[q])) return c->fail(CQ_ERR_TRANSCRIPT, "permuted lookup commitment is the identity");
-    for (size_t l = 0; l < L; l++) {
-      const G1Affine f_cm = f_linear[l] ? jac_to_affine(f_host[l]) : cm[f_slot[l]];
-      if (!tr.write_point(f_cm)) return c->fail(CQ_ERR_TRANSCRIPT, "f commitment is the identity");
-      if (!tr.write_point(early_m ? m_commitments[l] : cm[m_first + l])) return c->fail(CQ_ERR_TRANSCRIPT, "m commitment is the identity");
-    }
+    return CQ_OK;
   }
-  mark("round 1 written");
-  const Fr beta = tr.squeeze();   // prover.rs:529
-  const Fr gamma = tr.squeeze();  // :532
-  const Fr beta_inv = beta.inv();
 
   // ---- permutation::Argument::commit (permutation/prover.rs:47-198): Lagrange values of every z ----------
-  auto column_values = [&](const std::pair<uint32_t, uint32_t>& col) -> const Fr* {
-    return col.first == CQ_COL_ADVICE ? adv + (size_t)col.second * n
-         : col.first == CQ_COL_FIXED  ? pk->fixed_values + (size_t)col.second * n
-                                      : B.inst_lag + (size_t)col.second * n;
-  };
-  if (S) {
+  int permutation_commit() {
+    if (!S) return CQ_OK;
+    auto column_values = [&](const std::pair<uint32_t, uint32_t>& col) -> const Fr* {
+      return col.first == CQ_COL_ADVICE ? B.adv + (size_t)col.second * n
+           : col.first == CQ_COL_FIXED  ? pk->fixed_values + (size_t)col.second * n
+                                        : B.inst_lag + (size_t)col.second * n;
+    };
     const Fr delta = fr_from_raw(FR_DELTA_RAW);
     std::vector<PermProductArgs> pa(S);
     Fr deltaomega = Fr::one();  // delta^(column position), :86-87,146
@@ -1030,11 +1087,12 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
     // blinding rows (:169-171)
     for (size_t st = 0; st < S; st++)
       CQ_HIP(c, hipMemcpyAsync(B.z + st * n + (n - bf), z_tails.data() + st * bf, bf * sizeof(Fr), hipMemcpyHostToDevice, s));
+    return CQ_OK;
   }
 
   // ---- legacy lookups: commit_product (lookup/prover.rs:163-300): z = running product of
   //      (A + beta)(S + gamma) / ((a' + beta)(s' + gamma)), rows n-bf.. random ---------------------------------------
-  if (PL) {
+  int legacy_commit_product() {
     for (size_t l = 0; l < PL; l++) CQ_TRY(lookup_denominators(c, plk_buf(l, 2), plk_buf(l, 3), beta, gamma, (uint32_t)n, plk_buf(l, 4)));
     for (size_t l = 0; l < PL; l++) {
       // the product vectors are not contiguous across lookups (stride 5n): one inversion launch each
@@ -1043,13 +1101,18 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       CQ_TRY(prefix_product(c, plk_buf(l, 4), plk_buf(l, 4), (uint32_t)n, 1));
       CQ_HIP(c, hipMemcpyAsync(plk_buf(l, 4) + (n - bf), plkz_tails.data() + l * bf, bf * sizeof(Fr), hipMemcpyHostToDevice, s));
     }
+    return CQ_OK;
   }
 
   // ---- CQ round 2 (static_lookup/prover.rs:187-342) -------------------------------------------------
-  std::vector<Fr> a_at_zero(L);
-  G1Affine random_cm = G1Affine::identity();
-  {
-    size_t woff = 0;
+  int cq_round2() {
+    bool random_late = false;
+    CQ_TRY(round2_prepare());
+    CQ_TRY(round2_random_late(random_late));
+    return round2_commit(random_late);
+  }
+  // round 2, before the launch: denominators, inversions, the values of a, b -> coefficients and b(0) on its way to the host
+  int round2_prepare() {
     for (size_t l0 = 0; l0 < L; l0 += CQ_FOLD_BATCH) {
       // per lookup: t_i = sum_j theta^(w-1-j) T_j[i] (compress_tables :224-240), den_i = m_i ? t_i + beta : 0 (:245-247),
       // B_r = f_r + beta for r < u, beta on the blinding rows (:261-269) -- one launch for the lookups of the proof
@@ -1063,21 +1126,21 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
         for (uint32_t j = 0; j < fb.width[q]; j++) fb.src[q][j] = lk.tables[j]->values;
         fb.out[q] = nullptr;
         const bool mine = !resident || (l >= lk_lo && l < lk_hi);  // resident: b_l on the owner of lookup l only
-        fb.f[q] = mine ? f_lag + l * n : nullptr;
-        fb.b[q] = bpoly + l * n;
-        fb.m[q] = m_counts + l * N;
-        fb.den[q] = den + l * N;
+        fb.f[q] = mine ? B.f_lag + l * n : nullptr;
+        fb.b[q] = B.bpoly + l * n;
+        fb.m[q] = B.m_counts + l * N;
+        fb.den[q] = B.den + l * N;
       }
       CQ_TRY(cq_round2_prep(c, fb, (uint32_t)n, (uint32_t)N, u, beta));
     }
     if (L && resident) {
-      if (lk_cnt) CQ_TRY(poly_batch_invert(c, bpoly + lk_lo * n, (uint32_t)(lk_cnt * n)));
-      CQ_TRY(poly_batch_invert(c, den, (uint32_t)(L * N)));  // the table side is small and stays replicated
+      if (lk_cnt) CQ_TRY(poly_batch_invert(c, B.bpoly + lk_lo * n, (uint32_t)(lk_cnt * n)));
+      CQ_TRY(poly_batch_invert(c, B.den, (uint32_t)(L * N)));  // the table side is small and stays replicated
     } else if (L) {
       // all inversions of the round in two launches (one Fermat inversion per lane dominates the latency)
-      CQ_TRY(poly_batch_invert(c, bpoly, (uint32_t)(L * n + L * N)));  // bpoly and den are adjacent
+      CQ_TRY(poly_batch_invert(c, B.bpoly, (uint32_t)(L * n + L * N)));  // bpoly and den are adjacent
     }
-    woff = 0;
+    size_t woff = 0;
     for (size_t l0 = 0; l0 < L; l0 += CQ_FOLD_BATCH) {  // a_i = m_i / (t_i + beta) and its theta-scaled copies for q_a (:247-256)
       CqAValuesBatch ab;
       ab.count = (uint32_t)std::min<size_t>(CQ_FOLD_BATCH, L - l0);
@@ -1086,10 +1149,10 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       for (uint32_t q = 0; q < ab.count; q++) {
         const size_t l = l0 + q;
         ab.width[q] = (uint32_t)pk->lookups[l].cols.size();
-        ab.den_inv[q] = den + l * N;
-        ab.m[q] = m_counts + l * N;
-        ab.a[q] = a_val + l * N;
-        ab.a_scaled[q] = a_scaled + woff * N;
+        ab.den_inv[q] = B.den + l * N;
+        ab.m[q] = B.m_counts + l * N;
+        ab.a[q] = B.a_val + l * N;
+        ab.a_scaled[q] = B.a_scaled + woff * N;
         ab.b_values[q] = b_by_rows ? B.b_values + l * (N + 1) : nullptr;
         woff += ab.width[q];
       }
@@ -1098,12 +1161,12 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
     if (L && resident) {
       // resident: the owner turns its b_l into coefficients; every rank commits its point range of b_0 = (b - b(0)) / X
       // (:279, 299, 310: the same coefficients over two base arrays), so slice r of b_l[1..n) goes from the owner to rank r
-      if (lk_cnt) CQ_TRY(domain_lagrange_to_coeff(dom, bpoly + lk_lo * n, bpoly + lk_lo * n, (uint32_t)lk_cnt, n, n));
+      if (lk_cnt) CQ_TRY(domain_lagrange_to_coeff(dom, B.bpoly + lk_lo * n, B.bpoly + lk_lo * n, (uint32_t)lk_cnt, n, n));
       for (size_t l = 0; l < L; l++) small_fr[l] = Fr::zero();
       if (lk_cnt) {
         GatherArgs ga;
         ga.count = (uint32_t)lk_cnt;
-        for (size_t l = lk_lo; l < lk_hi; l++) ga.src[l - lk_lo] = bpoly + l * n;
+        for (size_t l = lk_lo; l < lk_hi; l++) ga.src[l - lk_lo] = B.bpoly + l * n;
         CQ_TRY(poly_gather_scalars(c, ga, B.gather));
         CQ_HIP(c, hipMemcpyAsync(small_fr + lk_lo, B.gather, lk_cnt * sizeof(Fr), hipMemcpyDeviceToHost, s));  // summed over the ranks below
       }
@@ -1113,39 +1176,43 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
         for (uint32_t r = 0; r < SW; r++) {
           size_t lo, hi;
           shard_range(n - 1, r, SW, lo, hi);
-          Fr* p = bpoly + l * n + 1 + lo;
+          Fr* p = B.bpoly + l * n + 1 + lo;
           if (hi > lo) xf.push_back({p, p, (hi - lo) * sizeof(Fr), own, r});
         }
       }
       CQ_TRY(shard_exchange(pk, xf.data(), xf.size(), s));
     } else if (L) {
-      CQ_TRY(lagrange_to_coeff_cols(bpoly, bpoly, L));  // f: under round 1's launch
+      CQ_TRY(lagrange_to_coeff_cols(B.bpoly, B.bpoly, L));  // f: under round 1's launch
       // b(0) of every lookup (for a(0), :318-324): on its way to the host while the round's MSMs run
       GatherArgs ga;
       ga.count = (uint32_t)L;
-      for (size_t l = 0; l < L; l++) ga.src[l] = bpoly + l * n;
+      for (size_t l = 0; l < L; l++) ga.src[l] = B.bpoly + l * n;
       CQ_TRY(poly_gather_scalars(c, ga, B.gather));
       CQ_HIP(c, hipMemcpyAsync(small_fr, B.gather, L * sizeof(Fr), hipMemcpyDeviceToHost, s));
     }
-    // The helper thread has had rounds 0 and 1 and this round's preparation to draw the random polynomial.  From
-    // k = 20 on that is not enough (2^25 words take ~25 ms at k = 22): then the polynomial is committed in a launch
-    // of its own after the round's other MSMs, which start now.
-    // Not done yet?  A launch of its own for the polynomial costs ~0.7 ms of GPU time; waiting costs what is left of
-    // the draws.  Wait while the estimate (from the chunks done so far) stays below that, give up otherwise.
-    // The choice is timing-dependent, so sharded ranks agree on it first (late on any rank = late on all: a rank that
-    // has the polynomial ready just commits it in the second launch too).  CQ_RANDOM_LATE=0/1 pins it (tests).
-    bool random_late = false;
-    {
-      const char* force = getenv("CQ_RANDOM_LATE");
-      const auto t0 = std::chrono::steady_clock::now();
-      while (!drawer.done.load()) {
-        if (force && force[0] == '1') break;
-        const double waited = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-        if (!(force && force[0] == '0') && waited > 100.0 && drawer.remaining_us() > 700.0) break;
-        std::this_thread::yield();
-      }
-      CQ_TRY(shard_any(pk, (force && force[0] == '1') || !drawer.done.load(), random_late));
+    return CQ_OK;
+  }
+  // The helper thread has had rounds 0 and 1 and this round's preparation to draw the random polynomial.  From
+  // k = 20 on that is not enough (2^25 words take ~25 ms at k = 22): then the polynomial is committed in a launch
+  // of its own after the round's other MSMs, which start now.
+  // Not done yet?  A launch of its own for the polynomial costs ~0.7 ms of GPU time; waiting costs what is left of
+  // the draws.  Wait while the estimate (from the chunks done so far) stays below that, give up otherwise.
+  // The choice is timing-dependent, so sharded ranks agree on it first (late on any rank = late on all: a rank that
+  // has the polynomial ready just commits it in the second launch too).  CQ_RANDOM_LATE=0/1 pins it (tests).
+  int round2_random_late(bool& random_late) {
+    const char* force = getenv("CQ_RANDOM_LATE");
+    const auto t0 = std::chrono::steady_clock::now();
+    while (!drawer.done.load()) {
+      if (force && force[0] == '1') break;
+      const double waited = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+      if (!(force && force[0] == '0') && waited > 100.0 && drawer.remaining_us() > 700.0) break;
+      std::this_thread::yield();
     }
+    CQ_TRY(shard_any(pk, (force && force[0] == '1') || !drawer.done.load(), random_late));
+    return CQ_OK;
+  }
+  // round 2, the launch: side-stream fork, collection, transcript writes and a(0)
+  int round2_commit(bool random_late) {
     if (!random_late) CQ_TRY(finish_random_poly());
     // commitments, one batch of launches: the permutation products (permutation/prover.rs:177, written first),
     // then a, a0 (dense over the table SRS), q_a (over [qs_0|qs_1|...]), p, b0 (n-1 terms of b[1..]) and the
@@ -1163,22 +1230,22 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
         for (size_t q = 0; q < 2; q++) { sc.push_back(B.b_values + l * (N + 1)); bs.push_back(B.b_sums + (2 * l + q) * (N + 1)); ln.push_back(N + 1); }
       for (size_t st = 0; st < S; st++) { at.push_back(sc.size()); sc.push_back(B.z + st * n); bs.push_back(pk->params->g_lagrange); ln.push_back(n); }
       for (size_t l = 0; l < PL; l++) { at.push_back(sc.size()); sc.push_back(plk_buf(l, 4)); bs.push_back(pk->params->g_lagrange); ln.push_back(n); }
-      woff = 0;
+      size_t woff = 0;
       for (size_t l = 0; l < L; l++) {
         const uint32_t w = (uint32_t)pk->lookups[l].cols.size();
-        at.push_back(sc.size()); sc.push_back(a_val + l * N); bs.push_back(pk->table_cfg->g1_lagrange); ln.push_back(N);             // a
-        at.push_back(sc.size()); sc.push_back(a_scaled + woff * N); bs.push_back(pk->qs_concat[l]); ln.push_back((size_t)w * N);      // q_a
-        at.push_back(sc.size()); sc.push_back(a_val + l * N); bs.push_back(pk->table_cfg->g_lagrange_opening_at_0); ln.push_back(N);  // a0
+        at.push_back(sc.size()); sc.push_back(B.a_val + l * N); bs.push_back(pk->table_cfg->g1_lagrange); ln.push_back(N);             // a
+        at.push_back(sc.size()); sc.push_back(B.a_scaled + woff * N); bs.push_back(pk->qs_concat[l]); ln.push_back((size_t)w * N);      // q_a
+        at.push_back(sc.size()); sc.push_back(B.a_val + l * N); bs.push_back(pk->table_cfg->g_lagrange_opening_at_0); ln.push_back(N);  // a0
         if (b_by_rows) {
           at.push_back(2 * l);      // b0 (:310)
           at.push_back(2 * l + 1);  // p (:299)
         } else {
-          at.push_back(sc.size()); sc.push_back(bpoly + l * n + 1); bs.push_back(pk->params->g); ln.push_back(n - 1);     // b0
-          at.push_back(sc.size()); sc.push_back(bpoly + l * n + 1); bs.push_back(pk->b0_g1_bound); ln.push_back(n - 1);   // p
+          at.push_back(sc.size()); sc.push_back(B.bpoly + l * n + 1); bs.push_back(pk->params->g); ln.push_back(n - 1);     // b0
+          at.push_back(sc.size()); sc.push_back(B.bpoly + l * n + 1); bs.push_back(pk->b0_g1_bound); ln.push_back(n - 1);   // p
         }
         woff += w;
       }
-      if (!random_late) { at.push_back(sc.size()); sc.push_back(random_poly); bs.push_back(pk->params->g); ln.push_back(n); }
+      if (!random_late) { at.push_back(sc.size()); sc.push_back(B.random_poly); bs.push_back(pk->params->g); ln.push_back(n); }
       Commit r2cm;
       const uint64_t seq = c->msm_tail_seq;
       CQ_TRY(r2cm.begin(pk, sc, bs, ln));
@@ -1188,11 +1255,11 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
         // (evaluation.rs:317-335), b onto the extended coset
         AuxFork fork(c);
         CQ_TRY(fork.begin(seq));
-        if (A && !adv_is_coeff) CQ_TRY(lagrange_to_coeff_cols(adv, adv, A));
+        if (A && !adv_is_coeff) CQ_TRY(lagrange_to_coeff_cols(B.adv, B.adv, A));
         if (L && resident) {  // resident: b_l's coset stays with the owner of lookup l (the quotient is folded there)
-          if (lk_cnt) CQ_TRY(domain_coeff_to_extended(dom, bpoly + lk_lo * n, cosets + lk_lo * ext, (uint32_t)lk_cnt, n, ext));
-        } else if (L) CQ_TRY(coeff_to_extended_cols(bpoly, cosets, L));
-        if (general && A) CQ_TRY(coeff_to_extended_cols(adv, B.adv_cosets, A));
+          if (lk_cnt) CQ_TRY(domain_coeff_to_extended(dom, B.bpoly + lk_lo * n, B.cosets + lk_lo * ext, (uint32_t)lk_cnt, n, ext));
+        } else if (L) CQ_TRY(coeff_to_extended_cols(B.bpoly, B.cosets, L));
+        if (general && A) CQ_TRY(coeff_to_extended_cols(B.adv, B.adv_cosets, A));
         CQ_TRY(fork.end());
       }
       if (random_late) CQ_TRY(finish_random_poly());  // queued behind the launch above
@@ -1205,7 +1272,7 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       mark("round 2 commitments on the host");
       if (random_late) {
         std::vector<G1Affine> rc;
-        CQ_TRY(commit_batch(pk, {random_poly}, {pk->params->g}, n, rc));
+        CQ_TRY(commit_batch(pk, {B.random_poly}, {pk->params->g}, n, rc));
         r2.push_back(rc[0]);
       }
     }
@@ -1231,19 +1298,11 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       for (size_t l = 0; l < L; l++)
         a_at_zero[l] = (small_fr[l] * Fr::from_u64(n) - Fr::from_u64(bf + 1) * beta_inv) * n_table_inv;
     }
+    return CQ_OK;
   }
 
-  // ---- vanishing::Argument::commit (vanishing/prover.rs:37-65): drawn and committed above ---------
-  if (!tr.write_point(random_cm)) return c->fail(CQ_ERR_TRANSCRIPT, "random poly commitment is the identity");
-  const Fr y = tr.squeeze();  // prover.rs:584
-  mark("y");
-
-  // advice polys (lagrange_to_coeff, :587-603) and the cosets of advice / instance / b / f were computed on the side
-  // stream under the round-1 and round-2 launches
-  CQ_TRY(join_aux(c));
-
   // ---- evaluate_h (evaluation.rs:285-551) + divide by the vanishing polynomial ------------------------
-  {
+  int evaluate_h() {
     if (general) {
       // advice / instance cosets (:317-335), permutation product cosets (permutation/prover.rs:182)
       if (I && !(L || PL)) CQ_TRY(coeff_to_extended_cols(B.inst_coeff, B.inst_cosets, I));  // no round 1
@@ -1262,9 +1321,9 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
         ga.size = (uint32_t)ext;
         ga.rot_scale = rot_scale;
         ga.y = y;
-        CQ_TRY(gate_eval(c, ga, h_ext));
+        CQ_TRY(gate_eval(c, ga, B.h_ext));
       } else {
-        CQ_HIP(c, hipMemsetAsync(h_ext, 0, ext * sizeof(Fr), s));
+        CQ_HIP(c, hipMemsetAsync(B.h_ext, 0, ext * sizeof(Fr), s));
       }
       if (S) {  // permutation constraints (:367-459)
         PermHArgs ph;
@@ -1292,7 +1351,7 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
         ph.ext = (uint32_t)ext;
         ph.rot_scale = rot_scale;
         ph.last_rot = bf + 1;
-        CQ_TRY(perm_h_terms(c, ph, h_ext));
+        CQ_TRY(perm_h_terms(c, ph, B.h_ext));
       }
     }
     for (size_t l = 0; l < PL; l++) {  // legacy lookup constraints (:461-531)
@@ -1329,16 +1388,16 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       la.y = y;
       la.ext = (uint32_t)ext;
       la.rot_scale = rot_scale;
-      CQ_TRY(lookup_h_terms(c, la, h_ext));
+      CQ_TRY(lookup_h_terms(c, la, B.h_ext));
     }
     // CQ terms (:533-548), then the division by X^n - 1 (vanishing/prover.rs:84, domain.rs:319-338)
     CqQuotientArgs qa;
     qa.count = (uint32_t)(resident ? lk_cnt : L);
     for (size_t l = 0; l < qa.count; l++) {
-      qa.b[l] = cosets + ((resident ? lk_lo : 0) + l) * ext;
-      qa.f[l] = cosets + (L + (resident ? lk_lo : 0) + l) * ext;
+      qa.b[l] = B.cosets + ((resident ? lk_lo : 0) + l) * ext;
+      qa.f[l] = B.cosets + (L + (resident ? lk_lo : 0) + l) * ext;
     }
-    qa.h_in = general ? h_ext : nullptr;
+    qa.h_in = general ? B.h_ext : nullptr;
     qa.l_active = pk->l_active_row;
     qa.t_evals = dom->t_evaluations_dev;
     qa.t_len = (uint32_t)dom->t_evaluations.size();
@@ -1350,159 +1409,145 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       qa.scale = y.pow_u64(L - lk_hi);
       qa.has_scale = 1;
     }
-    if (!resident || lk_cnt) CQ_TRY(poly_cq_quotient(c, qa, (uint32_t)ext, h_ext));
+    if (!resident || lk_cnt) CQ_TRY(poly_cq_quotient(c, qa, (uint32_t)ext, B.h_ext));
+    return CQ_OK;
   }
   // vanishing.construct (vanishing/prover.rs:69-120): coefficients, n-sized pieces, blinds, commitments
-  const size_t pieces = dom->quotient_poly_degree;
-  if (!resident || lk_cnt) CQ_TRY(domain_extended_to_coeff(dom, h_ext, h_coeff));
-  if (resident) {
-    // resident: division by X^n - 1, extended_to_coeff and the commitments are all linear, so each owner transformed its
-    // PARTIAL quotient; rank r now collects slice r of every piece from every owner and adds them up -- it holds the
-    // coefficients of h on its own point range only (which is all its share of the commitments, evaluations and the
-    // opening reads).  Staging: the buffer reserved at set-up.
-    const size_t slice_max = res_slice_max;
-    Fr* const stage = (Fr*)res_stage_v;
-    std::vector<uint32_t> owners;  // ranks that own a lookup
-    for (uint32_t q = 0; q < SW; q++) {
+  int construct_h() {
+    if (!resident || lk_cnt) CQ_TRY(domain_extended_to_coeff(dom, B.h_ext, B.h_coeff));
+    if (resident) {
+      // resident: division by X^n - 1, extended_to_coeff and the commitments are all linear, so each owner transformed its
+      // PARTIAL quotient; rank r now collects slice r of every piece from every owner and adds them up -- it holds the
+      // coefficients of h on its own point range only (which is all its share of the commitments, evaluations and the
+      // opening reads).  Staging: the buffer reserved at set-up.
+      const size_t slice_max = res_slice_max;
+      Fr* const stage = (Fr*)res_stage_v;
+      std::vector<uint32_t> owners;  // ranks that own a lookup
+      for (uint32_t q = 0; q < SW; q++) {
+        size_t lo, hi;
+        shard_range(L, q, SW, lo, hi);
+        if (hi > lo) owners.push_back(q);
+      }
+      if (owners.size() * pieces * slice_max > res_stage_elems) return c->fail(CQ_ERR_INTERNAL, "resident sharding: staging too small");
+      std::vector<Xfer> xf;
+      for (size_t oi = 0; oi < owners.size(); oi++)
+        for (size_t i = 0; i < pieces; i++)
+          for (uint32_t r = 0; r < SW; r++) {
+            size_t lo, hi;
+            shard_range(n, r, SW, lo, hi);
+            if (hi > lo) xf.push_back({B.h_coeff + i * n + lo, stage + (oi * pieces + i) * slice_max, (hi - lo) * sizeof(Fr), owners[oi], r});
+          }
+      CQ_TRY(shard_exchange(pk, xf.data(), xf.size(), s));
       size_t lo, hi;
-      shard_range(L, q, SW, lo, hi);
-      if (hi > lo) owners.push_back(q);
+      shard_range(n, me, SW, lo, hi);
+      for (size_t i = 0; i < pieces && hi > lo; i++) {
+        std::vector<Term> terms;
+        for (size_t oi = 0; oi < owners.size(); oi++) terms.push_back({stage + (oi * pieces + i) * slice_max, (uint32_t)(hi - lo), Fr::one()});
+        CQ_TRY(lincomb_many(c, terms, Fr::zero(), (uint32_t)(hi - lo), B.h_coeff + i * n + lo));
+      }
     }
-    if (owners.size() * pieces * slice_max > res_stage_elems) return c->fail(CQ_ERR_INTERNAL, "resident sharding: staging too small");
-    std::vector<Xfer> xf;
-    for (size_t oi = 0; oi < owners.size(); oi++)
-      for (size_t i = 0; i < pieces; i++)
-        for (uint32_t r = 0; r < SW; r++) {
-          size_t lo, hi;
-          shard_range(n, r, SW, lo, hi);
-          if (hi > lo) xf.push_back({h_coeff + i * n + lo, stage + (oi * pieces + i) * slice_max, (hi - lo) * sizeof(Fr), owners[oi], r});
-        }
-    CQ_TRY(shard_exchange(pk, xf.data(), xf.size(), s));
-    size_t lo, hi;
-    shard_range(n, me, SW, lo, hi);
-    for (size_t i = 0; i < pieces && hi > lo; i++) {
-      std::vector<Term> terms;
-      for (size_t oi = 0; oi < owners.size(); oi++) terms.push_back({stage + (oi * pieces + i) * slice_max, (uint32_t)(hi - lo), Fr::one()});
-      CQ_TRY(lincomb_many(c, terms, Fr::zero(), (uint32_t)(hi - lo), h_coeff + i * n + lo));
+    for (size_t i = 0; i < pieces; i++) (void)rng.fr();  // h_blinds (:95-98)
+    {
+      std::vector<const Fr*> sc(pieces);
+      std::vector<const G1Affine*> bs(pieces, pk->params->g);
+      for (size_t i = 0; i < pieces; i++) sc[i] = B.h_coeff + i * n;
+      std::vector<G1Affine> o;
+      CQ_TRY(commit_batch(pk, sc, bs, n, o));
+      for (auto& p : o)
+        if (!tr.write_point(p)) return c->fail(CQ_ERR_TRANSCRIPT, "h piece commitment is the identity");
     }
+    return CQ_OK;
   }
-  for (size_t i = 0; i < pieces; i++) (void)rng.fr();  // h_blinds (:95-98)
-  {
-    std::vector<const Fr*> sc(pieces);
-    std::vector<const G1Affine*> bs(pieces, pk->params->g);
-    for (size_t i = 0; i < pieces; i++) sc[i] = h_coeff + i * n;
-    std::vector<G1Affine> o;
-    CQ_TRY(commit_batch(pk, sc, bs, n, o));
-    for (auto& p : o)
-      if (!tr.write_point(p)) return c->fail(CQ_ERR_TRANSCRIPT, "h piece commitment is the identity");
-  }
-  const Fr x = tr.squeeze();  // prover.rs:629
-  mark("x");
-  const Fr xn = x.pow_u64(n);
 
   // ---- evaluations (prover.rs:654-719) and opening queries (:721-773) ------------------------------------
-  // Every polynomial opened by the proof, in the order ProverGWC receives the queries; `written` marks the
-  // evaluations the transcript carries (h is opened but its value is derived, vanishing/prover.rs:131-153).
-  struct Query {
-    const Fr* p;
-    uint32_t len;
-    int32_t rot;
-    int h_piece;  // -1, or the index of an h piece (folded into one query with coefficient xn^i)
-    Fr eval;
-  };
-  std::vector<Query> qs;
-  auto add_query = [&](const Fr* p, size_t len, int32_t rot) {
-    qs.push_back({p, (uint32_t)len, rot, -1, Fr::zero()});
-    return qs.size() - 1;
-  };
-  const int32_t rot_last = -(int32_t)(bf + 1);
-  std::vector<size_t> q_advice, q_fixed, q_sigma, q_z, q_z_next, q_z_last(S, (size_t)-1), q_b0, q_f, q_h;
-  for (auto& q : pk->advice_queries) q_advice.push_back(add_query(adv_poly + (size_t)q.first * n, n, q.second));
-  for (size_t st = 0; st < S; st++) {  // permutation::Evaluated::open (permutation/prover.rs:294-344)
-    q_z.push_back(add_query(B.z + st * n, n, 0));
-    q_z_next.push_back(add_query(B.z + st * n, n, 1));
-  }
-  for (size_t st = S > 0 ? S - 1 : 0; st-- > 0;) q_z_last[st] = add_query(B.z + st * n, n, rot_last);
-  std::vector<std::array<size_t, 5>> q_plk(PL);  // lookup::Evaluated::open (lookup/prover.rs:343-392): z, a', s' @ x, a' @ x/w, z @ wx
-  for (size_t l = 0; l < PL; l++)
-    q_plk[l] = {add_query(plk_buf(l, 4), n, 0), add_query(plk_buf(l, 2), n, 0), add_query(plk_buf(l, 3), n, 0),
-                add_query(plk_buf(l, 2), n, -1), add_query(plk_buf(l, 4), n, 1)};
-  for (size_t l = 0; l < L; l++) {  // static_lookup::Evaluated::open
-    q_b0.push_back(add_query(bpoly + l * n + 1, n - 1, 0));  // b0 = (b - b(0))/X
-    q_f.push_back(add_query(f_coeff + l * n, n, 0));
-  }
-  for (auto& q : pk->fixed_queries) q_fixed.push_back(add_query(pk->fixed_polys + (size_t)q.first * n, n, q.second));
-  for (size_t ci = 0; ci < PC; ci++) q_sigma.push_back(add_query(pk->perm_polys + ci * n, n, 0));  // ProvingKey::open (:215-225)
-  for (size_t i = 0; i < pieces; i++) {
-    q_h.push_back(add_query(h_coeff + i * n, n, 0));
-    qs.back().h_piece = (int)i;
-  }
-  const size_t q_random = add_query(random_poly, n, 0);
-  // distinct points in first-seen order (gwc.rs:36-61); rotate_omega (domain.rs:414-424)
-  std::vector<int32_t> rots;
-  for (auto& q : qs)
-    if (std::find(rots.begin(), rots.end(), q.rot) == rots.end()) rots.push_back(q.rot);
-  auto point_of = [&](int32_t rot) { return rot >= 0 ? x * dom->omega.pow_u64((uint64_t)rot) : x * dom->omega_inv.pow_u64((uint64_t)(-(int64_t)rot)); };
-  // resident: who holds what -- an advice polynomial on the owner of its column, b_0 / f of a lookup on its owner (whole
-  // polynomials, evaluated there), the h pieces and the random polynomial on every rank by point range (each rank
-  // evaluates its range and multiplies by x^lo).  qowner[i] = owning rank, or -1 for "by point range".
-  std::vector<int> qowner(qs.size(), -1);
-  size_t my_lo = 0, my_hi = n;  // this rank's point range of a length-n vector
-  if (resident) {
-    shard_range(n, me, SW, my_lo, my_hi);
-    for (size_t j = 0; j < q_advice.size(); j++) qowner[q_advice[j]] = (int)owner_of(pk->advice_queries[j].first, A);
-    for (size_t l = 0; l < L; l++) qowner[q_b0[l]] = qowner[q_f[l]] = (int)owner_of(l, L);
-    std::vector<const Fr*> ps;
-    std::vector<uint32_t> ls;
-    std::vector<size_t> idx;
-    for (size_t i = 0; i < qs.size(); i++) {
-      if (qowner[i] >= 0 && qowner[i] != (int)me) continue;
-      const bool whole = qowner[i] >= 0;
-      if (!whole && my_hi <= my_lo) continue;
-      ps.push_back(whole ? qs[i].p : qs[i].p + my_lo);
-      ls.push_back(whole ? qs[i].len : (uint32_t)(my_hi - my_lo));
-      idx.push_back(i);
+  int evaluate_and_write() {
+    const int32_t rot_last = -(int32_t)(bf + 1);
+    std::vector<size_t> q_advice, q_fixed, q_sigma, q_z, q_z_next, q_z_last(S, (size_t)-1), q_b0, q_f;
+    for (auto& q : pk->advice_queries) q_advice.push_back(add_query(adv_poly + (size_t)q.first * n, n, q.second));
+    for (size_t st = 0; st < S; st++) {  // permutation::Evaluated::open (permutation/prover.rs:294-344)
+      q_z.push_back(add_query(B.z + st * n, n, 0));
+      q_z_next.push_back(add_query(B.z + st * n, n, 1));
     }
-    std::vector<Fr> ev(ps.size()), contrib(qs.size(), Fr::zero());
-    if (!ps.empty()) CQ_TRY(eval_many(c, ps, ls, x, ev.data()));
-    const Fr x_lo = x.pow_u64(my_lo);
-    for (size_t j = 0; j < idx.size(); j++) contrib[idx[j]] = qowner[idx[j]] >= 0 ? ev[j] : ev[j] * x_lo;
-    CQ_TRY(shard_sum_scalars(pk, contrib.data(), contrib.size()));  // one all-gather: every evaluation is a sum over the ranks
-    for (size_t i = 0; i < qs.size(); i++) qs[i].eval = contrib[i];
-  } else
-  for (int32_t rot : rots) {
-    std::vector<const Fr*> ps;
-    std::vector<uint32_t> ls;
-    std::vector<size_t> idx;
-    for (size_t i = 0; i < qs.size(); i++)
-      if (qs[i].rot == rot) {
-        ps.push_back(qs[i].p);
-        ls.push_back(qs[i].len);
+    for (size_t st = S > 0 ? S - 1 : 0; st-- > 0;) q_z_last[st] = add_query(B.z + st * n, n, rot_last);
+    std::vector<std::array<size_t, 5>> q_plk(PL);  // lookup::Evaluated::open (lookup/prover.rs:343-392): z, a', s' @ x, a' @ x/w, z @ wx
+    for (size_t l = 0; l < PL; l++)
+      q_plk[l] = {add_query(plk_buf(l, 4), n, 0), add_query(plk_buf(l, 2), n, 0), add_query(plk_buf(l, 3), n, 0),
+                  add_query(plk_buf(l, 2), n, -1), add_query(plk_buf(l, 4), n, 1)};
+    for (size_t l = 0; l < L; l++) {  // static_lookup::Evaluated::open
+      q_b0.push_back(add_query(B.bpoly + l * n + 1, n - 1, 0));  // b0 = (b - b(0))/X
+      q_f.push_back(add_query(B.f_coeff + l * n, n, 0));
+    }
+    for (auto& q : pk->fixed_queries) q_fixed.push_back(add_query(pk->fixed_polys + (size_t)q.first * n, n, q.second));
+    for (size_t ci = 0; ci < PC; ci++) q_sigma.push_back(add_query(pk->perm_polys + ci * n, n, 0));  // ProvingKey::open (:215-225)
+    for (size_t i = 0; i < pieces; i++) {
+      q_h.push_back(add_query(B.h_coeff + i * n, n, 0));
+      qs.back().h_piece = (int)i;
+    }
+    const size_t q_random = add_query(B.random_poly, n, 0);
+    // distinct points in first-seen order (gwc.rs:36-61)
+    for (auto& q : qs)
+      if (std::find(rots.begin(), rots.end(), q.rot) == rots.end()) rots.push_back(q.rot);
+    // resident: who holds what -- an advice polynomial on the owner of its column, b_0 / f of a lookup on its owner (whole
+    // polynomials, evaluated there), the h pieces and the random polynomial on every rank by point range (each rank
+    // evaluates its range and multiplies by x^lo).  qowner[i] = owning rank, or -1 for "by point range".
+    qowner.assign(qs.size(), -1);
+    if (resident) {
+      shard_range(n, me, SW, my_lo, my_hi);
+      for (size_t j = 0; j < q_advice.size(); j++) qowner[q_advice[j]] = (int)owner_of(pk->advice_queries[j].first, A);
+      for (size_t l = 0; l < L; l++) qowner[q_b0[l]] = qowner[q_f[l]] = (int)owner_of(l, L);
+      std::vector<const Fr*> ps;
+      std::vector<uint32_t> ls;
+      std::vector<size_t> idx;
+      for (size_t i = 0; i < qs.size(); i++) {
+        if (qowner[i] >= 0 && qowner[i] != (int)me) continue;
+        const bool whole = qowner[i] >= 0;
+        if (!whole && my_hi <= my_lo) continue;
+        ps.push_back(whole ? qs[i].p : qs[i].p + my_lo);
+        ls.push_back(whole ? qs[i].len : (uint32_t)(my_hi - my_lo));
         idx.push_back(i);
       }
-    std::vector<Fr> ev(ps.size());
-    CQ_TRY(eval_many(c, ps, ls, point_of(rot), ev.data()));
-    for (size_t j = 0; j < idx.size(); j++) qs[idx[j]].eval = ev[j];
-  }
-  for (size_t i : q_advice) tr.write_scalar(qs[i].eval);  // :654-672
-  for (size_t i : q_fixed) tr.write_scalar(qs[i].eval);   // :674-687
-  tr.write_scalar(qs[q_random].eval);                     // vanishing/prover.rs:145-146
-  for (size_t i : q_sigma) tr.write_scalar(qs[i].eval);   // permutation/prover.rs:227-239
-  for (size_t st = 0; st < S; st++) {                     // :243-290
-    tr.write_scalar(qs[q_z[st]].eval);
-    tr.write_scalar(qs[q_z_next[st]].eval);
-    if (st + 1 < S) tr.write_scalar(qs[q_z_last[st]].eval);
-  }
-  for (size_t l = 0; l < PL; l++)  // lookup::Committed::evaluate (lookup/prover.rs:303-340): z, z(wx), a', a'(x/w), s'
-    for (size_t which : {(size_t)0, (size_t)4, (size_t)1, (size_t)3, (size_t)2}) tr.write_scalar(qs[q_plk[l][which]].eval);
-  for (size_t l = 0; l < L; l++) {  // static_lookup/prover.rs:360-370
-    tr.write_scalar(qs[q_b0[l]].eval);
-    tr.write_scalar(qs[q_f[l]].eval);
-    tr.write_scalar(a_at_zero[l]);
+      std::vector<Fr> ev(ps.size()), contrib(qs.size(), Fr::zero());
+      if (!ps.empty()) CQ_TRY(eval_many(c, ps, ls, x, ev.data()));
+      const Fr x_lo = x.pow_u64(my_lo);
+      for (size_t j = 0; j < idx.size(); j++) contrib[idx[j]] = qowner[idx[j]] >= 0 ? ev[j] : ev[j] * x_lo;
+      CQ_TRY(shard_sum_scalars(pk, contrib.data(), contrib.size()));  // one all-gather: every evaluation is a sum over the ranks
+      for (size_t i = 0; i < qs.size(); i++) qs[i].eval = contrib[i];
+    } else
+    for (int32_t rot : rots) {
+      std::vector<const Fr*> ps;
+      std::vector<uint32_t> ls;
+      std::vector<size_t> idx;
+      for (size_t i = 0; i < qs.size(); i++)
+        if (qs[i].rot == rot) {
+          ps.push_back(qs[i].p);
+          ls.push_back(qs[i].len);
+          idx.push_back(i);
+        }
+      std::vector<Fr> ev(ps.size());
+      CQ_TRY(eval_many(c, ps, ls, point_of(rot), ev.data()));
+      for (size_t j = 0; j < idx.size(); j++) qs[idx[j]].eval = ev[j];
+    }
+    for (size_t i : q_advice) tr.write_scalar(qs[i].eval);  // :654-672
+    for (size_t i : q_fixed) tr.write_scalar(qs[i].eval);   // :674-687
+    tr.write_scalar(qs[q_random].eval);                     // vanishing/prover.rs:145-146
+    for (size_t i : q_sigma) tr.write_scalar(qs[i].eval);   // permutation/prover.rs:227-239
+    for (size_t st = 0; st < S; st++) {                     // :243-290
+      tr.write_scalar(qs[q_z[st]].eval);
+      tr.write_scalar(qs[q_z_next[st]].eval);
+      if (st + 1 < S) tr.write_scalar(qs[q_z_last[st]].eval);
+    }
+    for (size_t l = 0; l < PL; l++)  // lookup::Committed::evaluate (lookup/prover.rs:303-340): z, z(wx), a', a'(x/w), s'
+      for (size_t which : {(size_t)0, (size_t)4, (size_t)1, (size_t)3, (size_t)2}) tr.write_scalar(qs[q_plk[l][which]].eval);
+    for (size_t l = 0; l < L; l++) {  // static_lookup/prover.rs:360-370
+      tr.write_scalar(qs[q_b0[l]].eval);
+      tr.write_scalar(qs[q_f[l]].eval);
+      tr.write_scalar(a_at_zero[l]);
+    }
+    return CQ_OK;
   }
 
   // ---- multiopen, SHPLONK (shplonk/prover.rs:120-286): two commitments whatever the number of points ---------
-  if (pk->opener == CQ_OPENER_SHPLONK) {
+  int open_shplonk() {
     Fr* sh_h = B.shplonk;           // h(X) = sum_i xn^i h_i as one polynomial (vanishing/prover.rs:131-135)
     Fr* sh_div[2] = {B.shplonk + n, B.shplonk + 2 * n};
     Fr* sh_hx = B.shplonk + 3 * n;
@@ -1513,7 +1558,7 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
       std::vector<Term> terms;
       Fr xp = Fr::one();
       for (size_t i = 0; i < pieces; i++) {
-        terms.push_back({h_coeff + i * n, (uint32_t)n, xp});
+        terms.push_back({B.h_coeff + i * n, (uint32_t)n, xp});
         xp = xp * xn;
       }
       CQ_TRY(lincomb_many(c, terms, Fr::zero(), (uint32_t)n, sh_h));
@@ -1547,33 +1592,6 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
     }
     if (sets.size() > 64) return c->fail(CQ_ERR_ARG, "too many rotation sets");
     const Fr v_ = tr.squeeze();  // :196
-    // lagrange_interpolate (arithmetic.rs:425-478) of a commitment's evaluations over its set's points
-    auto interpolate = [&](const std::vector<Fr>& pts, const std::vector<Fr>& evals) {
-      const size_t m = pts.size();
-      if (m == 1) return std::vector<Fr>{evals[0]};
-      std::vector<Fr> fin(m, Fr::zero());
-      for (size_t j = 0; j < m; j++) {
-        std::vector<Fr> tmp{Fr::one()};
-        for (size_t kk = 0; kk < m; kk++) {
-          if (kk == j) continue;
-          const Fr denom = (pts[j] - pts[kk]).inv();
-          std::vector<Fr> nxt(tmp.size() + 1, Fr::zero());
-          for (size_t i = 0; i <= tmp.size(); i++) {
-            const Fr a_ = i < tmp.size() ? tmp[i] : Fr::zero();
-            const Fr b_ = i > 0 ? tmp[i - 1] : Fr::zero();
-            nxt[i] = a_ * (Fr::zero() - denom * pts[kk]) + b_ * denom;
-          }
-          tmp.swap(nxt);
-        }
-        for (size_t i = 0; i < m; i++) fin[i] = fin[i] + tmp[i] * evals[j];
-      }
-      return fin;
-    };
-    auto eval_small = [](const std::vector<Fr>& poly, const Fr& at) {
-      Fr acc = Fr::zero();
-      for (size_t i = poly.size(); i-- > 0;) acc = acc * at + poly[i];
-      return acc;
-    };
     // per set: low-degree equivalents r_j and the y-combined remainder (CommitmentExtension, :36-76)
     std::vector<std::vector<Fr>> set_points(sets.size());
     std::vector<std::vector<std::vector<Fr>>> low(sets.size());
@@ -1589,7 +1607,7 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
           const size_t pos = std::find(coms[ci].rots.begin(), coms[ci].rots.end(), r) - coms[ci].rots.begin();
           evals.push_back(coms[ci].evals[pos]);
         }
-        low[si].push_back(interpolate(set_points[si], evals));
+        low[si].push_back(lagrange_interpolate(set_points[si], evals));
         for (size_t i = 0; i < low[si].back().size(); i++) rem_host[si * 8 + i] = rem_host[si * 8 + i] + py * low[si].back()[i];
         py = py * y_;
       }
@@ -1667,12 +1685,11 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
     std::vector<G1Affine> o;
     CQ_TRY(commit_batch(pk, sc, bs, n - 1, o));  // :270
     if (!tr.write_point(o[0])) return c->fail(CQ_ERR_TRANSCRIPT, "shplonk opening commitment is the identity");
-    proof_out.swap(tr.proof);
     return CQ_OK;
   }
 
   // ---- multiopen, GWC (gwc/prover.rs:42-91): one witness polynomial per distinct point ---------------------
-  {
+  int open_gwc() {
     const Fr v = tr.squeeze();
     // h(X) = sum_i xn^i h_i (vanishing/prover.rs:131-135); its value follows from the piece evaluations
     Fr h_eval = Fr::zero();
@@ -1771,8 +1788,59 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
     CQ_TRY(commit_batch(pk, sc, bs, n - 1, o));  // :85
     for (auto& w : o)
       if (!tr.write_point(w)) return c->fail(CQ_ERR_TRANSCRIPT, "opening witness commitment is the identity");
+    return CQ_OK;
   }
-  mark("done");
+};
+
+}  // namespace
+
+size_t prover_arena_elems(const cq_pk* pk) {
+  Arena ar{nullptr};
+  Buffers b;
+  carve(pk, ar, b);
+  return ar.used + 1024;
+}
+
+int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_t* const* instances,
+                     const size_t* instance_lens, cq_phase_fn phase_fn, void* phase_user, cq_rng_next_u64 rng_next,
+                     void* rng_state, std::vector<uint8_t>& proof_out) {
+  ProofRun run(pk, rng_next, rng_state);
+  Transcript& tr = run.tr;
+  cq_ctx* c = pk->ctx;
+  CQ_TRY(run.setup());
+  tr.common_scalar(pk->vk_repr);  // prover.rs:85 -- vk.hash_into(transcript)
+  CQ_TRY(run.absorb_instances(instances, instance_lens));
+  CQ_TRY(run.advice_phases(advice_dev, phase_fn, phase_user));
+  run.theta = tr.squeeze();  // :472
+  run.mark("theta");
+  CQ_TRY(run.legacy_commit_permuted());
+  CQ_TRY(run.cq_round1());
+  run.mark("round 1 written");
+  run.beta = tr.squeeze();   // prover.rs:529
+  run.gamma = tr.squeeze();  // :532
+  run.beta_inv = run.beta.inv();
+  CQ_TRY(run.permutation_commit());
+  CQ_TRY(run.legacy_commit_product());
+  CQ_TRY(run.cq_round2());
+  // ---- vanishing::Argument::commit (vanishing/prover.rs:37-65): drawn and committed in round 2 ---------
+  if (!tr.write_point(run.random_cm)) return c->fail(CQ_ERR_TRANSCRIPT, "random poly commitment is the identity");
+  run.y = tr.squeeze();  // prover.rs:584
+  run.mark("y");
+  // advice polys (lagrange_to_coeff, :587-603) and the cosets of advice / instance / b / f were computed on the side
+  // stream under the round-1 and round-2 launches
+  CQ_TRY(join_aux(c));
+  CQ_TRY(run.evaluate_h());
+  CQ_TRY(run.construct_h());
+  run.x = tr.squeeze();  // prover.rs:629
+  run.mark("x");
+  run.xn = run.x.pow_u64(run.n);
+  CQ_TRY(run.evaluate_and_write());
+  if (pk->opener == CQ_OPENER_SHPLONK) {
+    CQ_TRY(run.open_shplonk());
+  } else {
+    CQ_TRY(run.open_gwc());
+    run.mark("done");
+  }
   proof_out.swap(tr.proof);
   return CQ_OK;
 }

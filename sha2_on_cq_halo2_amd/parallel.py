@@ -28,7 +28,7 @@ def shard_range(n: int, rank: int, world: int):
 
 def column_owner(column: int, batch: int, world: int) -> int:
     """Owner rank of column `column` of a batch of `batch` independent column transforms: the rank whose
-    `shard_range(batch, rank, world)` holds it (what `sharded_transform` in csrc/prover.hip uses)."""
+    `shard_range(batch, rank, world)` holds it (what `ProofRun::sharded_transform` in csrc/prover.hip uses)."""
     for r in range(world):
         lo, hi = shard_range(batch, r, world)
         if lo <= column < hi:

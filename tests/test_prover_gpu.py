@@ -74,10 +74,12 @@ def test_my_test_shape_proof_bytes(ctx):
     assert CV.verify_proof(proof, env["circ"], env["vk_repr"], env["s"], tv, 16, 16)
 
 
-@pytest.mark.parametrize("k,nbits,pairs", [(5, 5, 1), (6, 6, 2), (7, 6, 4)])
+@pytest.mark.parametrize("k,nbits,pairs", [(5, 5, 1), (6, 6, 2), (7, 6, 4), (5, 5, 9)])
 def test_sha_shaped_proof_bytes(ctx, k, nbits, pairs):
     """SHA-shaped CQ circuit at small k: `pairs` (dense, spread) column pairs, one width-2 vector
-    lookup per pair against (dense, spread) tables of 2^nbits entries."""
+    lookup per pair against (dense, spread) tables of 2^nbits entries.  9 lookups are the fewest that reach the second
+    iteration of the prover's loops over batches of 8 (round 1, the folds), which carry offsets from one batch to the
+    next.  (A key takes at most CQ_MAX_LOOKUPS = 16 lookups, so the bucket-sum launches never see a second batch.)"""
     N = 1 << nbits
     n = 1 << k
 
