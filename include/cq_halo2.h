@@ -295,6 +295,15 @@ size_t cq_params_serialized_size_full(const cq_params* params, int format);
 /* g_to_lagrange(g, k) (arithmetic.rs:277-301): the Lagrange-basis SRS from the monomial one by an inverse FFT
  * over G1 (device arrays of 2^k affine points). */
 int cq_g_to_lagrange_dev(cq_ctx* ctx, const uint64_t* g_dev, uint32_t k, uint64_t* g_lagrange_dev);
+/* The same points, the same bytes, by the G1 FFT whose twiddle products are fixed-window chains with wave-uniform control
+ * flow (csrc/g1window.hpp) -- the transform behind the trapdoor-free constructors below, for circuit-SRS sizes. */
+int cq_g_to_lagrange_windowed_dev(cq_ctx* ctx, const uint64_t* g_dev, uint32_t k, uint64_t* g_lagrange_dev);
+/* ParamsKZG from the monomial powers alone -- what a ceremony file holds (commitment.rs:31-39; the reader derives nothing,
+ * :383-459, so a deployment that has only g must run g_to_lagrange, arithmetic.rs:277-301, itself).  `g`: 2^k affine points
+ * [s^i]_1 in host memory, or in device memory when `g_on_device` != 0 (copied: the caller keeps its array).  g_lagrange is
+ * computed on the GPU straight into the resident array.  Window tables are registered and the G2 tail is absent exactly as
+ * after cq_params_create. */
+int cq_params_from_powers(cq_ctx* ctx, uint32_t k, const uint64_t* g, int g_on_device, cq_params** out);
 /* ParamsKZG::downsize(k) (kzg/commitment.rs:480-492): the first 2^k powers and their Lagrange basis (recomputed with
  * g_to_lagrange), as a new object. */
 int cq_params_downsize(cq_params* params, uint32_t k, cq_params** out);
@@ -315,6 +324,15 @@ int cq_table_config_create(cq_ctx* ctx, size_t size, const uint64_t* g1_lagrange
                            const uint64_t* g_lagrange_opening_at_0, cq_table_config** out);
 /* G1 part of TableSRS::setup_from_toxic_waste (kzg/commitment.rs:73-178), built on the GPU (tests/benches). */
 int cq_table_config_setup_from_toxic_waste(cq_ctx* ctx, size_t size, const uint64_t s[4], cq_table_config** out);
+/* StaticTableConfig from the first `size` monomial powers, without the trapdoor: the two arrays that
+ * TableSRS::setup_from_toxic_waste computes from s (kzg/commitment.rs:125-170) are linear in the powers,
+ *   g1_lagrange[i] = [L_i(s)]_1 = (1/N) sum_j w^(-ij) [s^j]_1                                  (commitment.rs:125-153)
+ *   g_lagrange_opening_at_0[i] = [(L_i(s) - L_i(0)) / s]_1 = (1/N) sum_(j<N-1) w^(-i(j+1)) [s^j]_1   (commitment.rs:156-170)
+ * -- two inverse FFTs over G1 (arithmetic.rs:277-301), the second of the powers moved up by one place.  `srs_g1`: `srs_len`
+ * affine points (host, or device when `on_device` != 0) of which the first `size` are used.  CQ_ERR_ARG when `size` is not a
+ * power of two, `srs_len < size` or `size > 2^28`.  MSM tables are registered as by cq_table_config_create. */
+int cq_table_config_from_srs(cq_ctx* ctx, size_t size, const uint64_t* srs_g1, size_t srs_len, int on_device,
+                             cq_table_config** out);
 void cq_table_config_destroy(cq_table_config* cfg);
 int cq_table_config_download(cq_table_config* cfg, uint64_t* g1_lagrange, uint64_t* g_lagrange_opening_at_0);
 /* StaticTableValues {size, value_index_mapping, qs}  static_lookup.rs:68-75.  `values`: `size` unique
@@ -333,6 +351,10 @@ int cq_static_table_new(cq_ctx* ctx, size_t size, const uint64_t* values, const 
 /* Same result as cq_static_table_new (bit-identical qs), computed FK-style ("fast amortized KZG proofs"): one cyclic
  * convolution of size 2N over G1 and one G1 DFT instead of N multiexps -- O(N log N) group operations. */
 int cq_static_table_new_fk(cq_ctx* ctx, size_t size, const uint64_t* values, const uint64_t* srs_g1, cq_static_table** out);
+/* cq_static_table_new_fk (static_lookup.rs:78-126) with the powers already in device memory, e.g. cq_params_g_dev of params
+ * just read: `srs_g1_dev` holds at least `size` affine points and is only read.  `values` stay in host memory. */
+int cq_static_table_new_fk_dev(cq_ctx* ctx, size_t size, const uint64_t* values, const uint64_t* srs_g1_dev,
+                               cq_static_table** out);
 void cq_static_table_destroy(cq_static_table* table);
 int cq_static_table_download_qs(cq_static_table* table, uint64_t* qs_affine);
 /* The G2 powers of TableSRS (kzg/commitment.rs:73-123, field `g2`): `count` affine points [s^i]_2 resident in HBM.

@@ -177,6 +177,16 @@ def _ctx_g_to_lagrange(self, points: np.ndarray, k: int) -> np.ndarray:
     return out.download((g.shape[0], 8), np.uint64)
 
 
+def _ctx_g_to_lagrange_windowed(self, points: np.ndarray, k: int) -> np.ndarray:
+    """`g_to_lagrange` by the fixed-window G1 FFT of the trapdoor-free setup path: the same bytes as `g_to_lagrange`."""
+    g = _g1(points)
+    if g.shape[0] != 1 << k:
+        raise CqError(-1, "g_to_lagrange: len != 1 << k")
+    dg, out = self.to_device(g), self.alloc(g.shape[0] * 64)
+    self._chk(self.lib.cq_g_to_lagrange_windowed_dev(self.h, dg.ptr, k, out.ptr))
+    return out.download((g.shape[0], 8), np.uint64)
+
+
 def _g2(a) -> np.ndarray:
     a = np.ascontiguousarray(a, dtype=np.uint64)
     assert a.ndim == 2 and a.shape[1] == 16, "expected uint64[n,16] G2 affine points"
@@ -205,10 +215,24 @@ Context.best_multiexp_g2_dev = _ctx_best_multiexp_g2_dev
 Context.set_msm_table_window = _ctx_set_msm_table_window
 Context.permute_expression_pair = _ctx_permute_expression_pair
 Context.g_to_lagrange = _ctx_g_to_lagrange
+Context.g_to_lagrange_windowed = _ctx_g_to_lagrange_windowed
 Context.best_multiexp = _ctx_best_multiexp
 Context.best_multiexp_dev = _ctx_best_multiexp_dev
 Context.msm_batch_dev = _ctx_msm_batch_dev
 Context.set_msm_window = _ctx_set_msm_window
+
+
+def _host_or_device_points(points, need: int):
+    """(address, on_device, keep-alive) of G1 points given as a uint64[n,8] host array (n >= need), a DevBuf or a device
+    address."""
+    if isinstance(points, DevBuf):
+        return points.ptr, 1, points
+    if isinstance(points, (int, np.integer)):
+        return int(points), 1, None
+    a = _g1(points)
+    if a.shape[0] < need:
+        raise CqError(-1, "fewer points than the object needs")
+    return a.ctypes.data, 0, a
 
 
 class ParamsKZG:
@@ -223,6 +247,21 @@ class ParamsKZG:
         sm = np.ascontiguousarray(s, dtype=np.uint64).reshape(4)
         h = C.c_void_p()
         ctx._chk(ctx.lib.cq_params_setup_from_toxic_waste(ctx.h, k, sm.ctypes.data, C.byref(h)))
+        self.h = h
+        ctx._children.add(self)
+        return self
+
+    @classmethod
+    def from_powers(cls, ctx: Context, k: int, g) -> "ParamsKZG":
+        """`ParamsKZG` from the monomial powers [s^i]_1 alone, as a ceremony file holds them: g_lagrange is derived on the GPU
+        (`g_to_lagrange`, arithmetic.rs:277-301).  `g`: uint64[2^k, 8] host array, or a device pointer (int / DevBuf) to 2^k
+        affine points, which is copied.  No G2 tail (`set_g2`), as after `ParamsKZG(ctx, k, g, g_lagrange)`."""
+        self = cls.__new__(cls)
+        self.ctx, self.k, self.n = ctx, k, 1 << k
+        ptr, on_device, keep = _host_or_device_points(g, 1 << k)
+        h = C.c_void_p()
+        ctx._chk(ctx.lib.cq_params_from_powers(ctx.h, k, ptr, on_device, C.byref(h)))
+        del keep
         self.h = h
         ctx._children.add(self)
         return self
@@ -458,6 +497,32 @@ class TableConfig(_Handle):
         sm = np.ascontiguousarray(s, dtype=np.uint64).reshape(4)
         h = C.c_void_p()
         ctx._chk(ctx.lib.cq_table_config_setup_from_toxic_waste(ctx.h, size, sm.ctypes.data, C.byref(h)))
+        self.h = h
+        ctx._children.add(self)
+        return self
+
+    @classmethod
+    def from_srs(cls, ctx: Context, size: int, srs, srs_len: int | None = None) -> "TableConfig":
+        """`StaticTableConfig` from the first `size` monomial powers [s^i]_1, no trapdoor: g1_lagrange = [L_i(s)]_1 and
+        g_lagrange_opening_at_0 = [(L_i(s) - L_i(0)) / s]_1 (kzg/commitment.rs:125-170) as two inverse FFTs over G1.
+        `srs`: a uint64[n,8] host array, a `ParamsKZG` (its resident g), or a device pointer (int / DevBuf) together with
+        `srs_len`, the number of points behind it."""
+        self = cls.__new__(cls)
+        self.ctx, self.size = ctx, size
+        if isinstance(srs, ParamsKZG):
+            ptr, on_device, keep, srs_len = srs.g_dev, 1, srs, srs.n
+        else:
+            if isinstance(srs, (int, np.integer, DevBuf)):
+                if srs_len is None:
+                    raise CqError(-1, "TableConfig.from_srs: a device pointer needs srs_len")
+                ptr, on_device, keep = _host_or_device_points(srs, 0)
+            else:
+                keep = _g1(srs)
+                ptr, on_device = keep.ctypes.data, 0
+                srs_len = keep.shape[0] if srs_len is None else min(srs_len, keep.shape[0])
+        h = C.c_void_p()
+        ctx._chk(ctx.lib.cq_table_config_from_srs(ctx.h, size, ptr, srs_len, on_device, C.byref(h)))
+        del keep
         self.h = h
         ctx._children.add(self)
         return self
@@ -1015,14 +1080,23 @@ def _static_table_new(cls, ctx: Context, values: np.ndarray, srs_g1: np.ndarray)
 StaticTable.new = classmethod(_static_table_new)
 
 
-def _static_table_new_fk(cls, ctx: Context, values: np.ndarray, srs_g1: np.ndarray) -> "StaticTable":
-    """Same table as `StaticTable.new` (bit-identical cached quotients), built FK-style in O(N log N) group operations."""
+def _static_table_new_fk(cls, ctx: Context, values: np.ndarray, srs_g1: np.ndarray | None = None, srs_dev=None) -> "StaticTable":
+    """Same table as `StaticTable.new` (bit-identical cached quotients), built FK-style in O(N log N) group operations.
+    The powers [s^i]_1 come from the host (`srs_g1`, uint64[N,8]) or are already resident (`srs_dev`: a device pointer or
+    DevBuf to at least N affine points, e.g. `params.g_dev`)."""
     self = cls.__new__(cls)
-    v, g = _fr(values), _g1(srs_g1)
-    assert v.shape[0] == g.shape[0]
+    v = _fr(values)
     self.ctx, self.size = ctx, v.shape[0]
     h = C.c_void_p()
-    ctx._chk(ctx.lib.cq_static_table_new_fk(ctx.h, self.size, v.ctypes.data, g.ctypes.data, C.byref(h)))
+    if (srs_g1 is None) == (srs_dev is None):
+        raise CqError(-1, "StaticTable.new_fk: give srs_g1 or srs_dev")
+    if srs_dev is not None:
+        ptr = srs_dev.ptr if isinstance(srs_dev, DevBuf) else int(srs_dev)
+        ctx._chk(ctx.lib.cq_static_table_new_fk_dev(ctx.h, self.size, v.ctypes.data, ptr, C.byref(h)))
+    else:
+        g = _g1(srs_g1)
+        assert v.shape[0] == g.shape[0]
+        ctx._chk(ctx.lib.cq_static_table_new_fk(ctx.h, self.size, v.ctypes.data, g.ctypes.data, C.byref(h)))
     self.h = h
     ctx._children.add(self)
     return self

@@ -110,6 +110,42 @@ int cq_table_config_setup_from_toxic_waste(cq_ctx* c, size_t size, const uint64_
   return CQ_OK;
 }
 
+// StaticTableConfig from the powers: both arrays are inverse G1 FFTs of them (kzg/commitment.rs:125-170)
+int cq_table_config_from_srs(cq_ctx* c, size_t size, const uint64_t* srs_g1, size_t srs_len, int on_device, cq_table_config** out) {
+  if (!c || !srs_g1 || !out || !is_pow2(size) || size > (1u << 28) || srs_len < size) return CQ_ERR_ARG;
+  CQ_HIP(c, hipSetDevice(c->device));
+  *out = nullptr;
+  cq_table_config* t = new cq_table_config();
+  Building<cq_table_config> guard(t, cq_table_config_destroy, c);
+  t->ctx = c;
+  t->N = size;
+  t->log_n = log2u(size);
+  const size_t bytes = size * sizeof(G1Affine);
+  if (hipMalloc(&t->g1_lagrange, bytes) != hipSuccess || hipMalloc(&t->g_lagrange_opening_at_0, bytes) != hipSuccess)
+    return c->fail(CQ_ERR_HIP, "hipMalloc(table config)");
+  const G1Affine* srs = (const G1Affine*)srs_g1;
+  if (!on_device) {
+    G1Affine* up = nullptr;
+    if (hipMalloc(&up, bytes) != hipSuccess) return c->fail(CQ_ERR_HIP, "hipMalloc(table config srs)");
+    guard.dev.push_back(up);
+    CQ_HIP(c, hipMemcpyAsync(up, srs_g1, bytes, hipMemcpyHostToDevice, c->stream));
+    srs = up;
+  }
+  int rc;
+  // [L_i(s)] = (1/N) sum_j w^(-ij) [s^j]
+  if ((rc = g1_to_lagrange(c, srs, t->log_n, t->g1_lagrange, true)) != CQ_OK) return rc;
+  // [(L_i(s) - L_i(0)) / s]: L_i(X) = (1/N) sum_m w^(-im) X^m and L_i(0) = 1/N, so the quotient is
+  // (1/N) sum_(m>=1) w^(-im) X^(m-1) -- power j = m - 1 < N - 1 sits at place j + 1 of the transform's input
+  if ((rc = g1_to_lagrange_shifted(c, srs, (uint32_t)(size - 1), 1, t->log_n, t->g_lagrange_opening_at_0, true)) != CQ_OK) return rc;
+  if (c->msm_precompute) {
+    if ((rc = msm_register_tables(c, t->g1_lagrange, size)) != CQ_OK) return rc;
+    if ((rc = msm_register_tables(c, t->g_lagrange_opening_at_0, size)) != CQ_OK) return rc;
+  }
+  CQ_HIP(c, hipStreamSynchronize(c->stream));
+  *out = guard.release();
+  return CQ_OK;
+}
+
 void cq_table_config_destroy(cq_table_config* t) {
   if (!t) return;
   if (t->key_users > 0) {  // a key still uses it: the last one frees it (see cq_params_destroy)
@@ -1210,7 +1246,8 @@ int cq_static_table_new(cq_ctx* c, size_t size, const uint64_t* values, const ui
   return CQ_OK;
 }
 
-int cq_static_table_new_fk(cq_ctx* c, size_t size, const uint64_t* values, const uint64_t* srs_g1, cq_static_table** out) {
+static int static_table_new_fk(cq_ctx* c, size_t size, const uint64_t* values, const uint64_t* srs_g1, bool srs_on_device,
+                               cq_static_table** out) {
   if (!c || !values || !srs_g1 || !out || !is_pow2(size) || size < 2 || size > (1u << 22)) return CQ_ERR_ARG;
   CQ_HIP(c, hipSetDevice(c->device));
   *out = nullptr;
@@ -1221,16 +1258,23 @@ int cq_static_table_new_fk(cq_ctx* c, size_t size, const uint64_t* values, const
   if ((rc = domain_create(c, 2, log2u(size), &guard.dom)) != CQ_OK) return rc;
   G1Affine* srs = nullptr;
   Fr* coeffs = nullptr;
-  const bool alloc_ok = hipMalloc(&srs, size * sizeof(G1Affine)) == hipSuccess && hipMalloc(&coeffs, size * sizeof(Fr)) == hipSuccess;
+  const bool alloc_ok = (srs_on_device || hipMalloc(&srs, size * sizeof(G1Affine)) == hipSuccess) && hipMalloc(&coeffs, size * sizeof(Fr)) == hipSuccess;
   for (void* d : {(void*)srs, (void*)coeffs})
     if (d) guard.dev.push_back(d);
   if (!alloc_ok) return c->fail(CQ_ERR_HIP, "hipMalloc(static_table_new_fk)");
-  CQ_HIP(c, hipMemcpyAsync(srs, srs_g1, size * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
+  if (!srs_on_device) CQ_HIP(c, hipMemcpyAsync(srs, srs_g1, size * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
   if ((rc = domain_lagrange_to_coeff(guard.dom, t->values, coeffs, 1, size, size)) != CQ_OK) return rc;  // :99-105
-  if ((rc = fk_table_quotients(c, coeffs, srs, log2u(size), t->qs)) != CQ_OK) return rc;
+  // resident powers belong to the trapdoor-free setup path and take its FFT; the quotients are the same bytes either way
+  if ((rc = fk_table_quotients(c, coeffs, srs_on_device ? (const G1Affine*)srs_g1 : srs, log2u(size), t->qs, srs_on_device)) != CQ_OK) return rc;
   CQ_HIP(c, hipStreamSynchronize(c->stream));
   *out = guard.release();
   return CQ_OK;
+}
+int cq_static_table_new_fk(cq_ctx* c, size_t size, const uint64_t* values, const uint64_t* srs_g1, cq_static_table** out) {
+  return static_table_new_fk(c, size, values, srs_g1, false, out);
+}
+int cq_static_table_new_fk_dev(cq_ctx* c, size_t size, const uint64_t* values, const uint64_t* srs_g1_dev, cq_static_table** out) {
+  return static_table_new_fk(c, size, values, srs_g1_dev, true, out);
 }
 
 // ---- harness RNGs ----------------------------------------------------------------------------------------

@@ -391,6 +391,28 @@ int cq_params_create(cq_ctx* c, uint32_t k, const uint64_t* g, const uint64_t* g
   return CQ_OK;
 }
 
+/* ParamsKZG from g alone: g_lagrange = g_to_lagrange(g, k) (arithmetic.rs:277-301) straight into the resident array */
+int cq_params_from_powers(cq_ctx* c, uint32_t k, const uint64_t* g, int g_on_device, cq_params** out) {
+  if (!c || !g || !out || k > FR_S) return CQ_ERR_ARG;
+  CQ_HIP(c, hipSetDevice(c->device));
+  *out = nullptr;
+  cq_params* p = params_new(c, k);
+  ParamsGuard guard(p);
+  const size_t bytes = p->n * sizeof(G1Affine);
+  hipError_t e;
+  if ((e = hipMalloc(&p->g, bytes)) != hipSuccess || (e = hipMalloc(&p->g_lagrange, bytes)) != hipSuccess)
+    return c->hip_fail(e, "hipMalloc(params)");
+  CQ_HIP(c, hipMemcpyAsync(p->g, g, bytes, g_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  int rc;
+  if ((rc = g1_to_lagrange(c, p->g, k, p->g_lagrange, true)) != CQ_OK) return rc;  // waits for the stream
+  if (c->msm_precompute) {
+    if ((rc = msm_register_tables(c, p->g, p->n)) != CQ_OK) return rc;
+    if ((rc = msm_register_tables(c, p->g_lagrange, p->n)) != CQ_OK) return rc;
+  }
+  *out = guard.release();
+  return CQ_OK;
+}
+
 /* ParamsKZG::setup_from_toxic_waste (kzg/commitment.rs:209-276), computed on the GPU */
 int cq_params_setup_from_toxic_waste(cq_ctx* c, uint32_t k, const uint64_t s[4], cq_params** out) {
   if (!c || !s || !out || k > FR_S) return CQ_ERR_ARG;
@@ -666,6 +688,12 @@ int cq_g_to_lagrange_dev(cq_ctx* c, const uint64_t* g_dev, uint32_t k, uint64_t*
 }
 
 // ParamsKZG::downsize (kzg/commitment.rs:480-492)
+int cq_g_to_lagrange_windowed_dev(cq_ctx* c, const uint64_t* g_dev, uint32_t k, uint64_t* g_lagrange_dev) {
+  if (!c || !g_dev || !g_lagrange_dev || k > FR_S) return CQ_ERR_ARG;
+  CQ_HIP(c, hipSetDevice(c->device));
+  return g1_to_lagrange(c, (const G1Affine*)g_dev, k, (G1Affine*)g_lagrange_dev, true);
+}
+
 int cq_params_downsize(cq_params* p, uint32_t k, cq_params** out) {
   if (!p || !out || k > p->k) return CQ_ERR_ARG;  // `assert!(k <= self.k)`
   cq_ctx* c = p->ctx;

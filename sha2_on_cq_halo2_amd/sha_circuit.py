@@ -80,6 +80,23 @@ def small_to_mont(vals) -> np.ndarray:
     return np.stack([fr_to_mont(int(v)) for v in vals])
 
 
+def srs_powers_dev(ctx: Context, s: int, count: int):
+    """[s^i]_1 for i < count as a device buffer of affine points (cq_fixed_base_mul_dev): what a powers-of-tau file holds."""
+    R_MOD = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001
+    s %= R_MOD
+    mont = bytearray()
+    acc = (1 << 256) % R_MOD  # Montgomery form of s^i
+    for _ in range(count):
+        mont += acc.to_bytes(32, "little")
+        acc = acc * s % R_MOD
+    sc = ctx.to_device(np.frombuffer(bytes(mont), dtype=np.uint64).reshape(count, 4))
+    out = ctx.alloc(count * 64)
+    ctx._chk(ctx.lib.cq_fixed_base_mul_dev(ctx.h, sc.ptr, count, out.ptr))
+    ctx.sync()
+    sc.free()
+    return out
+
+
 TABLE_BITS = 12
 BLOCKS_FOR_K = {14: 1, 16: 16, 18: 64, 20: 256, 22: 1024}
 
@@ -88,7 +105,7 @@ class ShaCqWorkload:
     """Proving key + device-resident witness for the SHA-shaped CQ circuit at 2^k rows."""
 
     def __init__(self, ctx: Context, k: int, pairs: int = 4, blocks: int | None = None, seed: int = 0x5348413243515F,
-                 table_bits: int = TABLE_BITS, share: "ShaCqWorkload | None" = None):
+                 table_bits: int = TABLE_BITS, share: "ShaCqWorkload | None" = None, setup: str = "toxic"):
         import ctypes as C
 
         self.ctx, self.k, self.pairs = ctx, k, pairs
@@ -98,7 +115,17 @@ class ShaCqWorkload:
         if share is not None:  # same SRS / tables as another workload of the same size (setup is not what is measured)
             assert share.k == k and share.cfg.size == N
             self.params, self.cfg, self.dense, self.spread = share.params, share.cfg, share.dense, share.spread
+        elif setup == "powers":
+            # the powers [s^i]_1 stand in for a ceremony file: s appears here and nowhere below
+            count = max(n, N)
+            self.srs = srs_powers_dev(ctx, seed * 0x9E3779B97F4A7C15 + 12345, count)
+            self.params = ParamsKZG.from_powers(ctx, k, self.srs)
+            self.cfg = TableConfig.from_srs(ctx, N, self.srs, srs_len=count)
+            idx = np.arange(N)
+            self.dense = StaticTable.new_fk(ctx, small_to_mont(idx), srs_dev=self.srs)
+            self.spread = StaticTable.new_fk(ctx, small_to_mont(spread16(idx)), srs_dev=self.srs)
         else:
+            assert setup == "toxic", setup
             s = fr_to_mont(seed * 0x9E3779B97F4A7C15 + 12345)
             self.params = ParamsKZG.setup_from_toxic_waste(ctx, k, s)
             self.cfg = TableConfig.setup_from_toxic_waste(ctx, N, s)
@@ -148,6 +175,8 @@ class ShaCqWorkload:
         objs = [self.pk, self.words_dev] + list(self.cols)
         if shared:
             objs += [self.dense, self.spread, self.cfg, self.params]
+            if getattr(self, "srs", None) is not None:
+                objs.append(self.srs)
         for o in objs:
             o.close()
 
