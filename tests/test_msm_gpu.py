@@ -19,6 +19,9 @@ def _check(ctx, scalars, points):
 
 @pytest.mark.parametrize("n", [0, 1, 2, 3, 4, 5, 31, 32, 33, 100, 257, 1000, 4096])
 def test_msm_random(ctx, n):
+    """Every length here is at most MSM_SHORT_MAX with no forced window: these launches reach msm_short_kernel, not the
+    generic pipeline (tests/test_msm_short_gpu.py is that kernel's own suite; tests/test_msm_edges_gpu.py covers the
+    generic pipeline and table mode on crafted inputs)."""
     _check(ctx, random_scalars(n, 10 + n), random_points(n, 20 + n))
 
 
@@ -33,6 +36,8 @@ def test_msm_window_sizes(ctx, c):
 
 
 def test_msm_edge_scalars(ctx):
+    """n = 300 without a forced window: msm_short_kernel today.  The same scalars, and the digit edges of every window
+    width, reach msm_digits_kernel / msm_scatter_kernel in tests/test_msm_edges_gpu.py."""
     n = 300
     pts = random_points(n, 5)
     sc = random_scalars(n, 6)
@@ -48,6 +53,8 @@ def test_msm_edge_scalars(ctx):
 
 
 def test_msm_identity_and_repeated_bases(ctx):
+    """n = 200 without a forced window: msm_short_kernel today.  The generic accumulate kernel and table mode see identity,
+    repeated and opposite bases in tests/test_msm_edges_gpu.py (test_special_cases_of_the_additions_inside_a_bucket)."""
     n = 200
     pts = random_points(n, 9)
     for i in range(0, n, 7):
@@ -63,6 +70,8 @@ def test_msm_identity_and_repeated_bases(ctx):
 
 
 def test_msm_all_same_point_small_scalars(ctx):
+    """n = 512 without a forced window: msm_short_kernel today.  One point on every row of the generic pipeline and of table
+    mode: tests/test_msm_edges_gpu.py (test_long_lists_that_cancel_or_double)."""
     n = 512
     pts = [B.G1_GEN] * n
     sc = [(i % 3) for i in range(n)]
@@ -98,7 +107,9 @@ def test_commit_equals_commit_lagrange(ctx):
 @pytest.mark.parametrize("kind", ["bits", "limb12", "const"])
 def test_msm_skewed_scalars_multilevel(ctx, kind):
     """Skewed digit distributions force the multi-level (bounded sub-list) accumulation path:
-    0/1 selector-like columns, 12-bit SHA limbs, and one repeated full-size scalar."""
+    0/1 selector-like columns, 12-bit SHA limbs, and one repeated full-size scalar.  The first check (forced 9-bit window) runs
+    the generic pipeline; the second one, unforced at n = 6000 <= MSM_SHORT_MAX, reaches msm_short_kernel today -- the generic
+    pipeline at its automatic widths is in tests/test_msm_edges_gpu.py (test_digit_edges_plain_automatic_window)."""
     n = 6000
     pts = random_points(n, 41)
     rng = B.Xoshiro256ss(42)
