@@ -194,6 +194,34 @@ int cq_kate_division_dev(cq_ctx* ctx, const uint64_t* a_dev, size_t n, const uin
 int cq_batch_invert(cq_ctx* ctx, uint64_t* a, size_t n);
 int cq_batch_invert_dev(cq_ctx* ctx, uint64_t* a_dev, size_t n);
 
+/* ---- plonk/assigned.rs, poly.rs: Assigned (rational) columns ---------------------------------------- */
+/* A column of `Assigned<F>` cells (plonk/assigned.rs:11-18: Zero, Trivial(x), Rational(num, den)) as synthesis leaves it,
+ * before batch_invert_assigned (poly.rs:174-241) turns it into field elements.  It crosses as the dense array of
+ * `Assigned::numerator` (assigned.rs:281-287) plus the SPARSE list of `Assigned::denominator` (:289-296), which is Some
+ * for Rational cells only: "if the denominator is trivial, we can skip it" (poly.rs:189-191, :228-230).  Resolved value
+ * of a cell, as `Assigned::evaluate` (assigned.rs:353-366) and the batched form give it:
+ *   num                where the row is not listed;
+ *   num * den^-1       where the row is listed and den != 0 -- a denominator of one is inverted like any other, as the
+ *                      batched path does (evaluate's shortcut for it, :358, gives the same value);
+ *   0                  where the row is listed and den == 0 ("x/0 -> 0": ff::BatchInvert leaves zeros at zero). */
+typedef struct {
+  const uint64_t* num;       /* n elements, Montgomery limbs: Zero -> 0, Trivial(x) -> x, Rational(a, b) -> a */
+  const uint32_t* den_rows;  /* den_count rows holding a Rational cell, strictly ascending, each < n */
+  const uint64_t* den;       /* den_count denominators, in the order of den_rows; 0 is allowed (x/0 -> 0) */
+  size_t den_count;          /* 0 = the column is all Zero / Trivial; den_rows / den may then be NULL */
+} cq_assigned_column;
+/* batch_invert_assigned / batch_invert_assigned_ref (poly.rs:174-241): `ncols` columns of `n` cells each, all their
+ * denominators inverted in one batch.  This is the call keygen makes on `assembly.fixed` (plonk/keygen.rs:244, :320) before
+ * the columns go into cq_pk_create, and the one create_proof makes on the advice columns (plonk/prover.rs:337).
+ * _dev: every pointer inside `cols` is a DEVICE pointer (the array of structs itself is host memory); out_dev: `ncols`
+ * device pointers to n elements each, out_dev[c] may be cols[c].num (in place).  The lists are checked on the GPU; unlike
+ * most `_dev` entry points this one returns after the stream has drained (it reads the verdict back).
+ * The other form takes host pointers throughout and is staged as cq_batch_invert is; its lists are checked on the host.
+ * A list that is not strictly ascending or names a row >= n is CQ_ERR_ARG, cq_last_error names the column and the first
+ * offending entry, no output is written and no such row is dereferenced. */
+int cq_batch_invert_assigned_dev(cq_ctx* ctx, const cq_assigned_column* cols, size_t ncols, size_t n, uint64_t* const* out_dev);
+int cq_batch_invert_assigned(cq_ctx* ctx, const cq_assigned_column* cols, size_t ncols, size_t n, uint64_t* const* out);
+
 /* ---- poly/domain.rs ------------------------------------------------------------------------ */
 /* EvaluationDomain::new(j, k)  domain.rs:39-142 */
 int cq_domain_create(cq_ctx* ctx, uint32_t j, uint32_t k, cq_domain** out);
@@ -588,6 +616,18 @@ int cq_create_proof_batch(cq_pk* pk, size_t count, const uint64_t* const* const*
 /* Same with host-resident advice columns (uploaded first). */
 int cq_create_proof_host(cq_pk* pk, const uint64_t* const* advice, cq_rng_next_u64 rng, void* rng_state,
                          uint8_t* proof, size_t proof_cap, size_t* proof_len);
+/* create_proof from the `WitnessCollection` hand-over (plonk/prover.rs:337-360): `cols` = num_advice HOST columns of
+ * Assigned cells (2^k rows each), resolved on the GPU by batch_invert_assigned before the blinding rows are drawn
+ * (:346-355).  Numerators are uploaded as cq_create_proof_host uploads columns (usable rows only), the sparse
+ * denominators next to them, and the proof continues as the host path does.  Listed rows >= usable_rows are ignored: the
+ * reference overwrites those cells with blinding (:346-349).  The step draws no randomness: the bytes are those of
+ * cq_create_proof_instances on the resolved dense witness with the same RNG stream.  instances / instance_lens as there
+ * (NULL without instance columns).  Sharded keys as cq_create_proof_host: every rank resolves its own copy.  CQ_ERR_ARG:
+ * a bad row list (as cq_batch_invert_assigned), a multi-phase circuit (cq_create_proof_phases: its callback writes device
+ * columns, which cq_batch_invert_assigned_dev resolves). */
+int cq_create_proof_assigned(cq_pk* pk, const cq_assigned_column* cols, const uint64_t* const* instances,
+                             const size_t* instance_lens, cq_rng_next_u64 rng, void* rng_state, uint8_t* proof,
+                             size_t proof_cap, size_t* proof_len);
 /* create_proof with public inputs (`instances: &[&[Fr]]`, prover.rs:64): `instances[c]` = HOST pointer to
  * `instance_lens[c]` elements of instance column c (CQ_ERR_ARG if longer than usable_rows: "InstanceTooLarge",
  * :108-110).  ProverGWC has QUERY_INSTANCE = false: the values are absorbed into the transcript (:305-312)

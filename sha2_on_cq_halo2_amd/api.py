@@ -397,6 +397,61 @@ def _ctx_batch_invert(self, a: np.ndarray) -> np.ndarray:
     return a
 
 
+class _CqAssignedColumn(C.Structure):
+    _fields_ = [("num", C.c_void_p), ("den_rows", C.c_void_p), ("den", C.c_void_p), ("den_count", C.c_size_t)]
+
+
+def _assigned_structs(columns):
+    """cq_assigned_column[] over the host arrays of plonk.AssignedColumn objects (which the caller keeps alive)."""
+    arr = (_CqAssignedColumn * max(len(columns), 1))()
+    for i, col in enumerate(columns):
+        m = col.den_rows.shape[0]
+        arr[i] = _CqAssignedColumn(col.num.ctypes.data, col.den_rows.ctypes.data if m else None, col.den.ctypes.data if m else None, m)
+    return arr
+
+
+def _ctx_batch_invert_assigned(self, columns):
+    """`batch_invert_assigned` (poly.rs:212-241) on plonk.AssignedColumn objects of one length: the resolved columns,
+    uint64[n, 4] each (cq_batch_invert_assigned)."""
+    columns = list(columns)
+    if not columns:
+        return []
+    n = columns[0].n
+    assert all(c.n == n for c in columns), "columns of one length"
+    out = [np.zeros((n, 4), dtype=np.uint64) for _ in columns]
+    optr = (C.c_void_p * len(out))(*[o.ctypes.data for o in out])
+    self._chk(self.lib.cq_batch_invert_assigned(self.h, _assigned_structs(columns), len(columns), n, optr))
+    return out
+
+
+def _ctx_batch_invert_assigned_dev(self, columns, n: int, out_ptrs):
+    """cq_batch_invert_assigned_dev: `columns` = (num_ptr, den_rows_ptr, den_ptr, den_count) of device arrays per column,
+    `out_ptrs` the device outputs (may be the numerator arrays)."""
+    arr = (_CqAssignedColumn * max(len(columns), 1))(*[_CqAssignedColumn(*c) for c in columns])
+    optr = (C.c_void_p * max(len(out_ptrs), 1))(*out_ptrs)
+    self._chk(self.lib.cq_batch_invert_assigned_dev(self.h, arr, len(columns), n, optr))
+
+
+def _ctx_resolve_assigned_to_device(self, columns):
+    """Uploads plonk.AssignedColumn objects and resolves them in place through the device entry point: one DevBuf each."""
+    bufs, keep, descr = [], [], []
+    for col in columns:
+        num = self.to_device(col.num)
+        m = col.den_rows.shape[0]
+        rows, den = (self.to_device(col.den_rows), self.to_device(col.den)) if m else (None, None)
+        keep += [rows, den]
+        bufs.append(num)
+        descr.append((num.ptr, rows.ptr if m else None, den.ptr if m else None, m))
+    if columns:
+        _ctx_batch_invert_assigned_dev(self, descr, columns[0].n, [b.ptr for b in bufs])
+    for b in keep:
+        if b is not None:
+            b.free()
+    return bufs
+
+
+Context.batch_invert_assigned = _ctx_batch_invert_assigned
+Context.batch_invert_assigned_dev = _ctx_batch_invert_assigned_dev
 Context.eval_polynomial = _ctx_eval_polynomial
 Context.kate_division = _ctx_kate_division
 Context.batch_invert = _ctx_batch_invert
@@ -867,6 +922,21 @@ class ProvingKey(_Handle):
         fn, st = self._rng(rng_words, seed)
         return self._run(self.ctx.lib.cq_create_proof_host, [c.ctypes.data for c in cols], fn, st, instances)
 
+    def create_proof_assigned(self, columns, rng_words=None, seed=None, instances=None) -> bytes:
+        """`create_proof` from the `WitnessCollection` hand-over (plonk/prover.rs:337-360): `columns` are
+        plonk.AssignedColumn objects of 2^k rows; batch_invert_assigned runs on the GPU (cq_create_proof_assigned)."""
+        columns = list(columns)
+        assert len(columns) == self.num_advice and all(c.n == 1 << self.k for c in columns)
+        fn, st = self._rng(rng_words, seed)
+        cols = [_fr(i) if len(i) else np.zeros((0, 4), dtype=np.uint64) for i in (instances or [])]
+        iptr = (C.c_void_p * max(len(cols), 1))(*[c_.ctypes.data for c_ in cols]) if instances is not None else None
+        ilen = (C.c_size_t * max(len(cols), 1))(*[c_.shape[0] for c_ in cols]) if instances is not None else None
+        proof = (C.c_uint8 * self.proof_size)()
+        plen = C.c_size_t()
+        self.ctx._chk(self.ctx.lib.cq_create_proof_assigned(self.h, _assigned_structs(columns), iptr, ilen, fn, st, proof,
+                                                            self.proof_size, C.byref(plen)))
+        return bytes(proof[: plen.value])
+
     def create_proof_phases(self, advice_bufs, phase_fn, rng_words=None, seed=None, instances=None) -> bytes:
         """Multi-phase circuits (prover.rs:436-463): `advice_bufs` are DevBufs of 2^k elements; before phase p > 0 is
         committed `phase_fn(p, challenges)` is called with the user challenges so far (Python ints, canonical) and
@@ -907,9 +977,13 @@ class ProvingKey(_Handle):
         """`MockProver::verify` (dev.rs:601-958) on the GPU, static lookups included (cq_pk_check_witness): checks the
         witness `create_proof*` would be given against the key and returns `(total, [WitnessFailure, ...])` -- the exact
         number of findings and the first `max_failures` of them in ascending (kind, index, row) order.  `advice`: every
-        advice column of every phase, as host arrays (uint64[n, 4]) or as device pointers (ints / DevBufs); `instances`
+        advice column of every phase, as host arrays (uint64[n, 4]), as device pointers (ints / DevBufs) or as
+        plonk.AssignedColumn objects (resolved first by cq_batch_invert_assigned_dev); `instances`
         as for create_proof; `challenges`: the user challenges the later phases were synthesised with (Python ints,
         canonical, or uint64[4] Montgomery limbs each)."""
+        resolved = None
+        if len(advice) > 0 and all(hasattr(a, "den_rows") for a in advice):  # plonk.AssignedColumn: resolved on the GPU first
+            advice = resolved = _ctx_resolve_assigned_to_device(self.ctx, advice)
         on_device = len(advice) > 0 and all(isinstance(a, (int, DevBuf)) for a in advice)
         if on_device:
             ptrs = [a.ptr if isinstance(a, DevBuf) else a for a in advice]
@@ -931,8 +1005,12 @@ class ProvingKey(_Handle):
         cap = max(int(max_failures), 0)
         out = np.zeros((max(cap, 1), 4), dtype=np.uint32)
         total = C.c_size_t()
-        self.ctx._chk(self.ctx.lib.cq_pk_check_witness(self.h, arr, 1 if on_device else 0, iptr, ilen, ch_ptr,
-                                                       out.ctypes.data if cap else None, cap, C.byref(total)))
+        try:
+            self.ctx._chk(self.ctx.lib.cq_pk_check_witness(self.h, arr, 1 if on_device else 0, iptr, ilen, ch_ptr,
+                                                           out.ctypes.data if cap else None, cap, C.byref(total)))
+        finally:
+            for b in resolved or []:
+                b.free()
         return total.value, [WitnessFailure(*(int(x) for x in row)) for row in out[: min(cap, total.value)]]
 
     def assert_satisfied(self, advice, instances=None, challenges=None, max_failures=8):

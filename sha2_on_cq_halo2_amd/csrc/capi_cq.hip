@@ -6,11 +6,13 @@
 #include <string>
 #include <thread>
 #include <vector>
+#include "assigned_host.hpp"
 #include "cq.hpp"
 #include "xoshiro.hpp"
 #include "ctx.hpp"
 #include "g1fft.hpp"
 #include "plonk.hpp"
+#include "poly.hpp"
 #include "prover.hpp"
 #include "setup.hpp"
 #include "msm.hpp"
@@ -1045,6 +1047,55 @@ static int create_proof_host_any(cq_pk* pk, const uint64_t* const* advice, const
     CQ_HIP(c, hipMemcpyAsync(d, advice[a], (size_t)pk->u * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
     ptrs[a] = (const uint64_t*)d;
   }
+  return create_proof_any(pk, ptrs.data(), instances, instance_lens, rng, rng_state, proof, proof_cap, proof_len);
+}
+
+// create_proof from the WitnessCollection hand-over (prover.rs:337-360): the advice columns still hold Assigned cells and
+// batch_invert_assigned (poly.rs:212-241) runs first.  Numerators go up as create_proof_host_any uploads columns, the
+// sparse denominators into a buffer of their own, and the columns are resolved in place on the proof's stream.  Entries
+// that name a blinding row are dropped here: those cells are overwritten with blinding (prover.rs:346-349).
+int cq_create_proof_assigned(cq_pk* pk, const cq_assigned_column* cols, const uint64_t* const* instances, const size_t* instance_lens,
+                             cq_rng_next_u64 rng, void* rng_state, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
+  if (!pk || (!cols && pk->num_advice)) return CQ_ERR_ARG;
+  cq_ctx* c = pk->ctx;
+  if (pk->num_phases > 1)
+    return c->fail(CQ_ERR_ARG, "create_proof_assigned: multi-phase circuits are not covered (the phase callback of cq_create_proof_phases writes device columns)");
+  CQ_HIP(c, hipSetDevice(c->device));
+  const size_t n = (size_t)1 << pk->k, A = pk->num_advice;
+  std::vector<uint32_t> off(A + 1, 0);
+  for (size_t a = 0; a < A; a++) {
+    const cq_assigned_column& col = cols[a];
+    if (!col.num || (col.den_count && (!col.den_rows || !col.den)))
+      return c->fail(CQ_ERR_ARG, "create_proof_assigned: column " + std::to_string(a) + ": null array");
+    const size_t bad = assigned_rows_first_bad(col.den_rows, col.den_count, n);
+    if (bad != col.den_count)
+      return c->fail(CQ_ERR_ARG, "create_proof_assigned: column " + std::to_string(a) + ", entry " + std::to_string(bad) + ": row " +
+                                     std::to_string(col.den_rows[bad]) + " is not below n or does not ascend");
+    const size_t kept = assigned_rows_below(col.den_rows, col.den_count, pk->u);
+    if ((uint64_t)off[a] + kept > 0x7fffffffull) return c->fail(CQ_ERR_ARG, "create_proof_assigned: too many rational cells");
+    off[a + 1] = off[a] + (uint32_t)kept;
+  }
+  void *stage, *sparse;
+  int rc;
+  if ((rc = c->ensure_scratch(Scratch::HostAdvice, A * n * sizeof(Fr) + 64, &stage)) != CQ_OK) return rc;
+  const size_t total = off[A], rows_bytes = (total * sizeof(uint32_t) + 31) & ~(size_t)31;
+  if ((rc = c->ensure_scratch(Scratch::AssignedDen, rows_bytes + 2 * total * sizeof(Fr) + 64, &sparse)) != CQ_OK) return rc;
+  uint32_t* rows = (uint32_t*)sparse;
+  Fr* den = (Fr*)((char*)sparse + rows_bytes);
+  Fr* work = den + total;
+  std::vector<const uint64_t*> ptrs(A);
+  std::vector<Fr*> out(A);
+  for (size_t a = 0; a < A; a++) {
+    out[a] = (Fr*)stage + a * n;
+    ptrs[a] = (const uint64_t*)out[a];
+    CQ_HIP(c, hipMemcpyAsync(out[a], cols[a].num, (size_t)pk->u * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+    const size_t cnt = off[a + 1] - off[a];
+    if (!cnt) continue;
+    CQ_HIP(c, hipMemcpyAsync(rows + off[a], cols[a].den_rows, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    CQ_HIP(c, hipMemcpyAsync(den + off[a], cols[a].den, cnt * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = poly_resolve_assigned(c, (const Fr* const*)out.data(), out.data(), off.data(), (uint32_t)A, rows, den, pk->u, work, nullptr)) != CQ_OK)
+    return rc;
   return create_proof_any(pk, ptrs.data(), instances, instance_lens, rng, rng_state, proof, proof_cap, proof_len);
 }
 

@@ -1,5 +1,8 @@
-// C ABI: EvaluationDomain transforms, eval_polynomial, kate_division, batch inversion.
+// C ABI: EvaluationDomain transforms, eval_polynomial, kate_division, batch inversion (plain and of Assigned columns).
 #include <cstring>
+#include <string>
+#include <vector>
+#include "assigned_host.hpp"
 #include "ctx.hpp"
 #include "poly.hpp"
 
@@ -16,6 +19,24 @@ struct HostStage {
     rc = c->ensure_scratch(Scratch::EntryB, out_bytes ? out_bytes : 32, &dout);
   }
 };
+
+// the shape checks the two batch_invert_assigned entry points share; off[c] = entries before column c
+int assigned_offsets(cq_ctx* c, const cq_assigned_column* cols, size_t ncols, size_t n, std::vector<uint32_t>& off) {
+  if (n > 0x7fffffffull) return c->fail(CQ_ERR_ARG, "batch_invert_assigned: n too large");
+  off.assign(ncols + 1, 0);
+  for (size_t a = 0; a < ncols; a++) {
+    const cq_assigned_column& col = cols[a];
+    if ((n && !col.num) || (col.den_count && (!col.den_rows || !col.den)))
+      return c->fail(CQ_ERR_ARG, "batch_invert_assigned: column " + std::to_string(a) + ": null array");
+    if (col.den_count > n)  // rows ascend strictly below n: more than n of them cannot be a good list
+      return c->fail(CQ_ERR_ARG, "batch_invert_assigned: column " + std::to_string(a) + ", entry " + std::to_string(n) +
+                                     ": more entries than rows");
+    if ((uint64_t)off[a] + col.den_count > 0x7fffffffull) return c->fail(CQ_ERR_ARG, "batch_invert_assigned: too many rational cells");
+    off[a + 1] = off[a] + (uint32_t)col.den_count;
+  }
+  return CQ_OK;
+}
+inline size_t round32(size_t b) { return (b + 31) & ~(size_t)31; }
 }  // namespace
 
 extern "C" {
@@ -149,6 +170,85 @@ int cq_batch_invert(cq_ctx* c, uint64_t* a, size_t n) {
   int rc = poly_batch_invert(c, (Fr*)st.din, (uint32_t)n);
   if (rc != CQ_OK) return rc;
   CQ_HIP(c, hipMemcpyAsync(a, st.din, n * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
+  CQ_HIP(c, hipStreamSynchronize(c->stream));
+  return CQ_OK;
+}
+
+
+// batch_invert_assigned(_ref) (poly.rs:174-241) on device columns.  The columns' sparse lists are gathered behind one
+// another in the entry scratch, checked there (a verdict cell, as the Processed readers use), and the resolve launches
+// write nothing when the check objects.
+int cq_batch_invert_assigned_dev(cq_ctx* c, const cq_assigned_column* cols, size_t ncols, size_t n, uint64_t* const* out_dev) {
+  if (!c || (ncols && (!cols || !out_dev))) return CQ_ERR_ARG;
+  CQ_HIP(c, hipSetDevice(c->device));
+  std::vector<uint32_t> off;
+  int rc;
+  if ((rc = assigned_offsets(c, cols, ncols, n, off)) != CQ_OK) return rc;
+  for (size_t a = 0; a < ncols; a++)
+    if (n && !out_dev[a]) return c->fail(CQ_ERR_ARG, "batch_invert_assigned: column " + std::to_string(a) + ": null output");
+  if (!ncols || !n) return CQ_OK;
+  const size_t total = off[ncols];
+  HostStage st(c, 64 + round32(total * sizeof(uint32_t)) + total * sizeof(Fr), total * sizeof(Fr));
+  if (st.rc != CQ_OK) return st.rc;
+  uint32_t* verdict = (uint32_t*)st.din;
+  uint32_t* rows = (uint32_t*)((char*)st.din + 64);
+  Fr* den = (Fr*)((char*)rows + round32(total * sizeof(uint32_t)));
+  std::vector<const Fr*> num(ncols);
+  std::vector<Fr*> out(ncols);
+  for (size_t a = 0; a < ncols; a++) {
+    num[a] = (const Fr*)cols[a].num;
+    out[a] = (Fr*)out_dev[a];
+    if (!cols[a].den_count) continue;
+    CQ_HIP(c, hipMemcpyAsync(rows + off[a], cols[a].den_rows, cols[a].den_count * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    CQ_HIP(c, hipMemcpyAsync(den + off[a], cols[a].den, cols[a].den_count * sizeof(Fr), hipMemcpyDeviceToDevice, c->stream));
+  }
+  if ((rc = poly_validate_assigned(c, off.data(), (uint32_t)ncols, rows, (uint32_t)n, verdict)) != CQ_OK) return rc;
+  if ((rc = poly_resolve_assigned(c, num.data(), out.data(), off.data(), (uint32_t)ncols, rows, den, (uint32_t)n, (Fr*)st.dout, verdict)) != CQ_OK)
+    return rc;
+  uint32_t first_bad = 0;
+  CQ_HIP(c, hipMemcpyAsync(&first_bad, verdict, sizeof(first_bad), hipMemcpyDeviceToHost, c->stream));
+  CQ_HIP(c, hipStreamSynchronize(c->stream));
+  if (first_bad != 0xffffffffu) {
+    size_t a = 0;
+    while (a + 1 < ncols && off[a + 1] <= first_bad) a++;
+    return c->fail(CQ_ERR_ARG, "batch_invert_assigned: column " + std::to_string(a) + ", entry " + std::to_string(first_bad - off[a]) +
+                                   ": the row is not below n or does not ascend (nothing was written)");
+  }
+  return CQ_OK;
+}
+
+int cq_batch_invert_assigned(cq_ctx* c, const cq_assigned_column* cols, size_t ncols, size_t n, uint64_t* const* out_host) {
+  if (!c || (ncols && (!cols || !out_host))) return CQ_ERR_ARG;
+  CQ_HIP(c, hipSetDevice(c->device));
+  std::vector<uint32_t> off;
+  int rc;
+  if ((rc = assigned_offsets(c, cols, ncols, n, off)) != CQ_OK) return rc;
+  for (size_t a = 0; a < ncols; a++) {
+    if (n && !out_host[a]) return c->fail(CQ_ERR_ARG, "batch_invert_assigned: column " + std::to_string(a) + ": null output");
+    const size_t bad = assigned_rows_first_bad(cols[a].den_rows, cols[a].den_count, n);
+    if (bad != cols[a].den_count)
+      return c->fail(CQ_ERR_ARG, "batch_invert_assigned: column " + std::to_string(a) + ", entry " + std::to_string(bad) + ": row " +
+                                     std::to_string(cols[a].den_rows[bad]) + " is not below n or does not ascend");
+  }
+  if (!ncols || !n) return CQ_OK;
+  const size_t total = off[ncols], col_bytes = n * sizeof(Fr);
+  HostStage st(c, ncols * col_bytes + round32(total * sizeof(uint32_t)) + total * sizeof(Fr), total * sizeof(Fr));
+  if (st.rc != CQ_OK) return st.rc;
+  uint32_t* rows = (uint32_t*)((char*)st.din + ncols * col_bytes);
+  Fr* den = (Fr*)((char*)rows + round32(total * sizeof(uint32_t)));
+  std::vector<const Fr*> num(ncols);
+  std::vector<Fr*> out(ncols);
+  for (size_t a = 0; a < ncols; a++) {
+    out[a] = (Fr*)st.din + a * n;
+    num[a] = out[a];
+    CQ_HIP(c, hipMemcpyAsync(out[a], cols[a].num, col_bytes, hipMemcpyHostToDevice, c->stream));
+    if (!cols[a].den_count) continue;
+    CQ_HIP(c, hipMemcpyAsync(rows + off[a], cols[a].den_rows, cols[a].den_count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    CQ_HIP(c, hipMemcpyAsync(den + off[a], cols[a].den, cols[a].den_count * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = poly_resolve_assigned(c, num.data(), out.data(), off.data(), (uint32_t)ncols, rows, den, (uint32_t)n, (Fr*)st.dout, nullptr)) != CQ_OK)
+    return rc;
+  for (size_t a = 0; a < ncols; a++) CQ_HIP(c, hipMemcpyAsync(out_host[a], out[a], col_bytes, hipMemcpyDeviceToHost, c->stream));
   CQ_HIP(c, hipStreamSynchronize(c->stream));
   return CQ_OK;
 }

@@ -33,6 +33,8 @@ enum class Scratch {
   ProverStage,  // create_proof_dev's resident receive staging or its legacy-lookup staging (never both: resident sharding
                 // requires no legacy lookups); capi_rounds.hip's stand-alone rounds, which a proof never calls
   HostAdvice,   // create_proof_host_any's copy of the caller's advice columns, held for the whole proof: nothing else takes it
+  AssignedDen,  // cq_create_proof_assigned's sparse denominators (rows, values, the resolve launch's work array), from the upload
+                // until the columns are resolved on the proof's stream, before the proof starts: nothing else takes it
   NttAux,       // domain.hip transforms while AuxFork has put `stream` on the side stream
   CommGather,   // comm.hip rccl_allgather_host; 1 MiB of it is taken in comm_rccl_init
   Check,        // check.hip cq_pk_check_witness, for that call only: the staged witness, verdict bitmaps, hash slots,

@@ -243,9 +243,29 @@ static __device__ __forceinline__ Fr29 bi_get29(const uint4* lo, const uint4* hi
 // the lane totals level by level together, and the unwinding two elements at a time (their "before" products, then
 // out / r, out / r): 8 + 1 + 8 + inversion + 1 + 24 product latencies per lane at 16 elements, down from 16 + 16 + 1 + 48.
 // A zero element takes part as a product by one (and is not written).
-template <int BI_PER_LANE>
-__global__ __launch_bounds__(256) void batch_invert_kernel(Fr* __restrict__ a, uint32_t n) {
-  CQ_CRITICAL_WAVES();
+//
+// The block's work is written against the steps of an `IO`: load(i, w) reads element i's memory words, slot(i) is where
+// the running prefix product of a non-zero element is parked until the unwinding reads it back, and the result goes out
+// either through emit(i, nz, x) (x = the memory word of the inverse, < 2 p) or, with IO::kNumerator, through the cell
+// that cell(i) names: the inverse is multiplied by the cell's numerator first, one more pair of products per step
+// (IO::times_numerators; IO::scaled_for_numerator prepares the lane's "before" products for it).
+struct BiInPlace {  // ff::BatchInvert over one array: parked in the element's own place, a zero element is left alone
+  static constexpr bool kNumerator = false;
+  Fr* __restrict__ a;
+  __device__ __forceinline__ void load(uint32_t i, uint32_t* w) const { ld8w(a + i, w); }
+  __device__ __forceinline__ Fr* slot(uint32_t i) const { return a + i; }
+  __device__ __forceinline__ void emit(uint32_t i, bool nz, const Fr29& out) const {
+    if (!nz) return;
+    uint32_t w[8];
+    out.pack(w);
+    Fr::cond_sub_p(w, 0);
+    uint4* dst = reinterpret_cast<uint4*>(a + i);
+    dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+  }
+};
+template <int BI_PER_LANE, class IO>
+static __device__ __forceinline__ void batch_invert_block(const IO io, const uint32_t n) {
   static_assert(BI_PER_LANE >= 2 && BI_PER_LANE % 2 == 0, "two half-chains per lane");
   constexpr int H = BI_PER_LANE / 2;
   __shared__ uint4 lo[256], hi[256], lo2[256], hi2[256];
@@ -261,7 +281,7 @@ __global__ __launch_bounds__(256) void batch_invert_kernel(Fr* __restrict__ a, u
     uint32_t o = 0;
     CQ_UNROLL for (int q = 0; q < 8; q++) v[k][q] = 0;
     if (i < n) {
-      ld8w(a + i, v[k]);
+      io.load(i, v[k]);
       CQ_UNROLL for (int q = 0; q < 8; q++) o |= v[k][q];
     }
     nz[k] = o != 0;
@@ -271,7 +291,7 @@ __global__ __launch_bounds__(256) void batch_invert_kernel(Fr* __restrict__ a, u
     if (!nz[k]) return;
     uint32_t w[8];
     x.pack(w);
-    uint4* dst = reinterpret_cast<uint4*>(a + (base + k * 256 + t));
+    uint4* dst = reinterpret_cast<uint4*>(io.slot(base + k * 256 + t));
     dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
     dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
   };
@@ -299,7 +319,7 @@ __global__ __launch_bounds__(256) void batch_invert_kernel(Fr* __restrict__ a, u
   bi_put29(lo, hi, t, inc);
   bi_put29(lo2, hi2, t, suf);
   __syncthreads();
-  const Fr29 exc = t ? bi_get29(lo, hi, t - 1) : Fr29::one();          // everything in the lanes before this one
+  Fr29 exc = t ? bi_get29(lo, hi, t - 1) : Fr29::one();          // everything in the lanes before this one
   const Fr29 total = bi_get29(lo, hi, 255);
   const Fr29 after = t < 255 ? bi_get29(lo2, hi2, t + 1) : Fr29::one();  // everything in the lanes after it
   __syncthreads();
@@ -309,6 +329,7 @@ __global__ __launch_bounds__(256) void batch_invert_kernel(Fr* __restrict__ a, u
     Fr::cond_sub_p(tc.v.l, 0);
     bi_put(lo, hi, 0, tc.inv_safegcd_var());  // Y = R^2 / T as canonical words (one lane: the variable-time form)
   }
+  if constexpr (IO::kNumerator) exc = IO::scaled_for_numerator(exc);  // (while the lanes wait for lane 0: off the chain)
   const Fr29 exc_b = Fr29::mul(exc, total_a);  // ... and this lane's first half-chain (while lane 0 inverts)
   __syncthreads();
   const Fr29 total_inv = bi_get29(lo, hi, 0);
@@ -316,17 +337,11 @@ __global__ __launch_bounds__(256) void batch_invert_kernel(Fr* __restrict__ a, u
   Fr29 r = Fr29::mul(total_inv, after);
   auto prefix = [&](int k) {
     uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (nz[k]) ld8w(a + (base + k * 256 + t), w);
+    if (nz[k]) ld8w(io.slot(base + k * 256 + t), w);
     return Fr29::unpack(w);
   };
   auto emit = [&](int k, const Fr29& out) {
-    if (!nz[k]) return;
-    uint32_t w[8];
-    out.pack(w);
-    Fr::cond_sub_p(w, 0);
-    uint4* dst = reinterpret_cast<uint4*>(a + (base + k * 256 + t));
-    dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    if constexpr (!IO::kNumerator) io.emit(base + k * 256 + t, nz[k], out);
   };
   Fr29::static_for<0, H>([&](auto K) {
     constexpr int k1 = BI_PER_LANE - 1 - 2 * decltype(K)::value, k0 = k1 - 1;  // two elements per step, last first
@@ -335,10 +350,24 @@ __global__ __launch_bounds__(256) void batch_invert_kernel(Fr* __restrict__ a, u
     Fr29::mul_pair(k1 >= H ? exc_b : exc, prefix(k1), k0 >= H ? exc_b : exc, prefix(k0), b1, b0);
     Fr29::mul_pair(b1, r, r, elem(k1), o1, r);
     Fr29::mul_pair(b0, r, r, elem(k0), o0, r);
-    emit(k1, o1);
-    emit(k0, o0);
+    if constexpr (IO::kNumerator) {
+      const auto c1 = io.cell(base + k1 * 256 + t, n), c0 = io.cell(base + k0 * 256 + t, n);
+      IO::times_numerators(c1, o1, c0, o0);
+      c1.emit(nz[k1], o1);
+      c0.emit(nz[k0], o0);
+    } else {
+      emit(k1, o1);
+      emit(k0, o0);
+    }
   });
 }
+template <int BI_PER_LANE>
+__global__ __launch_bounds__(256) void batch_invert_kernel(Fr* __restrict__ a, uint32_t n) {
+  CQ_CRITICAL_WAVES();
+  batch_invert_block<BI_PER_LANE>(BiInPlace{a}, n);
+}
+
+#include "assigned_kernels.hpp"  // BiResolve and the assigned_* kernels: batch_invert_block over Assigned columns
 
 // ---- out[i] = sum_j coeff[j] * p_j[i]  (Polynomial * scalar / + of poly.rs:261-322; theta- and v-folds) ----
 // On the lazy 29-bit limbs (field29.hpp): the coefficients arrive as R' constants (poly_lincomb converts them), a
@@ -589,15 +618,56 @@ int poly_kate_division(cq_ctx* c, const Fr* a, uint32_t n, const Fr& z, Fr* q) {
   return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "kate launch failed");
 }
 
+// measured stand-alone on one box (tools/batch_invert_perf.py, profiles/r03_batch_invert_per_lane.txt): 4 elements per lane
+// up to ~5 x 2^16 (the lane's chain is what the launch waits for), 8 up to ~3 M (k=18's 1.3 M: 127 us against 140), 16 beyond
+static inline int batch_invert_per_lane(uint32_t n) { return n <= 5u * (1u << 16) ? 4 : n <= 3u * (1u << 20) ? 8 : 16; }
+
 int poly_batch_invert(cq_ctx* c, Fr* a, uint32_t n) {
   if (!n) return CQ_OK;
-  // measured stand-alone on one box (tools/batch_invert_perf.py, profiles/r03_batch_invert_per_lane.txt): 4 elements per lane
-  // up to ~5 x 2^16 (the lane's chain is what the launch waits for), 8 up to ~3 M (k=18's 1.3 M: 127 us against 140), 16 beyond
-  const int per = n <= 5u * (1u << 16) ? 4 : n <= 3u * (1u << 20) ? 8 : 16;
+  const int per = batch_invert_per_lane(n);
   if (per == 4) batch_invert_kernel<4><<<(n + 256 * 4 - 1) / (256 * 4), 256, 0, c->stream>>>(a, n);
   else if (per == 8) batch_invert_kernel<8><<<(n + 256 * 8 - 1) / (256 * 8), 256, 0, c->stream>>>(a, n);
   else batch_invert_kernel<16><<<(n + 256 * 16 - 1) / (256 * 16), 256, 0, c->stream>>>(a, n);
   return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "batch_invert launch failed");
+}
+
+int poly_validate_assigned(cq_ctx* c, const uint32_t* off, uint32_t ncols, const uint32_t* rows_dev, uint32_t nrows, uint32_t* verdict_dev) {
+  if (hipMemsetAsync(verdict_dev, 0xff, sizeof(uint32_t), c->stream) != hipSuccess) return c->fail(CQ_ERR_HIP, "assigned: verdict reset failed");
+  for (uint32_t c0 = 0; c0 < ncols; c0 += ASSIGNED_MAX_COLS) {
+    AssignedCols cols{};
+    cols.count = std::min(ASSIGNED_MAX_COLS, ncols - c0);
+    for (uint32_t j = 0; j <= cols.count; j++) cols.off[j] = off[c0 + j] - off[c0];
+    const uint32_t total = cols.off[cols.count];
+    if (total) assigned_validate_kernel<<<blocks_for(total), 256, 0, c->stream>>>(cols, rows_dev + off[c0], nrows, off[c0], verdict_dev);
+  }
+  return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "assigned validate launch failed");
+}
+
+int poly_resolve_assigned(cq_ctx* c, const Fr* const* num, Fr* const* out, const uint32_t* off, uint32_t ncols, const uint32_t* rows_dev,
+                          const Fr* den_dev, uint32_t nrows, Fr* work_dev, const uint32_t* verdict_dev) {
+  for (uint32_t c0 = 0; c0 < ncols; c0 += ASSIGNED_MAX_COLS) {
+    AssignedCols cols{};
+    cols.count = std::min(ASSIGNED_MAX_COLS, ncols - c0);
+    bool copies = false;
+    for (uint32_t j = 0; j < cols.count; j++) {
+      cols.num[j] = num[c0 + j];
+      cols.out[j] = out[c0 + j];
+      copies |= cols.out[j] != cols.num[j];
+    }
+    for (uint32_t j = 0; j <= cols.count; j++) cols.off[j] = off[c0 + j] - off[c0];
+    const uint32_t total = cols.off[cols.count];
+    const uint32_t* rows = rows_dev + off[c0];
+    const Fr* den = den_dev + off[c0];
+    Fr* work = work_dev + off[c0];
+    if (copies && nrows) assigned_copy_kernel<<<dim3(blocks_for(2 * nrows), cols.count), 256, 0, c->stream>>>(cols, nrows, verdict_dev);
+    if (!total) continue;
+    const int per = batch_invert_per_lane(total);
+    const uint32_t blocks = (total + 256 * per - 1) / (256 * per);
+    if (per == 4) assigned_resolve_kernel<4><<<blocks, 256, 0, c->stream>>>(cols, rows, den, work, nrows, verdict_dev);
+    else if (per == 8) assigned_resolve_kernel<8><<<blocks, 256, 0, c->stream>>>(cols, rows, den, work, nrows, verdict_dev);
+    else assigned_resolve_kernel<16><<<blocks, 256, 0, c->stream>>>(cols, rows, den, work, nrows, verdict_dev);
+  }
+  return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "assigned resolve launch failed");
 }
 
 int poly_lincomb(cq_ctx* c, const LincombArgs& args_in, uint32_t n, Fr* out) {

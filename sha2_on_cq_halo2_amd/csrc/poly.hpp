@@ -57,6 +57,23 @@ int poly_eval(cq_ctx* c, const Fr* a_dev, uint32_t n, const Fr& z, Fr* out_host)
 int poly_eval_batch(cq_ctx* c, const Fr* const* p_dev, const uint32_t* len, uint32_t count, const Fr& z, Fr* out_host);
 int poly_kate_division(cq_ctx* c, const Fr* a_dev, uint32_t n, const Fr& z, Fr* q_dev);
 int poly_batch_invert(cq_ctx* c, Fr* a_dev, uint32_t n);
+// batch_invert_assigned (poly.rs:174-241) over `ncols` columns of `nrows` cells: out[c][row] = num[c][row] / den[i] for the
+// entries i in [off[c], off[c + 1]) of the concatenated row / denominator lists (device; `off`: ncols + 1 host words), 0 for
+// a zero denominator, num[c][row] for the cells no entry names; out[c] may be num[c].  work_dev: off[ncols] elements the
+// launch may use.  An entry whose row is not below nrows is skipped, never dereferenced.  verdict_dev: null, or the cell
+// poly_validate_assigned wrote on the same stream -- the launches then write nothing when it names an entry.
+// poly_validate_assigned: *verdict_dev = the lowest entry whose row is >= nrows or not above its predecessor's in the same
+// column, 0xffffffff when there is none.
+constexpr uint32_t ASSIGNED_MAX_COLS = 32;  // columns per launch (more go in several)
+struct AssignedCols {
+  const Fr* num[ASSIGNED_MAX_COLS];
+  Fr* out[ASSIGNED_MAX_COLS];
+  uint32_t off[ASSIGNED_MAX_COLS + 1];  // relative to the launch's first entry
+  uint32_t count;
+};
+int poly_validate_assigned(cq_ctx* c, const uint32_t* off, uint32_t ncols, const uint32_t* rows_dev, uint32_t nrows, uint32_t* verdict_dev);
+int poly_resolve_assigned(cq_ctx* c, const Fr* const* num_dev, Fr* const* out_dev, const uint32_t* off, uint32_t ncols,
+                          const uint32_t* rows_dev, const Fr* den_dev, uint32_t nrows, Fr* work_dev, const uint32_t* verdict_dev);
 int poly_lincomb(cq_ctx* c, const LincombArgs& args, uint32_t n, Fr* out_dev);
 int poly_from_u512(cq_ctx* c, const uint64_t* words_dev, uint32_t n, Fr* out_dev);
 int poly_cq_b_denominators(cq_ctx* c, const Fr* f, uint32_t n, uint32_t u, const Fr& beta, Fr* out);

@@ -263,3 +263,195 @@ class PermutationAssembly:
                                                     lc, left_row, rc, right_row)
         if rc_ != 0:
             raise IndexError("Error::BoundsFailure")
+
+
+class Assigned:
+    """`Assigned<F>` (plonk/assigned.rs:11-18): a cell value kept as a fraction so that the backend can invert all
+    denominators in one batch.  Three variants -- `Assigned.zero()`, `Assigned.trivial(x)`, `Assigned.rational(num, den)`
+    -- over Python integers mod r; a denominator of zero maps to the value zero.  The case analysis of every operation is
+    the reference's (cited per method)."""
+
+    __slots__ = ("kind", "num", "den")
+    ZERO, TRIVIAL, RATIONAL = 0, 1, 2
+
+    def __init__(self, kind: int, num: int = 0, den: int = 0):
+        self.kind, self.num, self.den = kind, num % FR_MODULUS, den % FR_MODULUS
+
+    @staticmethod
+    def zero() -> "Assigned":
+        return Assigned(Assigned.ZERO)
+
+    @staticmethod
+    def trivial(x: int) -> "Assigned":
+        return Assigned(Assigned.TRIVIAL, x)
+
+    @staticmethod
+    def rational(num: int, den: int) -> "Assigned":
+        return Assigned(Assigned.RATIONAL, num, den)
+
+    def __repr__(self):
+        return ("Zero", f"Trivial({self.num:#x})", f"Rational({self.num:#x}, {self.den:#x})")[self.kind]
+
+    def numerator(self) -> int:
+        """assigned.rs:281-287."""
+        return 0 if self.kind == Assigned.ZERO else self.num
+
+    def denominator(self):
+        """assigned.rs:289-296: None unless the cell is Rational."""
+        return self.den if self.kind == Assigned.RATIONAL else None
+
+    def is_zero_vartime(self) -> bool:
+        """assigned.rs:299-308."""
+        if self.kind == Assigned.ZERO:
+            return True
+        if self.kind == Assigned.TRIVIAL:
+            return self.num == 0
+        return self.num == 0 or self.den == 0
+
+    def _den_is_zero(self) -> bool:
+        return self.kind == Assigned.RATIONAL and self.den == 0
+
+    def __eq__(self, o):
+        """assigned.rs:44-70."""
+        if not isinstance(o, Assigned):
+            return NotImplemented
+        Z, T = Assigned.ZERO, Assigned.TRIVIAL
+        if self.kind == Z and o.kind == Z:
+            return True
+        if self.kind == Z:
+            return o.is_zero_vartime()
+        if o.kind == Z:
+            return self.is_zero_vartime()
+        if self._den_is_zero():  # one side is x/0 which maps to zero (:48-56)
+            return o.is_zero_vartime()
+        if o._den_is_zero():
+            return self.is_zero_vartime()
+        if self.kind == T and o.kind == T:
+            return self.num == o.num
+        if self.kind == T:
+            return self.num * o.den % FR_MODULUS == o.num
+        if o.kind == T:
+            return o.num * self.den % FR_MODULUS == self.num
+        return self.num * o.den % FR_MODULUS == self.den * o.num % FR_MODULUS
+
+    __hash__ = None
+
+    def __neg__(self):
+        """assigned.rs:74-83."""
+        return Assigned(self.kind, -self.num, self.den)
+
+    def __add__(self, o):
+        """assigned.rs:92-122, with the x/0 rules of :97-104."""
+        o = _assigned(o)
+        Z, T = Assigned.ZERO, Assigned.TRIVIAL
+        if self.kind == Z:
+            return o
+        if o.kind == Z:
+            return self
+        if self._den_is_zero():
+            return o
+        if o._den_is_zero():
+            return self
+        if self.kind == T and o.kind == T:
+            return Assigned.trivial(self.num + o.num)
+        if o.kind == T:
+            return Assigned.rational(self.num + self.den * o.num, self.den)
+        if self.kind == T:
+            return Assigned.rational(o.num + o.den * self.num, o.den)
+        return Assigned.rational(self.num * o.den + self.den * o.num, self.den * o.den)
+
+    def __sub__(self, o):
+        """assigned.rs:171-176: `self + (-rhs)`."""
+        return self + (-_assigned(o))
+
+    def __mul__(self, o):
+        """assigned.rs:225-244."""
+        o = _assigned(o)
+        Z, T = Assigned.ZERO, Assigned.TRIVIAL
+        if self.kind == Z or o.kind == Z:
+            return Assigned.zero()
+        if self.kind == T and o.kind == T:
+            return Assigned.trivial(self.num * o.num)
+        if o.kind == T:
+            return Assigned.rational(self.num * o.num, self.den)
+        if self.kind == T:
+            return Assigned.rational(o.num * self.num, o.den)
+        return Assigned.rational(self.num * o.num, self.den * o.den)
+
+    def double(self):
+        """assigned.rs:312-320."""
+        return Assigned(self.kind, 2 * self.num, self.den)
+
+    def square(self):
+        """assigned.rs:324-332."""
+        return Assigned(self.kind, self.num * self.num, self.den * self.den)
+
+    def cube(self):
+        """assigned.rs:336-338."""
+        return self.square() * self
+
+    def invert(self):
+        """assigned.rs:341-347 (the inverse of zero is zero)."""
+        if self.kind == Assigned.ZERO:
+            return Assigned.zero()
+        if self.kind == Assigned.TRIVIAL:
+            return Assigned.rational(1, self.num)
+        return Assigned.rational(self.den, self.num)
+
+    def evaluate(self) -> int:
+        """assigned.rs:353-366: one unbatched inversion; a zero denominator gives zero."""
+        if self.kind != Assigned.RATIONAL:
+            return self.numerator()
+        if self.den == 1:
+            return self.num
+        return self.num * pow(self.den, FR_MODULUS - 2, FR_MODULUS) % FR_MODULUS
+
+
+def _assigned(o) -> Assigned:
+    return o if isinstance(o, Assigned) else Assigned.trivial(int(o))  # `From<F>` (assigned.rs:32-36)
+
+
+_MONT_R = (1 << 256) % FR_MODULUS
+
+
+def _mont_limbs(values) -> np.ndarray:
+    out = np.zeros((len(values), 4), dtype=np.uint64)
+    for i, v in enumerate(values):
+        m = v * _MONT_R % FR_MODULUS
+        for j in range(4):
+            out[i, j] = (m >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
+    return out
+
+
+class AssignedColumn:
+    """One column of Assigned cells in the layout of `cq_assigned_column` (include/cq_halo2.h): `num` uint64[n, 4] (the
+    numerators, Montgomery limbs), `den_rows` uint32[m] (the rows of the Rational cells, ascending) and `den`
+    uint64[m, 4] (their denominators) -- the sparse form of `Assigned::denominator` (assigned.rs:289-296) that
+    batch_invert_assigned filters for (poly.rs:189-191)."""
+
+    def __init__(self, num, den_rows, den):
+        self.num = np.ascontiguousarray(num, dtype=np.uint64)
+        self.den_rows = np.ascontiguousarray(den_rows, dtype=np.uint32).reshape(-1)
+        self.den = np.ascontiguousarray(den, dtype=np.uint64).reshape(-1, 4)
+        assert self.num.ndim == 2 and self.num.shape[1] == 4 and self.den.shape[0] == self.den_rows.shape[0]
+
+    @property
+    def n(self) -> int:
+        return self.num.shape[0]
+
+    @classmethod
+    def from_cells(cls, cells, n: int) -> "AssignedColumn":
+        """`cells`: up to n Assigned values (or plain integers, taken as Trivial); the rows beyond them are Zero."""
+        cells = [_assigned(c) for c in cells]
+        assert len(cells) <= n
+        rows = [r for r, c in enumerate(cells) if c.kind == Assigned.RATIONAL]
+        return cls(_mont_limbs([c.numerator() for c in cells] + [0] * (n - len(cells))), rows, _mont_limbs([cells[r].den for r in rows]))
+
+    def cells(self):
+        """The column back as Assigned values (a zero numerator on an unlisted row reads as Zero)."""
+        inv_r = pow(_MONT_R, FR_MODULUS - 2, FR_MODULUS)
+        val = lambda limbs: sum(int(limbs[j]) << (64 * j) for j in range(4)) * inv_r % FR_MODULUS
+        out = [Assigned.trivial(v) if v else Assigned.zero() for v in (val(self.num[r]) for r in range(self.n))]
+        for i, r in enumerate(self.den_rows):
+            out[int(r)] = Assigned.rational(val(self.num[int(r)]), val(self.den[i]))
+        return out
