@@ -159,6 +159,14 @@ def ifft(a, omega_inv, log_n, divisor) -> np.ndarray:
     return a
 
 
+def distribute_powers(a, c1, c2) -> np.ndarray:
+    """`distribute_powers_zeta` (domain.rs:347-363): a[i] *= c1 for i = 1 mod 3, c2 for i = 2 mod 3; returns the copy."""
+    a = _a(a).reshape(-1, 4).copy()
+    m1, m2 = _a(c1).reshape(4), _a(c2).reshape(4)
+    lib().cqo_distribute_powers(a.ctypes.data, a.shape[0], m1.ctypes.data, m2.ctypes.data)
+    return a
+
+
 def keygen_l_active(k: int, blinding_factors: int) -> np.ndarray:
     """keygen.rs:344-373: l_active_row on the extended coset (degree-3 circuit => 2n values)."""
     L = lib()

@@ -503,6 +503,19 @@ class EvaluationDomain:
         self.ctx._chk(self.ctx.lib.cq_extended_to_coeff(self.h, a.ctypes.data, out.ctypes.data))
         return out
 
+    # device forms: `batch` columns stored back to back; they return once the work is queued on the context's stream
+    def lagrange_to_coeff_dev(self, src: DevBuf, dst: DevBuf, batch: int = 1):
+        """`batch` columns of n elements, stride n in and out; `dst` may be `src`."""
+        self.ctx._chk(self.ctx.lib.cq_lagrange_to_coeff_dev(self.h, src.ptr, dst.ptr, batch))
+
+    def coeff_to_extended_dev(self, src: DevBuf, dst: DevBuf, batch: int = 1):
+        """`batch` columns of n coefficients (stride n) to columns of 2^extended_k evaluations; `dst` may not be `src`."""
+        self.ctx._chk(self.ctx.lib.cq_coeff_to_extended_dev(self.h, src.ptr, dst.ptr, batch))
+
+    def extended_to_coeff_dev(self, src: DevBuf, dst: DevBuf):
+        """2^extended_k evaluations to n (j-1) coefficients, the only rows of `dst` written; `dst` may be `src`."""
+        self.ctx._chk(self.ctx.lib.cq_extended_to_coeff_dev(self.h, src.ptr, dst.ptr))
+
     def close(self):
         if self.h and self.ctx.h:
             self.ctx.lib.cq_domain_destroy(self.h)

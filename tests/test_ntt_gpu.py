@@ -73,10 +73,11 @@ def test_best_fft_two_level_twiddles(monkeypatch):
         c2.close()
 
 
-@pytest.mark.parametrize("log_n", [18, 19, 20])
+@pytest.mark.parametrize("log_n", [14, 15, 16, 17, 18, 19, 20, 21])
 def test_best_fft_full_size_matches_c_oracle(ctx, log_n):
-    """The BASELINE sizes themselves, element for element against the C restatement of `best_fft`
-    (arithmetic.rs:171-274): 2^18 and 2^19 take three Stockham passes (k = 18 and its extended domain), 2^20 four."""
+    """The BASELINE sizes themselves (k = 18 and its extended domain 2^19, 2^20) and every pass split around them, element
+    for element against the C restatement of `best_fft` (arithmetic.rs:171-274).  Three Stockham passes up to 2^18
+    (14 = 6+4+4, 15 = 6+5+4, 16 = 6+6+4, 17 = 6+6+5, 18 = 6+6+6), four above (19 = 6+5+4+4, 20 = 6+6+4+4, 21 = 6+6+5+4)."""
     from oracle import cbind as OC
 
     rs = np.random.RandomState(1000 + log_n)

@@ -5,7 +5,8 @@ import numpy as np
 from oracle import bn254 as B
 from oracle import cbind as OC
 from oracle import poly as OP
-from tests.util import random_points, random_scalars
+from tests import domain_model as DM
+from tests.util import full_range_words, random_points, random_scalars
 
 
 def _omega(log_n):
@@ -67,3 +68,22 @@ def test_c_g1_mul_and_affine():
     k = random_scalars(1, 10)[0]
     j = OC.g1_mul(B.points_to_mont_limbs([P])[0], B.to_mont_limbs([k])[0])
     assert B.points_from_mont_limbs(OC.g1_to_affine(j))[0] == B.g1_mul(P, k)
+
+
+def test_c_domain_composition_matches_python_domain():
+    """tests/domain_model.py states the three EvaluationDomain transforms through cqo_ifft, cqo_distribute_powers and
+    cqo_best_fft; at every (j, k) of the GPU sweep's grid up to an extended size of 2^10 it must equal
+    oracle.poly.EvaluationDomain's own methods element for element, on full-range words."""
+    pairs = DM.grid(10)
+    assert {(2, 0), (3, 0), (2, 1), (17, 3), (4, 8), (7, 7)} <= set(pairs)
+    for j, k in pairs:
+        m = DM.DomainModel(j, k)
+        od = m.od
+        a = full_range_words(m.n, 31 * j + k)
+        e = full_range_words(m.ext, 37 * j + k)
+        ai, ei = B.from_mont_limbs(a), B.from_mont_limbs(e)
+        assert np.array_equal(m.lagrange_to_coeff(a), B.to_mont_limbs(od.lagrange_to_coeff(ai))), (j, k)
+        assert np.array_equal(m.coeff_to_extended(a), B.to_mont_limbs(od.coeff_to_extended(ai))), (j, k)
+        back = m.extended_to_coeff(e)
+        assert back.shape == (m.n * (j - 1), 4)
+        assert np.array_equal(back, B.to_mont_limbs(od.extended_to_coeff(ei))), (j, k)
