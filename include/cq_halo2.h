@@ -727,6 +727,73 @@ int cq_quotient_dev(cq_pk* pk, const uint64_t* b_coeff_dev, const uint64_t* f_co
  * the table (Error::ConstraintSystemFailure, :456-460). */
 int cq_permute_expression_pair_dev(cq_ctx* ctx, uint32_t k, uint32_t usable, const uint64_t* input_dev, const uint64_t* table_dev,
                                    uint64_t* permuted_input_dev, uint64_t* permuted_table_dev);
+/* ---- the other heavy stages of create_proof on their own: with the calls above, every stage of a general circuit's
+ * proof can be swapped in one by one (INTEGRATION.md has the whole call sequence).  They run the code cq_create_proof*
+ * runs for the same stage (prover.hip), on the key's domain, window tables and scratch buffers.  Shapes: n = 2^k,
+ * ext = 2^extended_k, bf = blinding_factors, S = permutation sets = ceil(permutation columns / (cs_degree - 2)),
+ * PL = legacy lookups of `pk` in cs.lookups order; field elements in Montgomery form, 4 limbs.  A sharded key
+ * (cq_pk_set_sharding world > 1) is CQ_ERR_ARG for all four, as for cq_pk_check_witness.
+ *
+ * permutation::Argument::commit (plonk/permutation/prover.rs:47-198), called at plonk/prover.rs:539-549: per set the
+ * grand product z over the set's columns (:106-166) starting from the previous set's last_z (:173), its bf blinding rows
+ * (:169-171) and its blind (:175, unused by KZG) drawn from the RNG in that order, set after set; commit_lagrange (:177),
+ * coefficient form (:179).  The fixed columns are the key's.
+ *   advice_dev:   num_advice DEVICE columns of n Lagrange values, blinding rows included
+ *   instance_dev: num_instance device columns of n Lagrange values, zero beyond the instance (NULL without instance columns)
+ *   rng, rng_state: as for cq_create_proof; S x (bf + 1) x 8 words are drawn, through cq_pk_set_rng_fill's hook when set
+ *   z_coeff_dev:  S x n elements out, the z polynomials in coefficient form (written when the call returns)
+ *   commitments:  HOST, S affine points (8 limbs each), in write order
+ * CQ_ERR_ARG for a key without a permutation argument. */
+int cq_permutation_commit_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_t* const* instance_dev, const uint64_t beta[4],
+                              const uint64_t gamma[4], cq_rng_next_u64 rng, void* rng_state, uint64_t* z_coeff_dev,
+                              uint64_t* commitments);
+/* lookup::Permuted::commit_product (plonk/lookup/prover.rs:173-318), called at plonk/prover.rs:552-560, for every legacy
+ * lookup of the key: z = the running product of (A + beta)(S + gamma) / ((A' + beta)(S' + gamma)) (:187-258), its bf
+ * blinding rows (:259) and its blind (:302) drawn from the RNG, lookup after lookup; commit_lagrange (:303), coefficient
+ * form (:304).
+ *   input_dev, table_dev: PL device pointers each, the theta-compressed input / table expressions, n Lagrange values
+ *   permuted_input_dev, permuted_table_dev: PL device pointers each, n values: cq_permute_expression_pair_dev's output
+ *       with the bf + 1 blinding rows of lookup/prover.rs:477-479 appended by the caller
+ *   z_coeff_dev: PL x n elements out;  commitments: HOST, PL affine points
+ * A key without legacy lookups: CQ_OK, nothing drawn or written. */
+int cq_lookup_commit_product_dev(cq_pk* pk, const uint64_t* const* input_dev, const uint64_t* const* table_dev,
+                                 const uint64_t* const* permuted_input_dev, const uint64_t* const* permuted_table_dev,
+                                 const uint64_t beta[4], const uint64_t gamma[4], cq_rng_next_u64 rng, void* rng_state,
+                                 uint64_t* z_coeff_dev, uint64_t* commitments);
+/* The part of Evaluator::evaluate_h before the static lookups (plonk/evaluation.rs:285-531; called at
+ * plonk/prover.rs:606-624): advice and instance polynomials onto the extended coset (:317-335), the custom gates folded
+ * with y (:348-365), the permutation terms (:367-459), the legacy-lookup terms (:461-531).  h_out_dev is what
+ * cq_quotient_dev takes as h_in_dev; for a key with none of the three it is all zero, and cq_quotient_dev then gives
+ * what it gives for h_in_dev = NULL.  Asynchronous on the context's stream, except for a circuit with user challenges:
+ * their upload is waited for before the call returns.
+ *   advice_coeff_dev:   num_advice device polynomials, n coefficients;  instance_coeff_dev: num_instance of them (or NULL)
+ *   perm_z_coeff_dev:   S x n, as left by cq_permutation_commit_dev (NULL when S = 0)
+ *   permuted_input_coeff_dev, permuted_table_coeff_dev: PL device pointers each, A' and S' in coefficient form
+ *   lookup_z_coeff_dev: PL x n, as left by cq_lookup_commit_product_dev (all three NULL when PL = 0)
+ *   challenges:         HOST, num_challenges x 4 limbs (NULL without user challenges)
+ *   h_out_dev:          ext elements out */
+int cq_evaluate_h_dev(cq_pk* pk, const uint64_t* const* advice_coeff_dev, const uint64_t* const* instance_coeff_dev,
+                      const uint64_t* perm_z_coeff_dev, const uint64_t* const* permuted_input_coeff_dev,
+                      const uint64_t* const* permuted_table_coeff_dev, const uint64_t* lookup_z_coeff_dev, const uint64_t* challenges,
+                      const uint64_t beta[4], const uint64_t gamma[4], const uint64_t theta[4], const uint64_t y[4], uint64_t* h_out_dev);
+/* The multi-open argument for arbitrary queries, with the key's opener (cq_pk_set_opener): ProverGWC::create_proof
+ * (poly/kzg/multiopen/gwc/prover.rs:42-91) or ProverSHPLONK::create_proof (shplonk/prover.rs:120-286), called at
+ * plonk/prover.rs:775-778.  A query names a polynomial in coefficient form on the device (1 <= len <= n coefficients) and
+ * a point; the evaluations are computed here.  Queries of one polynomial carry the same pointer and length (that is how
+ * SHPLONK's construct_intermediate_sets, shplonk.rs:56-133, tells commitments apart); points are compared by value.  At
+ * most 8 points per polynomial and 64 distinct point sets with SHPLONK.
+ * The transcript stays with the caller: squeeze_challenge yields the next challenge scalar, write_point takes a
+ * commitment (affine, 8 limbs), both return 0 or fail the call with CQ_ERR_ARG.  Call order: GWC squeezes v (:49), then
+ * writes one witness commitment per distinct point in first-seen order (:85-87); SHPLONK squeezes y (:136) and v (:196),
+ * writes the quotient commitment (:204), squeezes u (:206), writes the opening commitment (:270). */
+typedef struct { const uint64_t* poly_dev; size_t len; uint64_t point[4]; } cq_open_query;
+typedef int (*cq_squeeze_challenge_fn)(void* user, uint64_t* out /* 4 limbs */);
+typedef int (*cq_write_point_fn)(void* user, const uint64_t* affine /* 8 limbs */);
+typedef struct { cq_squeeze_challenge_fn squeeze_challenge; cq_write_point_fn write_point; void* user; } cq_open_transcript;
+int cq_multiopen_dev(cq_pk* pk, const cq_open_query* queries, size_t count, const cq_open_transcript* transcript);
+/* S and PL of the key: what sizes the buffers of the stage calls above. */
+uint32_t cq_pk_permutation_sets(const cq_pk* pk);
+uint32_t cq_pk_legacy_lookups(const cq_pk* pk);
 /* The verifying-key commitments the prover's key implies: commit_lagrange of every fixed column
  * (keygen.rs:247-250) and of every permutation polynomial (permutation/keygen.rs:115-149), as affine
  * points (num_fixed x 8 and num_perm_columns x 8 words). */

@@ -1115,6 +1115,112 @@ def _pk_cq_quotient(self, b_coeff: DevBuf, f_coeff: DevBuf, y, beta, h_in: DevBu
     return out
 
 
+def _ptr_array(ptrs):
+    ptrs = list(ptrs or [])
+    return (C.c_void_p * max(len(ptrs), 1))(*ptrs) if ptrs else None
+
+
+def _limbs4(v):
+    return np.ascontiguousarray(v, dtype=np.uint64).reshape(4)
+
+
+def _pk_permutation_commit(self, advice_ptrs, beta, gamma, instance_ptrs=None, rng_words=None, seed=None, rng=None):
+    """`permutation::Argument::commit` (permutation/prover.rs:47-198) on its own (cq_permutation_commit_dev): the columns
+    are device pointers to n Lagrange values (blinding rows included); returns (z DevBuf [sets x n coefficients],
+    commitments uint64[sets, 8]).  RNG: a pre-drawn u64 stream, a xoshiro256** seed, or `rng` = the (function, state) pair
+    of an earlier `_rng` call to go on drawing from the same stream."""
+    ctx, n = self.ctx, 1 << self.k
+    if len(list(advice_ptrs)) != self.num_advice:
+        raise CqError(-1, f"permutation_commit: the key has {self.num_advice} advice columns, {len(list(advice_ptrs))} given")
+    sets = ctx.lib.cq_pk_permutation_sets(self.h)  # the key's own count sizes the outputs
+    z = ctx.alloc(max(sets * n * 32, 32))
+    cm = np.zeros((max(sets, 1), 8), dtype=np.uint64)
+    fn, st = rng if rng is not None else self._rng(rng_words, seed)
+    be, ga = _limbs4(beta), _limbs4(gamma)
+    ctx._chk(ctx.lib.cq_permutation_commit_dev(self.h, _ptr_array(advice_ptrs), _ptr_array(instance_ptrs), be.ctypes.data, ga.ctypes.data,
+                                               fn, st, z.ptr, cm.ctypes.data))
+    return z, cm[:sets]
+
+
+def _pk_lookup_commit_product(self, input_ptrs, table_ptrs, permuted_input_ptrs, permuted_table_ptrs, beta, gamma, rng_words=None,
+                              seed=None, rng=None):
+    """`lookup::Permuted::commit_product` (lookup/prover.rs:173-318) for every legacy lookup of the key
+    (cq_lookup_commit_product_dev): per lookup the compressed input / table and the permuted pair (blinding rows appended),
+    device pointers to n Lagrange values; returns (z DevBuf [lookups x n coefficients], commitments uint64[lookups, 8])."""
+    ctx, n = self.ctx, 1 << self.k
+    PL = ctx.lib.cq_pk_legacy_lookups(self.h)
+    for ptrs in (input_ptrs, table_ptrs, permuted_input_ptrs, permuted_table_ptrs):
+        if len(list(ptrs)) != PL:
+            raise CqError(-1, f"lookup_commit_product: the key has {PL} legacy lookups, {len(list(ptrs))} columns given")
+    z = ctx.alloc(max(PL * n * 32, 32))
+    cm = np.zeros((max(PL, 1), 8), dtype=np.uint64)
+    fn, st = rng if rng is not None else self._rng(rng_words, seed)
+    be, ga = _limbs4(beta), _limbs4(gamma)
+    ctx._chk(ctx.lib.cq_lookup_commit_product_dev(self.h, _ptr_array(input_ptrs), _ptr_array(table_ptrs), _ptr_array(permuted_input_ptrs),
+                                                  _ptr_array(permuted_table_ptrs), be.ctypes.data, ga.ctypes.data, fn, st, z.ptr,
+                                                  cm.ctypes.data))
+    return z, cm[:PL]
+
+
+def _pk_evaluate_h(self, advice_coeff_ptrs, beta, gamma, theta, y, ext: int, instance_coeff_ptrs=None, perm_z: DevBuf = None,
+                   permuted_input_coeff_ptrs=None, permuted_table_coeff_ptrs=None, lookup_z: DevBuf = None, challenges=None) -> DevBuf:
+    """The gates, permutation terms and legacy-lookup terms of `Evaluator::evaluate_h` (evaluation.rs:285-531) on the
+    extended coset (cq_evaluate_h_dev): all polynomials in coefficient form on the device; the `ext` elements that come
+    back are `cq_quotient`'s `h_in`."""
+    ctx = self.ctx
+    out = ctx.alloc(ext * 32)
+    ch = np.ascontiguousarray(challenges, dtype=np.uint64) if challenges is not None else None
+    be, ga, th, yy = _limbs4(beta), _limbs4(gamma), _limbs4(theta), _limbs4(y)
+    ctx._chk(ctx.lib.cq_evaluate_h_dev(self.h, _ptr_array(advice_coeff_ptrs), _ptr_array(instance_coeff_ptrs), perm_z.ptr if perm_z else None,
+                                       _ptr_array(permuted_input_coeff_ptrs), _ptr_array(permuted_table_coeff_ptrs),
+                                       lookup_z.ptr if lookup_z else None, ch.ctypes.data if ch is not None else None, be.ctypes.data,
+                                       ga.ctypes.data, th.ctypes.data, yy.ctypes.data, out.ptr))
+    return out
+
+
+class _CqOpenQuery(C.Structure):
+    _fields_ = [("poly_dev", C.c_void_p), ("len", C.c_size_t), ("point", C.c_uint64 * 4)]
+
+
+class _CqOpenTranscript(C.Structure):
+    _fields_ = [("squeeze_challenge", C.c_void_p), ("write_point", C.c_void_p), ("user", C.c_void_p)]
+
+
+_SQUEEZE_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64))
+_WRITE_POINT_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64))
+
+
+def _pk_multiopen(self, queries, squeeze_challenge, write_point):
+    """The multi-open argument with the key's opener (`set_opener`) for arbitrary queries (cq_multiopen_dev): `queries`
+    = [(device pointer, length <= n, point uint64[4])]; `squeeze_challenge()` returns the next challenge as Montgomery
+    limbs uint64[4], `write_point(affine uint64[8])` takes a commitment.  An exception in either fails the call."""
+    ctx = self.ctx
+    qs = (_CqOpenQuery * max(len(queries), 1))()
+    for q, (ptr, length, point) in zip(qs, queries):
+        q.poly_dev, q.len = ptr, length
+        for i, limb in enumerate(_limbs4(point)):
+            q.point[i] = int(limb)
+
+    def _squeeze(_user, out):
+        try:
+            for i, limb in enumerate(_limbs4(squeeze_challenge())):
+                out[i] = int(limb)
+            return 0
+        except Exception:  # the C side maps a non-zero status to CQ_ERR_ARG
+            return 1
+
+    def _write(_user, affine):
+        try:
+            write_point(np.array([affine[i] for i in range(8)], dtype=np.uint64))
+            return 0
+        except Exception:
+            return 1
+
+    sq, wr = _SQUEEZE_T(_squeeze), _WRITE_POINT_T(_write)
+    tr = _CqOpenTranscript(C.cast(sq, C.c_void_p), C.cast(wr, C.c_void_p), None)
+    ctx._chk(ctx.lib.cq_multiopen_dev(self.h, qs, len(queries), C.byref(tr)))
+
+
 def _pk_create_proof_batch(self, advice_ptr_lists, seeds, lanes: int = 0, opaque_rng: bool = False):
     """cq_create_proof_batch: one proof per entry of `advice_ptr_lists` (each a list of num_advice device pointers), blinded
     from xoshiro256** streams seeded with `seeds[i]`; returns the list of proofs."""
@@ -1140,6 +1246,10 @@ ProvingKey.b_row_bases = lambda self, which: self.ctx.lib.cq_pk_b_row_bases_dev(
 ProvingKey.cq_round1 = _pk_cq_round1
 ProvingKey.cq_round2 = _pk_cq_round2
 ProvingKey.cq_quotient = _pk_cq_quotient
+ProvingKey.permutation_commit = _pk_permutation_commit
+ProvingKey.lookup_commit_product = _pk_lookup_commit_product
+ProvingKey.evaluate_h = _pk_evaluate_h
+ProvingKey.multiopen = _pk_multiopen
 
 
 def _ctx_msm_precompute(self, bases_ptr: int, n: int):

@@ -6,14 +6,22 @@
 //                       by EvaluationDomain::divide_by_vanishing_poly (poly/domain.rs:319-338)
 //   cq_permute_expression_pair_dev = permute_expression_pair of the legacy lookup argument (plonk/lookup/prover.rs:400-502)
 // They run the same kernels as cq_create_proof (prover.hip), without its cross-round overlap.
+// The remaining heavy stages are entry points onto the very functions ProofRun's stages call (prover.hip, stage_*); here
+// are their argument checks:
+//   cq_permutation_commit_dev    = permutation::Argument::commit        (plonk/permutation/prover.rs:47-198)
+//   cq_lookup_commit_product_dev = lookup::Permuted::commit_product     (plonk/lookup/prover.rs:173-318)
+//   cq_evaluate_h_dev            = Evaluator::evaluate_h before the static lookups (plonk/evaluation.rs:285-531)
+//   cq_multiopen_dev             = ProverGWC / ProverSHPLONK::create_proof (gwc/prover.rs:42-91, shplonk/prover.rs:120-286)
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 #include "cq.hpp"
 #include "ctx.hpp"
 #include "msm.hpp"
 #include "plonk.hpp"
 #include "poly.hpp"
+#include "prover.hpp"
 
 using namespace cq;
 
@@ -40,6 +48,22 @@ void theta_powers(const Fr& theta, uint32_t w, Fr* pow) {
     pow[j] = p;
     p = p * theta;
   }
+}
+
+// what the four stage entry points share: a key, on its device, not sharded across ranks
+int stage_entry(cq_pk* pk, const char* who) {
+  if (!pk) return CQ_ERR_ARG;
+  cq_ctx* c = pk->ctx;
+  if (pk->shard_world > 1) return c->fail(CQ_ERR_ARG, std::string(who) + ": the key is sharded");
+  CQ_HIP(c, hipSetDevice(c->device));
+  return CQ_OK;
+}
+
+// the pre-drawn stream of cq_buffer_rng ran out during `rc`'s call: blinding rows would be zero (as cq_create_proof reports it)
+int rng_ran_out(cq_pk* pk, cq_rng_next_u64 rng, void* rng_state, int rc, const char* who) {
+  if (rc == CQ_OK && rng == cq_buffer_rng_next_u64 && ((cq_buffer_rng*)rng_state)->overrun)
+    return pk->ctx->fail(CQ_ERR_ARG, std::string(who) + ": the pre-drawn RNG stream ran out (blinding would be zero)");
+  return rc;
 }
 
 }  // namespace
@@ -270,6 +294,87 @@ int cq_permute_expression_pair_dev(cq_ctx* c, uint32_t k, uint32_t usable, const
   CQ_HIP(c, hipStreamSynchronize(c->stream));
   if (st[0] != 0 || st[1] != st[2]) return c->fail(CQ_ERR_LOOKUP, "lookup input not in table (Error::ConstraintSystemFailure)");
   return CQ_OK;
+}
+
+int cq_permutation_commit_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_t* const* instance_dev, const uint64_t beta[4],
+                              const uint64_t gamma[4], cq_rng_next_u64 rng, void* rng_state, uint64_t* z_coeff_dev,
+                              uint64_t* commitments) {
+  CQ_TRY(stage_entry(pk, "permutation_commit"));
+  cq_ctx* c = pk->ctx;
+  if (!pk->perm_sets()) return c->fail(CQ_ERR_ARG, "permutation_commit: the key has no permutation argument");
+  if (!beta || !gamma || !z_coeff_dev || !commitments) return c->fail(CQ_ERR_ARG, "permutation_commit: NULL argument");
+  if (!rng && !pk->rng_fill) return c->fail(CQ_ERR_ARG, "permutation_commit: no RNG");
+  for (auto& col : pk->perm_columns)
+    if ((col.first == CQ_COL_ADVICE && !advice_dev) || (col.first == CQ_COL_INSTANCE && !instance_dev))
+      return c->fail(CQ_ERR_ARG, "permutation_commit: advice / instance columns missing");
+  if (rng == cq_buffer_rng_next_u64) ((cq_buffer_rng*)rng_state)->overrun = 0;
+  const int rc = stage_permutation_commit(pk, advice_dev, instance_dev, Fr::from_limbs64(beta), Fr::from_limbs64(gamma), rng, rng_state,
+                                          (Fr*)z_coeff_dev, commitments);
+  return rng_ran_out(pk, rng, rng_state, rc, "permutation_commit");
+}
+
+int cq_lookup_commit_product_dev(cq_pk* pk, const uint64_t* const* input_dev, const uint64_t* const* table_dev,
+                                 const uint64_t* const* permuted_input_dev, const uint64_t* const* permuted_table_dev,
+                                 const uint64_t beta[4], const uint64_t gamma[4], cq_rng_next_u64 rng, void* rng_state,
+                                 uint64_t* z_coeff_dev, uint64_t* commitments) {
+  CQ_TRY(stage_entry(pk, "lookup_commit_product"));
+  cq_ctx* c = pk->ctx;
+  const size_t PL = pk->legacy.size();
+  if (!PL) return CQ_OK;
+  if (!input_dev || !table_dev || !permuted_input_dev || !permuted_table_dev || !beta || !gamma || !z_coeff_dev || !commitments)
+    return c->fail(CQ_ERR_ARG, "lookup_commit_product: NULL argument");
+  for (size_t l = 0; l < PL; l++)
+    if (!input_dev[l] || !table_dev[l] || !permuted_input_dev[l] || !permuted_table_dev[l])
+      return c->fail(CQ_ERR_ARG, "lookup_commit_product: NULL column");
+  if (!rng && !pk->rng_fill) return c->fail(CQ_ERR_ARG, "lookup_commit_product: no RNG");
+  if (rng == cq_buffer_rng_next_u64) ((cq_buffer_rng*)rng_state)->overrun = 0;
+  const int rc = stage_lookup_commit_product(pk, input_dev, table_dev, permuted_input_dev, permuted_table_dev, Fr::from_limbs64(beta),
+                                             Fr::from_limbs64(gamma), rng, rng_state, (Fr*)z_coeff_dev, commitments);
+  return rng_ran_out(pk, rng, rng_state, rc, "lookup_commit_product");
+}
+
+int cq_evaluate_h_dev(cq_pk* pk, const uint64_t* const* advice_coeff_dev, const uint64_t* const* instance_coeff_dev,
+                      const uint64_t* perm_z_coeff_dev, const uint64_t* const* permuted_input_coeff_dev,
+                      const uint64_t* const* permuted_table_coeff_dev, const uint64_t* lookup_z_coeff_dev, const uint64_t* challenges,
+                      const uint64_t beta[4], const uint64_t gamma[4], const uint64_t theta[4], const uint64_t y[4], uint64_t* h_out_dev) {
+  CQ_TRY(stage_entry(pk, "evaluate_h"));
+  cq_ctx* c = pk->ctx;
+  if (!beta || !gamma || !theta || !y || !h_out_dev) return c->fail(CQ_ERR_ARG, "evaluate_h: NULL argument");
+  if (pk->general()) {
+    const size_t PL = pk->legacy.size();
+    if ((pk->num_advice && !advice_coeff_dev) || (pk->num_instance && !instance_coeff_dev) || (pk->perm_sets() && !perm_z_coeff_dev) ||
+        (PL && (!permuted_input_coeff_dev || !permuted_table_coeff_dev || !lookup_z_coeff_dev)) ||
+        (!pk->challenge_phase.empty() && !challenges))
+      return c->fail(CQ_ERR_ARG, "evaluate_h: a polynomial the key's circuit reads is missing");
+    for (size_t a = 0; a < pk->num_advice; a++)
+      if (!advice_coeff_dev[a]) return c->fail(CQ_ERR_ARG, "evaluate_h: NULL advice polynomial");
+    for (size_t i = 0; i < pk->num_instance; i++)
+      if (!instance_coeff_dev[i]) return c->fail(CQ_ERR_ARG, "evaluate_h: NULL instance polynomial");
+    for (size_t l = 0; l < PL; l++)
+      if (!permuted_input_coeff_dev[l] || !permuted_table_coeff_dev[l]) return c->fail(CQ_ERR_ARG, "evaluate_h: NULL permuted polynomial");
+  }
+  return stage_evaluate_h(pk, advice_coeff_dev, instance_coeff_dev, (const Fr*)perm_z_coeff_dev, permuted_input_coeff_dev,
+                          permuted_table_coeff_dev, (const Fr*)lookup_z_coeff_dev, challenges, Fr::from_limbs64(beta), Fr::from_limbs64(gamma),
+                          Fr::from_limbs64(theta), Fr::from_limbs64(y), (Fr*)h_out_dev);
+}
+
+uint32_t cq_pk_permutation_sets(const cq_pk* pk) { return pk ? (uint32_t)pk->perm_sets() : 0; }
+uint32_t cq_pk_legacy_lookups(const cq_pk* pk) { return pk ? (uint32_t)pk->legacy.size() : 0; }
+
+int cq_multiopen_dev(cq_pk* pk, const cq_open_query* queries, size_t count, const cq_open_transcript* transcript) {
+  CQ_TRY(stage_entry(pk, "multiopen"));
+  cq_ctx* c = pk->ctx;
+  const size_t n = (size_t)1 << pk->k;
+  if (!queries || !count || !transcript || !transcript->squeeze_challenge || !transcript->write_point)
+    return c->fail(CQ_ERR_ARG, "multiopen: no queries or no transcript callbacks");
+  for (size_t i = 0; i < count; i++) {
+    if (!queries[i].poly_dev || queries[i].len == 0 || queries[i].len > n)
+      return c->fail(CQ_ERR_ARG, "multiopen: a query's polynomial is NULL, empty or longer than n");
+    for (size_t j = 0; j < i; j++)
+      if (queries[j].poly_dev == queries[i].poly_dev && queries[j].len != queries[i].len)
+        return c->fail(CQ_ERR_ARG, "multiopen: two queries of one polynomial differ in length");
+  }
+  return stage_multiopen(pk, queries, count, transcript);
 }
 
 }  // extern "C"

@@ -31,7 +31,11 @@ enum class Scratch {
   PolyTmp,      // poly.hip eval / kate, plonk.hip prefix_product partials, for one call each
   ProverArena,  // create_proof_dev's arena, for the whole proof
   ProverStage,  // create_proof_dev's resident receive staging or its legacy-lookup staging (never both: resident sharding
-                // requires no legacy lookups); capi_rounds.hip's stand-alone rounds, which a proof never calls
+                // requires no legacy lookups); capi_rounds.hip's stand-alone rounds, which a proof never calls; prover.hip's
+                // stand-alone stages (stage_permutation_commit: the inverted denominators; stage_evaluate_h: the cosets and
+                // the challenges; stage_multiopen: the opener's buffers; stage_lookup_commit_product takes none), each for
+                // its own call only.  They are public entry points that call no other entry point and that create_proof_dev
+                // never calls, and calls on one context follow one another on its stream, so no two hold it at a time
   HostAdvice,   // create_proof_host_any's copy of the caller's advice columns, held for the whole proof: nothing else takes it
   AssignedDen,  // cq_create_proof_assigned's sparse denominators (rows, values, the resolve launch's work array), from the upload
                 // until the columns are resolved on the proof's stream, before the proof starts: nothing else takes it

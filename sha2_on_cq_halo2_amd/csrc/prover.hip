@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <thread>
 #include <vector>
 #include "blake2b.hpp"
@@ -427,6 +428,7 @@ struct Query {
   int32_t rot;
   int h_piece;  // -1, or the index of an h piece (folded into one query with coefficient xn^i)
   Fr eval;
+  uint32_t pt = 0;  // the query's point, as an index into the distinct points in first-seen order: what the openers go by
 };
 
 // lagrange_interpolate (arithmetic.rs:425-478) of a commitment's evaluations over its set's points
@@ -455,6 +457,380 @@ Fr eval_small(const std::vector<Fr>& poly, const Fr& at) {
   Fr acc = Fr::zero();
   for (size_t i = poly.size(); i-- > 0;) acc = acc * at + poly[i];
   return acc;
+}
+
+// ---- The stages a caller may also run on their own (cq_permutation_commit_dev, cq_lookup_commit_product_dev,
+//      cq_evaluate_h_dev, cq_multiopen_dev at the end of this file): one implementation each, which ProofRun's methods and
+//      the stand-alone entry points both call.  They take device pointers and challenges, enqueue on the context's stream,
+//      and know nothing of the proof's arena, transcript or RNG. ---------------------------------------------------------
+
+// permutation::Argument::commit (permutation/prover.rs:47-198) up to the Lagrange values of every z.  cols[ci]: the
+// Lagrange values of permutation column ci; z_tails: sets x bf blinding rows (host, :169-171); mv, z: sets x n each.
+int perm_products(const cq_pk* pk, const Fr* const* cols, const Fr& beta, const Fr& gamma, const Fr* z_tails, Fr* mv, Fr* z) {
+  cq_ctx* c = pk->ctx;
+  const hipStream_t s = c->stream;
+  const size_t n = (size_t)1 << pk->k, S = pk->perm_sets(), PC = pk->perm_columns.size(), chunk_len = pk->cs_degree - 2;
+  const uint32_t bf = pk->bf, u = pk->u;
+  const Fr delta = fr_from_raw(FR_DELTA_RAW);
+  std::vector<PermProductArgs> pa(S);
+  Fr deltaomega = Fr::one();  // delta^(column position), :86-87,146
+  for (size_t st = 0; st < S; st++) {
+    PermProductArgs& a = pa[st];
+    a.count = (uint32_t)std::min(chunk_len, PC - st * chunk_len);
+    a.beta = beta;
+    a.gamma = gamma;
+    a.omega_powers = pk->omega_powers;
+    for (uint32_t j = 0; j < a.count; j++) {
+      const size_t ci = st * chunk_len + j;
+      a.col[j] = cols[ci];
+      a.sigma[j] = pk->perm_values + ci * n;
+      a.delta_beta[j] = deltaomega * beta;
+      deltaomega = deltaomega * delta;
+    }
+    CQ_TRY(perm_denominators(c, a, (uint32_t)n, mv + st * n));  // :106-121
+  }
+  CQ_TRY(poly_batch_invert(c, mv, (uint32_t)(S * n)));  // :124
+  for (size_t st = 0; st < S; st++) CQ_TRY(perm_numerators(c, pa[st], (uint32_t)n, mv + st * n));  // :128-147
+  // z[0] = last_z, z[row] = z[row-1] * mv[row-1] (:160-166): a multiplicative scan per set, then the
+  // chain last_z = z[n - (bf+1)] of the previous set (:173) as one scalar per set
+  CQ_TRY(prefix_product(c, mv, z, (uint32_t)n, (uint32_t)S));
+  std::vector<Fr> at_u(S);
+  for (size_t st = 0; st < S; st++) CQ_HIP(c, hipMemcpyAsync(&at_u[st], z + st * n + u, sizeof(Fr), hipMemcpyDeviceToHost, s));
+  CQ_TRY(c->wait(s));
+  PermScaleArgs sa;
+  Fr last_z = Fr::one();
+  for (size_t st = 0; st < S; st++) {
+    sa.mult[st] = last_z;
+    last_z = last_z * at_u[st];
+  }
+  CQ_TRY(perm_scale(c, z, (uint32_t)n, u + 1, (uint32_t)S, sa));
+  // blinding rows (:169-171)
+  for (size_t st = 0; st < S; st++)
+    CQ_HIP(c, hipMemcpyAsync(z + st * n + (n - bf), z_tails + st * bf, bf * sizeof(Fr), hipMemcpyHostToDevice, s));
+  return CQ_OK;
+}
+
+// lookup::Permuted::commit_product (lookup/prover.rs:163-300) up to the Lagrange values of z: the running product of
+// (A + beta)(S + gamma) / ((a' + beta)(s' + gamma)), rows n - bf .. from `tails` (host, bf elements).  All vectors: n.
+int lookup_product(cq_ctx* c, const Fr* cin, const Fr* ctab, const Fr* perm_in, const Fr* perm_tab, const Fr& beta, const Fr& gamma,
+                   const Fr* tails, uint32_t n, uint32_t bf, Fr* z) {
+  CQ_TRY(lookup_denominators(c, perm_in, perm_tab, beta, gamma, n, z));
+  CQ_TRY(poly_batch_invert(c, z, n));
+  CQ_TRY(lookup_numerators(c, cin, ctab, beta, gamma, n, z));
+  CQ_TRY(prefix_product(c, z, z, n, 1));
+  CQ_HIP(c, hipMemcpyAsync(z + (n - bf), tails, bf * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+  return CQ_OK;
+}
+
+// The non-CQ part of Evaluator::evaluate_h (evaluation.rs:285-531): custom gates, permutation terms, legacy-lookup terms,
+// folded with y in that order into h_ext.  The columns come on the extended coset already (their transforms are the
+// caller's to place); the legacy lookups' a', s', z come as coefficients and are extended here.  A key without any of
+// the three (CQ-only) leaves h_ext untouched.
+struct HTermsArgs {
+  const Fr *adv_cosets, *inst_cosets, *z_cosets;  // num_advice / num_instance / sets x ext
+  const Fr* challenges;                           // device: user challenges
+  const Fr* const* plk_polys;                     // per legacy lookup: a', s', z, three consecutive vectors of n coefficients
+  Fr* plk_cosets;                                 // legacy lookups x 5 x ext, written here
+  Fr beta, gamma, theta, y;
+};
+int h_terms(const cq_pk* pk, const HTermsArgs& t, Fr* h_ext) {
+  cq_ctx* c = pk->ctx;
+  cq_domain* dom = pk->domain;
+  const size_t n = (size_t)1 << pk->k, ext = dom->ext(), S = pk->perm_sets(), PC = pk->perm_columns.size();
+  const uint32_t rot_scale = 1u << (dom->extended_k - dom->k);
+  if (!pk->general()) return CQ_OK;
+  GateEvalArgs coset_eval;  // `evaluate` over the extended coset: the gates folded with y, a legacy lookup's expressions with theta
+  coset_eval.constants = pk->constants;
+  coset_eval.challenges = t.challenges;
+  coset_eval.advice = t.adv_cosets;
+  coset_eval.fixed = pk->fixed_cosets;
+  coset_eval.instance = t.inst_cosets;
+  coset_eval.stride = ext;
+  coset_eval.size = (uint32_t)ext;
+  coset_eval.rot_scale = rot_scale;
+  if (pk->num_gate_polys) {  // custom gates (:348-365)
+    GateEvalArgs ga = coset_eval;
+    ga.prog = pk->gate_prog;
+    ga.num_polys = pk->num_gate_polys;
+    ga.y = t.y;
+    CQ_TRY(gate_eval(c, ga, h_ext));
+  } else {
+    CQ_HIP(c, hipMemsetAsync(h_ext, 0, ext * sizeof(Fr), c->stream));
+  }
+  if (S) {  // permutation constraints (:367-459)
+    PermHArgs ph;
+    ph.z = t.z_cosets;
+    ph.sigma = pk->perm_cosets;
+    for (size_t ci = 0; ci < PC; ci++) {
+      const auto& col = pk->perm_columns[ci];
+      ph.col[ci] = col.first == CQ_COL_ADVICE ? t.adv_cosets + (size_t)col.second * ext
+                 : col.first == CQ_COL_FIXED  ? pk->fixed_cosets + (size_t)col.second * ext
+                                              : t.inst_cosets + (size_t)col.second * ext;
+    }
+    ph.sets = (uint32_t)S;
+    ph.chunk_len = pk->cs_degree - 2;
+    ph.ncols = (uint32_t)PC;
+    ph.l0 = pk->l0;
+    ph.l_last = pk->l_last;
+    ph.l_active = pk->l_active_row;
+    ph.beta = t.beta;
+    ph.gamma = t.gamma;
+    ph.y = t.y;
+    ph.delta_start = t.beta * dom->g_coset;  // beta * ZETA (:375)
+    ph.ext_pow_lo = pk->ext_pow_lo;
+    ph.ext_pow_hi = pk->ext_pow_hi;
+    ph.delta = fr_from_raw(FR_DELTA_RAW);
+    ph.ext = (uint32_t)ext;
+    ph.rot_scale = rot_scale;
+    ph.last_rot = pk->bf + 1;
+    CQ_TRY(perm_h_terms(c, ph, h_ext));
+  }
+  for (size_t l = 0; l < pk->legacy.size(); l++) {  // legacy lookup constraints (:461-531)
+    const auto& lk = pk->legacy[l];
+    Fr* co = t.plk_cosets + l * 5 * ext;  // a', s', z cosets, then the compressed input / table on the coset
+    CQ_TRY(domain_coeff_to_extended(dom, t.plk_polys[l], co, 3, n, ext));
+    for (int side = 0; side < 2; side++) {
+      GateEvalArgs ga = coset_eval;
+      ga.prog = pk->legacy_prog + (side ? lk.tab_off : lk.in_off);
+      ga.num_polys = lk.width;
+      ga.y = t.theta;
+      CQ_TRY(gate_eval(c, ga, co + (3 + side) * ext));
+    }
+    LookupHArgs la;
+    la.a = co;
+    la.s = co + ext;
+    la.z = co + 2 * ext;
+    la.cin = co + 3 * ext;
+    la.ctab = co + 4 * ext;
+    la.l0 = pk->l0;
+    la.l_last = pk->l_last;
+    la.l_active = pk->l_active_row;
+    la.beta = t.beta;
+    la.gamma = t.gamma;
+    la.y = t.y;
+    la.ext = (uint32_t)ext;
+    la.rot_scale = rot_scale;
+    CQ_TRY(lookup_h_terms(c, la, h_ext));
+  }
+  return CQ_OK;
+}
+
+// The multi-open argument over a list of queries.  Polynomials may be shorter than n: every combination below is one
+// poly_lincomb launch (lincomb_kernel: one lane per coefficient, a term contributes only where the lane is below its
+// own length), so mixed lengths need no kernel of their own.  The transcript is reached through two hooks, the
+// proof's own or a caller's callbacks; both return CQ_OK or the error to pass on.
+struct OpenTranscript {
+  std::function<int(Fr&)> squeeze;
+  std::function<int(const G1Affine&, const char* what)> write_point;  // `what` names the point should it be the identity
+};
+struct OpenJob {
+  const cq_pk* pk;
+  const std::vector<Query>* qs;    // evaluations filled in
+  const std::vector<Fr>* points;   // the distinct points, first-seen order (Query::pt)
+  const std::vector<size_t>* q_h;  // the queries that are pieces of h (none outside a proof); they share one power of v
+  Fr xn;                           // x^n, the pieces' weight
+  Fr *gwc_batch, *gwc_wit;         // GWC: points x n each
+  Fr* shplonk;                     // SHPLONK: 5 n + 64 * 8 (h, two division buffers, h_x, l_x, low-degree remainders)
+  OpenTranscript tr;
+  // GWC, optional: forms point g's witness polynomial from the combination's terms in place of lincomb + kate_division
+  // (resident sharding, where no rank holds every term)
+  std::function<int(size_t g, const std::vector<Term>& terms, const Fr& eval_batch, Fr* batch, Fr* wit)> witness;
+};
+Fr h_value(const OpenJob& j) {  // h(x) = sum_i xn^i h_i(x) (vanishing/prover.rs:131-135)
+  Fr h_eval = Fr::zero();
+  for (size_t i = j.q_h->size(); i-- > 0;) h_eval = h_eval * j.xn + (*j.qs)[(*j.q_h)[i]].eval;
+  return h_eval;
+}
+
+// ---- multiopen, GWC (gwc/prover.rs:42-91): one witness polynomial per distinct point ---------------------
+int open_gwc_queries(OpenJob& j) {
+  const cq_pk* pk = j.pk;
+  cq_ctx* c = pk->ctx;
+  const size_t n = (size_t)1 << pk->k, pieces = j.q_h->size();
+  const std::vector<Query>& qs = *j.qs;
+  Fr v;
+  CQ_TRY(j.tr.squeeze(v));
+  const Fr h_eval = h_value(j);  // its value follows from the piece evaluations
+  std::vector<const Fr*> sc;
+  for (size_t g = 0; g < j.points->size(); g++) {
+    std::vector<Term> terms;
+    Fr pv = Fr::one(), eval_batch = Fr::zero(), xp = Fr::one();
+    for (auto& q : qs) {
+      if (q.pt != g) continue;
+      if (q.h_piece >= 0) {  // the pieces of h share one power of v
+        terms.push_back({q.p, q.len, pv * xp});
+        xp = xp * j.xn;
+        if ((size_t)q.h_piece + 1 < pieces) continue;
+        eval_batch = eval_batch + h_eval * pv;
+      } else {
+        terms.push_back({q.p, q.len, pv});
+        eval_batch = eval_batch + q.eval * pv;
+      }
+      pv = pv * v;
+    }
+    Fr* batch = j.gwc_batch + g * n;
+    Fr* wit = j.gwc_wit + g * n;
+    if (j.witness) {
+      CQ_TRY(j.witness(g, terms, eval_batch, batch, wit));
+    } else {
+      CQ_TRY(lincomb_many(c, terms, eval_batch, (uint32_t)n, batch));  // poly_batch - eval_batch (gwc/prover.rs:62-78)
+      CQ_TRY(poly_kate_division(c, batch, (uint32_t)n, (*j.points)[g], wit));  // :80
+    }
+    sc.push_back(wit);
+  }
+  std::vector<const G1Affine*> bs(sc.size(), pk->params->g);
+  std::vector<G1Affine> o;
+  CQ_TRY(commit_batch(pk, sc, bs, n - 1, o));  // :85
+  for (auto& w : o) CQ_TRY(j.tr.write_point(w, "opening witness commitment is the identity"));
+  return CQ_OK;
+}
+
+// ---- multiopen, SHPLONK (shplonk/prover.rs:120-286): two commitments whatever the number of points ---------
+int open_shplonk_queries(OpenJob& j) {
+  const cq_pk* pk = j.pk;
+  cq_ctx* c = pk->ctx;
+  const hipStream_t s = c->stream;
+  const size_t n = (size_t)1 << pk->k, pieces = j.q_h->size();
+  const std::vector<Query>& qs = *j.qs;
+  const std::vector<Fr>& points = *j.points;
+  Fr* sh_h = j.shplonk;           // h(X) = sum_i xn^i h_i as one polynomial (vanishing/prover.rs:131-135)
+  Fr* sh_div[2] = {j.shplonk + n, j.shplonk + 2 * n};
+  Fr* sh_hx = j.shplonk + 3 * n;
+  Fr* sh_lx = j.shplonk + 4 * n;
+  Fr* sh_rem = j.shplonk + 5 * n;  // per rotation set: sum_j y^j r_j (at most 8 coefficients)
+  const Fr h_eval = h_value(j);
+  if (pieces) {
+    std::vector<Term> terms;
+    Fr xp = Fr::one();
+    for (size_t i = 0; i < pieces; i++) {
+      const Query& q = qs[(*j.q_h)[i]];
+      terms.push_back({q.p, q.len, xp});
+      xp = xp * j.xn;
+    }
+    CQ_TRY(lincomb_many(c, terms, Fr::zero(), (uint32_t)n, sh_h));
+  }
+  Fr y_;
+  CQ_TRY(j.tr.squeeze(y_));  // :136
+  // construct_intermediate_sets (shplonk.rs:56-133): commitments by polynomial identity, grouped by point set
+  struct Com { const Fr* p; uint32_t len; std::vector<uint32_t> pts; std::vector<Fr> evals; };
+  std::vector<Com> coms;
+  for (auto& q : qs) {
+    const Fr* key = q.h_piece >= 0 ? sh_h : q.p;
+    if (q.h_piece > 0) continue;
+    const Fr ev = q.h_piece == 0 ? h_eval : q.eval;
+    auto it = std::find_if(coms.begin(), coms.end(), [&](const Com& cm) { return cm.p == key; });
+    if (it == coms.end()) {
+      coms.push_back({key, q.h_piece == 0 ? (uint32_t)n : q.len, {q.pt}, {ev}});
+    } else if (std::find(it->pts.begin(), it->pts.end(), q.pt) == it->pts.end()) {
+      it->pts.push_back(q.pt);
+      it->evals.push_back(ev);
+    }
+  }
+  struct RotSet { std::vector<uint32_t> pts; std::vector<size_t> members; };
+  std::vector<RotSet> sets;
+  auto same_set = [](const std::vector<uint32_t>& a, const std::vector<uint32_t>& b) {
+    return a.size() == b.size() && std::all_of(a.begin(), a.end(), [&](uint32_t r) { return std::find(b.begin(), b.end(), r) != b.end(); });
+  };
+  for (size_t ci = 0; ci < coms.size(); ci++) {
+    auto it = std::find_if(sets.begin(), sets.end(), [&](const RotSet& rs) { return same_set(rs.pts, coms[ci].pts); });
+    if (it == sets.end()) sets.push_back({coms[ci].pts, {ci}});
+    else it->members.push_back(ci);
+  }
+  if (sets.size() > 64) return c->fail(CQ_ERR_ARG, "too many rotation sets");
+  Fr v_;
+  CQ_TRY(j.tr.squeeze(v_));  // :196
+  // per set: low-degree equivalents r_j and the y-combined remainder (CommitmentExtension, :36-76)
+  std::vector<std::vector<Fr>> set_points(sets.size());
+  std::vector<std::vector<std::vector<Fr>>> low(sets.size());
+  std::vector<Fr> rem_host(sets.size() * 8, Fr::zero());
+  for (size_t si = 0; si < sets.size(); si++) {
+    for (uint32_t r : sets[si].pts) set_points[si].push_back(points[r]);
+    if (set_points[si].size() > 8) return c->fail(CQ_ERR_ARG, "rotation set too large");
+    Fr py = Fr::one();
+    for (size_t ci : sets[si].members) {
+      // the commitment's evaluations, aligned with the set's point order
+      std::vector<Fr> evals;
+      for (uint32_t r : sets[si].pts) {
+        const size_t pos = std::find(coms[ci].pts.begin(), coms[ci].pts.end(), r) - coms[ci].pts.begin();
+        evals.push_back(coms[ci].evals[pos]);
+      }
+      low[si].push_back(lagrange_interpolate(set_points[si], evals));
+      for (size_t i = 0; i < low[si].back().size(); i++) rem_host[si * 8 + i] = rem_host[si * 8 + i] + py * low[si].back()[i];
+      py = py * y_;
+    }
+  }
+  CQ_HIP(c, hipMemcpyAsync(sh_rem, rem_host.data(), rem_host.size() * sizeof(Fr), hipMemcpyHostToDevice, s));
+  // h_x = sum_i v^i * (sum_j y^j (p_j - r_j)) / prod_{pt in set_i} (X - pt)   (quotient_contribution, :138-168)
+  Fr pv = Fr::one();
+  for (size_t si = 0; si < sets.size(); si++) {
+    std::vector<Term> terms;
+    Fr py = Fr::one();
+    for (size_t ci : sets[si].members) {
+      terms.push_back({coms[ci].p, coms[ci].len, py});
+      py = py * y_;
+    }
+    terms.push_back({sh_rem + si * 8, (uint32_t)set_points[si].size(), Fr::zero() - Fr::one()});
+    CQ_TRY(lincomb_many(c, terms, Fr::zero(), (uint32_t)n, sh_div[0]));
+    uint32_t len = (uint32_t)n;
+    int cur = 0;
+    for (const Fr& pt : set_points[si]) {  // div_by_vanishing (:28-34)
+      CQ_TRY(poly_kate_division(c, sh_div[cur], len, pt, sh_div[cur ^ 1]));
+      cur ^= 1;
+      len--;
+    }
+    std::vector<Term> acc;
+    if (si) acc.push_back({sh_hx, (uint32_t)n, Fr::one()});
+    acc.push_back({sh_div[cur], len, pv});
+    CQ_TRY(lincomb_many(c, acc, Fr::zero(), (uint32_t)n, sh_hx));
+    pv = pv * v_;
+  }
+  {
+    std::vector<const Fr*> sc{sh_hx};
+    std::vector<const G1Affine*> bs{pk->params->g};
+    std::vector<G1Affine> o;
+    CQ_TRY(commit_batch(pk, sc, bs, n, o));  // :204
+    CQ_TRY(j.tr.write_point(o[0], "shplonk quotient commitment is the identity"));
+  }
+  Fr u_;
+  CQ_TRY(j.tr.squeeze(u_));  // :206
+  // l_x = sum_i v^i z_i sum_j y^j (p_j - r_j(u)) - Z_T(u) h_x, then / (X - u) and / z_0   (:208-283); the
+  // scaling by 1/z_0 is folded into the coefficients (the division is linear)
+  auto vanish = [&](const std::vector<Fr>& roots) {
+    Fr acc = Fr::one();
+    for (auto& r : roots) acc = (u_ - r) * acc;
+    return acc;
+  };
+  std::vector<Fr> z_diff(sets.size());
+  for (size_t si = 0; si < sets.size(); si++) {
+    std::vector<Fr> diffs;
+    for (uint32_t pi = 0; pi < points.size(); pi++)  // super_point_set: every distinct point
+      if (std::find(sets[si].pts.begin(), sets[si].pts.end(), pi) == sets[si].pts.end()) diffs.push_back(points[pi]);
+    z_diff[si] = vanish(diffs);
+  }
+  const Fr z0_inv = z_diff[0].inv();
+  const Fr zt_eval = vanish(points);
+  std::vector<Term> terms;
+  Fr sub = Fr::zero();
+  pv = Fr::one();
+  for (size_t si = 0; si < sets.size(); si++) {
+    const Fr scale = pv * z_diff[si] * z0_inv;
+    Fr py = Fr::one();
+    for (size_t m = 0; m < sets[si].members.size(); m++) {
+      const Com& cm = coms[sets[si].members[m]];
+      terms.push_back({cm.p, cm.len, scale * py});
+      sub = sub + scale * py * eval_small(low[si][m], u_);
+      py = py * y_;
+    }
+    pv = pv * v_;
+  }
+  terms.push_back({sh_hx, (uint32_t)n, Fr::zero() - zt_eval * z0_inv});
+  CQ_TRY(lincomb_many(c, terms, sub, (uint32_t)n, sh_lx));
+  CQ_TRY(poly_kate_division(c, sh_lx, (uint32_t)n, u_, sh_div[0]));  // :257
+  std::vector<const Fr*> sc{sh_div[0]};
+  std::vector<const G1Affine*> bs{pk->params->g};
+  std::vector<G1Affine> o;
+  CQ_TRY(commit_batch(pk, sc, bs, n - 1, o));  // :270
+  return j.tr.write_point(o[0], "shplonk opening commitment is the identity");
 }
 
 // The vanishing argument's random polynomial (vanishing/prover.rs:51-55: n field elements = 8n words, then one
@@ -586,6 +962,7 @@ struct ProofRun {
   std::vector<Query> qs;
   std::vector<size_t> q_h;
   std::vector<int32_t> rots;
+  std::vector<Fr> points;
   std::vector<int> qowner;
   size_t my_lo = 0, my_hi = n;
   RandomPolyDrawer drawer;  // last member: joined (destroyed) before anything its thread reads goes away
@@ -1045,62 +1422,22 @@ struct ProofRun {
   // ---- permutation::Argument::commit (permutation/prover.rs:47-198): Lagrange values of every z ----------
   int permutation_commit() {
     if (!S) return CQ_OK;
-    auto column_values = [&](const std::pair<uint32_t, uint32_t>& col) -> const Fr* {
-      return col.first == CQ_COL_ADVICE ? B.adv + (size_t)col.second * n
-           : col.first == CQ_COL_FIXED  ? pk->fixed_values + (size_t)col.second * n
-                                        : B.inst_lag + (size_t)col.second * n;
-    };
-    const Fr delta = fr_from_raw(FR_DELTA_RAW);
-    std::vector<PermProductArgs> pa(S);
-    Fr deltaomega = Fr::one();  // delta^(column position), :86-87,146
-    for (size_t st = 0; st < S; st++) {
-      PermProductArgs& a = pa[st];
-      a.count = (uint32_t)std::min(chunk_len, PC - st * chunk_len);
-      a.beta = beta;
-      a.gamma = gamma;
-      a.omega_powers = pk->omega_powers;
-      for (uint32_t j = 0; j < a.count; j++) {
-        const size_t ci = st * chunk_len + j;
-        a.col[j] = column_values(pk->perm_columns[ci]);
-        a.sigma[j] = pk->perm_values + ci * n;
-        a.delta_beta[j] = deltaomega * beta;
-        deltaomega = deltaomega * delta;
-      }
-      CQ_TRY(perm_denominators(c, a, (uint32_t)n, B.mv + st * n));  // :106-121
+    std::vector<const Fr*> cols(PC);
+    for (size_t ci = 0; ci < PC; ci++) {
+      const auto& col = pk->perm_columns[ci];
+      cols[ci] = col.first == CQ_COL_ADVICE ? B.adv + (size_t)col.second * n
+               : col.first == CQ_COL_FIXED  ? pk->fixed_values + (size_t)col.second * n
+                                            : B.inst_lag + (size_t)col.second * n;
     }
-    CQ_TRY(poly_batch_invert(c, B.mv, (uint32_t)(S * n)));  // :124
-    for (size_t st = 0; st < S; st++) CQ_TRY(perm_numerators(c, pa[st], (uint32_t)n, B.mv + st * n));  // :128-147
-    // z[0] = last_z, z[row] = z[row-1] * mv[row-1] (:160-166): a multiplicative scan per set, then the
-    // chain last_z = z[n - (bf+1)] of the previous set (:173) as one scalar per set
-    CQ_TRY(prefix_product(c, B.mv, B.z, (uint32_t)n, (uint32_t)S));
-    std::vector<Fr> at_u(S);
-    for (size_t st = 0; st < S; st++)
-      CQ_HIP(c, hipMemcpyAsync(&at_u[st], B.z + st * n + u, sizeof(Fr), hipMemcpyDeviceToHost, s));
-    CQ_TRY(c->wait(s));
-    PermScaleArgs sa;
-    Fr last_z = Fr::one();
-    for (size_t st = 0; st < S; st++) {
-      sa.mult[st] = last_z;
-      last_z = last_z * at_u[st];
-    }
-    CQ_TRY(perm_scale(c, B.z, (uint32_t)n, u + 1, (uint32_t)S, sa));
-    // blinding rows (:169-171)
-    for (size_t st = 0; st < S; st++)
-      CQ_HIP(c, hipMemcpyAsync(B.z + st * n + (n - bf), z_tails.data() + st * bf, bf * sizeof(Fr), hipMemcpyHostToDevice, s));
-    return CQ_OK;
+    return perm_products(pk, cols.data(), beta, gamma, z_tails.data(), B.mv, B.z);
   }
 
   // ---- legacy lookups: commit_product (lookup/prover.rs:163-300): z = running product of
   //      (A + beta)(S + gamma) / ((a' + beta)(s' + gamma)), rows n-bf.. random ---------------------------------------
   int legacy_commit_product() {
-    for (size_t l = 0; l < PL; l++) CQ_TRY(lookup_denominators(c, plk_buf(l, 2), plk_buf(l, 3), beta, gamma, (uint32_t)n, plk_buf(l, 4)));
-    for (size_t l = 0; l < PL; l++) {
-      // the product vectors are not contiguous across lookups (stride 5n): one inversion launch each
-      CQ_TRY(poly_batch_invert(c, plk_buf(l, 4), (uint32_t)n));
-      CQ_TRY(lookup_numerators(c, plk_buf(l, 0), plk_buf(l, 1), beta, gamma, (uint32_t)n, plk_buf(l, 4)));
-      CQ_TRY(prefix_product(c, plk_buf(l, 4), plk_buf(l, 4), (uint32_t)n, 1));
-      CQ_HIP(c, hipMemcpyAsync(plk_buf(l, 4) + (n - bf), plkz_tails.data() + l * bf, bf * sizeof(Fr), hipMemcpyHostToDevice, s));
-    }
+    for (size_t l = 0; l < PL; l++)
+      CQ_TRY(lookup_product(c, plk_buf(l, 0), plk_buf(l, 1), plk_buf(l, 2), plk_buf(l, 3), beta, gamma, plkz_tails.data() + l * bf, (uint32_t)n, bf,
+                            plk_buf(l, 4)));
     return CQ_OK;
   }
 
@@ -1307,88 +1644,20 @@ struct ProofRun {
       // advice / instance cosets (:317-335), permutation product cosets (permutation/prover.rs:182)
       if (I && !(L || PL)) CQ_TRY(coeff_to_extended_cols(B.inst_coeff, B.inst_cosets, I));  // no round 1
       if (S) CQ_TRY(coeff_to_extended_cols(B.z, B.z_cosets, S));
-      const uint32_t rot_scale = 1u << (dom->extended_k - dom->k);
-      if (pk->num_gate_polys) {  // custom gates (:348-365)
-        GateEvalArgs ga;
-        ga.prog = pk->gate_prog;
-        ga.num_polys = pk->num_gate_polys;
-        ga.constants = pk->constants;
-        ga.challenges = B.challenges;
-        ga.advice = B.adv_cosets;
-        ga.fixed = pk->fixed_cosets;
-        ga.instance = B.inst_cosets;
-        ga.stride = ext;
-        ga.size = (uint32_t)ext;
-        ga.rot_scale = rot_scale;
-        ga.y = y;
-        CQ_TRY(gate_eval(c, ga, B.h_ext));
-      } else {
-        CQ_HIP(c, hipMemsetAsync(B.h_ext, 0, ext * sizeof(Fr), s));
-      }
-      if (S) {  // permutation constraints (:367-459)
-        PermHArgs ph;
-        ph.z = B.z_cosets;
-        ph.sigma = pk->perm_cosets;
-        for (size_t ci = 0; ci < PC; ci++) {
-          const auto& col = pk->perm_columns[ci];
-          ph.col[ci] = col.first == CQ_COL_ADVICE ? B.adv_cosets + (size_t)col.second * ext
-                     : col.first == CQ_COL_FIXED  ? pk->fixed_cosets + (size_t)col.second * ext
-                                                  : B.inst_cosets + (size_t)col.second * ext;
-        }
-        ph.sets = (uint32_t)S;
-        ph.chunk_len = (uint32_t)chunk_len;
-        ph.ncols = (uint32_t)PC;
-        ph.l0 = pk->l0;
-        ph.l_last = pk->l_last;
-        ph.l_active = pk->l_active_row;
-        ph.beta = beta;
-        ph.gamma = gamma;
-        ph.y = y;
-        ph.delta_start = beta * dom->g_coset;  // beta * ZETA (:375)
-        ph.ext_pow_lo = pk->ext_pow_lo;
-        ph.ext_pow_hi = pk->ext_pow_hi;
-        ph.delta = fr_from_raw(FR_DELTA_RAW);
-        ph.ext = (uint32_t)ext;
-        ph.rot_scale = rot_scale;
-        ph.last_rot = bf + 1;
-        CQ_TRY(perm_h_terms(c, ph, B.h_ext));
-      }
-    }
-    for (size_t l = 0; l < PL; l++) {  // legacy lookup constraints (:461-531)
-      const auto& lk = pk->legacy[l];
-      Fr* co = B.plk_cosets + l * 5 * ext;  // a', s', z cosets, then the compressed input / table on the coset
-      CQ_TRY(domain_coeff_to_extended(dom, plk_buf(l, 2), co, 3, n, ext));
-      const uint32_t rot_scale = 1u << (dom->extended_k - dom->k);
-      for (int side = 0; side < 2; side++) {
-        GateEvalArgs ga;
-        ga.prog = pk->legacy_prog + (side ? lk.tab_off : lk.in_off);
-        ga.num_polys = lk.width;
-        ga.constants = pk->constants;
-        ga.challenges = B.challenges;
-        ga.advice = B.adv_cosets;
-        ga.fixed = pk->fixed_cosets;
-        ga.instance = B.inst_cosets;
-        ga.stride = ext;
-        ga.size = (uint32_t)ext;
-        ga.rot_scale = rot_scale;
-        ga.y = theta;
-        CQ_TRY(gate_eval(c, ga, co + (3 + side) * ext));
-      }
-      LookupHArgs la;
-      la.a = co;
-      la.s = co + ext;
-      la.z = co + 2 * ext;
-      la.cin = co + 3 * ext;
-      la.ctab = co + 4 * ext;
-      la.l0 = pk->l0;
-      la.l_last = pk->l_last;
-      la.l_active = pk->l_active_row;
-      la.beta = beta;
-      la.gamma = gamma;
-      la.y = y;
-      la.ext = (uint32_t)ext;
-      la.rot_scale = rot_scale;
-      CQ_TRY(lookup_h_terms(c, la, B.h_ext));
+      std::vector<const Fr*> plk_polys(PL);
+      for (size_t l = 0; l < PL; l++) plk_polys[l] = plk_buf(l, 2);
+      HTermsArgs ht;
+      ht.adv_cosets = B.adv_cosets;
+      ht.inst_cosets = B.inst_cosets;
+      ht.z_cosets = B.z_cosets;
+      ht.challenges = B.challenges;
+      ht.plk_polys = plk_polys.data();
+      ht.plk_cosets = B.plk_cosets;
+      ht.beta = beta;
+      ht.gamma = gamma;
+      ht.theta = theta;
+      ht.y = y;
+      CQ_TRY(h_terms(pk, ht, B.h_ext));  // gates, permutation, legacy lookups (:348-531)
     }
     // CQ terms (:533-548), then the division by X^n - 1 (vanishing/prover.rs:84, domain.rs:319-338)
     CqQuotientArgs qa;
@@ -1485,8 +1754,11 @@ struct ProofRun {
     }
     const size_t q_random = add_query(B.random_poly, n, 0);
     // distinct points in first-seen order (gwc.rs:36-61)
-    for (auto& q : qs)
+    for (auto& q : qs) {
       if (std::find(rots.begin(), rots.end(), q.rot) == rots.end()) rots.push_back(q.rot);
+      q.pt = (uint32_t)(std::find(rots.begin(), rots.end(), q.rot) - rots.begin());
+    }
+    for (int32_t rot : rots) points.push_back(point_of(rot));
     // resident: who holds what -- an advice polynomial on the owner of its column, b_0 / f of a lookup on its owner (whole
     // polynomials, evaluated there), the h pieces and the random polynomial on every rank by point range (each rank
     // evaluates its range and multiplies by x^lo).  qowner[i] = owning rank, or -1 for "by point range".
@@ -1546,248 +1818,99 @@ struct ProofRun {
     return CQ_OK;
   }
 
-  // ---- multiopen, SHPLONK (shplonk/prover.rs:120-286): two commitments whatever the number of points ---------
-  int open_shplonk() {
-    Fr* sh_h = B.shplonk;           // h(X) = sum_i xn^i h_i as one polynomial (vanishing/prover.rs:131-135)
-    Fr* sh_div[2] = {B.shplonk + n, B.shplonk + 2 * n};
-    Fr* sh_hx = B.shplonk + 3 * n;
-    Fr* sh_lx = B.shplonk + 4 * n;
-    Fr* sh_rem = B.shplonk + 5 * n;  // per rotation set: sum_j y^j r_j (at most 8 coefficients)
-    Fr h_eval = Fr::zero();
-    {
-      std::vector<Term> terms;
-      Fr xp = Fr::one();
-      for (size_t i = 0; i < pieces; i++) {
-        terms.push_back({B.h_coeff + i * n, (uint32_t)n, xp});
-        xp = xp * xn;
-      }
-      CQ_TRY(lincomb_many(c, terms, Fr::zero(), (uint32_t)n, sh_h));
-      for (size_t i = pieces; i-- > 0;) h_eval = h_eval * xn + qs[q_h[i]].eval;
-    }
-    const Fr y_ = tr.squeeze();  // :136
-    // construct_intermediate_sets (shplonk.rs:56-133): commitments by polynomial identity, grouped by point set
-    struct Com { const Fr* p; uint32_t len; std::vector<int32_t> rots; std::vector<Fr> evals; };
-    std::vector<Com> coms;
-    for (auto& q : qs) {
-      const Fr* key = q.h_piece >= 0 ? sh_h : q.p;
-      if (q.h_piece > 0) continue;
-      const Fr ev = q.h_piece == 0 ? h_eval : q.eval;
-      auto it = std::find_if(coms.begin(), coms.end(), [&](const Com& cm) { return cm.p == key; });
-      if (it == coms.end()) {
-        coms.push_back({key, q.h_piece == 0 ? (uint32_t)n : q.len, {q.rot}, {ev}});
-      } else if (std::find(it->rots.begin(), it->rots.end(), q.rot) == it->rots.end()) {
-        it->rots.push_back(q.rot);
-        it->evals.push_back(ev);
-      }
-    }
-    struct RotSet { std::vector<int32_t> rots; std::vector<size_t> members; };
-    std::vector<RotSet> sets;
-    auto same_set = [](const std::vector<int32_t>& a, const std::vector<int32_t>& b) {
-      return a.size() == b.size() && std::all_of(a.begin(), a.end(), [&](int32_t r) { return std::find(b.begin(), b.end(), r) != b.end(); });
+  // ---- multiopen over the proof's queries: ProverGWC (gwc/prover.rs:42-91) or ProverSHPLONK (shplonk/prover.rs:120-286)
+  OpenJob open_job() {
+    OpenJob j;
+    j.pk = pk;
+    j.qs = &qs;
+    j.points = &points;
+    j.q_h = &q_h;
+    j.xn = xn;
+    j.gwc_batch = B.gwc_batch;
+    j.gwc_wit = B.gwc_wit;
+    j.shplonk = B.shplonk;
+    j.tr.squeeze = [this](Fr& out) {
+      out = tr.squeeze();
+      return (int)CQ_OK;
     };
-    for (size_t ci = 0; ci < coms.size(); ci++) {
-      auto it = std::find_if(sets.begin(), sets.end(), [&](const RotSet& rs) { return same_set(rs.rots, coms[ci].rots); });
-      if (it == sets.end()) sets.push_back({coms[ci].rots, {ci}});
-      else it->members.push_back(ci);
-    }
-    if (sets.size() > 64) return c->fail(CQ_ERR_ARG, "too many rotation sets");
-    const Fr v_ = tr.squeeze();  // :196
-    // per set: low-degree equivalents r_j and the y-combined remainder (CommitmentExtension, :36-76)
-    std::vector<std::vector<Fr>> set_points(sets.size());
-    std::vector<std::vector<std::vector<Fr>>> low(sets.size());
-    std::vector<Fr> rem_host(sets.size() * 8, Fr::zero());
-    for (size_t si = 0; si < sets.size(); si++) {
-      for (int32_t r : sets[si].rots) set_points[si].push_back(point_of(r));
-      if (set_points[si].size() > 8) return c->fail(CQ_ERR_ARG, "rotation set too large");
-      Fr py = Fr::one();
-      for (size_t ci : sets[si].members) {
-        // the commitment's evaluations, aligned with the set's point order
-        std::vector<Fr> evals;
-        for (int32_t r : sets[si].rots) {
-          const size_t pos = std::find(coms[ci].rots.begin(), coms[ci].rots.end(), r) - coms[ci].rots.begin();
-          evals.push_back(coms[ci].evals[pos]);
-        }
-        low[si].push_back(lagrange_interpolate(set_points[si], evals));
-        for (size_t i = 0; i < low[si].back().size(); i++) rem_host[si * 8 + i] = rem_host[si * 8 + i] + py * low[si].back()[i];
-        py = py * y_;
-      }
-    }
-    CQ_HIP(c, hipMemcpyAsync(sh_rem, rem_host.data(), rem_host.size() * sizeof(Fr), hipMemcpyHostToDevice, s));
-    // h_x = sum_i v^i * (sum_j y^j (p_j - r_j)) / prod_{pt in set_i} (X - pt)   (quotient_contribution, :138-168)
-    Fr pv = Fr::one();
-    for (size_t si = 0; si < sets.size(); si++) {
-      std::vector<Term> terms;
-      Fr py = Fr::one();
-      for (size_t ci : sets[si].members) {
-        terms.push_back({coms[ci].p, coms[ci].len, py});
-        py = py * y_;
-      }
-      terms.push_back({sh_rem + si * 8, (uint32_t)set_points[si].size(), Fr::zero() - Fr::one()});
-      CQ_TRY(lincomb_many(c, terms, Fr::zero(), (uint32_t)n, sh_div[0]));
-      uint32_t len = (uint32_t)n;
-      int cur = 0;
-      for (const Fr& pt : set_points[si]) {  // div_by_vanishing (:28-34)
-        CQ_TRY(poly_kate_division(c, sh_div[cur], len, pt, sh_div[cur ^ 1]));
-        cur ^= 1;
-        len--;
-      }
-      std::vector<Term> acc;
-      if (si) acc.push_back({sh_hx, (uint32_t)n, Fr::one()});
-      acc.push_back({sh_div[cur], len, pv});
-      CQ_TRY(lincomb_many(c, acc, Fr::zero(), (uint32_t)n, sh_hx));
-      pv = pv * v_;
-    }
-    {
-      std::vector<const Fr*> sc{sh_hx};
-      std::vector<const G1Affine*> bs{pk->params->g};
-      std::vector<G1Affine> o;
-      CQ_TRY(commit_batch(pk, sc, bs, n, o));  // :204
-      if (!tr.write_point(o[0])) return c->fail(CQ_ERR_TRANSCRIPT, "shplonk quotient commitment is the identity");
-    }
-    const Fr u_ = tr.squeeze();  // :206
-    // l_x = sum_i v^i z_i sum_j y^j (p_j - r_j(u)) - Z_T(u) h_x, then / (X - u) and / z_0   (:208-283); the
-    // scaling by 1/z_0 is folded into the coefficients (the division is linear)
-    std::vector<Fr> all_points;
-    for (int32_t r : rots) all_points.push_back(point_of(r));  // super_point_set: every distinct point
-    auto vanish = [&](const std::vector<Fr>& roots) {
-      Fr acc = Fr::one();
-      for (auto& r : roots) acc = (u_ - r) * acc;
-      return acc;
-    };
-    std::vector<Fr> z_diff(sets.size());
-    for (size_t si = 0; si < sets.size(); si++) {
-      std::vector<Fr> diffs;
-      for (size_t pi = 0; pi < rots.size(); pi++)
-        if (std::find(sets[si].rots.begin(), sets[si].rots.end(), rots[pi]) == sets[si].rots.end()) diffs.push_back(all_points[pi]);
-      z_diff[si] = vanish(diffs);
-    }
-    const Fr z0_inv = z_diff[0].inv();
-    const Fr zt_eval = vanish(all_points);
-    std::vector<Term> terms;
-    Fr sub = Fr::zero();
-    pv = Fr::one();
-    for (size_t si = 0; si < sets.size(); si++) {
-      const Fr scale = pv * z_diff[si] * z0_inv;
-      Fr py = Fr::one();
-      for (size_t j = 0; j < sets[si].members.size(); j++) {
-        const Com& cm = coms[sets[si].members[j]];
-        terms.push_back({cm.p, cm.len, scale * py});
-        sub = sub + scale * py * eval_small(low[si][j], u_);
-        py = py * y_;
-      }
-      pv = pv * v_;
-    }
-    terms.push_back({sh_hx, (uint32_t)n, Fr::zero() - zt_eval * z0_inv});
-    CQ_TRY(lincomb_many(c, terms, sub, (uint32_t)n, sh_lx));
-    CQ_TRY(poly_kate_division(c, sh_lx, (uint32_t)n, u_, sh_div[0]));  // :257
-    std::vector<const Fr*> sc{sh_div[0]};
-    std::vector<const G1Affine*> bs{pk->params->g};
-    std::vector<G1Affine> o;
-    CQ_TRY(commit_batch(pk, sc, bs, n - 1, o));  // :270
-    if (!tr.write_point(o[0])) return c->fail(CQ_ERR_TRANSCRIPT, "shplonk opening commitment is the identity");
-    return CQ_OK;
+    j.tr.write_point = [this](const G1Affine& p, const char* what) { return tr.write_point(p) ? (int)CQ_OK : c->fail(CQ_ERR_TRANSCRIPT, what); };
+    return j;
   }
-
-  // ---- multiopen, GWC (gwc/prover.rs:42-91): one witness polynomial per distinct point ---------------------
+  int open_shplonk() {
+    OpenJob j = open_job();
+    return open_shplonk_queries(j);
+  }
   int open_gwc() {
-    const Fr v = tr.squeeze();
-    // h(X) = sum_i xn^i h_i (vanishing/prover.rs:131-135); its value follows from the piece evaluations
-    Fr h_eval = Fr::zero();
-    for (size_t i = pieces; i-- > 0;) h_eval = h_eval * xn + qs[q_h[i]].eval;
-    std::vector<const Fr*> sc;
-    for (size_t g = 0; g < rots.size(); g++) {
-      std::vector<Term> terms;
-      Fr pv = Fr::one(), eval_batch = Fr::zero(), xp = Fr::one();
-      for (auto& q : qs) {
-        if (q.rot != rots[g]) continue;
-        if (q.h_piece >= 0) {  // the pieces of h share one power of v
-          terms.push_back({q.p, q.len, pv * xp});
-          xp = xp * xn;
-          if ((size_t)q.h_piece + 1 < pieces) continue;
-          eval_batch = eval_batch + h_eval * pv;
-        } else {
-          terms.push_back({q.p, q.len, pv});
-          eval_batch = eval_batch + q.eval * pv;
-        }
-        pv = pv * v;
-      }
-      Fr* batch = B.gwc_batch + g * n;
-      Fr* wit = B.gwc_wit + g * n;
-      if (resident) {
-        // resident: poly_batch = sum_j v^j p_j is assembled where the p_j live -- whole polynomials on their owner, the
-        // by-range ones on each rank's range -- as a partial sum P_r over all n coefficients; rank r then collects the
-        // slice of every P_q that its share of the witness polynomial needs and adds them up.  kate_division
-        // (q_i = a_(i+1) + z q_(i+1)) runs per range: the carry into a range from above is the Horner value of the
-        // slices above it, S_q = sum_t slice_q[t] z^t, exchanged as one field element per rank.
-        const Fr z = point_of(rots[g]);
-        std::vector<Term> whole, ranged;
-        size_t ti = 0;
-        for (size_t i = 0; i < qs.size(); i++) {
-          if (qs[i].rot != rots[g]) continue;
-          const Term& t = terms[ti++];
-          if (qowner[i] < 0) ranged.push_back({t.p + my_lo, (uint32_t)(my_hi - my_lo), t.coeff});
-          else if (qowner[i] == (int)me) whole.push_back(t);
-        }
-        if (whole.empty()) CQ_HIP(c, hipMemsetAsync(batch, 0, n * sizeof(Fr), s));
-        else CQ_TRY(lincomb_many(c, whole, Fr::zero(), (uint32_t)n, batch));
-        if (my_hi > my_lo) {  // the by-range terms on this rank's range; "- eval_batch" touches coefficient 0 only
-          std::vector<Term> tt{{batch + my_lo, (uint32_t)(my_hi - my_lo), Fr::one()}};
-          tt.insert(tt.end(), ranged.begin(), ranged.end());
-          CQ_TRY(lincomb_many(c, tt, my_lo == 0 ? eval_batch : Fr::zero(), (uint32_t)(my_hi - my_lo), batch + my_lo));
-        }
-        // rank r commits witness coefficients [wlo, whi) (its point range of the n - 1 term MSM) and needs a[wlo+1 .. whi]
-        const size_t slice_max = res_slice_max;
-        Fr* const stage = (Fr*)res_stage_v;
-        std::vector<Xfer> xf;
-        for (uint32_t q = 0; q < SW; q++)
-          for (uint32_t r = 0; r < SW; r++) {
-            size_t wlo, whi;
-            shard_range(n - 1, r, SW, wlo, whi);
-            if (whi > wlo) xf.push_back({batch + 1 + wlo, stage + (size_t)q * slice_max, (whi - wlo) * sizeof(Fr), q, r});
-          }
-        CQ_TRY(shard_exchange(pk, xf.data(), xf.size(), s));
-        size_t wlo, whi;
-        shard_range(n - 1, me, SW, wlo, whi);
-        const size_t len = whi - wlo;
-        // [0] unused, [1 .. len] the summed slice, [len + 1] the carry -- behind the received slices in the staging area
-        Fr* a_loc = stage + (size_t)SW * slice_max + 8;
-        if ((size_t)SW * slice_max + 8 + len + 2 > res_stage_elems) return c->fail(CQ_ERR_INTERNAL, "resident sharding: staging too small");
-        Fr slice_eval = Fr::zero();
-        if (len) {
-          std::vector<Term> tt;
-          for (uint32_t q = 0; q < SW; q++) tt.push_back({stage + (size_t)q * slice_max, (uint32_t)len, Fr::one()});
-          CQ_TRY(lincomb_many(c, tt, Fr::zero(), (uint32_t)len, a_loc + 1));
-          const Fr* pp = a_loc + 1;
-          const uint32_t ll = (uint32_t)len;
-          CQ_TRY(poly_eval_batch(c, &pp, &ll, 1, z, &slice_eval));
-        }
-        std::vector<Fr> all_s(SW);
-        CQ_TRY(shard_allgather_host(pk, &slice_eval, all_s.data(), sizeof(Fr)));
-        Fr carry = Fr::zero();  // q_(whi) = S_(r+1) + z^len_(r+1) (S_(r+2) + ...)
-        for (uint32_t q = SW; q-- > me + 1;) {
-          size_t qlo, qhi;
-          shard_range(n - 1, q, SW, qlo, qhi);
-          carry = all_s[q] + z.pow_u64(qhi - qlo) * carry;
-        }
-        if (len) {
-          Fr edge[2] = {Fr::zero(), carry};
-          CQ_HIP(c, hipMemcpyAsync(a_loc, &edge[0], sizeof(Fr), hipMemcpyHostToDevice, s));
-          CQ_HIP(c, hipMemcpyAsync(a_loc + len + 1, &edge[1], sizeof(Fr), hipMemcpyHostToDevice, s));
-          CQ_TRY(c->wait(s));  // `edge` is on this frame
-          CQ_TRY(poly_kate_division(c, a_loc, (uint32_t)(len + 2), z, wit + wlo));  // wit[wlo .. whi) (and the carry at [whi])
-        }
-        sc.push_back(wit);
-        continue;
-      }
-      CQ_TRY(lincomb_many(c, terms, eval_batch, (uint32_t)n, batch));  // poly_batch - eval_batch (gwc/prover.rs:62-78)
-      CQ_TRY(poly_kate_division(c, batch, (uint32_t)n, point_of(rots[g]), wit));  // :80
-      sc.push_back(wit);
+    OpenJob j = open_job();
+    if (resident)
+      j.witness = [this](size_t g, const std::vector<Term>& terms, const Fr& eval_batch, Fr* batch, Fr* wit) {
+        return resident_witness(g, terms, eval_batch, batch, wit);
+      };
+    return open_gwc_queries(j);
+  }
+  // resident: poly_batch = sum_j v^j p_j is assembled where the p_j live -- whole polynomials on their owner, the
+  // by-range ones on each rank's range -- as a partial sum P_r over all n coefficients; rank r then collects the
+  // slice of every P_q that its share of the witness polynomial needs and adds them up.  kate_division
+  // (q_i = a_(i+1) + z q_(i+1)) runs per range: the carry into a range from above is the Horner value of the
+  // slices above it, S_q = sum_t slice_q[t] z^t, exchanged as one field element per rank.
+  int resident_witness(size_t g, const std::vector<Term>& terms, const Fr& eval_batch, Fr* batch, Fr* wit) {
+    const Fr z = points[g];
+    std::vector<Term> whole, ranged;
+    size_t ti = 0;
+    for (size_t i = 0; i < qs.size(); i++) {
+      if (qs[i].pt != g) continue;
+      const Term& t = terms[ti++];
+      if (qowner[i] < 0) ranged.push_back({t.p + my_lo, (uint32_t)(my_hi - my_lo), t.coeff});
+      else if (qowner[i] == (int)me) whole.push_back(t);
     }
-    std::vector<const G1Affine*> bs(sc.size(), pk->params->g);
-    std::vector<G1Affine> o;
-    CQ_TRY(commit_batch(pk, sc, bs, n - 1, o));  // :85
-    for (auto& w : o)
-      if (!tr.write_point(w)) return c->fail(CQ_ERR_TRANSCRIPT, "opening witness commitment is the identity");
+    if (whole.empty()) CQ_HIP(c, hipMemsetAsync(batch, 0, n * sizeof(Fr), s));
+    else CQ_TRY(lincomb_many(c, whole, Fr::zero(), (uint32_t)n, batch));
+    if (my_hi > my_lo) {  // the by-range terms on this rank's range; "- eval_batch" touches coefficient 0 only
+      std::vector<Term> tt{{batch + my_lo, (uint32_t)(my_hi - my_lo), Fr::one()}};
+      tt.insert(tt.end(), ranged.begin(), ranged.end());
+      CQ_TRY(lincomb_many(c, tt, my_lo == 0 ? eval_batch : Fr::zero(), (uint32_t)(my_hi - my_lo), batch + my_lo));
+    }
+    // rank r commits witness coefficients [wlo, whi) (its point range of the n - 1 term MSM) and needs a[wlo+1 .. whi]
+    const size_t slice_max = res_slice_max;
+    Fr* const stage = (Fr*)res_stage_v;
+    std::vector<Xfer> xf;
+    for (uint32_t q = 0; q < SW; q++)
+      for (uint32_t r = 0; r < SW; r++) {
+        size_t wlo, whi;
+        shard_range(n - 1, r, SW, wlo, whi);
+        if (whi > wlo) xf.push_back({batch + 1 + wlo, stage + (size_t)q * slice_max, (whi - wlo) * sizeof(Fr), q, r});
+      }
+    CQ_TRY(shard_exchange(pk, xf.data(), xf.size(), s));
+    size_t wlo, whi;
+    shard_range(n - 1, me, SW, wlo, whi);
+    const size_t len = whi - wlo;
+    // [0] unused, [1 .. len] the summed slice, [len + 1] the carry -- behind the received slices in the staging area
+    Fr* a_loc = stage + (size_t)SW * slice_max + 8;
+    if ((size_t)SW * slice_max + 8 + len + 2 > res_stage_elems) return c->fail(CQ_ERR_INTERNAL, "resident sharding: staging too small");
+    Fr slice_eval = Fr::zero();
+    if (len) {
+      std::vector<Term> tt;
+      for (uint32_t q = 0; q < SW; q++) tt.push_back({stage + (size_t)q * slice_max, (uint32_t)len, Fr::one()});
+      CQ_TRY(lincomb_many(c, tt, Fr::zero(), (uint32_t)len, a_loc + 1));
+      const Fr* pp = a_loc + 1;
+      const uint32_t ll = (uint32_t)len;
+      CQ_TRY(poly_eval_batch(c, &pp, &ll, 1, z, &slice_eval));
+    }
+    std::vector<Fr> all_s(SW);
+    CQ_TRY(shard_allgather_host(pk, &slice_eval, all_s.data(), sizeof(Fr)));
+    Fr carry = Fr::zero();  // q_(whi) = S_(r+1) + z^len_(r+1) (S_(r+2) + ...)
+    for (uint32_t q = SW; q-- > me + 1;) {
+      size_t qlo, qhi;
+      shard_range(n - 1, q, SW, qlo, qhi);
+      carry = all_s[q] + z.pow_u64(qhi - qlo) * carry;
+    }
+    if (len) {
+      Fr edge[2] = {Fr::zero(), carry};
+      CQ_HIP(c, hipMemcpyAsync(a_loc, &edge[0], sizeof(Fr), hipMemcpyHostToDevice, s));
+      CQ_HIP(c, hipMemcpyAsync(a_loc + len + 1, &edge[1], sizeof(Fr), hipMemcpyHostToDevice, s));
+      CQ_TRY(c->wait(s));  // `edge` is on this frame
+      CQ_TRY(poly_kate_division(c, a_loc, (uint32_t)(len + 2), z, wit + wlo));  // wit[wlo .. whi) (and the carry at [whi])
+    }
     return CQ_OK;
   }
 };
@@ -1843,6 +1966,189 @@ int create_proof_dev(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_
   }
   proof_out.swap(tr.proof);
   return CQ_OK;
+}
+
+// ---- the same stages for a caller that keeps its own create_proof (capi_rounds.hip checks the arguments) ------------------
+namespace {
+
+// `count` scalars as Fr::random draws them, through the caller's bulk hook when the key has one
+void draw_scalars(Rng& rng, Fr* out, size_t count) {
+  std::vector<uint64_t> w(8 * count);
+  rng.fill(w.data(), w.size());
+  for (size_t i = 0; i < count; i++) out[i] = Fr::from_u512(w.data() + 8 * i);
+}
+
+void affine_to_limbs(const G1Affine& p, uint64_t* out) {
+  p.x.to_limbs64(out);
+  p.y.to_limbs64(out + 4);
+}
+
+// commit_lagrange of `count` vectors of n values, one behind the other, as affine points on the host; then each in
+// coefficient form in place (waits for the stream: what the caller reads next is there)
+int commit_then_coeff(cq_pk* pk, Fr* z, size_t count, uint64_t* commitments) {
+  const size_t n = (size_t)1 << pk->k;
+  std::vector<const Fr*> sc(count);
+  std::vector<const G1Affine*> bs(count, pk->params->g_lagrange);
+  for (size_t i = 0; i < count; i++) sc[i] = z + i * n;
+  std::vector<G1Affine> o;
+  CQ_TRY(commit_batch(pk, sc, bs, n, o));
+  for (size_t i = 0; i < count; i++) affine_to_limbs(o[i], commitments + 8 * i);
+  CQ_TRY(domain_lagrange_to_coeff(pk->domain, z, z, (uint32_t)count, n, n));
+  return pk->ctx->wait(pk->ctx->stream);
+}
+
+}  // namespace
+
+int stage_permutation_commit(cq_pk* pk, const uint64_t* const* advice_dev, const uint64_t* const* instance_dev, const Fr& beta,
+                             const Fr& gamma, cq_rng_next_u64 rng_next, void* rng_state, Fr* z, uint64_t* commitments) {
+  cq_ctx* c = pk->ctx;
+  const size_t n = (size_t)1 << pk->k, S = pk->perm_sets(), PC = pk->perm_columns.size();
+  const uint32_t bf = pk->bf;
+  std::vector<const Fr*> cols(PC);
+  for (size_t ci = 0; ci < PC; ci++) {
+    const auto& col = pk->perm_columns[ci];
+    cols[ci] = col.first == CQ_COL_ADVICE ? (const Fr*)advice_dev[col.second]
+             : col.first == CQ_COL_FIXED  ? pk->fixed_values + (size_t)col.second * n
+                                          : (const Fr*)instance_dev[col.second];
+    if (!cols[ci]) return c->fail(CQ_ERR_ARG, "permutation_commit: a permutation column is NULL");
+  }
+  void* mv;
+  CQ_TRY(c->ensure_scratch(Scratch::ProverStage, S * n * sizeof(Fr), &mv));
+  // per set: bf blinding rows, then the blind (permutation/prover.rs:169-175)
+  Rng rng{rng_next, rng_state, pk->rng_fill, &c->pool()};
+  std::vector<Fr> tails(S * bf), drawn(bf + 1);
+  for (size_t st = 0; st < S; st++) {
+    draw_scalars(rng, drawn.data(), bf + 1);
+    std::copy(drawn.begin(), drawn.begin() + bf, tails.begin() + st * bf);
+  }
+  CQ_TRY(perm_products(pk, cols.data(), beta, gamma, tails.data(), (Fr*)mv, z));
+  return commit_then_coeff(pk, z, S, commitments);  // :177-179
+}
+
+int stage_lookup_commit_product(cq_pk* pk, const uint64_t* const* input_dev, const uint64_t* const* table_dev,
+                                const uint64_t* const* permuted_input_dev, const uint64_t* const* permuted_table_dev, const Fr& beta,
+                                const Fr& gamma, cq_rng_next_u64 rng_next, void* rng_state, Fr* z, uint64_t* commitments) {
+  cq_ctx* c = pk->ctx;
+  const size_t n = (size_t)1 << pk->k, PL = pk->legacy.size();
+  const uint32_t bf = pk->bf;
+  Rng rng{rng_next, rng_state, pk->rng_fill, &c->pool()};
+  std::vector<Fr> tails(PL * bf), drawn(bf + 1);
+  for (size_t l = 0; l < PL; l++) {  // per lookup: bf blinding rows, then the blind
+    draw_scalars(rng, drawn.data(), bf + 1);
+    std::copy(drawn.begin(), drawn.begin() + bf, tails.begin() + l * bf);
+  }
+  for (size_t l = 0; l < PL; l++)
+    CQ_TRY(lookup_product(c, (const Fr*)input_dev[l], (const Fr*)table_dev[l], (const Fr*)permuted_input_dev[l], (const Fr*)permuted_table_dev[l],
+                          beta, gamma, tails.data() + l * bf, (uint32_t)n, bf, z + l * n));
+  return commit_then_coeff(pk, z, PL, commitments);
+}
+
+int stage_evaluate_h(cq_pk* pk, const uint64_t* const* advice_coeff_dev, const uint64_t* const* instance_coeff_dev, const Fr* perm_z,
+                     const uint64_t* const* permuted_input_coeff_dev, const uint64_t* const* permuted_table_coeff_dev, const Fr* lookup_z,
+                     const uint64_t* challenges, const Fr& beta, const Fr& gamma, const Fr& theta, const Fr& y, Fr* h_out) {
+  cq_ctx* c = pk->ctx;
+  cq_domain* dom = pk->domain;
+  const hipStream_t s = c->stream;
+  const size_t n = (size_t)1 << pk->k, ext = dom->ext(), A = pk->num_advice, I = pk->num_instance, S = pk->perm_sets();
+  const size_t PL = pk->legacy.size(), NC = pk->challenge_phase.size();
+  if (!pk->general()) {  // nothing to fold: the static lookups are cq_quotient_dev's
+    CQ_HIP(c, hipMemsetAsync(h_out, 0, ext * sizeof(Fr), s));
+    return CQ_OK;
+  }
+  void* scr;
+  CQ_TRY(c->ensure_scratch(Scratch::ProverStage, ((A + I + S + 5 * PL) * ext + 3 * PL * n + NC + 8) * sizeof(Fr), &scr));
+  Fr* adv_cosets = (Fr*)scr;
+  Fr* inst_cosets = adv_cosets + A * ext;
+  Fr* z_cosets = inst_cosets + I * ext;
+  Fr* plk_cosets = z_cosets + S * ext;
+  Fr* plk = plk_cosets + 5 * PL * ext;  // per legacy lookup: a', s', z side by side (one batched transform)
+  Fr* chal = plk + 3 * PL * n;
+  for (size_t a = 0; a < A; a++) CQ_TRY(domain_coeff_to_extended(dom, (const Fr*)advice_coeff_dev[a], adv_cosets + a * ext, 1, n, ext));
+  for (size_t i = 0; i < I; i++) CQ_TRY(domain_coeff_to_extended(dom, (const Fr*)instance_coeff_dev[i], inst_cosets + i * ext, 1, n, ext));
+  if (S) CQ_TRY(domain_coeff_to_extended(dom, perm_z, z_cosets, (uint32_t)S, n, ext));
+  std::vector<const Fr*> plk_polys(PL);
+  for (size_t l = 0; l < PL; l++) {
+    Fr* p3 = plk + 3 * l * n;
+    CQ_HIP(c, hipMemcpyAsync(p3, permuted_input_coeff_dev[l], n * sizeof(Fr), hipMemcpyDeviceToDevice, s));
+    CQ_HIP(c, hipMemcpyAsync(p3 + n, permuted_table_coeff_dev[l], n * sizeof(Fr), hipMemcpyDeviceToDevice, s));
+    CQ_HIP(c, hipMemcpyAsync(p3 + 2 * n, lookup_z + l * n, n * sizeof(Fr), hipMemcpyDeviceToDevice, s));
+    plk_polys[l] = p3;
+  }
+  if (NC) {
+    std::vector<Fr> ch(NC);
+    for (size_t i = 0; i < NC; i++) ch[i] = Fr::from_limbs64(challenges + 4 * i);
+    CQ_HIP(c, hipMemcpyAsync(chal, ch.data(), NC * sizeof(Fr), hipMemcpyHostToDevice, s));
+    CQ_TRY(c->wait(s));  // `ch` is on this frame
+  }
+  HTermsArgs ht;
+  ht.adv_cosets = adv_cosets;
+  ht.inst_cosets = inst_cosets;
+  ht.z_cosets = z_cosets;
+  ht.challenges = chal;
+  ht.plk_polys = plk_polys.data();
+  ht.plk_cosets = plk_cosets;
+  ht.beta = beta;
+  ht.gamma = gamma;
+  ht.theta = theta;
+  ht.y = y;
+  return h_terms(pk, ht, h_out);
+}
+
+int stage_multiopen(cq_pk* pk, const cq_open_query* queries, size_t count, const cq_open_transcript* transcript) {
+  cq_ctx* c = pk->ctx;
+  const size_t n = (size_t)1 << pk->k;
+  const bool shplonk = pk->opener == CQ_OPENER_SHPLONK;
+  // distinct points by value, first-seen order (gwc.rs:36-61, shplonk.rs:56-133)
+  std::vector<Query> qs(count);
+  std::vector<Fr> points;
+  for (size_t i = 0; i < count; i++) {
+    const Fr pt = Fr::from_limbs64(queries[i].point);
+    size_t g = 0;
+    while (g < points.size() && !(points[g] - pt).is_zero()) g++;
+    if (g == points.size()) points.push_back(pt);
+    qs[i] = {(const Fr*)queries[i].poly_dev, (uint32_t)queries[i].len, 0, -1, Fr::zero(), (uint32_t)g};
+  }
+  void* scr;
+  CQ_TRY(c->ensure_scratch(Scratch::ProverStage, (shplonk ? 5 * n + 64 * 8 : 2 * points.size() * n) * sizeof(Fr), &scr));
+  // the evaluations (plonk/prover.rs:654-719 computes them before the opener is called): chunked Horner, per point
+  for (size_t g = 0; g < points.size(); g++) {
+    std::vector<const Fr*> ps;
+    std::vector<uint32_t> ls;
+    std::vector<size_t> idx;
+    for (size_t i = 0; i < count; i++)
+      if (qs[i].pt == g) {
+        ps.push_back(qs[i].p);
+        ls.push_back(qs[i].len);
+        idx.push_back(i);
+      }
+    std::vector<Fr> ev(ps.size());
+    CQ_TRY(eval_many(c, ps, ls, points[g], ev.data()));
+    for (size_t m = 0; m < idx.size(); m++) qs[idx[m]].eval = ev[m];
+  }
+  const std::vector<size_t> no_pieces;
+  OpenJob j;
+  j.pk = pk;
+  j.qs = &qs;
+  j.points = &points;
+  j.q_h = &no_pieces;
+  j.xn = Fr::one();
+  j.gwc_batch = (Fr*)scr;
+  j.gwc_wit = (Fr*)scr + points.size() * n;
+  j.shplonk = (Fr*)scr;
+  j.tr.squeeze = [&](Fr& out) {
+    uint64_t limbs[4];
+    if (transcript->squeeze_challenge(transcript->user, limbs) != 0) return c->fail(CQ_ERR_ARG, "multiopen: the squeeze_challenge callback failed");
+    out = Fr::from_limbs64(limbs);
+    return (int)CQ_OK;
+  };
+  j.tr.write_point = [&](const G1Affine& p, const char* what) {
+    if (p.is_identity()) return c->fail(CQ_ERR_TRANSCRIPT, what);  // transcript.rs:221-233
+    uint64_t limbs[8];
+    affine_to_limbs(p, limbs);
+    if (transcript->write_point(transcript->user, limbs) != 0) return c->fail(CQ_ERR_ARG, "multiopen: the write_point callback failed");
+    return (int)CQ_OK;
+  };
+  return shplonk ? open_shplonk_queries(j) : open_gwc_queries(j);
 }
 
 }  // namespace cq
