@@ -1,4 +1,5 @@
-// C ABI: CQ table objects, proving key, create_proof, SHA witness fill, harness RNGs.
+// C ABI: CQ table objects, create_proof and the proving-key accessors around it, SHA witness fill and tables, harness RNGs.
+// (The proving key itself is built, serialized and destroyed in pk.hip.)
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -7,6 +8,7 @@
 #include <thread>
 #include <vector>
 #include "assigned_host.hpp"
+#include "building.hpp"
 #include "cq.hpp"
 #include "xoshiro.hpp"
 #include "ctx.hpp"
@@ -28,124 +30,79 @@ static uint32_t log2u(size_t x) {
   return l;
 }
 
-// Owns a half-built object (and plain device allocations) until release(): every early return -- CQ_HIP included --
-// destroys it, so a failing constructor leaks nothing and never hands back a live handle next to an error code.
-namespace {
-template <class T>
-struct Building {
-  T* p;
-  void (*destroy)(T*);
-  std::vector<void*> dev;       // temporaries, hipFree'd on every path
-  std::vector<const void*> reg; // temporary MSM window tables, unregistered on every path
-  cq_ctx* c = nullptr;
-  cq_domain* dom = nullptr;
-  Building(T* p_, void (*d)(T*), cq_ctx* c_) : p(p_), destroy(d), c(c_) {}
-  ~Building() {
-    if (c) hipStreamSynchronize(c->stream);
-    for (const void* r : reg) msm_unregister_tables(c, r);
-    for (void* d : dev) hipFree(d);
-    if (dom) domain_destroy(dom);
-    if (p) destroy(p);
-  }
-  T* release() {
-    T* q = p;
-    p = nullptr;
-    return q;
-  }
-};
-}  // namespace
-
 extern "C" {
 
 // ---- StaticTableConfig ---------------------------------------------------------------------------
-int cq_table_config_create(cq_ctx* c, size_t size, const uint64_t* g1_lagrange, const uint64_t* opening_at_0,
-                           cq_table_config** out) {
-  if (!c || !g1_lagrange || !opening_at_0 || !out || !is_pow2(size) || size > (1u << 28)) return CQ_ERR_ARG;
-  CQ_HIP(c, hipSetDevice(c->device));
+// Shared by the constructors: the object `t` (already under its Building guard) gets its two arrays ...
+static int table_config_alloc(cq_ctx* c, size_t size, cq_table_config* t, cq_table_config** out) {
   *out = nullptr;
-  cq_table_config* t = new cq_table_config();
-  Building<cq_table_config> guard(t, cq_table_config_destroy, c);
   t->ctx = c;
   t->N = size;
   t->log_n = log2u(size);
+  CQ_HIP(c, hipSetDevice(c->device));
+  int rc = c->dev_alloc(&t->g1_lagrange, size, "table config");
+  return rc != CQ_OK ? rc : c->dev_alloc(&t->g_lagrange_opening_at_0, size, "table config");
+}
+// ... and, once they are filled, their window tables
+static int table_config_finish(Building<cq_table_config>& guard, cq_table_config** out) {
+  cq_ctx* c = guard.c;
+  int rc;
+  if (c->msm_precompute && ((rc = msm_register_tables(c, guard.p->g1_lagrange, guard.p->N)) != CQ_OK ||
+                            (rc = msm_register_tables(c, guard.p->g_lagrange_opening_at_0, guard.p->N)) != CQ_OK))
+    return rc;
+  return guard.finish(out);
+}
+
+int cq_table_config_create(cq_ctx* c, size_t size, const uint64_t* g1_lagrange, const uint64_t* opening_at_0,
+                           cq_table_config** out) {
+  if (!c || !g1_lagrange || !opening_at_0 || !out || !is_pow2(size) || size > (1u << 28)) return CQ_ERR_ARG;
+  Building<cq_table_config> guard(new cq_table_config(), cq_table_config_destroy, c);
+  cq_table_config* t = guard.p;
+  int rc = table_config_alloc(c, size, t, out);
+  if (rc != CQ_OK) return rc;
   const size_t bytes = size * sizeof(G1Affine);
-  if (hipMalloc(&t->g1_lagrange, bytes) != hipSuccess || hipMalloc(&t->g_lagrange_opening_at_0, bytes) != hipSuccess)
-    return c->fail(CQ_ERR_HIP, "hipMalloc(table config)");
   CQ_HIP(c, hipMemcpyAsync(t->g1_lagrange, g1_lagrange, bytes, hipMemcpyHostToDevice, c->stream));
   CQ_HIP(c, hipMemcpyAsync(t->g_lagrange_opening_at_0, opening_at_0, bytes, hipMemcpyHostToDevice, c->stream));
   CQ_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->msm_precompute) {
-    int rc2;
-    if ((rc2 = msm_register_tables(c, t->g1_lagrange, size)) != CQ_OK) return rc2;
-    if ((rc2 = msm_register_tables(c, t->g_lagrange_opening_at_0, size)) != CQ_OK) return rc2;
-  }
-  *out = guard.release();
-  return CQ_OK;
+  return table_config_finish(guard, out);
 }
 
 int cq_table_config_setup_from_toxic_waste(cq_ctx* c, size_t size, const uint64_t s[4], cq_table_config** out) {
   if (!c || !s || !out || !is_pow2(size) || size > (1u << 28)) return CQ_ERR_ARG;
-  CQ_HIP(c, hipSetDevice(c->device));
-  *out = nullptr;
-  cq_table_config* t = new cq_table_config();
-  Building<cq_table_config> guard(t, cq_table_config_destroy, c);
-  t->ctx = c;
-  t->N = size;
-  t->log_n = log2u(size);
-  const size_t bytes = size * sizeof(G1Affine);
-  if (hipMalloc(&t->g1_lagrange, bytes) != hipSuccess || hipMalloc(&t->g_lagrange_opening_at_0, bytes) != hipSuccess)
-    return c->fail(CQ_ERR_HIP, "hipMalloc(table config)");
+  Building<cq_table_config> guard(new cq_table_config(), cq_table_config_destroy, c);
+  cq_table_config* t = guard.p;
+  int rc = table_config_alloc(c, size, t, out);
+  if (rc != CQ_OK) return rc;
   void* tmp;
-  int rc;
   if ((rc = c->ensure_scratch(Scratch::EntryA, 2 * size * sizeof(Fr), &tmp)) != CQ_OK) return rc;
   Fr* lag_sc = (Fr*)tmp;
   Fr* tmp_sc = lag_sc + size;
   const Fr sf = Fr::from_limbs64(s);
   if ((rc = srs_powers_and_lagrange(c, t->log_n, sf, nullptr, t->g1_lagrange, tmp_sc, lag_sc)) != CQ_OK) return rc;
   if ((rc = srs_opening_at_zero(c, t->log_n, sf, lag_sc, tmp_sc, t->g_lagrange_opening_at_0)) != CQ_OK) return rc;
-  if (c->msm_precompute) {
-    if ((rc = msm_register_tables(c, t->g1_lagrange, size)) != CQ_OK) return rc;
-    if ((rc = msm_register_tables(c, t->g_lagrange_opening_at_0, size)) != CQ_OK) return rc;
-  }
-  CQ_HIP(c, hipStreamSynchronize(c->stream));
-  *out = guard.release();
-  return CQ_OK;
+  return table_config_finish(guard, out);
 }
 
 // StaticTableConfig from the powers: both arrays are inverse G1 FFTs of them (kzg/commitment.rs:125-170)
 int cq_table_config_from_srs(cq_ctx* c, size_t size, const uint64_t* srs_g1, size_t srs_len, int on_device, cq_table_config** out) {
   if (!c || !srs_g1 || !out || !is_pow2(size) || size > (1u << 28) || srs_len < size) return CQ_ERR_ARG;
-  CQ_HIP(c, hipSetDevice(c->device));
-  *out = nullptr;
-  cq_table_config* t = new cq_table_config();
-  Building<cq_table_config> guard(t, cq_table_config_destroy, c);
-  t->ctx = c;
-  t->N = size;
-  t->log_n = log2u(size);
-  const size_t bytes = size * sizeof(G1Affine);
-  if (hipMalloc(&t->g1_lagrange, bytes) != hipSuccess || hipMalloc(&t->g_lagrange_opening_at_0, bytes) != hipSuccess)
-    return c->fail(CQ_ERR_HIP, "hipMalloc(table config)");
+  Building<cq_table_config> guard(new cq_table_config(), cq_table_config_destroy, c);
+  cq_table_config* t = guard.p;
+  int rc = table_config_alloc(c, size, t, out);
+  if (rc != CQ_OK) return rc;
   const G1Affine* srs = (const G1Affine*)srs_g1;
   if (!on_device) {
     G1Affine* up = nullptr;
-    if (hipMalloc(&up, bytes) != hipSuccess) return c->fail(CQ_ERR_HIP, "hipMalloc(table config srs)");
-    guard.dev.push_back(up);
-    CQ_HIP(c, hipMemcpyAsync(up, srs_g1, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = guard.temp(&up, size, "table config srs")) != CQ_OK) return rc;
+    CQ_HIP(c, hipMemcpyAsync(up, srs_g1, size * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
     srs = up;
   }
-  int rc;
   // [L_i(s)] = (1/N) sum_j w^(-ij) [s^j]
   if ((rc = g1_to_lagrange(c, srs, t->log_n, t->g1_lagrange, true)) != CQ_OK) return rc;
   // [(L_i(s) - L_i(0)) / s]: L_i(X) = (1/N) sum_m w^(-im) X^m and L_i(0) = 1/N, so the quotient is
   // (1/N) sum_(m>=1) w^(-im) X^(m-1) -- power j = m - 1 < N - 1 sits at place j + 1 of the transform's input
   if ((rc = g1_to_lagrange_shifted(c, srs, (uint32_t)(size - 1), 1, t->log_n, t->g_lagrange_opening_at_0, true)) != CQ_OK) return rc;
-  if (c->msm_precompute) {
-    if ((rc = msm_register_tables(c, t->g1_lagrange, size)) != CQ_OK) return rc;
-    if ((rc = msm_register_tables(c, t->g_lagrange_opening_at_0, size)) != CQ_OK) return rc;
-  }
-  CQ_HIP(c, hipStreamSynchronize(c->stream));
-  *out = guard.release();
-  return CQ_OK;
+  return table_config_finish(guard, out);
 }
 
 void cq_table_config_destroy(cq_table_config* t) {
@@ -173,38 +130,34 @@ int cq_table_config_download(cq_table_config* t, uint64_t* g1_lagrange, uint64_t
 }
 
 // ---- StaticTableValues -----------------------------------------------------------------------------
-// fills a fresh object the caller already guards (Building): nothing to undo here on failure
-static int table_alloc(cq_ctx* c, size_t size, const uint64_t* values, cq_static_table* t) {
+// Shared by the constructors, after their argument check: the object `t` (already under its Building guard) gets its arrays,
+// the values and their index; nothing to undo here on failure
+static int table_alloc(cq_ctx* c, size_t size, const uint64_t* values, cq_static_table* t, cq_static_table** out) {
+  *out = nullptr;
   t->ctx = c;
   t->N = size;
-  if (hipMalloc(&t->values, size * sizeof(Fr)) != hipSuccess || hipMalloc(&t->qs, size * sizeof(G1Affine)) != hipSuccess)
-    return c->fail(CQ_ERR_HIP, "hipMalloc(static table)");
+  CQ_HIP(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = c->dev_alloc(&t->values, size, "static table")) != CQ_OK || (rc = c->dev_alloc(&t->qs, size, "static table")) != CQ_OK) return rc;
   CQ_HIP(c, hipMemcpyAsync(t->values, values, size * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
   return cq_table_build_index(c, t->values, (uint32_t)size, &t->slots, &t->nslots);
 }
-
 int cq_static_table_create(cq_ctx* c, size_t size, const uint64_t* values, const uint64_t* qs_affine, cq_static_table** out) {
   if (!c || !values || !qs_affine || !out || !is_pow2(size) || size > (1u << 28)) return CQ_ERR_ARG;  // static_lookup.rs:80
-  CQ_HIP(c, hipSetDevice(c->device));
-  *out = nullptr;
-  cq_static_table* t = new cq_static_table();
-  Building<cq_static_table> guard(t, cq_static_table_destroy, c);
-  int rc = table_alloc(c, size, values, t);
+  Building<cq_static_table> guard(new cq_static_table(), cq_static_table_destroy, c);
+  cq_static_table* t = guard.p;
+  int rc = table_alloc(c, size, values, t, out);
   if (rc != CQ_OK) return rc;
   CQ_HIP(c, hipMemcpyAsync(t->qs, qs_affine, size * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
-  CQ_HIP(c, hipStreamSynchronize(c->stream));
-  *out = guard.release();
-  return CQ_OK;
+  return guard.finish(out);
 }
 
 int cq_static_table_setup_from_toxic_waste(cq_ctx* c, size_t size, const uint64_t* values, const uint64_t s[4],
                                            cq_static_table** out) {
   if (!c || !values || !s || !out || !is_pow2(size) || size > (1u << 28)) return CQ_ERR_ARG;
-  CQ_HIP(c, hipSetDevice(c->device));
-  *out = nullptr;
-  cq_static_table* t = new cq_static_table();
-  Building<cq_static_table> guard(t, cq_static_table_destroy, c);
-  int rc = table_alloc(c, size, values, t);
+  Building<cq_static_table> guard(new cq_static_table(), cq_static_table_destroy, c);
+  cq_static_table* t = guard.p;
+  int rc = table_alloc(c, size, values, t, out);
   if (rc != CQ_OK) return rc;
   // T(s): interpolate the values over the size-N domain, evaluate at s
   if ((rc = domain_create(c, 2, log2u(size), &guard.dom)) != CQ_OK) return rc;
@@ -219,9 +172,7 @@ int cq_static_table_setup_from_toxic_waste(cq_ctx* c, size_t size, const uint64_
   if ((rc = poly_eval(c, coeffs, (uint32_t)size, sf, &ts)) != CQ_OK) return rc;
   if ((rc = cq_qs_scalars(c, t->values, (uint32_t)size, ts, sf, dom->omega, dom->ifft_divisor, sc)) != CQ_OK) return rc;
   if ((rc = fixed_base_mul(c, sc, (uint32_t)size, t->qs)) != CQ_OK) return rc;
-  CQ_HIP(c, hipStreamSynchronize(c->stream));
-  *out = guard.release();
-  return CQ_OK;
+  return guard.finish(out);
 }
 
 void cq_static_table_destroy(cq_static_table* t) {
@@ -241,584 +192,7 @@ int cq_static_table_download_qs(cq_static_table* t, uint64_t* qs_affine) {
   return CQ_OK;
 }
 
-// ---- proving key -------------------------------------------------------------------------------------
-// `rc` is passed through
-static int pk_abort(cq_pk*, int rc) { return rc; }  // the Building guard of pk_create_impl destroys the key
-
-// Cursor over a ProvingKey::write byte stream (plonk.rs:349-362): big-endian u32 counts, raw 32-byte elements
-namespace {
-struct RawReader {
-  const uint8_t* p = nullptr;
-  size_t left = 0;
-  bool ok = true;
-  uint32_t be32() {
-    if (left < 4) { ok = false; return 0; }
-    const uint32_t v = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-    p += 4;
-    left -= 4;
-    return v;
-  }
-  const uint8_t* take(size_t bytes) {
-    if (left < bytes) { ok = false; return nullptr; }
-    const uint8_t* q = p;
-    p += bytes;
-    left -= bytes;
-    return q;
-  }
-};
-void put_be32(uint8_t*& o, uint32_t v) {
-  o[0] = (uint8_t)(v >> 24); o[1] = (uint8_t)(v >> 16); o[2] = (uint8_t)(v >> 8); o[3] = (uint8_t)v;
-  o += 4;
-}
-// unit vector at `row` on the extended coset (l0 / l_last, keygen.rs:340-363); tmp: n elements of scratch
-int unit_coset(cq_pk* pk, size_t row, Fr* tmp, Fr* dst) {
-  cq_ctx* c = pk->ctx;
-  const size_t n = (size_t)1 << pk->k, ext = pk->domain->ext();
-  const Fr one = Fr::one();
-  CQ_HIP(c, hipMemsetAsync(tmp, 0, n * sizeof(Fr), c->stream));
-  CQ_HIP(c, hipMemcpyAsync(tmp + row, &one, sizeof(Fr), hipMemcpyHostToDevice, c->stream));
-  CQ_HIP(c, hipStreamSynchronize(c->stream));
-  int rc;
-  if ((rc = domain_lagrange_to_coeff(pk->domain, tmp, tmp, 1, n, n)) != CQ_OK) return rc;
-  return domain_coeff_to_extended(pk->domain, tmp, dst, 1, n, ext);
-}
-}  // namespace
-
-// Window tables of the arrays a key multiplies over besides its SRS, at the width of the SRS tables (so that all MSMs of
-// a round share one launch): the cached quotients and an own b0 bound are the key's; the table SRS may be shared with
-// keys of other sizes and then carries a table per width (2^12 points: 4 MiB each).  The width follows the length of
-// the point range a rank multiplies: 2^k / world.
-static int pk_small_tables(cq_pk* pk) {
-  cq_ctx* c = pk->ctx;
-  const size_t n = (size_t)1 << pk->k;
-  const uint32_t width = c->msm_table_c ? c->msm_table_c : msm_table_window_bits(n / std::max<uint32_t>(pk->shard_world, 1));
-  if (width == pk->table_c && !pk->held_tables.empty()) return CQ_OK;
-  pk->table_c = width;
-  if (!c->msm_precompute) return CQ_OK;
-  std::vector<cq_pk::TableRef> old;
-  old.swap(pk->held_tables);
-  int rc = CQ_OK;
-  auto want = [&](const G1Affine* b, size_t len) {
-    bool held = false;
-    if (rc == CQ_OK) rc = msm_register_tables(c, b, len, pk->table_c, &held);
-    if (held) pk->held_tables.push_back({b, len, pk->table_c});
-  };
-  const cq_table_config* cfg = pk->table_cfg;
-  for (size_t l = 0; l < pk->qs_concat.size(); l++) want(pk->qs_concat[l], pk->lookups[l].tables.size() * cfg->N);
-  if (cfg && !pk->lookups.empty()) {
-    want(cfg->g1_lagrange, cfg->N);
-    want(cfg->g_lagrange_opening_at_0, cfg->N);
-  }
-  if (pk->b0_g1_bound) want(pk->b0_g1_bound, n - 1);
-  for (auto& t : old) msm_release_table(c, t.bases, t.n, t.c);  // after the new ones: a shared entry is never rebuilt in between
-  return rc;
-}
-
-static int pk_create_impl(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq_table_config* cfg, const uint64_t* b0_g1_bound,
-                          int b0_on_device, const uint8_t* raw, size_t raw_len, uint32_t num_selectors, int checked, bool processed,
-                          cq_pk** out) {
-  if (!c || !params || !cs || !out) return CQ_ERR_ARG;
-  if (cs->num_lookups && (!cfg || !b0_g1_bound)) return c->fail(CQ_ERR_ARG, "pk: static lookups need a table config and b0_g1_bound");
-  if (cs->k != params->k) return c->fail(CQ_ERR_ARG, "pk: circuit k differs from params k");
-  if (cs->num_lookups > CQ_MAX_LOOKUPS) return c->fail(CQ_ERR_ARG, "pk: too many lookups");
-  CQ_HIP(c, hipSetDevice(c->device));
-  const cq_plonk* pl = cs->plonk;
-  *out = nullptr;
-  cq_pk* pk = new cq_pk();
-  Building<cq_pk> guard(pk, cq_pk_destroy, c);  // every failing return below (CQ_HIP included) destroys the key
-  pk->ctx = c;
-  pk->params = params;
-  pk->k = cs->k;
-  pk->num_advice = cs->num_advice;
-  pk->table_cfg = cfg;
-  pk->vk_repr = Fr::from_limbs64(cs->vk_repr);
-  params->key_users++;
-  if (cfg) cfg->key_users++;
-  pk->counted_users = true;
-  const size_t n = (size_t)1 << pk->k;
-  size_t off = 0;
-  for (uint32_t l = 0; l < cs->num_lookups; l++) {
-    cq_lookup_desc d;
-    const uint32_t w = cs->lookup_widths[l];
-    if (w == 0 || w > CQ_MAX_WIDTH) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: lookup width out of range"));
-    for (uint32_t j = 0; j < w; j++) {
-      const uint32_t col = cs->lookup_columns[off + j];
-      cq_static_table* t = cs->lookup_tables[off + j];
-      const bool is_expr = pl && pl->lookup_input_program_lens;
-      if ((!is_expr && col >= cs->num_advice) || !t) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: bad lookup column / table"));
-      // "Tables should all be of the same size" (static_lookup/prover.rs:81-83)
-      if (t->N != cfg->N) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: table size differs from the table config"));
-      d.cols.push_back(col);
-      d.prog.push_back(-1);
-      d.tables.push_back(t);
-      // query_advice_index (plonk/circuit.rs:1619-1633)
-      if (!(pl && pl->num_advice_queries) && !is_expr &&
-          std::find(pk->advice_queries.begin(), pk->advice_queries.end(), std::make_pair(col, (int32_t)0)) == pk->advice_queries.end())
-        pk->advice_queries.push_back({col, 0});
-    }
-    off += w;
-    pk->lookups.push_back(d);
-  }
-  if (pl) {
-    pk->num_fixed = pl->num_fixed;
-    pk->num_instance = pl->num_instance;
-    pk->cs_degree = pl->cs_degree ? pl->cs_degree : 3;
-    if (pk->cs_degree < 3 || pk->cs_degree - 2 > PERM_MAX_CHUNK) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: cs_degree out of range"));
-    if (pl->num_perm_columns > PERM_MAX_COLUMNS) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: too many permutation columns"));
-    if ((pl->num_fixed && !pl->fixed && !raw) || (pl->num_gate_polys && (!pl->gate_program_lens || !pl->gate_programs)) ||
-        (pl->num_constants && !pl->constants) || (pl->num_perm_columns && (!pl->perm_column_kinds || !pl->perm_column_indices)))
-      return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: null pointer in cq_plonk"));
-    for (uint32_t q = 0; q < pl->num_advice_queries; q++) {
-      if (pl->advice_query_columns[q] >= cs->num_advice) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: advice query column out of range"));
-      pk->advice_queries.push_back({pl->advice_query_columns[q], pl->advice_query_rotations[q]});
-    }
-    for (uint32_t q = 0; q < pl->num_fixed_queries; q++) {
-      if (pl->fixed_query_columns[q] >= pl->num_fixed) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: fixed query column out of range"));
-      pk->fixed_queries.push_back({pl->fixed_query_columns[q], pl->fixed_query_rotations[q]});
-    }
-    // phases (circuit.rs advice_column_phase / challenge_phase)
-    pk->advice_phase.assign(cs->num_advice, 0);
-    for (uint32_t a = 0; a < cs->num_advice && pl->advice_column_phases; a++) pk->advice_phase[a] = pl->advice_column_phases[a];
-    if (pl->num_challenges && !pl->challenge_phases) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: null pointer in cq_plonk"));
-    pk->challenge_phase.assign(pl->challenge_phases, pl->challenge_phases + pl->num_challenges);
-    for (uint8_t ph : pk->advice_phase) pk->num_phases = std::max<uint32_t>(pk->num_phases, ph + 1u);
-    for (uint8_t ph : pk->challenge_phase) pk->num_phases = std::max<uint32_t>(pk->num_phases, ph + 1u);
-    if (pk->num_phases > 3) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: the API only supports 3 phases (prover.rs:337)"));
-    for (uint32_t q = 0; q < pl->num_perm_columns; q++) {
-      const uint32_t kind = pl->perm_column_kinds[q], idx = pl->perm_column_indices[q];
-      const uint32_t lim = kind == CQ_COL_ADVICE ? cs->num_advice : kind == CQ_COL_FIXED ? pl->num_fixed : kind == CQ_COL_INSTANCE ? pl->num_instance : 0;
-      if (idx >= lim) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: permutation column out of range"));
-      pk->perm_columns.push_back({kind, idx});
-    }
-  }
-  // ---- expression programs (gates, legacy lookups, static lookup inputs): validated and uploaded ----
-  int rc;
-  if (pl && pl->num_gate_polys) {
-    const char* why = nullptr;
-    size_t words = 0;
-    if (!gate_program_check(pl->gate_program_lens, pl->gate_programs, pl->num_gate_polys, pl->num_constants, cs->num_advice,
-                            pl->num_fixed, pl->num_instance, pl->num_challenges, &why, &words))
-      return pk_abort(pk, c->fail(CQ_ERR_ARG, why));
-    std::vector<uint32_t> blob;
-    size_t o = 0;
-    for (uint32_t g = 0; g < pl->num_gate_polys; g++) {
-      blob.push_back(pl->gate_program_lens[g]);
-      blob.insert(blob.end(), pl->gate_programs + o, pl->gate_programs + o + pl->gate_program_lens[g]);
-      o += pl->gate_program_lens[g];
-    }
-    pk->num_gate_polys = pl->num_gate_polys;
-    if (hipMalloc(&pk->gate_prog, blob.size() * sizeof(uint32_t)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(gate program)"));
-    CQ_HIP(c, hipMemcpy(pk->gate_prog, blob.data(), blob.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  if (pl && pl->num_constants) {
-    if (hipMalloc(&pk->constants, pl->num_constants * sizeof(Fr)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(gate constants)"));
-    CQ_HIP(c, hipMemcpy(pk->constants, pl->constants, pl->num_constants * sizeof(Fr), hipMemcpyHostToDevice));
-  }
-  if (pl && pl->num_legacy_lookups) {
-    if (!pl->legacy_lookup_widths || !pl->legacy_program_lens || !pl->legacy_programs) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: null pointer in cq_plonk"));
-    size_t nprog = 0;
-    for (uint32_t l = 0; l < pl->num_legacy_lookups; l++) {
-      if (pl->legacy_lookup_widths[l] == 0 || pl->legacy_lookup_widths[l] > 64) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: legacy lookup width out of range"));
-      nprog += 2 * (size_t)pl->legacy_lookup_widths[l];
-    }
-    const char* why = nullptr;
-    size_t words = 0;
-    if (!gate_program_check(pl->legacy_program_lens, pl->legacy_programs, (uint32_t)nprog, pl->num_constants, cs->num_advice, pl->num_fixed,
-                            pl->num_instance, pl->num_challenges, &why, &words))
-      return pk_abort(pk, c->fail(CQ_ERR_ARG, why));
-    std::vector<uint32_t> blob;
-    size_t o = 0, idx = 0;
-    for (uint32_t l = 0; l < pl->num_legacy_lookups; l++) {
-      cq_pk::LegacyLookup lk;
-      lk.width = pl->legacy_lookup_widths[l];
-      for (int side = 0; side < 2; side++) {
-        (side ? lk.tab_off : lk.in_off) = blob.size();
-        for (uint32_t j = 0; j < lk.width; j++, idx++) {
-          blob.push_back(pl->legacy_program_lens[idx]);
-          blob.insert(blob.end(), pl->legacy_programs + o, pl->legacy_programs + o + pl->legacy_program_lens[idx]);
-          o += pl->legacy_program_lens[idx];
-        }
-      }
-      pk->legacy.push_back(lk);
-    }
-    if (hipMalloc(&pk->legacy_prog, blob.size() * sizeof(uint32_t)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(legacy lookup programs)"));
-    CQ_HIP(c, hipMemcpy(pk->legacy_prog, blob.data(), blob.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  if (pl && pl->lookup_input_program_lens && off) {
-    // static lookup inputs given as expressions: one single-polynomial program each
-    if (!pl->lookup_input_programs) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: null pointer in cq_plonk"));
-    const char* why = nullptr;
-    size_t words = 0;
-    if (!gate_program_check(pl->lookup_input_program_lens, pl->lookup_input_programs, (uint32_t)off, pl->num_constants,
-                            cs->num_advice, pl->num_fixed, pl->num_instance, pl->num_challenges, &why, &words))
-      return pk_abort(pk, c->fail(CQ_ERR_ARG, why));
-    std::vector<uint32_t> blob;
-    size_t o = 0, idx = 0;
-    for (auto& lk : pk->lookups)
-      for (size_t j = 0; j < lk.cols.size(); j++, idx++) {
-        lk.prog[j] = (int64_t)blob.size();
-        blob.push_back(pl->lookup_input_program_lens[idx]);
-        blob.insert(blob.end(), pl->lookup_input_programs + o, pl->lookup_input_programs + o + pl->lookup_input_program_lens[idx]);
-        o += pl->lookup_input_program_lens[idx];
-      }
-    pk->lookup_exprs = true;
-    if (hipMalloc(&pk->lookup_prog, blob.size() * sizeof(uint32_t)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(lookup programs)"));
-    CQ_HIP(c, hipMemcpy(pk->lookup_prog, blob.data(), blob.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  // blinding_factors (plonk/circuit.rs:2022-2047)
-  if (pl && pl->blinding_factors) {
-    pk->bf = pl->blinding_factors;
-  } else {
-    std::vector<uint32_t> per_col(cs->num_advice, 0);
-    for (auto& q : pk->advice_queries) per_col[q.first]++;
-    uint32_t factors = 1;
-    for (uint32_t v : per_col) factors = std::max(factors, v);
-    pk->bf = std::max(3u, factors) + 2;
-  }
-  if (n < (size_t)pk->bf + 3)  // minimum_rows (circuit.rs:2051-2059)
-    return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: not enough rows available"));
-  pk->u = (uint32_t)(n - (pk->bf + 1));
-  // extended domain for cs.degree(): 3 for permutation / static lookups (static_lookup.rs:181-190), more with gates
-  if ((rc = domain_create(c, pk->cs_degree, pk->k, &pk->domain)) != CQ_OK) return pk_abort(pk, rc);
-  const size_t ext = pk->domain->ext();
-  // SerdeFormat::Processed: verdict words of the device conversions, [0] the commitments, [1 + j] polynomial j of the stream
-  const size_t cells = 4 + 3 * ((size_t)pk->num_fixed + pk->perm_columns.size());
-  void* tmp;
-  if ((rc = c->ensure_scratch(Scratch::EntryA, std::max(n * sizeof(Fr), 2 * cells * sizeof(uint32_t)), &tmp)) != CQ_OK) return pk_abort(pk, rc);
-  // The cells live in `tmp` from the reset below to the read-back after the last section.  That holds because nothing in
-  // between asks for a larger EntryA (growing a scratch buffer frees it): the raw paths use `tmp` for nothing else, the
-  // sections stage through EntryB, and the checked-raw branch, which takes EntryA for its flag, excludes the Processed one.
-  uint32_t* count_dev = (uint32_t*)tmp;
-  uint32_t* first_dev = count_dev + cells;
-  if (raw && processed && (rc = serde_verdict_reset(c, count_dev, first_dev, cells)) != CQ_OK) return pk_abort(pk, rc);
-  size_t poly_index = 0;
-  // l_active_row = 1 - (l_last + l_blind) on the extended coset (keygen.rs:344-373); by linearity it is
-  // the coset extension of the indicator of the usable rows
-  if (hipMalloc(&pk->l_active_row, ext * sizeof(Fr)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(l_active_row)"));
-  // ---- ProvingKey::read (plonk.rs:379-403): with a serialized key the polynomial data below is uploaded straight
-  // into HBM instead of being recomputed.  The VerifyingKey part (k, fixed / permutation commitments, selector
-  // bits; :92-113) is skipped: the prover only needs its shape, which the circuit description gives.
-  RawReader rd;
-  std::vector<std::pair<Fr*, size_t>> to_check;  // uploaded vectors to validate under SerdeFormat::RawBytes
-  auto read_poly = [&](Fr* dst, size_t expect) -> int {
-    const uint32_t len = rd.be32();
-    const uint8_t* src = rd.take((size_t)len * sizeof(Fr));
-    if (!rd.ok || len != expect) return c->fail(CQ_ERR_ARG, "pk: serialized polynomial has the wrong length");
-    const size_t j = poly_index++;
-    if (dst) {
-      CQ_HIP(c, hipMemcpyAsync(dst, src, (size_t)len * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
-      if (processed)  // canonical scalars: converted where they landed (helpers.rs:68-79)
-        return fr_from_repr(c, (const uint8_t*)dst, len, dst, count_dev + 1 + j, first_dev + 1 + j);
-      to_check.push_back({dst, len});
-    } else if (processed && len) {  // a section the prover does not keep (l0 / l_last of a CQ-only key): validated in scratch
-      void* stage;
-      int r2 = c->ensure_scratch(Scratch::EntryB, (size_t)len * sizeof(Fr), &stage);
-      if (r2 != CQ_OK) return r2;
-      CQ_HIP(c, hipMemcpyAsync(stage, src, (size_t)len * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
-      return fr_from_repr(c, (const uint8_t*)stage, len, (Fr*)stage, count_dev + 1 + j, first_dev + 1 + j);
-    }
-    return CQ_OK;
-  };
-  auto read_slice = [&](Fr* dst, size_t count, size_t each) -> int {
-    if (rd.be32() != count || !rd.ok) return c->fail(CQ_ERR_ARG, "pk: serialized key has a different number of polynomials");
-    for (size_t i = 0; i < count; i++) {
-      int r2 = read_poly(dst ? dst + i * each : nullptr, each);
-      if (r2 != CQ_OK) return r2;
-    }
-    return CQ_OK;
-  };
-  if (raw) {
-    rd.p = raw;
-    rd.left = raw_len;
-    const uint32_t rk = rd.be32(), nfix = rd.be32();
-    const size_t nperm = pk->perm_columns.size();
-    const size_t ncm = (size_t)nfix + nperm, cm_bytes = ncm * (processed ? 32 : sizeof(G1Affine));
-    const uint8_t* cm = rd.take(cm_bytes);
-    rd.take((size_t)num_selectors * ((n + 7) / 8));
-    if (!rd.ok || rk != pk->k || nfix != pk->num_fixed) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: serialized key does not match the circuit"));
-    if (processed && ncm) {  // compressed commitments: decompressed to validate them (`C::read`, plonk.rs:120-127), then dropped
-      void* stage;
-      if ((rc = c->ensure_scratch(Scratch::EntryB, cm_bytes + ncm * sizeof(G1Affine), &stage)) != CQ_OK) return pk_abort(pk, rc);
-      CQ_HIP(c, hipMemcpyAsync(stage, cm, cm_bytes, hipMemcpyHostToDevice, c->stream));
-      if ((rc = g1_decompress(c, (const uint8_t*)stage, (uint32_t)ncm, (G1Affine*)((uint8_t*)stage + cm_bytes), count_dev, first_dev)) != CQ_OK)
-        return pk_abort(pk, rc);
-    }
-  }
-  if (raw) {
-    // l0, l_last, l_active_row (keygen.rs:338-373) come first; a CQ-only prover reads only the last
-    for (int which = 0; which < 2; which++) {
-      Fr** dst = which ? &pk->l_last : &pk->l0;
-      if (pk->general() && hipMalloc(dst, ext * sizeof(Fr)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(l0/l_last)"));
-      if ((rc = read_poly(pk->general() ? *dst : nullptr, ext)) != CQ_OK) return pk_abort(pk, rc);
-    }
-    if ((rc = read_poly(pk->l_active_row, ext)) != CQ_OK) return pk_abort(pk, rc);
-  } else {
-    if ((rc = poly_fill_usable_rows(c, (Fr*)tmp, (uint32_t)n, pk->u)) != CQ_OK) return pk_abort(pk, rc);
-    if ((rc = domain_lagrange_to_coeff(pk->domain, (Fr*)tmp, (Fr*)tmp, 1, n, n)) != CQ_OK) return pk_abort(pk, rc);
-    if ((rc = domain_coeff_to_extended(pk->domain, (Fr*)tmp, pk->l_active_row, 1, n, ext)) != CQ_OK) return pk_abort(pk, rc);
-    if (pk->general()) {
-      // l0 (keygen.rs:340-345) and l_last (:357-363): unit vectors at rows 0 and n - bf - 1
-      for (int which = 0; which < 2; which++) {
-        Fr** dst = which ? &pk->l_last : &pk->l0;
-        if (hipMalloc(dst, ext * sizeof(Fr)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(l0/l_last)"));
-        if ((rc = unit_coset(pk, which ? n - pk->bf - 1 : 0, (Fr*)tmp, *dst)) != CQ_OK) return pk_abort(pk, rc);
-      }
-    }
-  }
-  if (pk->num_fixed) {
-    const size_t F = pk->num_fixed;
-    if (hipMalloc(&pk->fixed_values, F * n * sizeof(Fr)) != hipSuccess || hipMalloc(&pk->fixed_polys, F * n * sizeof(Fr)) != hipSuccess ||
-        hipMalloc(&pk->fixed_cosets, F * ext * sizeof(Fr)) != hipSuccess)
-      return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(fixed columns)"));
-    if (raw) {
-      if ((rc = read_slice(pk->fixed_values, F, n)) != CQ_OK || (rc = read_slice(pk->fixed_polys, F, n)) != CQ_OK ||
-          (rc = read_slice(pk->fixed_cosets, F, ext)) != CQ_OK)
-        return pk_abort(pk, rc);
-    } else {
-      for (size_t f = 0; f < F; f++)
-        CQ_HIP(c, hipMemcpyAsync(pk->fixed_values + f * n, pl->fixed[f], n * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
-      if ((rc = domain_lagrange_to_coeff(pk->domain, pk->fixed_values, pk->fixed_polys, (uint32_t)F, n, n)) != CQ_OK) return pk_abort(pk, rc);
-      if ((rc = domain_coeff_to_extended(pk->domain, pk->fixed_polys, pk->fixed_cosets, (uint32_t)F, n, ext)) != CQ_OK) return pk_abort(pk, rc);
-    }
-  } else if (raw) {
-    if ((rc = read_slice(nullptr, 0, n)) != CQ_OK || (rc = read_slice(nullptr, 0, n)) != CQ_OK || (rc = read_slice(nullptr, 0, ext)) != CQ_OK)
-      return pk_abort(pk, rc);
-  }
-  if (!pk->perm_columns.empty()) {
-    // permutation::keygen::Assembly::build_pk (permutation/keygen.rs:151-208)
-    const size_t PC = pk->perm_columns.size();
-    if (hipMalloc(&pk->omega_powers, n * sizeof(Fr)) != hipSuccess || hipMalloc(&pk->perm_values, PC * n * sizeof(Fr)) != hipSuccess ||
-        hipMalloc(&pk->perm_polys, PC * n * sizeof(Fr)) != hipSuccess || hipMalloc(&pk->perm_cosets, PC * ext * sizeof(Fr)) != hipSuccess)
-      return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(permutation key)"));
-    if ((rc = fr_powers(c, pk->domain->omega, (uint32_t)n, pk->omega_powers)) != CQ_OK) return pk_abort(pk, rc);
-    {
-      const size_t hi = std::max<size_t>(ext / 256, 1);
-      if (hipMalloc(&pk->ext_pow_lo, 256 * sizeof(Fr)) != hipSuccess || hipMalloc(&pk->ext_pow_hi, hi * sizeof(Fr)) != hipSuccess)
-        return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(extended omega powers)"));
-      if ((rc = fr_powers(c, pk->domain->extended_omega, 256, pk->ext_pow_lo)) != CQ_OK ||
-          (rc = fr_powers(c, pk->domain->extended_omega.pow_u64(256), (uint32_t)hi, pk->ext_pow_hi)) != CQ_OK)
-        return pk_abort(pk, rc);
-    }
-    if (raw) {  // permutation::ProvingKey::read (permutation.rs:124-134)
-      if ((rc = read_slice(pk->perm_values, PC, n)) != CQ_OK || (rc = read_slice(pk->perm_polys, PC, n)) != CQ_OK ||
-          (rc = read_slice(pk->perm_cosets, PC, ext)) != CQ_OK)
-        return pk_abort(pk, rc);
-    } else {
-    std::vector<uint32_t> ident;
-    const uint32_t* mapping = pl->perm_mapping;
-    if (!mapping) {
-      ident.resize(PC * n * 2);
-      for (size_t col = 0; col < PC; col++)
-        for (size_t r = 0; r < n; r++) {
-          ident[(col * n + r) * 2] = (uint32_t)col;
-          ident[(col * n + r) * 2 + 1] = (uint32_t)r;
-        }
-      mapping = ident.data();
-    } else {
-      for (size_t cell = 0; cell < PC * n; cell++)
-        if (mapping[2 * cell] >= PC || mapping[2 * cell + 1] >= n) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: permutation mapping out of range"));
-    }
-    std::vector<Fr> dp(PC);
-    const Fr delta = fr_from_raw(FR_DELTA_RAW);
-    Fr cur = Fr::one();
-    for (size_t col = 0; col < PC; col++) {
-      dp[col] = cur;
-      cur = cur * delta;
-    }
-    void* stage;
-    if ((rc = c->ensure_scratch(Scratch::EntryB, PC * n * 2 * sizeof(uint32_t) + PC * sizeof(Fr), &stage)) != CQ_OK) return pk_abort(pk, rc);
-    Fr* dp_dev = (Fr*)stage;
-    uint32_t* map_dev = (uint32_t*)(dp_dev + PC);
-    CQ_HIP(c, hipMemcpy(dp_dev, dp.data(), PC * sizeof(Fr), hipMemcpyHostToDevice));
-    CQ_HIP(c, hipMemcpy(map_dev, mapping, PC * n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if ((rc = perm_sigma(c, map_dev, (uint32_t)PC, (uint32_t)n, pk->omega_powers, dp_dev, pk->perm_values)) != CQ_OK) return pk_abort(pk, rc);
-    if ((rc = domain_lagrange_to_coeff(pk->domain, pk->perm_values, pk->perm_polys, (uint32_t)PC, n, n)) != CQ_OK) return pk_abort(pk, rc);
-    if ((rc = domain_coeff_to_extended(pk->domain, pk->perm_polys, pk->perm_cosets, (uint32_t)PC, n, ext)) != CQ_OK) return pk_abort(pk, rc);
-    }
-  } else if (raw) {
-    if ((rc = read_slice(nullptr, 0, n)) != CQ_OK || (rc = read_slice(nullptr, 0, n)) != CQ_OK || (rc = read_slice(nullptr, 0, ext)) != CQ_OK)
-      return pk_abort(pk, rc);
-  }
-  if (raw && rd.left != 0) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: trailing bytes after the serialized key"));
-  if (raw && processed) {  // SerdeFormat::Processed: the verdicts of the conversions above
-    std::vector<uint32_t> verdict(2 * cells);
-    CQ_HIP(c, hipMemcpyAsync(verdict.data(), count_dev, 2 * cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    CQ_HIP(c, hipStreamSynchronize(c->stream));
-    if (verdict[0])
-      return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: invalid point encoding at commitment " + std::to_string(verdict[cells]) +
-                                                  " (fixed commitments first, then permutation commitments)"));
-    for (size_t j = 1; j < cells; j++)
-      if (verdict[j])
-        return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: field element not below the modulus at polynomial " + std::to_string(j - 1) + " element " +
-                                                    std::to_string(verdict[cells + j]) + " (polynomials in stream order, l0 = 0)"));
-  } else if (raw && checked) {  // SerdeFormat::RawBytes: every field element below the modulus (helpers.rs:62-79)
-    void* flag;
-    if ((rc = c->ensure_scratch(Scratch::EntryA, 64, &flag)) != CQ_OK) return pk_abort(pk, rc);
-    CQ_HIP(c, hipMemsetAsync(flag, 0, 4, c->stream));
-    for (auto& v : to_check)
-      if ((rc = fr_validate(c, v.first, v.second, (uint32_t*)flag)) != CQ_OK) return pk_abort(pk, rc);
-    uint32_t bad = 0;
-    CQ_HIP(c, hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, c->stream));
-    CQ_HIP(c, hipStreamSynchronize(c->stream));
-    if (bad) return pk_abort(pk, c->fail(CQ_ERR_ARG, "pk: field element not below the modulus"));
-  }
-  // b0_g1_bound: n-1 points (best_multiexp asserts equal lengths, arithmetic.rs:133)
-  if (b0_g1_bound) {
-    if (b0_on_device) {
-      pk->b0_g1_bound = (G1Affine*)b0_g1_bound;
-    } else {
-      if (hipMalloc(&pk->b0_g1_bound, (n - 1) * sizeof(G1Affine)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(b0 bound)"));
-      pk->own_b0 = true;
-      CQ_HIP(c, hipMemcpyAsync(pk->b0_g1_bound, b0_g1_bound, (n - 1) * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
-    }
-  }
-  // per lookup: [qs_0 | qs_1 | ...] so that q_a is one MSM
-  for (auto& lk : pk->lookups) {
-    G1Affine* cat = nullptr;
-    const size_t N = cfg->N;
-    if (hipMalloc(&cat, lk.tables.size() * N * sizeof(G1Affine)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(qs)"));
-    pk->qs_concat.push_back(cat);
-    for (size_t j = 0; j < lk.tables.size(); j++)
-      CQ_HIP(c, hipMemcpyAsync(cat + j * N, lk.tables[j]->qs, N * sizeof(G1Affine), hipMemcpyDeviceToDevice, c->stream));
-  }
-  if ((rc = pk_small_tables(pk)) != CQ_OK) return pk_abort(pk, rc);
-  CQ_HIP(c, hipStreamSynchronize(c->stream));
-  // the per-row bases of [b_0] and [p] (cq.hpp): two G1 transforms, once per key
-  if (!pk->lookups.empty() && pk->b0_g1_bound && cfg->N + 1 <= ((size_t)1 << (MSM_TABLE_C - 1)) && n >= 2) {
-    const G1Affine* src[2] = {params->g, pk->b0_g1_bound};
-    for (int q = 0; q < 2; q++) {
-      if (hipMalloc(&pk->b_row_bases[q], n * sizeof(G1Affine)) != hipSuccess) return pk_abort(pk, c->fail(CQ_ERR_HIP, "hipMalloc(b row bases)"));
-      if ((rc = g1_to_lagrange_shifted(c, src[q], (uint32_t)(n - 1), 1, pk->k, pk->b_row_bases[q])) != CQ_OK) return pk_abort(pk, rc);
-      if (msm_bases29(c, pk->b_row_bases[q], (uint32_t)n, pk->b_row_bases[q]) != 0) return pk_abort(pk, c->fail(CQ_ERR_HIP, "b row bases"));
-    }
-    CQ_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  *out = guard.release();
-  return CQ_OK;
-}
-
-int cq_pk_create(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq_table_config* cfg, const uint64_t* b0_g1_bound,
-                 int b0_on_device, cq_pk** out) {
-  return pk_create_impl(c, params, cs, cfg, b0_g1_bound, b0_on_device, nullptr, 0, 0, 0, false, out);
-}
-
-int cq_pk_read_raw(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq_table_config* cfg, const uint64_t* b0_g1_bound,
-                   int b0_on_device, const uint8_t* buf, size_t len, uint32_t num_selectors, int checked, cq_pk** out) {
-  if (!buf) return CQ_ERR_ARG;
-  return pk_create_impl(c, params, cs, cfg, b0_g1_bound, b0_on_device, buf, len, num_selectors, checked, false, out);
-}
-
-// ProvingKey::read in any SerdeFormat (plonk.rs:379-403)
-int cq_pk_read(cq_ctx* c, cq_params* params, const cq_circuit* cs, cq_table_config* cfg, const uint64_t* b0_g1_bound, int b0_on_device,
-               const uint8_t* buf, size_t len, uint32_t num_selectors, int format, cq_pk** out) {
-  if (!buf) return CQ_ERR_ARG;
-  if (format != CQ_SERDE_PROCESSED && format != CQ_SERDE_RAW_BYTES && format != CQ_SERDE_RAW_BYTES_UNCHECKED)
-    return c ? c->fail(CQ_ERR_ARG, "pk: unknown serde format") : CQ_ERR_ARG;
-  return pk_create_impl(c, params, cs, cfg, b0_g1_bound, b0_on_device, buf, len, num_selectors, format == CQ_SERDE_RAW_BYTES,
-                        format == CQ_SERDE_PROCESSED, out);
-}
-
-static size_t pk_stream_size(const cq_pk* pk, uint32_t num_selectors, size_t point_bytes) {
-  if (!pk) return 0;
-  const size_t n = (size_t)1 << pk->k, ext = pk->domain->ext(), F = pk->num_fixed, PC = pk->perm_columns.size();
-  const size_t poly_n = 4 + n * sizeof(Fr), poly_e = 4 + ext * sizeof(Fr);
-  return 8 + (F + PC) * point_bytes + (size_t)num_selectors * ((n + 7) / 8) + 3 * poly_e + 3 * 4 + F * (2 * poly_n + poly_e) + 3 * 4 +
-         PC * (2 * poly_n + poly_e);
-}
-size_t cq_pk_raw_size(const cq_pk* pk, uint32_t num_selectors) { return pk_stream_size(pk, num_selectors, sizeof(G1Affine)); }
-// a canonical scalar is as long as a raw one: the formats differ by the commitments alone
-size_t cq_pk_serialized_size(const cq_pk* pk, int format, uint32_t num_selectors) {
-  if (format == CQ_SERDE_PROCESSED) return pk_stream_size(pk, num_selectors, 32);
-  if (format == CQ_SERDE_RAW_BYTES || format == CQ_SERDE_RAW_BYTES_UNCHECKED) return pk_stream_size(pk, num_selectors, sizeof(G1Affine));
-  return 0;
-}
-
-// ProvingKey::write (plonk.rs:349-362); processed: compressed commitments, canonical scalars (converted into the second
-// entry buffer, one polynomial at a time, and copied out from there)
-static int pk_write_impl(cq_pk* pk, bool processed, const uint8_t* selector_bits, uint32_t num_selectors, uint8_t* buf, size_t cap,
-                         size_t* written) {
-  if (!pk || !buf || !written || (num_selectors && !selector_bits)) return CQ_ERR_ARG;
-  cq_ctx* c = pk->ctx;
-  CQ_HIP(c, hipSetDevice(c->device));
-  const size_t n = (size_t)1 << pk->k, ext = pk->domain->ext(), F = pk->num_fixed, PC = pk->perm_columns.size();
-  const size_t total = pk_stream_size(pk, num_selectors, processed ? 32 : sizeof(G1Affine));
-  if (cap < total) return c->fail(CQ_ERR_ARG, "pk: output buffer too small");
-  uint8_t* o = buf;
-  // VerifyingKey::write (:92-113): k, fixed commitments, permutation commitments, packed selector bits
-  put_be32(o, pk->k);
-  put_be32(o, (uint32_t)F);
-  std::vector<uint64_t> cm((F + PC) * 8 + 8);
-  int rc = cq_pk_vk_commitments(pk, cm.data(), cm.data() + F * 8);
-  if (rc != CQ_OK) return rc;
-  void* stage = nullptr;  // processed only
-  if (processed) {
-    if ((rc = c->ensure_scratch(Scratch::EntryB, std::max(ext * sizeof(Fr), (F + PC) * (sizeof(G1Affine) + 32)), &stage)) != CQ_OK) return rc;
-    if (F + PC) {
-      uint8_t* packed = (uint8_t*)stage + (F + PC) * sizeof(G1Affine);
-      CQ_HIP(c, hipMemcpyAsync(stage, cm.data(), (F + PC) * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
-      if ((rc = g1_compress(c, (const G1Affine*)stage, (uint32_t)(F + PC), packed)) != CQ_OK) return rc;
-      CQ_HIP(c, hipMemcpyAsync(o, packed, (F + PC) * 32, hipMemcpyDeviceToHost, c->stream));
-      CQ_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    o += (F + PC) * 32;
-  } else {
-    memcpy(o, cm.data(), (F + PC) * sizeof(G1Affine));
-    o += (F + PC) * sizeof(G1Affine);
-  }
-  const size_t sel_bytes = (size_t)num_selectors * ((n + 7) / 8);
-  if (sel_bytes) memcpy(o, selector_bits, sel_bytes);
-  o += sel_bytes;
-  auto write_poly = [&](const Fr* src, size_t len) -> int {
-    put_be32(o, (uint32_t)len);
-    if (processed) {  // (stream order: the next conversion waits for this copy)
-      int r2 = fr_to_repr(c, src, (uint32_t)len, (uint8_t*)stage);
-      if (r2 != CQ_OK) return r2;
-      src = (const Fr*)stage;
-    }
-    CQ_HIP(c, hipMemcpyAsync(o, src, len * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
-    o += len * sizeof(Fr);
-    return CQ_OK;
-  };
-  auto write_slice = [&](const Fr* src, size_t count, size_t each) -> int {
-    put_be32(o, (uint32_t)count);
-    for (size_t i = 0; i < count; i++) {
-      int r2 = write_poly(src + i * each, each);
-      if (r2 != CQ_OK) return r2;
-    }
-    return CQ_OK;
-  };
-  // l0, l_last (a CQ-only key does not keep them: computed here), l_active_row
-  void* tmp;
-  if ((rc = c->ensure_scratch(Scratch::EntryA, (n + 2 * ext) * sizeof(Fr), &tmp)) != CQ_OK) return rc;
-  Fr* l0 = pk->l0;
-  Fr* l_last = pk->l_last;
-  if (!l0) {
-    l0 = (Fr*)tmp + n;
-    l_last = l0 + ext;
-    if ((rc = unit_coset(pk, 0, (Fr*)tmp, l0)) != CQ_OK || (rc = unit_coset(pk, n - pk->bf - 1, (Fr*)tmp, l_last)) != CQ_OK) return rc;
-  }
-  if ((rc = write_poly(l0, ext)) != CQ_OK || (rc = write_poly(l_last, ext)) != CQ_OK || (rc = write_poly(pk->l_active_row, ext)) != CQ_OK) return rc;
-  if ((rc = write_slice(pk->fixed_values, F, n)) != CQ_OK || (rc = write_slice(pk->fixed_polys, F, n)) != CQ_OK ||
-      (rc = write_slice(pk->fixed_cosets, F, ext)) != CQ_OK)
-    return rc;
-  if ((rc = write_slice(pk->perm_values, PC, n)) != CQ_OK || (rc = write_slice(pk->perm_polys, PC, n)) != CQ_OK ||
-      (rc = write_slice(pk->perm_cosets, PC, ext)) != CQ_OK)
-    return rc;
-  CQ_HIP(c, hipStreamSynchronize(c->stream));
-  *written = (size_t)(o - buf);
-  return *written == total ? CQ_OK : c->fail(CQ_ERR_INTERNAL, "pk: serialized size mismatch");
-}
-
-int cq_pk_write_raw(cq_pk* pk, const uint8_t* selector_bits, uint32_t num_selectors, uint8_t* buf, size_t cap, size_t* written) {
-  return pk_write_impl(pk, false, selector_bits, num_selectors, buf, cap, written);
-}
-
-int cq_pk_write(cq_pk* pk, int format, const uint8_t* selector_bits, uint32_t num_selectors, uint8_t* buf, size_t cap, size_t* written) {
-  if (format != CQ_SERDE_PROCESSED && format != CQ_SERDE_RAW_BYTES && format != CQ_SERDE_RAW_BYTES_UNCHECKED)
-    return pk ? pk->ctx->fail(CQ_ERR_ARG, "pk: unknown serde format") : CQ_ERR_ARG;
-  return pk_write_impl(pk, format == CQ_SERDE_PROCESSED, selector_bits, num_selectors, buf, cap, written);
-}
-
+// ---- proving key: everything that is not construction, serialization or sharding (pk.hip) ------------
 int cq_pk_set_opener(cq_pk* pk, int opener) {
   if (!pk || (opener != CQ_OPENER_GWC && opener != CQ_OPENER_SHPLONK)) return CQ_ERR_ARG;
   pk->opener = opener;
@@ -828,91 +202,6 @@ int cq_pk_set_opener(cq_pk* pk, int opener) {
 int cq_pk_set_rng_fill(cq_pk* pk, cq_rng_fill_fn fill) {
   if (!pk) return CQ_ERR_ARG;
   pk->rng_fill = fill;
-  return CQ_OK;
-}
-
-// MSM window tables of a sharded key: a rank only ever multiplies its slice of every (scalars, bases) range, so the
-// 17 x SRS tables are built for those slices alone (the union of the slices over the MSMs that share an array: lengths
-// n, n - 1, N, w N).  The whole-array tables of the SRS objects the key is built on are given up for that only while this
-// key is their one user -- another key on the same params / table config keeps finding them, and the slices then resolve
-// into them -- and are rebuilt when the key returns to world = 1 or is destroyed.
-static int pk_shard_tables(cq_pk* pk) {
-  cq_ctx* c = pk->ctx;
-  for (auto& t : pk->shard_tables) msm_release_table(c, t.bases, t.n, t.c);
-  pk->shard_tables.clear();
-  if (!c->msm_precompute) return CQ_OK;
-  const size_t n = (size_t)1 << pk->k, N = pk->table_cfg ? pk->table_cfg->N : 0;
-  const bool has_cfg = pk->table_cfg && !pk->lookups.empty();
-  int rc;
-  if ((rc = pk_small_tables(pk)) != CQ_OK) return rc;  // the window width follows the length of a rank's point range
-  if (pk->shard_world <= 1) {  // back to whole arrays
-    if (pk->dropped_params_tables) {
-      pk->dropped_params_tables = false;
-      if ((rc = msm_register_tables(c, pk->params->g, n)) != CQ_OK || (rc = msm_register_tables(c, pk->params->g_lagrange, n)) != CQ_OK) return rc;
-    }
-    if (pk->dropped_cfg_tables) {
-      pk->dropped_cfg_tables = false;
-      if ((rc = msm_register_tables(c, pk->table_cfg->g1_lagrange, N)) != CQ_OK ||
-          (rc = msm_register_tables(c, pk->table_cfg->g_lagrange_opening_at_0, N)) != CQ_OK)
-        return rc;
-    }
-    return CQ_OK;
-  }
-  if (pk->params->key_users <= 1 && !pk->dropped_params_tables) {
-    msm_unregister_tables(c, pk->params->g);
-    msm_unregister_tables(c, pk->params->g_lagrange);
-    pk->dropped_params_tables = true;
-  }
-  if (has_cfg && pk->table_cfg->key_users <= 1 && !pk->dropped_cfg_tables) {
-    msm_unregister_tables(c, pk->table_cfg->g1_lagrange);
-    msm_unregister_tables(c, pk->table_cfg->g_lagrange_opening_at_0);
-    pk->dropped_cfg_tables = true;
-  }
-  struct Use { const G1Affine* b; size_t len; };
-  std::vector<Use> uses{{pk->params->g_lagrange, n}, {pk->params->g, n}, {pk->params->g, n - 1}};
-  if (has_cfg) {
-    uses.push_back({pk->table_cfg->g1_lagrange, N});
-    uses.push_back({pk->table_cfg->g_lagrange_opening_at_0, N});
-  }
-  if (pk->b0_g1_bound) uses.push_back({pk->b0_g1_bound, n - 1});
-  // (the cached quotients [qs_0 | qs_1 | ...] are the key's own small arrays: their whole-array tables stay)
-  std::vector<std::pair<const G1Affine*, const G1Affine*>> iv;
-  for (auto& u : uses) {
-    size_t lo, hi;
-    shard_range(u.len, pk->shard_rank, pk->shard_world, lo, hi);
-    if (hi > lo) iv.push_back({u.b + lo, u.b + hi});
-  }
-  std::sort(iv.begin(), iv.end());
-  std::vector<std::pair<const G1Affine*, const G1Affine*>> merged;
-  for (auto& x : iv) {
-    if (!merged.empty() && x.first <= merged.back().second) merged.back().second = std::max(merged.back().second, x.second);
-    else merged.push_back(x);
-  }
-  for (auto& m : merged) {
-    bool held = false;
-    const size_t len = (size_t)(m.second - m.first);
-    if ((rc = msm_register_tables(c, m.first, len, pk->table_c, &held)) != CQ_OK) return rc;
-    if (held) pk->shard_tables.push_back({m.first, len, pk->table_c});  // not held: served by a whole-array table that stayed
-  }
-  return CQ_OK;
-}
-
-int cq_pk_set_sharding(cq_pk* pk, uint32_t rank, uint32_t world, cq_allgather_fn fn, void* user) {
-  if (!pk || world == 0 || rank >= world) return CQ_ERR_ARG;
-  cq_ctx* c = pk->ctx;
-  if (world > 1 && !fn && (!c->rccl_comm || c->rccl_world != world || c->rccl_rank != rank))
-    return c->fail(CQ_ERR_ARG, "set_sharding: no all-gather callback and no matching RCCL communicator on the context");
-  CQ_HIP(c, hipSetDevice(c->device));
-  CQ_HIP(c, hipStreamSynchronize(c->stream));
-  pk->shard_rank = rank;
-  pk->shard_world = world;
-  // world = 1 over a one-rank RCCL communicator: still "sharded" -- every collective of the prover runs, over one rank
-  pk->shard_single = world == 1 && !fn && c->rccl_comm && c->rccl_world == 1;
-  pk->allgather = world > 1 ? fn : nullptr;
-  pk->allgather_user = user;
-  int rc = pk_shard_tables(pk);
-  if (rc != CQ_OK) return rc;
-  CQ_HIP(c, hipStreamSynchronize(c->stream));
   return CQ_OK;
 }
 
@@ -930,41 +219,6 @@ int cq_pk_set_resident_sharding(cq_pk* pk, int on, cq_exchange_fn fn, void* user
   pk->exchange = fn;
   pk->exchange_user = user;
   return CQ_OK;
-}
-
-void cq_pk_destroy(cq_pk* pk) {
-  if (!pk) return;
-  hipStreamSynchronize(pk->ctx->stream);
-  if (pk->domain) domain_destroy(pk->domain);
-  if (pk->l_active_row) hipFree(pk->l_active_row);
-  for (void* p : {(void*)pk->fixed_values, (void*)pk->fixed_polys, (void*)pk->fixed_cosets, (void*)pk->l0, (void*)pk->l_last,
-                  (void*)pk->gate_prog, (void*)pk->constants, (void*)pk->lookup_prog, (void*)pk->legacy_prog, (void*)pk->perm_values, (void*)pk->perm_polys, (void*)pk->perm_cosets,
-                  (void*)pk->omega_powers, (void*)pk->ext_pow_lo, (void*)pk->ext_pow_hi})
-    if (p) hipFree(p);
-  // window tables: the slices of a sharded key go, the whole-array tables it had given up come back (their owners --
-  // params, table config -- are still alive: a key never outlives them), its references are returned
-  if (pk->shard_world > 1 || pk->dropped_params_tables || pk->dropped_cfg_tables) {
-    pk->shard_world = 1;
-    (void)pk_shard_tables(pk);
-  }
-  for (auto& t : pk->held_tables) msm_release_table(pk->ctx, t.bases, t.n, t.c);
-  for (int q = 0; q < 2; q++)
-    if (pk->b_row_bases[q]) hipFree(pk->b_row_bases[q]);
-  if (pk->own_b0 && pk->b0_g1_bound) {
-    msm_unregister_tables(pk->ctx, pk->b0_g1_bound);
-    hipFree(pk->b0_g1_bound);
-  }
-  for (auto p : pk->qs_concat) {
-    msm_unregister_tables(pk->ctx, p);
-    hipFree(p);
-  }
-  if (pk->counted_users) {
-    cq_params* params = pk->params;
-    cq_table_config* cfg = pk->table_cfg;
-    if (--params->key_users == 0 && params->owner_released) cq_params_destroy(params);
-    if (cfg && --cfg->key_users == 0 && cfg->owner_released) cq_table_config_destroy(cfg);
-  }
-  delete pk;
 }
 
 uint32_t cq_pk_usable_rows(const cq_pk* pk) { return pk ? pk->u : 0; }
@@ -1255,11 +509,9 @@ int cq_sha_decomposition_table_dev(cq_ctx* c, uint32_t first_limb_len, uint32_t 
 // ---- StaticTableValues::new (static_lookup.rs:78-126): the reference's O(N^2) construction on the GPU ----
 int cq_static_table_new(cq_ctx* c, size_t size, const uint64_t* values, const uint64_t* srs_g1, cq_static_table** out) {
   if (!c || !values || !srs_g1 || !out || !is_pow2(size) || size > (1u << 20)) return CQ_ERR_ARG;
-  CQ_HIP(c, hipSetDevice(c->device));
-  *out = nullptr;
-  cq_static_table* t = new cq_static_table();
-  Building<cq_static_table> guard(t, cq_static_table_destroy, c);
-  int rc = table_alloc(c, size, values, t);
+  Building<cq_static_table> guard(new cq_static_table(), cq_static_table_destroy, c);
+  cq_static_table* t = guard.p;
+  int rc = table_alloc(c, size, values, t, out);
   if (rc != CQ_OK) return rc;
   const uint32_t N = (uint32_t)size;
   if ((rc = domain_create(c, 2, log2u(size), &guard.dom)) != CQ_OK) return rc;
@@ -1267,11 +519,9 @@ int cq_static_table_new(cq_ctx* c, size_t size, const uint64_t* values, const ui
   const uint32_t group = 16;  // roots per MSM launch
   G1Affine* srs = nullptr;
   Fr *coeffs = nullptr, *quot = nullptr;
-  const bool alloc_ok = hipMalloc(&srs, size * sizeof(G1Affine)) == hipSuccess && hipMalloc(&coeffs, size * sizeof(Fr)) == hipSuccess &&
-                        hipMalloc(&quot, (size_t)group * size * sizeof(Fr)) == hipSuccess;
-  for (void* d : {(void*)srs, (void*)coeffs, (void*)quot})
-    if (d) guard.dev.push_back(d);
-  if (!alloc_ok) return c->fail(CQ_ERR_HIP, "hipMalloc(static_table_new)");
+  if ((rc = guard.temp(&srs, size, "static_table_new")) != CQ_OK || (rc = guard.temp(&coeffs, size, "static_table_new")) != CQ_OK ||
+      (rc = guard.temp(&quot, (size_t)group * size, "static_table_new")) != CQ_OK)
+    return rc;
   CQ_HIP(c, hipMemcpyAsync(srs, srs_g1, size * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
   guard.reg.push_back(srs);  // unregistering an array that never got tables is a no-op
   if (c->msm_precompute && (rc = msm_register_tables(c, srs, size)) != CQ_OK) return rc;
@@ -1292,34 +542,26 @@ int cq_static_table_new(cq_ctx* c, size_t size, const uint64_t* values, const ui
     }
   }
   CQ_HIP(c, hipMemcpyAsync(t->qs, host_qs.data(), size * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
-  CQ_HIP(c, hipStreamSynchronize(c->stream));
-  *out = guard.release();
-  return CQ_OK;
+  return guard.finish(out);
 }
 
 static int static_table_new_fk(cq_ctx* c, size_t size, const uint64_t* values, const uint64_t* srs_g1, bool srs_on_device,
                                cq_static_table** out) {
   if (!c || !values || !srs_g1 || !out || !is_pow2(size) || size < 2 || size > (1u << 22)) return CQ_ERR_ARG;
-  CQ_HIP(c, hipSetDevice(c->device));
-  *out = nullptr;
-  cq_static_table* t = new cq_static_table();
-  Building<cq_static_table> guard(t, cq_static_table_destroy, c);
-  int rc = table_alloc(c, size, values, t);
+  Building<cq_static_table> guard(new cq_static_table(), cq_static_table_destroy, c);
+  cq_static_table* t = guard.p;
+  int rc = table_alloc(c, size, values, t, out);
   if (rc != CQ_OK) return rc;
   if ((rc = domain_create(c, 2, log2u(size), &guard.dom)) != CQ_OK) return rc;
   G1Affine* srs = nullptr;
   Fr* coeffs = nullptr;
-  const bool alloc_ok = (srs_on_device || hipMalloc(&srs, size * sizeof(G1Affine)) == hipSuccess) && hipMalloc(&coeffs, size * sizeof(Fr)) == hipSuccess;
-  for (void* d : {(void*)srs, (void*)coeffs})
-    if (d) guard.dev.push_back(d);
-  if (!alloc_ok) return c->fail(CQ_ERR_HIP, "hipMalloc(static_table_new_fk)");
+  if ((!srs_on_device && (rc = guard.temp(&srs, size, "static_table_new_fk")) != CQ_OK) || (rc = guard.temp(&coeffs, size, "static_table_new_fk")) != CQ_OK)
+    return rc;
   if (!srs_on_device) CQ_HIP(c, hipMemcpyAsync(srs, srs_g1, size * sizeof(G1Affine), hipMemcpyHostToDevice, c->stream));
   if ((rc = domain_lagrange_to_coeff(guard.dom, t->values, coeffs, 1, size, size)) != CQ_OK) return rc;  // :99-105
   // resident powers belong to the trapdoor-free setup path and take its FFT; the quotients are the same bytes either way
   if ((rc = fk_table_quotients(c, coeffs, srs_on_device ? (const G1Affine*)srs_g1 : srs, log2u(size), t->qs, srs_on_device)) != CQ_OK) return rc;
-  CQ_HIP(c, hipStreamSynchronize(c->stream));
-  *out = guard.release();
-  return CQ_OK;
+  return guard.finish(out);
 }
 int cq_static_table_new_fk(cq_ctx* c, size_t size, const uint64_t* values, const uint64_t* srs_g1, cq_static_table** out) {
   return static_table_new_fk(c, size, values, srs_g1, false, out);

@@ -4,6 +4,7 @@
 #include <vector>
 #include "../../include/cq_halo2.h"
 #include "curve.hpp"
+#include "pk.hpp"
 #include "poly.hpp"
 
 struct cq_ctx;
@@ -132,20 +133,14 @@ struct cq_static_table {
   uint32_t nslots = 0;
 };
 
-struct cq_lookup_desc {
-  std::vector<uint32_t> cols;             // advice column per table column (input = advice[col] @ Rotation::cur())
-  std::vector<int64_t> prog;              // or: word offset of the input's program in cq_pk::lookup_prog (-1 = plain column)
-  std::vector<cq_static_table*> tables;
-};
-
 // the slice of ProvingKey (plonk.rs:291-308) the CQ-only proving path reads
-struct cq_pk {
+// The host description (cq_pk_desc, pk.hpp) comes first; below it, what pk.hip builds on the device.  The device pointers
+// are raw pointers freed by cq_pk_destroy, on purpose: cq_create_proof_batch makes a shallow copy of the key per lane
+// (`cq_pk lane_pk = *pk`), which an owning member type would either forbid or turn into a double free.
+struct cq_pk : cq_pk_desc {
   cq_ctx* ctx;
   cq_params* params;
   cq_domain* domain = nullptr;
-  uint32_t k, num_advice, bf, u;
-  std::vector<cq_lookup_desc> lookups;
-  std::vector<std::pair<uint32_t, int32_t>> advice_queries;  // (column, rotation), registration order
   cq_table_config* table_cfg;
   cq::G1Affine* b0_g1_bound = nullptr;  // n-1 points
   bool own_b0 = false;
@@ -156,25 +151,16 @@ struct cq_pk {
   // short MSMs over per-table-row sums of these bases (prover.hip, round 2).
   cq::G1Affine* b_row_bases[2] = {nullptr, nullptr};
   cq::Fr* l_active_row = nullptr;       // extended coset
-  // ---- general PLONK part (empty for a CQ-only circuit) ----
-  uint32_t num_fixed = 0, num_instance = 0, cs_degree = 3;
-  std::vector<std::pair<uint32_t, int32_t>> fixed_queries;
+  // ---- general PLONK part (null for a CQ-only circuit) ----
   cq::Fr* fixed_values = nullptr;   // num_fixed x n   (pk.fixed_values, keygen.rs:320-326)
   cq::Fr* fixed_polys = nullptr;    // num_fixed x n   (:328-331)
   cq::Fr* fixed_cosets = nullptr;   // num_fixed x ext (:333-336)
   cq::Fr* l0 = nullptr;             // ext (:340-345)
   cq::Fr* l_last = nullptr;         // ext (:357-363)
-  uint32_t num_gate_polys = 0;
   uint32_t* gate_prog = nullptr;    // device: [len, words...] per polynomial
   cq::Fr* constants = nullptr;      // device
   uint32_t* lookup_prog = nullptr;  // device: [1-poly program] per expression-valued lookup input
-  bool lookup_exprs = false;
-  // legacy lookups: per lookup the number of (input, table) expression pairs and the word offsets of the two
-  // program lists ([len, words...] x width each) in `legacy_prog`
-  struct LegacyLookup { uint32_t width; size_t in_off, tab_off; };
-  std::vector<LegacyLookup> legacy;
-  uint32_t* legacy_prog = nullptr;
-  std::vector<std::pair<uint32_t, uint32_t>> perm_columns;  // (CQ_COL_*, index) = cs.permutation.columns
+  uint32_t* legacy_prog = nullptr;  // device: the legacy lookups' program lists (LegacyLookup::in_off / tab_off)
   cq::Fr* perm_values = nullptr;    // columns x n   (permutation::ProvingKey::permutations)
   cq::Fr* perm_polys = nullptr;     // columns x n   (::polys)
   cq::Fr* perm_cosets = nullptr;    // columns x ext (::cosets)
@@ -183,14 +169,6 @@ struct cq_pk {
   cq::Fr* ext_pow_hi = nullptr;     // extended_omega^(256 b), b < max(ext / 256, 1)
   int opener = CQ_OPENER_GWC;
   cq_rng_fill_fn rng_fill = nullptr;     // caller's bulk form of its RNG (cq_pk_set_rng_fill)
-  std::vector<uint8_t> advice_phase;     // phase of every advice column
-  std::vector<uint8_t> challenge_phase;  // phase after which user challenge i is squeezed
-  uint32_t num_phases = 1;
-  bool general() const { return num_gate_polys || !perm_columns.empty() || !legacy.empty(); }
-  size_t perm_sets() const {
-    const size_t chunk = cs_degree - 2;
-    return (perm_columns.size() + chunk - 1) / chunk;
-  }
   cq::Fr vk_repr;
   std::vector<cq::G1Affine*> qs_concat;  // per lookup: [qs_0 | qs_1 | ...] (width*N points)
   // MSM sharding across ranks (one process per GPU): every rank commits its slice of each point range,
@@ -212,7 +190,7 @@ struct cq_pk {
   void* exchange_user = nullptr;
   // MSM window tables: the width this key's launches use (its SRS length decides; small arrays shared with keys of other
   // sizes get a second table of this width), the registry entries the key holds a reference of, and -- when sharded --
-  // the tables of the rank's slices (capi_cq.hip: pk_shard_tables)
+  // the tables of the rank's slices (pk.hip: pk_shard_tables)
   uint32_t table_c = 0;
   struct TableRef { const void* bases; size_t n; uint32_t c; };
   std::vector<TableRef> held_tables, shard_tables;

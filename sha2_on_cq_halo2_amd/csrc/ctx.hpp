@@ -20,9 +20,10 @@ enum class Scratch {
   Ntt,          // domain.hip transforms on any stream but the side stream, for one launch
   EntryA,       // a public entry point's own staging or temporaries, for that call only: capi.hip fft, capi_poly.hip HostStage
                 // input, capi_msm.hip (multiexp scalars, params set-up temp, validate flag), capi_g2.hip scalars, capi_cq.hip
-                // (table config, static table, pk create / validate / write temps), comm.hip self-test, the verdict words of
-                // the Processed conversions (serde.hip entry points, params / pk / G2 SRS readers).  Nothing they call takes an entry buffer
-  EntryB,       // the second buffer of the same entry points (outputs, bases, pk permutation mapping, the staged compressed
+                // (table config, static table), pk.hip (keygen and write temps; PkStreamReader's verdict words or validity
+                // flag, from its begin() to its finish()), comm.hip self-test, the verdict words of the Processed conversions
+                // (serde.hip entry points, params / G2 SRS readers).  Nothing they call takes an entry buffer
+  EntryB,       // the second buffer of the same entry points (outputs, bases, pk.hip's permutation mapping, the staged compressed
                 // bytes of the Processed params / pk / G2 SRS readers and writers, the two G2 points of a params set-up or full
                 // stream); also g1_fft's twiddles: its callers (g1_to_lagrange,
                 // fk_table_quotients) run under entry points that hold neither entry buffer
@@ -133,6 +134,11 @@ struct cq_ctx {
   int hip_fail(hipError_t e, const char* what) {
     err = std::string(what) + ": " + hipGetErrorString(e);
     return CQ_ERR_HIP;
+  }
+  // an allocation that lives as long as the object it belongs to (the caller's destructor frees it): `count` elements of T
+  template <class T>
+  int dev_alloc(T** p, size_t count, const char* what) {
+    return hipMalloc(p, count * sizeof(T)) == hipSuccess ? CQ_OK : fail(CQ_ERR_HIP, std::string("hipMalloc(") + what + ")");
   }
   // grows `b` to at least max(bytes, min_bytes); the old allocation is freed once `stream` has drained
   int grow(cq::GrowBuf& b, size_t bytes, size_t min_bytes, bool host, void** out) {

@@ -1,6 +1,6 @@
 // SerdeFormat::Processed on the device: point decompression / compression (derive/curve.rs:603-646) for G1 and G2 and the
 // canonical scalar encodings (helpers.rs:68-91), with their C entry points.  The params, proving-key and G2 SRS readers
-// built on them live next to their raw twins (capi_msm.hip, capi_cq.hip, capi_g2.hip).
+// built on them live next to their raw twins (capi_msm.hip, pk.hip, capi_g2.hip).
 #include <cstdint>
 #include <string>
 #include "ctx.hpp"

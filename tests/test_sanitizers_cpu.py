@@ -51,3 +51,19 @@ def test_host_glue_under_sanitizers(tmp_path, sanitizer):
     for n in (0, 1, 128, 129, 1000):
         tag = "blake2b_empty" if n == 0 else "blake2b_%d" % n
         assert kv[tag] == hashlib.blake2b(msg[:n], digest_size=64, person=b"Halo2-Transcript").hexdigest(), tag
+
+
+def test_pk_describe_under_asan_ubsan(tmp_path):
+    """The host half of proving-key construction (csrc/pk.hpp: every argument check, the lowered fields, the program blobs and
+    their offsets; tests/host/pk_describe_check.cpp) over one good and seventeen bad descriptions."""
+    exe = str(tmp_path / "pk_describe_check")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "host", "pk_describe_check.cpp"), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", ASAN_OPTIONS="detect_leaks=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-3000:] + r.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+    lines = r.stdout.strip().splitlines()
+    assert lines[0] == "0 " and len(lines) == 1 + 17 + 1 and all(ln.startswith("-1 ") for ln in lines[1:-1])
