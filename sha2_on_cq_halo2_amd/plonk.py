@@ -12,10 +12,14 @@ import ctypes as C
 
 import numpy as np
 
+from ._lib import constants
+
 FR_MODULUS = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 
-GATE_CONST, GATE_ADVICE, GATE_FIXED, GATE_INSTANCE, GATE_NEG, GATE_ADD, GATE_MUL, GATE_SCALE, GATE_CHALLENGE = range(9)
-COL_ADVICE, COL_FIXED, COL_INSTANCE = 0, 1, 2
+_CQ = constants()  # the opcodes and column kinds are the header's
+GATE_CONST, GATE_ADVICE, GATE_FIXED, GATE_INSTANCE, GATE_NEG, GATE_ADD, GATE_MUL, GATE_SCALE, GATE_CHALLENGE = (
+    _CQ["CQ_GATE_" + s] for s in ("CONST", "ADVICE", "FIXED", "INSTANCE", "NEG", "ADD", "MUL", "SCALE", "CHALLENGE"))
+COL_ADVICE, COL_FIXED, COL_INSTANCE = (_CQ["CQ_COL_" + s] for s in ("ADVICE", "FIXED", "INSTANCE"))
 _QUERY_OP = {COL_ADVICE: GATE_ADVICE, COL_FIXED: GATE_FIXED, COL_INSTANCE: GATE_INSTANCE}
 
 

@@ -82,6 +82,29 @@ static int layout(void) {
   FIELD(cq_buffer_rng, pos);
   FIELD(cq_buffer_rng, len);
   FIELD(cq_buffer_rng, overrun);
+  printf("sizeof.cq_assigned_column %zu\n", sizeof(cq_assigned_column));
+  FIELD(cq_assigned_column, num);
+  FIELD(cq_assigned_column, den_rows);
+  FIELD(cq_assigned_column, den);
+  FIELD(cq_assigned_column, den_count);
+  printf("sizeof.cq_open_query %zu\n", sizeof(cq_open_query));
+  FIELD(cq_open_query, poly_dev);
+  FIELD(cq_open_query, len);
+  FIELD(cq_open_query, point);
+  printf("sizeof.cq_open_transcript %zu\n", sizeof(cq_open_transcript));
+  FIELD(cq_open_transcript, squeeze_challenge);
+  FIELD(cq_open_transcript, write_point);
+  FIELD(cq_open_transcript, user);
+  printf("sizeof.cq_xfer %zu\n", sizeof(cq_xfer));
+  FIELD(cq_xfer, peer);
+  FIELD(cq_xfer, send);
+  FIELD(cq_xfer, buf);
+  FIELD(cq_xfer, bytes);
+  printf("sizeof.cq_witness_failure %zu\n", sizeof(cq_witness_failure));
+  FIELD(cq_witness_failure, kind);
+  FIELD(cq_witness_failure, index);
+  FIELD(cq_witness_failure, row);
+  FIELD(cq_witness_failure, detail);
 #undef FIELD
   printf("version %s\n", cq_version());
   return 0;

@@ -34,12 +34,18 @@ def _kv(text):
 
 
 def test_header_is_plain_c_and_struct_layouts_match_the_binding():
+    from sha2_on_cq_halo2_amd import _lib
     from sha2_on_cq_halo2_amd.api import _BufferRng, _CqCircuit, _CqPlonk
 
     r = subprocess.run([_build(), "layout"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr
     kv = _kv(r.stdout)
-    for cname, cls in (("cq_plonk", _CqPlonk), ("cq_circuit", _CqCircuit), ("cq_buffer_rng", _BufferRng)):
+    structs = [name for name, _ in _lib.header_declarations().structs]  # every struct of the header, none left out
+    assert sorted(structs) == sorted(["cq_plonk", "cq_circuit", "cq_buffer_rng", "cq_assigned_column", "cq_open_query",
+                                      "cq_open_transcript", "cq_xfer", "cq_witness_failure"])
+    assert (_lib.struct("cq_plonk"), _lib.struct("cq_circuit"), _lib.struct("cq_buffer_rng")) == (_CqPlonk, _CqCircuit, _BufferRng)
+    for cname in structs:
+        cls = _lib.struct(cname)
         assert int(kv["sizeof." + cname]) == C.sizeof(cls), cname
         fields = [k.split(".", 1)[1] for k in kv if k.startswith(cname + ".")]
         assert fields == [f[0] for f in cls._fields_], cname  # same members, same order
@@ -70,6 +76,47 @@ def test_binding_signatures_are_derived_from_the_header():
     nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(LIBDIR, "libcq_halo2.so")], capture_output=True, text=True)
     exported = {line.split()[-1] for line in nm.stdout.splitlines() if line.split() and line.split()[-1].startswith("cq_")}
     assert exported - declared == set(), "exported but not declared in include/cq_halo2.h"
+
+
+def test_binding_constants_and_callback_types_are_the_headers():
+    """Every `#define CQ_<NAME> <integer>` is in _lib.constants() with the header's value (read here with a pattern of the
+    test's own), the binding's PROF_* / SERDE_* / FAIL_* / GATE_* / COL_* / RCCL_UNIQUE_ID_BYTES are those values, and every
+    function-pointer typedef yields a CFUNCTYPE of the typedef's parameter count and return type."""
+    import re
+
+    from sha2_on_cq_halo2_amd import _lib, api, plonk
+
+    raw = open(os.path.join(ROOT, "include", "cq_halo2.h")).read()
+    defines = {}
+    for line in raw.splitlines():
+        m = re.match(r"#define\s+(CQ_\w+)\s+(\S+)", line)
+        if m and re.fullmatch(r"\(?-?\d+[uU]?\)?", m.group(2)):
+            defines[m.group(1)] = int(m.group(2).strip("()uU"))
+    consts = _lib.constants()
+    assert consts == defines and len(defines) >= 30 and consts["CQ_ERR_ARG"] == -1 and consts["CQ_GATE_CHALLENGE"] == 8
+    bound = 0
+    for prefix, module in (("PROF_", api), ("SERDE_", api), ("FAIL_", api), ("GATE_", plonk), ("COL_", plonk)):
+        names = [n for n in defines if n.startswith("CQ_" + prefix)]
+        assert names, prefix
+        for n in names:
+            assert getattr(module, n[3:]) == defines[n], n
+            bound += 1
+        assert sorted(n for n in vars(module) if n.startswith(prefix)) == sorted(n[3:] for n in names), prefix  # no constant of the binding's own
+    assert bound == 5 + 3 + 5 + 9 + 3 and api.RCCL_UNIQUE_ID_BYTES == defines["CQ_RCCL_UNIQUE_ID_BYTES"] == 128
+
+    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    typedefs = re.findall(r"typedef\s+(\w+)\s*\(\s*\*\s*(cq_\w+)\s*\)\s*\(([^()]*)\)\s*;", text)
+    assert {name for _, name, _ in typedefs} == _lib.header_fnptr_typedefs() >= {"cq_rng_next_u64", "cq_phase_fn", "cq_exchange_fn"}
+    assert len(typedefs) >= 8
+    for ret, name, params in typedefs:
+        fn = _lib.callback(name)
+        assert issubclass(fn, C._CFuncPtr) and fn is _lib.callback(name), name
+        assert len(fn._argtypes_) == len(params.split(",")), name
+        assert fn._restype_ is {"int": C.c_int, "void": None, "uint64_t": C.c_uint64}[ret], name
+    # pointers to scalars and structs stay indexable from Python, void* stays an address
+    assert _lib.callback("cq_squeeze_challenge_fn")._argtypes_ == (C.c_void_p, C.POINTER(C.c_uint64))
+    assert _lib.callback("cq_exchange_fn")._argtypes_ == (C.c_void_p, C.POINTER(_lib.struct("cq_xfer")), C.c_size_t)
+    assert api._ALLGATHER_T is _lib.callback("cq_allgather_fn") and api._ALLGATHER_T._argtypes_ == (C.c_void_p,) * 3 + (C.c_size_t,)
 
 
 @pytest.mark.gpu

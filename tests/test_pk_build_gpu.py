@@ -135,7 +135,7 @@ def test_every_rejection_keeps_its_code_and_text(ctx, monkeypatch):
     """Each bad description or stream raises CqError -1 with the text of the check it trips; afterwards the same context and
     params still build a key that proves to the same bytes, and the objects close in either order."""
     from sha2_on_cq_halo2_amd import CqError, ParamsKZG, StaticTable
-    from sha2_on_cq_halo2_amd import api
+    from sha2_on_cq_halo2_amd import proving_key as api  # the module `ProvingKey` resolves `_lower_plonk` in
 
     fx = _env("lookup")
     be = _Backend(ctx, fx)

@@ -1,7 +1,8 @@
 """CPU: the four stage entry points (cq_permutation_commit_dev, cq_lookup_commit_product_dev, cq_evaluate_h_dev,
-cq_multiopen_dev) are declared in include/cq_halo2.h, exported by the library, and bound in api.py with the argument counts
-the header states.  The header is parsed the way tests/test_abi_cpu.py does (sha2_on_cq_halo2_amd._lib)."""
+cq_multiopen_dev) are declared in include/cq_halo2.h, exported by the library, and bound in the package's modules with the
+argument counts the header states.  The header is parsed the way tests/test_abi_cpu.py does (sha2_on_cq_halo2_amd._lib)."""
 import ast
+import glob
 import os
 
 from sha2_on_cq_halo2_amd import _lib, header_symbols, load
@@ -28,11 +29,12 @@ def test_the_header_declares_the_stage_entry_points_and_the_library_exports_them
 
 
 def test_api_binds_every_stage_with_the_headers_argument_count():
-    tree = ast.parse(open(os.path.join(ROOT, "sha2_on_cq_halo2_amd", "api.py")).read())
     seen = {}
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in STAGES:
-            seen.setdefault(node.func.attr, []).append(len(node.args) + len(node.keywords))
+    for path in sorted(glob.glob(os.path.join(ROOT, "sha2_on_cq_halo2_amd", "*.py"))):  # every module of the binding
+        for node in ast.walk(ast.parse(open(path).read())):
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in STAGES:
+                assert not any(isinstance(a, ast.Starred) for a in node.args) and not any(k.arg is None for k in node.keywords), path
+                seen.setdefault(node.func.attr, []).append(len(node.args) + len(node.keywords))
     for name, argc in STAGES.items():
         assert seen.get(name) == [argc], (name, seen.get(name))
     from sha2_on_cq_halo2_amd import ProvingKey
