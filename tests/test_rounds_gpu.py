@@ -22,8 +22,9 @@ def _pts(points):
     return B.points_to_mont_limbs(list(points))
 
 
-@pytest.mark.parametrize("k,nbits,pairs", [(5, 5, 1), (7, 6, 3)])
+@pytest.mark.parametrize("k,nbits,pairs", [(5, 5, 1), (7, 6, 3), (5, 7, 1)])
 def test_cq_rounds_and_quotient_match_the_oracle_trace(ctx, k, nbits, pairs):
+    """N = n, N < n and N > n: round 2's prep kernel sizes its grid by max(n, N) and guards the two halves separately."""
     N, n = 1 << nbits, 1 << k
     tv = {"dense": list(range(N)), "spread": [_spread(i) for i in range(N)]}
     lookups = [[(2 * p, "dense"), (2 * p + 1, "spread")] for p in range(pairs)]
