@@ -68,6 +68,7 @@ void cq_ctx_destroy(cq_ctx* c) {
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
   if (c->msm_tail_event) hipEventDestroy(c->msm_tail_event);
   if (c->aux_done) hipEventDestroy(c->aux_done);
+  if (c->b_sums_done) hipEventDestroy(c->b_sums_done);
   if (c->aux_stream) hipStreamDestroy(c->aux_stream);
   if (c->fb_table) hipFree(c->fb_table);
   for (auto& t : c->msm_tables) hipFree(t.table);

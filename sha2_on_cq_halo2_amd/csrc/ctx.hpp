@@ -27,7 +27,8 @@ enum class Scratch {
                 // bytes of the Processed params / pk / G2 SRS readers and writers, the two G2 points of a params set-up or full
                 // stream); also g1_fft's twiddles: its callers (g1_to_lagrange,
                 // fk_table_quotients) run under entry points that hold neither entry buffer
-  MsmWork,      // capi_msm.hip, msm.hip (msm_bucket_sums): the workspace of one MSM launch; launches follow one another on `stream`
+  MsmWork,      // capi_msm.hip, msm.hip (msm_bucket_sums): the workspace of one MSM launch on any stream but a side stream;
+                // those launches follow one another on `stream`
   MsmSums,      // capi_msm.hip: window sums, from msm_multi_begin to its msm_multi_end (launches are never nested)
   PolyTmp,      // poly.hip eval / kate, plonk.hip prefix_product partials, for one call each
   ProverArena,  // create_proof_dev's arena, for the whole proof
@@ -41,6 +42,10 @@ enum class Scratch {
   AssignedDen,  // cq_create_proof_assigned's sparse denominators (rows, values, the resolve launch's work array), from the upload
                 // until the columns are resolved on the proof's stream, before the proof starts: nothing else takes it
   NttAux,       // domain.hip transforms while AuxFork has put `stream` on the side stream
+  MsmWorkAux,   // msm.hip (msm_bucket_sums) while the prover has put `stream` on a side stream (cq_ctx::on_side_stream): the
+                // workspace of a proof's bucket-sum launches, which run beside an MSM launch of the main stream that holds
+                // MsmWork.  A proof issues them one after another on the side stream, and nothing else launches an MSM there:
+                // stream order keeps two holders apart, within a proof and from one proof to the next
   CommGather,   // comm.hip rccl_allgather_host; 1 MiB of it is taken in comm_rccl_init
   Check,        // check.hip cq_pk_check_witness, for that call only: the staged witness, verdict bitmaps, hash slots,
                 // expression values, the compacted findings.  A public entry point that calls no other: nothing else takes it
@@ -174,11 +179,17 @@ struct cq_ctx {
   // column sums, weighted sums) that leave most of the GPU idle; the prover uses that time for transforms whose
   // inputs are already fixed (prover.hip, AuxFork).  msm_run records `msm_tail_event` right after its accumulate
   // kernel; work on `aux_stream` starts there; `aux_done` orders the main stream after it.  While the prover has
-  // `stream` pointed at the side stream, NTTs take their scratch from Scratch::NttAux (domain.hip).
+  // `stream` pointed at the side stream, NTTs take their scratch from Scratch::NttAux (domain.hip) and a bucket-sum launch
+  // its workspace from Scratch::MsmWorkAux (msm.hip).
+  // msm_tail_event / msm_tail_seq belong to the MAIN stream's launches: an MSM launched on a side stream (the prover's
+  // bucket-sum launch, msm.hip) neither records the event nor bumps the number, so a fork still orders itself after the
+  // main-stream launch it runs beside.  `b_sums_done` is recorded behind a proof's last bucket-sum launch; round 2 makes the
+  // main stream wait for it before its first reader of the sums (prover.hip).
   hipStream_t aux_stream = nullptr;
-  hipEvent_t msm_tail_event = nullptr, aux_done = nullptr;
+  hipEvent_t msm_tail_event = nullptr, aux_done = nullptr, b_sums_done = nullptr;
   uint64_t msm_tail_seq = 0;
   bool aux_pending = false;
+  bool on_side_stream() const { return aux_stream && stream == aux_stream; }
   int ensure_aux_stream() {
     if (aux_stream) return CQ_OK;
     int least = 0, greatest = 0;
@@ -187,6 +198,7 @@ struct cq_ctx {
     if (e != hipSuccess) return hip_fail(e, "hipStreamCreate(aux)");
     e = hipEventCreateWithFlags(&msm_tail_event, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&aux_done, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&b_sums_done, hipEventDisableTiming);
     if (e != hipSuccess) return hip_fail(e, "hipEventCreate(aux)");
     return CQ_OK;
   }

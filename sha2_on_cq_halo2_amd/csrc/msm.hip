@@ -1684,7 +1684,11 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
   // -0.07 on another), hence the size floor.
   constexpr size_t TAIL_EARLY_POINTS = (size_t)1 << 20;
   const bool tail_early = n >= TAIL_EARLY_POINTS;
-  if (tail_early && ctx->msm_tail_event) {
+  // (a launch on a side stream runs beside a main-stream launch and hands nothing over: the tail event and its sequence
+  // number stay the main stream's, ctx.hpp.  The profiling brackets below are a pair of events of their own per launch,
+  // both recorded on `s`, and the entry counter is a slot per launch: neither can pair up across streams.)
+  const bool hand_over = ctx->msm_tail_event && !ctx->on_side_stream();
+  if (tail_early && hand_over) {
     (void)hipEventRecord(ctx->msm_tail_event, s);
     ctx->msm_tail_seq++;
   }
@@ -1692,7 +1696,7 @@ int msm_run(cq_ctx* ctx, const Fr* const* scalars_host_ptrs, const G1Affine* con
   msm_accumulate_kernel<<<(uint32_t)((L.tmax[0] + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS), MSM_ACC_THREADS, 0, s>>>(
       d_bases, L.B, pre ? 1u : 0u, d_strides, d_src, sorted, counts, off0, tk, off + (size_t)(Bt + 1), Bt, part[0], buckets);
   ctx->prof_end(pe);
-  if (ctx->msm_tail_event && !tail_early) {  // from here on the launch is latency-bound: side-stream work may start (ctx.hpp)
+  if (hand_over && !tail_early) {  // from here on the launch is latency-bound: side-stream work may start (ctx.hpp)
     (void)hipEventRecord(ctx->msm_tail_event, s);
     ctx->msm_tail_seq++;
   }
@@ -1756,7 +1760,8 @@ int msm_bucket_sums(cq_ctx* ctx, const uint32_t* const* index, const G1Affine* c
   if (!count || count > (1u << (c - 1)) || !msm_bucket_sums_fit(n, batch)) return -2;
   MsmLayout L(n, c, batch, true);
   void* ws;
-  if (ctx->ensure_scratch(Scratch::MsmWork, L.total, &ws) != 0) return -1;
+  // (beside a main-stream launch, which holds MsmWork: the side workspace, ctx.hpp)
+  if (ctx->ensure_scratch(ctx->on_side_stream() ? Scratch::MsmWorkAux : Scratch::MsmWork, L.total, &ws) != 0) return -1;
   const std::vector<size_t> lens(batch, n), strides(batch, n);  // (window 0 only: the stride is never multiplied by anything but 0)
   return msm_run(ctx, nullptr, bases29, lens.data(), n, c, batch, true, strides.data(), ws, nullptr, out, count, index);
 }

@@ -220,6 +220,8 @@ int shard_any(const cq_pk* pk, bool flag, bool& out) {
 // lands on the low-priority stream instead, ordered after the accumulate kernel of the MSM launch queued last (all
 // earlier kernels of the main stream are complete by then, and what remains of the MSM only touches its own
 // workspace).  join_aux() makes the main stream wait for it.  The destructor restores the context on an error path.
+// (An MSM launched between begin() and end() -- ProofRun::fork_bucket_sums -- leaves msm_tail_event and msm_tail_seq alone,
+// msm.hip: the next fork's begin(seq) still finds the main-stream launch it was sampled for.)
 struct AuxFork {
   cq_ctx* c;
   hipStream_t main = nullptr;
@@ -302,8 +304,12 @@ struct Buffers {
   Fr* challenges;  // user challenges (Expression::Challenge), uploaded as the phases complete
   // b's commitments from per-table-row sums (round 2): the N + 1 values b takes, per lookup; the bucket sums -- per lookup
   // two arrays of N + 1 affine points (64 B = 2 Fr each) -- that a launch before theta leaves there
+  // and, per lookup, the n bucket indices cq_round1 writes for the launch that forms the sums.  The indices have a region of
+  // their own, not b's then unused buffer: the launch runs on a side stream beside the main stream's work up to round 2,
+  // whose preparation writes b -- with their own region the main stream never has to wait for the launch's last reader
   Fr* b_values;
   G1Affine* b_sums;
+  uint32_t* b_index;
   Fr *tails, *gather;  // blinding rows of a phase's advice columns (staging); scalars on their way to the host
   uint64_t* rng_dev;
   uint32_t *m_counts, *err_dev;
@@ -368,6 +374,7 @@ void carve(const cq_pk* pk, Arena& ar, Buffers& b) {
   // (an even element count: the 64-byte points behind it stay 64-byte aligned)
   b.b_values = ar.take(pk->b_row_bases[0] ? (L * (N + 1) + 1) & ~(size_t)1 : 0);
   b.b_sums = (G1Affine*)ar.take(pk->b_row_bases[0] ? 2 * 2 * L * (N + 1) : 0);
+  b.b_index = (uint32_t*)ar.take(pk->b_row_bases[0] ? (L * n + 7) / 8 : 0);  // L * n words of 4 bytes
   b.challenges = ar.take(pk->challenge_phase.size() + 8);
   b.tails = ar.take(A * (pk->bf + 1) + 8);
   b.gather = ar.take(GATHER_MAX);
@@ -915,6 +922,16 @@ struct ProofRun {
   // A launch the MSM engine cannot plan (entry bound, workspace cap) leaves the coefficient path too.
   const bool b_by_rows = L > 0 && !pk->sharded() && pk->b_row_bases[0] != nullptr &&
                          msm_bucket_sums_fit((uint32_t)n, (uint32_t)std::min<size_t>(2 * L, MSM_MAX_BATCH));
+  // Round 2 is the first reader of those sums, so their launch does not stand in front of the launch that commits [m]
+  // (the advice launch with `early_m`, round 1's otherwise) but runs beside it on a side stream, from that launch's
+  // accumulate kernel on (fork_bucket_sums); round2_commit joins it.  CQ_BUCKET_SUMS_SIDE=0 keeps it on the main stream,
+  // in front (the A/B of profiles/r16_bucket_sums_side_ab.txt, tests); read once per proof.
+  const bool sums_side = b_by_rows && side_switch();
+  bool sums_pending = false;  // the side launch is queued, and nothing has made the main stream or the host wait for it yet
+  static bool side_switch() {
+    const char* e = getenv("CQ_BUCKET_SUMS_SIDE");
+    return !(e && e[0] == '0');
+  }
 
   // Resident column sharding (cq_pk_set_resident_sharding; DESIGN.md, multi-GPU): for the CQ-shaped circuits of the
   // BASELINE configs -- advice columns, static lookups on plain advice inputs, one phase, ProverGWC -- a transformed
@@ -975,6 +992,11 @@ struct ProofRun {
       shard_range(A, me, SW, adv_lo, adv_hi);
     }
     lk_cnt = lk_hi - lk_lo;
+  }
+  // an error return between the fork and round 2's join: the side launch reads the arena and writes its workspace, both of
+  // which the next proof reuses, so it has finished before this proof's frame goes
+  ~ProofRun() {
+    if (sums_pending) hipStreamSynchronize(c->aux_stream);
   }
 
   // CQ_TRACE_HOST=1: microseconds since the start of the proof at the host's milestones, on stderr (development aid)
@@ -1085,7 +1107,7 @@ struct ProofRun {
         ra.slots[j] = lk.tables[j]->slots;
         ra.nslots[j] = lk.tables[j]->nslots;
       }
-      r1b.bucket[r1b.count] = b_by_rows ? (uint32_t*)(B.bpoly + l * n) : nullptr;  // (b's own buffer is free until round 2 writes it)
+      r1b.bucket[r1b.count] = b_by_rows ? B.b_index + l * n : nullptr;
       r1b.n = b_by_rows ? (uint32_t)n : 0;
       r1b.blind_bucket = (uint32_t)N;
       r1b.m_counts[r1b.count++] = B.m_counts + l * N;
@@ -1095,17 +1117,34 @@ struct ProofRun {
       }
     }
     CQ_TRY(cq_m_to_fr(c, B.m_counts, (uint32_t)(L * N), B.m_fr));  // the L vectors are adjacent
+    if (!sums_side) CQ_TRY(bucket_sum_launches());  // (otherwise beside the launch that commits [m]: fork_bucket_sums)
+    *herr = 0;
+    CQ_HIP(c, hipMemcpyAsync((void*)herr, B.err_dev, 4, hipMemcpyDeviceToHost, s));  // read after the next synchronisation
+    return CQ_OK;
+  }
+  // the per-table-row sums of the key's row bases over cq_round1's bucket indices (b_by_rows), on c->stream
+  int bucket_sum_launches() {
     for (size_t l0 = 0; b_by_rows && l0 < L; l0 += MSM_MAX_BATCH / 2) {
       std::vector<const uint32_t*> sc;
       std::vector<const G1Affine*> bs;
       for (size_t l = l0; l < std::min(L, l0 + MSM_MAX_BATCH / 2); l++)
-        for (int q = 0; q < 2; q++) { sc.push_back((const uint32_t*)(B.bpoly + l * n)); bs.push_back(pk->b_row_bases[q]); }
+        for (int q = 0; q < 2; q++) { sc.push_back(B.b_index + l * n); bs.push_back(pk->b_row_bases[q]); }
       if (msm_bucket_sums(c, sc.data(), bs.data(), (uint32_t)n, (uint32_t)sc.size(), (uint32_t)(N + 1), B.b_sums + 2 * l0 * (N + 1)) != 0)
         return c->fail(CQ_ERR_HIP, "bucket-sum launch failed");
     }
-    *herr = 0;
-    CQ_HIP(c, hipMemcpyAsync((void*)herr, B.err_dev, 4, hipMemcpyDeviceToHost, s));  // read after the next synchronisation
     return CQ_OK;
+  }
+  // The same launches on the side stream, queued right after the main-stream launch they run beside (`seq_before`: as for
+  // AuxFork): ordered after that launch's accumulate kernel, hence after cq_round1, which wrote the indices, and when the
+  // main stream is down to its latency-bound tail.  They go in front of the transforms AuxFork puts on that stream.
+  int fork_bucket_sums(uint64_t seq_before) {
+    if (!sums_side) return CQ_OK;
+    AuxFork fork(c);
+    CQ_TRY(fork.begin(seq_before));
+    sums_pending = true;
+    CQ_TRY(bucket_sum_launches());
+    CQ_HIP(c, hipEventRecord(c->b_sums_done, c->aux_stream));
+    return fork.end();
   }
   int lookup_error() {
     if (*herr == 1) return c->fail(CQ_ERR_LOOKUP, "witness value not in table");
@@ -1217,6 +1256,7 @@ struct ProofRun {
     Commit adv_cm;
     const uint64_t seq_adv = c->msm_tail_seq;
     if (!sc.empty()) CQ_TRY(adv_cm.begin(pk, sc, bs, ln));
+    if (early_m) CQ_TRY(fork_bucket_sums(seq_adv));
     if (early_adv) {
       // advice -> coefficients (prover.rs:587-603) on the side stream, behind this launch's accumulate kernel: it runs
       // under the launch's tail and the host's round trip for theta, when the GPU has little else to do -- after theta
@@ -1362,6 +1402,7 @@ struct ProofRun {
       Commit r1;
       const uint64_t seq = c->msm_tail_seq;
       if (!sc.empty()) CQ_TRY(r1.begin(pk, sc, bs, ln));
+      if (L && !early_m) CQ_TRY(fork_bucket_sums(seq));
       // (on the context's worker threads: the main thread goes on queueing the work that needs theta only)
       std::vector<size_t> f_lin;
       for (size_t l = 0; l < L; l++)
@@ -1585,6 +1626,10 @@ struct ProofRun {
       if (!random_late) { at.push_back(sc.size()); sc.push_back(B.random_poly); bs.push_back(pk->params->g); ln.push_back(n); }
       Commit r2cm;
       const uint64_t seq = c->msm_tail_seq;
+      if (sums_pending) {  // the short MSMs over B.b_sums are the first thing this launch queues
+        CQ_HIP(c, hipStreamWaitEvent(s, c->b_sums_done, 0));
+        sums_pending = false;
+      }
       CQ_TRY(r2cm.begin(pk, sc, bs, ln));
       {
         // under the launch's tail, none of it depending on y: advice -> coefficients (prover.rs:587-603, in place: the
