@@ -27,9 +27,9 @@ enum class Scratch {
                 // bytes of the Processed params / pk / G2 SRS readers and writers, the two G2 points of a params set-up or full
                 // stream); also g1_fft's twiddles: its callers (g1_to_lagrange,
                 // fk_table_quotients) run under entry points that hold neither entry buffer
-  MsmWork,      // capi_msm.hip, msm.hip (msm_bucket_sums): the workspace of one MSM launch on any stream but a side stream;
+  MsmWork,      // msm_multi.hip, msm.hip (msm_bucket_sums): the workspace of one MSM launch on any stream but a side stream;
                 // those launches follow one another on `stream`
-  MsmSums,      // capi_msm.hip: window sums, from msm_multi_begin to its msm_multi_end (launches are never nested)
+  MsmSums,      // msm_multi.hip: window sums, from msm_multi_begin to its msm_multi_end (launches are never nested)
   PolyTmp,      // poly.hip eval / kate, plonk.hip prefix_product partials, for one call each
   ProverArena,  // create_proof_dev's arena, for the whole proof
   ProverStage,  // create_proof_dev's resident receive staging or its legacy-lookup staging (never both: resident sharding

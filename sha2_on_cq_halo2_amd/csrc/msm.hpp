@@ -1,8 +1,12 @@
-// Internal interface of the MSM engine (see msm.hip).
+// Internal interface of the G1 MSM engine: msm.hip (launch driver, host folds), msm_sort.hip (sorting fronts), msm_plan.hip (plan scans),
+// msm_accumulate.hip (accumulate, combine, reduction, window tables), msm_short.hip (one-kernel short MSM), msm_multi.hip
+// (launch planner, table registry); the workspace description is msm_layout.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <optional>
 #include <vector>
 #include "curve.hpp"
+#include "msm_layout.hpp"
 
 struct cq_ctx;
 
@@ -27,20 +31,12 @@ constexpr uint32_t MSM_S1_BIG_LOAD = CQ_MSM_S1_BIG_LOAD;
 #endif
 constexpr uint32_t MSM_PARTIALS_TARGET = CQ_MSM_PARTIALS_TARGET;  // partial sums per bucket aimed at under heavy load (< MSM_SHORT)
 static_assert(MSM_S1_BIG >= MSM_S1, "the workspace is sized for MSM_S1");
-// Small launches (fewer than MSM_SMALL_LANES sub-lists of MSM_S1 entries): shorter sub-lists, down to MSM_S1_MIN, so that
-// the accumulate kernel -- a chain of dependent additions per lane, ~7 us each -- has a lane per few entries instead of
-// 17-24 of them on a fraction of the SIMDs (k = 14: one 16 384-term MSM was 140 us of pure latency).  A function of the
-// launch's entry BOUND (batch x windows x n), so that the workspace layout and the launch agree.
 #ifndef CQ_MSM_SMALL_LANES
 #define CQ_MSM_SMALL_LANES 65536
 #endif
 constexpr uint32_t MSM_S1_MIN = 4;
 constexpr uint64_t MSM_SMALL_LANES = CQ_MSM_SMALL_LANES;
-__host__ __device__ inline uint32_t msm_small_launch_s1(uint64_t entry_bound) {
-  if (entry_bound >= (uint64_t)MSM_S1 * MSM_SMALL_LANES) return MSM_S1;
-  const uint64_t s = entry_bound / MSM_SMALL_LANES;
-  return (uint32_t)(s < MSM_S1_MIN ? MSM_S1_MIN : s);
-}
+// (msm_small_launch_s1, the sub-list length of a small launch from its entry bound: msm_layout.hpp)
 // sub-lists of a launch whose entry COUNT (known on the device only) is small: at most 65536 x (s1 + 1) / s1 <= 1.25 x 65536
 // lanes' worth, plus an MSM that reads another one's lists (counted once more); 3 x 65536 bounds both
 constexpr uint64_t MSM_SMALL_PARTIALS = 3 * MSM_SMALL_LANES;
@@ -74,29 +70,71 @@ struct MsmStrides {
   uint64_t s[MSM_MAX_BATCH];
 };
 
-// Workspace carve-up for `batch` MSMs of n terms each with c-bit signed windows.
-struct MsmLayout {
-  // M: buckets per bucket SET (the reduction's rows x cols matrix), Wb: sets per MSM, B = Wb * M: buckets per MSM.
-  // Table mode has one set per MSM up to c = 15 (M = 2^(c-1)) and 2^(c-15) sets of 2^14 buckets for wider windows.
-  uint32_t n, c, batch, W, Wb, M, B, Bt, levels, nseq, nblk, rows, cols, npart, nfinal, shift1;
-  bool pre, part_sort, mid;
-  uint64_t tmax[8];
-  size_t off_ptrs, off_ranks, off_poff, off_poff2, off_counts, off_cursor, off_psize, off_psize2, off_buckets, off_ticket, zero_end, off_blocksums,
-      off_off, off_tk, off_sorted, off_part[2], off_pairs, total;
-  MsmLayout(uint32_t n_, uint32_t c_, uint32_t batch_, bool pre_ = false);
+// The tables a launch's first kernel (msm_set_ptrs_kernel) takes by value and writes to the workspace's pointer table.
+// lens: the length the SORT sees (0 for an MSM whose entry lists are another MSM's); src: the MSM whose lists an MSM reads.
+struct MsmTableRows {
+  MsmPtrs lists, bases;
+  MsmStrides strides, lens, src;
+};
+
+// Typed view of a launch's workspace: one member per thing the kernels are handed, built from the layout (msm_layout.hpp)
+// and the base pointer in ONE place.  Nothing else adds a layout offset to the workspace.
+struct MsmBuffers {
+  // the pointer table, five rows of `batch` entries (what msm_set_ptrs_kernel writes through `ptrs`)
+  const void** ptrs;
+  const void* const* lists;      // row 0: the scalars (Fr) -- in index mode the bucket numbers (uint32_t) stand here
+  const G1Affine* const* bases;  // row 1
+  const uint64_t *strides, *lens, *src;  // rows 2..4
+  const Fr* const* scalars() const { return (const Fr* const*)lists; }
+  const uint32_t* const* index() const { return (const uint32_t* const*)lists; }
+  // counts .. ticket are one span, cleared by the launch's first kernel as `zero_quads` 16-byte stores from `counts`
+  uint32_t *counts, *cursor, *ticket;
+  size_t zero_quads;
+  uint32_t* ranks;  // off_ranks, plain front: one rank per entry.  The partition front cuts the same region in up to four:
+  uint32_t *part_pay, *pay2;  // ... payloads of the partition pass and (refinement pass only, else null) of its output
+  void* part_low;             // ... the bucket inside the partition: uint8_t, with a refinement pass uint16_t
+  uint8_t* low2;              // ... what the refinement pass leaves of it (else null)
+  uint32_t *poff, *poff2;     // partition starts of the first pass / of the refinement pass
+  uint32_t *psize, *psize2;   // P sizes then P cursors, of the first pass / of the refinement pass
+  uint32_t *totals, *index_ticket;  // off_psize again, index front: the lists' entry totals and the count kernel's ticket
+  uint32_t* blocksums;        // [nseq][nblk] tile totals of the plan scans ...
+  uint32_t* s1_dev;           // ... and, behind them in the same region, the sub-list length the launch settles on
+  uint32_t *off /* [nseq][Bt + 1] */, *tk /* [levels][Bt] */, *sorted;
+  XYZZ *buckets, *part[2] /* partial sums, ping-pong over the combine levels */, *pairs /* row / column sums */;
+  MsmBuffers(const MsmLayout& L, void* workspace);
 };
 
 uint32_t msm_window_bits(uint32_t n);
-// Enqueues the whole pipeline on ctx->stream.
-// `scalars` / `bases`: HOST arrays of `batch` device pointers; window_sums_dev receives MSM_SET_POINTS points per
-// bucket set -- bit-plane sums the host folds into the set's value (msm_set_value; cols = MsmLayout::cols).
-// `index` (msm_bucket_sums only; `scalars` is then unused): bucket numbers instead of scalars, one entry per point.
-// `pre`: every bases[j] points to a precomputed table [W][table_stride] with table[w][i] = 2^(c*w)*base[i]
-// (msm_precompute_tables); then there is ONE bucket set per MSM.
-// lens[j] <= n: per-MSM lengths (one launch may mix lengths; n is the maximum)
-int msm_run(cq_ctx* ctx, const Fr* const* scalars, const G1Affine* const* bases, const size_t* lens, uint32_t n, uint32_t c,
-            uint32_t batch, bool pre, const size_t* table_strides, void* workspace, G1Jac* window_sums_dev,
-            G1Affine* raw_out = nullptr, uint32_t raw_count = 0, const uint32_t* const* index = nullptr);
+// What one launch of the generic pipeline works on; its shape (n, c, batch, table mode) is the layout's.  Table mode: every
+// bases[j] points to a precomputed table [W][stride] with table[w][i] = 2^(c*w)*base[i] (msm_precompute_tables); then there is
+// ONE bucket set (or 2^(c-15) of them) per MSM.  by_index (msm_bucket_sums, a table-mode layout): lists[j] holds bucket numbers
+// instead of scalars, one entry per point, and the launch ends at the bucket sums (raw_out).
+struct MsmLaunch {
+  bool by_index;
+  const void* const* lists;      // HOST array of `batch` device pointers: Fr scalars; by_index: uint32_t bucket numbers
+  const G1Affine* const* bases;  // HOST array of `batch` device pointers
+  const size_t* lens;            // per-MSM lengths <= n (one launch may mix lengths); null: n each
+  const size_t* strides;         // table mode: table stride per MSM; null: n each (a one-window table)
+  G1Jac* window_sums;            // MSM_SET_POINTS points per bucket set -- bit-plane sums the host folds (msm_set_value)
+  G1Affine* raw_out;             // by_index: the first raw_count buckets of every MSM, affine; else null
+  uint32_t raw_count;
+  size_t len(uint32_t i, const MsmLayout& L) const { return lens ? lens[i] : L.n; }
+  size_t stride(uint32_t i, const MsmLayout& L) const { return !L.pre ? 0 : strides ? strides[i] : L.n; }
+};
+// Enqueues the whole pipeline on ctx->stream.  L: the launch's shape; the caller sized `workspace` by it.
+int msm_run(cq_ctx* ctx, const MsmLaunch& ln, const MsmLayout& L, void* workspace);
+
+// The stages msm_run enqueues on stream s (msm_sort.hip, msm_plan.hip, msm_accumulate.hip).  s1: the host's sub-list length; any_alias:
+// some MSM reads another one's lists.
+void msm_enqueue_tables(hipStream_t s, const MsmLayout& L, const MsmBuffers& b, const MsmTableRows& rows);
+void msm_plan(hipStream_t s, const MsmLayout& L, const MsmBuffers& b, uint32_t s1, const uint32_t* s1_dev);
+void msm_front_plain(hipStream_t s, const MsmLayout& L, const MsmBuffers& b, uint32_t s1);
+void msm_front_partition(hipStream_t s, const MsmLayout& L, const MsmBuffers& b, uint32_t s1, bool any_alias);
+void msm_front_index(hipStream_t s, const MsmLayout& L, const MsmBuffers& b, uint32_t s1, bool any_alias, uint32_t count);
+void msm_accumulate(hipStream_t s, const MsmLayout& L, const MsmBuffers& b);
+void msm_combine_levels(hipStream_t s, const MsmLayout& L, const MsmBuffers& b);
+void msm_reduce_sets(hipStream_t s, const MsmLayout& L, const MsmBuffers& b, G1Jac* window_sums);
+void msm_emit_buckets(hipStream_t s, const MsmLayout& L, const MsmBuffers& b, uint32_t count, G1Affine* out);
 // `batch` plain-mode MSMs of n <= MSM_SHORT_LIMIT terms each in ONE kernel on ctx->stream; window_sums_dev as for msm_run with
 // c = MSM_SHORT_C (MSM_SHORT_W one-row bucket sets per MSM: the column planes and the total of every set are written);
 // workspace: msm_short_workspace(n, batch) bytes
@@ -136,8 +174,9 @@ int cq_msm_multi_v(cq_ctx* c, const cq::Fr* const* scalars, const cq::G1Affine* 
 struct MsmPending {
   struct Launch {
     size_t first = 0, slot = 0;
-    uint32_t batch = 0, c = 0, nmax = 0, W = 0, Wb = 0, M = 0, cols = 0;
-    bool pre = false, empty = false;
+    uint32_t batch = 0;
+    bool empty = false;
+    std::optional<cq::MsmLayout> L;  // the launch's shape and workspace (a short launch: the plain c = 8 layout it is folded by); none for an empty one
     bool short_path = false;  // msm_short_run: the result has a plain launch's layout (c = 8), msm_multi_end folds it the same way
   };
   std::vector<Launch> launches;
@@ -153,7 +192,7 @@ int msm_multi_end(cq_ctx* c, MsmPending& pend, uint64_t* out_jac);
 constexpr uint32_t MSM_TABLE_C = 15, MSM_TABLE_C_MIN = 8, MSM_TABLE_C_MAX = 20;
 uint32_t msm_table_window_bits(size_t n);
 
-// Registry of the window tables (capi_msm.hip).  msm_register_tables: makes sure MSMs over [bases, bases + n) find a table --
+// Registry of the window tables (msm_multi.hip).  msm_register_tables: makes sure MSMs over [bases, bases + n) find a table --
 // of width `want_c` when given, else of the width the array's own length calls for (or the caller's override).  *held
 // (optional) tells whether the caller now holds a reference of an entry for exactly (bases, n, width) -- created, or found
 // and shared -- that it must give back with msm_release_table; false when the range is served by a larger array's table.

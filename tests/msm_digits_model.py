@@ -1,4 +1,4 @@
-"""CPU model of the MSM's signed-digit recoding (msm.hip: signed_digit) and of which sorting front a launch takes
+"""CPU model of the MSM's signed-digit recoding (msm_sort.hip: signed_digit) and of which sorting front a launch takes
 (MsmLayout::part_sort / mid, part_shift_of, msm_multi_begin's cut-over to the short kernel), plus the crafted scalars the
 edge tests feed to every front: each family is built for ONE digit event (a digit exactly M, a zero digit that still
 carries, a carry chain into the top window, ...).  tests/test_msm_digits_cpu.py holds the model to the events, and
@@ -15,7 +15,9 @@ R = B.R_MOD
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _CSRC = os.path.join(ROOT, "sha2_on_cq_halo2_amd", "csrc")
 _HPP = open(os.path.join(_CSRC, "msm.hpp")).read()
-_HIP = open(os.path.join(_CSRC, "msm.hip")).read()
+_HIP = open(os.path.join(_CSRC, "msm.hip")).read()            # msm_window_bits; the overview quotes the layout's routing lines
+_SORT = open(os.path.join(_CSRC, "msm_sort.hip")).read()      # the partition front and its specialisations
+_LAYOUT = open(os.path.join(_CSRC, "msm_layout.hpp")).read()  # MsmLayout: what routes a launch to a front
 
 
 def _shift_const(text, name):
@@ -23,20 +25,22 @@ def _shift_const(text, name):
     return 1 << int(re.search(r"\b%s = 1u << (\d+)" % name, text).group(1))
 
 
+def routing_constants(text):
+    """(PSC_MAX_WIN, PART_BITS, PART_BITS_WIDE, DIGITS_LDS_MAX_M, REFINE_ABOVE, REFINE_SHIFT, WIDE_ABOVE, MID_ABOVE) as `text` states them:
+    part_shift_of(c): c > REFINE_ABOVE ? c - REFINE_SHIFT : c > WIDE_ABOVE ? PART_BITS_WIDE : PART_BITS;
+    MsmLayout: mid = part_sort && c > MID_ABOVE"""
+    m = re.search(r"part_shift_of\(uint32_t c\) \{ return c > (\d+) \? c - (\d+) : c > (\d+) \? PART_BITS_WIDE : PART_BITS; \}", text)
+    return (int(re.search(r"PSC_MAX_WIN = (\d+)", text).group(1)), int(re.search(r"\bPART_BITS = (\d+)", text).group(1)),
+            int(re.search(r"\bPART_BITS_WIDE = (\d+)", text).group(1)), _shift_const(text, "DIGITS_LDS_MAX_M")) + tuple(int(g) for g in m.groups()) + (
+                int(re.search(r"mid = part_sort && c > (\d+);", text).group(1)),)
+
+
 MSM_SHORT_MAX = int(re.search(r"#define CQ_MSM_SHORT_MAX (\d+)", _HPP).group(1))
 MSM_TABLE_C_MIN = int(re.search(r"MSM_TABLE_C_MIN = (\d+)", _HPP).group(1))
 MSM_TABLE_C_MAX = int(re.search(r"MSM_TABLE_C_MAX = (\d+)", _HPP).group(1))
-PSC_MAX_WIN = int(re.search(r"PSC_MAX_WIN = (\d+)", _HIP).group(1))
-PART_BITS = int(re.search(r"\bPART_BITS = (\d+)", _HIP).group(1))
-PART_BITS_WIDE = int(re.search(r"\bPART_BITS_WIDE = (\d+)", _HIP).group(1))
-DIGITS_LDS_MAX_M = _shift_const(_HIP, "DIGITS_LDS_MAX_M")
-# part_shift_of(c): c > REFINE_ABOVE ? c - REFINE_SHIFT : c > WIDE_ABOVE ? PART_BITS_WIDE : PART_BITS
-_m = re.search(r"part_shift_of\(uint32_t c\) \{ return c > (\d+) \? c - (\d+) : c > (\d+) \? PART_BITS_WIDE : PART_BITS; \}", _HIP)
-REFINE_ABOVE, REFINE_SHIFT, WIDE_ABOVE = (int(g) for g in _m.groups())
-# MsmLayout: mid = part_sort && c > MID_ABOVE
-MID_ABOVE = int(re.search(r"mid = part_sort && c > (\d+);", _HIP).group(1))
+PSC_MAX_WIN, PART_BITS, PART_BITS_WIDE, DIGITS_LDS_MAX_M, REFINE_ABOVE, REFINE_SHIFT, WIDE_ABOVE, MID_ABOVE = routing_constants(_LAYOUT)
 # the (c, W) pairs whose first partition pass has the window width and count as compile-time constants
-PART_SPECIALISED = [(int(a), int(b)) for a, b in re.findall(r"launch_part_pass1<(\d+), (\d+), uint\d+_t>", _HIP) if int(a)]
+PART_SPECIALISED = [(int(a), int(b)) for a, b in re.findall(r"launch_part_pass1<(\d+), (\d+), uint\d+_t>", _SORT) if int(a)]
 # msm_window_bits(n): [(threshold, c)], largest threshold first, and the width below the last one
 _body = re.search(r"uint32_t msm_window_bits\(uint32_t n\) \{(.*?)\n\}", _HIP, re.S).group(1)
 WINDOW_BITS = [((1 << int(s)) if s else int(v), int(c)) for s, v, c in

@@ -1,4 +1,4 @@
-"""GPU: the index front of the bucket-sum launch (msm.hip: msm_index_count_kernel / msm_index_place_kernel).
+"""GPU: the index front of the bucket-sum launch (msm_sort.hip: msm_index_count_kernel / msm_index_place_kernel).
 
 Context.msm_bucket_sums hands uint32 bucket indices straight to the launch; every bucket of every array is checked against
 host sums of the same points (the C oracle's multiexp with unit scalars).  The shapes are the smallest at which the two

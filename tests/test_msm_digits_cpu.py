@@ -137,6 +137,11 @@ def test_routing_table_the_gpu_tests_rely_on():
     assert (D.PART_BITS, D.PART_BITS_WIDE) == (7, 8)
 
 
+def test_driver_overview_quotes_the_layout():
+    """msm.hip's overview quotes the layout's routing lines for the reader of the driver: the quotation says what msm_layout.hpp says"""
+    assert D.routing_constants(D._HIP) == D.routing_constants(D._LAYOUT)
+
+
 def test_short_cut_over_and_automatic_widths():
     assert D.MSM_SHORT_MAX == 16384
     assert D.plain_path(D.MSM_SHORT_MAX) == ("short", 8)

@@ -435,7 +435,7 @@ def test_quad_add_matches_lane_serial_addition(tmp_path):
 
 
 def test_combine_wave_half_strides_over_more_slots_than_waves():
-    """The combine levels' wave half is a capped grid whose waves stride over the sub-list slots (msm.hip: one block per four
+    """The combine levels' wave half is a capped grid whose waves stride over the sub-list slots (msm_accumulate.hip: one block per four
     POSSIBLE slots was a million empty blocks per level at k = 22).  With the default cap of 2048 blocks only launches of
     2^20 equal scalars and more have more slots than waves, so a child process shrinks the cap to ONE block
     (CQ_MSM_COMBINE_WAVE_BLOCKS=1: four waves) and sums columns whose entries all fall into one bucket per window -- a

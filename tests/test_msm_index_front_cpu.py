@@ -6,7 +6,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-INDEX_SLOTS = 2 * 256 * 8  # msm.hip: two slots per row of a tile
+INDEX_SLOTS = 2 * 256 * 8  # msm_sort.hip: two slots per row of a tile
 COUNT_LDS = 2 * INDEX_SLOTS * 4 + 4  # keys, counts, the tile's total
 PLACE_LDS = 2 * INDEX_SLOTS * 4      # keys, runs
 

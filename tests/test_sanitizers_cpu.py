@@ -67,3 +67,18 @@ def test_pk_describe_under_asan_ubsan(tmp_path):
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
     lines = r.stdout.strip().splitlines()
     assert lines[0] == "0 " and len(lines) == 1 + 17 + 1 and all(ln.startswith("-1 ") for ln in lines[1:-1])
+
+
+def test_msm_layout_under_asan_ubsan(tmp_path):
+    """The workspace description of an MSM launch (csrc/msm_layout.hpp, HIP-free; tests/host/msm_layout_check.cpp) over 342
+    plain and table shapes: regions aligned, ordered and long enough, the typed view's sub-regions inside theirs, and the
+    values the constructor gave before it moved into the header."""
+    exe = str(tmp_path / "msm_layout_check")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "host", "msm_layout_check.cpp"), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", ASAN_OPTIONS="detect_leaks=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().splitlines() == ["342 shapes", "ok"], r.stdout[-3000:] + r.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of two variants of some csrc files (on the GPU box): ab_tmp/old/* and ab_tmp/new/* are copied over
 # sha2_on_cq_halo2_amd/csrc in turn, the library is rebuilt, and bench.py's headline numbers are printed (two rounds).
-#   mkdir -p ab_tmp/old ab_tmp/new; git show HEAD:sha2_on_cq_halo2_amd/csrc/msm.hip > ab_tmp/old/msm.hip; cp ... ab_tmp/new/
+#   mkdir -p ab_tmp/old ab_tmp/new; git show HEAD:sha2_on_cq_halo2_amd/csrc/msm_sort.hip > ab_tmp/old/msm_sort.hip; cp ... ab_tmp/new/
 #   gpurun -- 'bash tools/ab_sources.sh > gpurun_out/ab.txt'
 cd $GRAFT_REPO_ROOT
 for round in 1 2 3; do
