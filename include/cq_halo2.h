@@ -815,6 +815,67 @@ int cq_sha_decomposition_table_dev(cq_ctx* ctx, uint32_t first_limb_len, uint32_
 /* dense[i] = i, spread[i] = bit-spread(i) for i < size (device arrays of `size` elements). */
 int cq_sha_spread_table_dev(cq_ctx* ctx, size_t size, uint64_t* dense_dev, uint64_t* spread_dev);
 
+/* ---- SHA-256 compression circuit: layout and witness synthesis (no counterpart in the reference) --------------- */
+/* The circuit (sha2_on_cq_halo2_amd/sha256_circuit.py, DESIGN.md "SHA-256 compression circuit") is laid out in regions
+ * of CQ_SHA256_REGION_ROWS rows over CQ_SHA256_ADVICE_COLUMNS advice columns: CQ_SHA256_PAIRS (dense, spread) column
+ * pairs -- columns 2j and 2j+1 -- and two plain columns behind them.  A block takes CQ_SHA256_BLOCK_REGIONS regions:
+ * four that hold the incoming state (a_-1 .. a_-4, e_-1 .. e_-4) and one per round; CQ_SHA256_TAIL_REGIONS more after
+ * the last block hold the digest.  Every cell of a region is a bit field of one 32-bit word of that region (the
+ * `kind`, CQ_SHA256_SRC_*), described once in csrc/sha256_layout.hpp; the synthesis kernel and the constraint system
+ * both read that table, the latter through cq_sha256_layout.  A cell is CQ_SHA256_CELL_WORDS words
+ * (kind, form, column, row, offset, per_table_bits, len):
+ *   form    CQ_SHA256_FORM_WORD: the field itself at (column, row); CQ_SHA256_FORM_SPREAD: its bit-spread form
+ *           (bit i -> bit 2i, a 64-bit value); CQ_SHA256_FORM_PAIR: the field at (column, row) and its bit-spread form
+ *           at (column + 1, row), both looked up
+ *   offset, per_table_bits, len    the field is bits [offset + per_table_bits * table_bits, .. + len) of the word;
+ *           len = 0 stands for "table_bits bits, or as many as the word has left" (a chunk of an even / odd word) */
+#define CQ_SHA256_REGION_ROWS 8
+#define CQ_SHA256_BLOCK_REGIONS 68
+#define CQ_SHA256_TAIL_REGIONS 4
+#define CQ_SHA256_PAIRS 8
+#define CQ_SHA256_ADVICE_COLUMNS 18
+#define CQ_SHA256_MIN_TABLE_BITS 11
+#define CQ_SHA256_MAX_TABLE_BITS 16
+#define CQ_SHA256_FORM_WORD 0
+#define CQ_SHA256_FORM_PAIR 1
+#define CQ_SHA256_FORM_SPREAD 2
+#define CQ_SHA256_SRC_A 0      /* a_r, the first working variable after round r (r < 0: the incoming state) */
+#define CQ_SHA256_SRC_E 1      /* e_r */
+#define CQ_SHA256_SRC_W 2      /* the schedule word W_r */
+#define CQ_SHA256_SRC_S0_EVEN 3   /* Sigma0(a_r): the even (xor) and odd (carry) bits of the three rotations' sum */
+#define CQ_SHA256_SRC_S0_ODD 4
+#define CQ_SHA256_SRC_S1_EVEN 5   /* Sigma1(e_r) */
+#define CQ_SHA256_SRC_S1_ODD 6
+#define CQ_SHA256_SRC_MAJ_EVEN 7  /* a_r + a_(r-1) + a_(r-2) bitwise: odd = Maj */
+#define CQ_SHA256_SRC_MAJ_ODD 8
+#define CQ_SHA256_SRC_CHP_EVEN 9  /* e_r + e_(r-1) bitwise: odd = e_r & e_(r-1) */
+#define CQ_SHA256_SRC_CHP_ODD 10
+#define CQ_SHA256_SRC_CHQ_EVEN 11 /* ~e_r + e_(r-2) bitwise: odd = ~e_r & e_(r-2) */
+#define CQ_SHA256_SRC_CHQ_ODD 12
+#define CQ_SHA256_SRC_G0_EVEN 13  /* sigma0(W_r) */
+#define CQ_SHA256_SRC_G0_ODD 14
+#define CQ_SHA256_SRC_G1_EVEN 15  /* sigma1(W_r) */
+#define CQ_SHA256_SRC_G1_ODD 16
+#define CQ_SHA256_SRC_CARRY_A 17  /* carry of the addition that gives a_r */
+#define CQ_SHA256_SRC_CARRY_E 18  /* carry of the addition that gives e_r */
+#define CQ_SHA256_SRC_CARRY_W 19  /* carry of the addition that gives W_r (rounds 16 .. 63) */
+#define CQ_SHA256_SRC_K 20        /* the witness copy of the round constant K_r */
+#define CQ_SHA256_SRC_CH 21       /* Ch(e_r, e_(r-1), e_(r-2)) = the two odd words above, added */
+#define CQ_SHA256_SRC_COUNT 22
+#define CQ_SHA256_CELL_WORDS 7 /* a cell of the layout table: kind, form, column, row, offset, per_table_bits, len */
+/* Host only: writes the first `cap` cells of the layout table to `cells` (CQ_SHA256_CELL_WORDS words each; may be NULL
+ * with cap = 0) and the number of cells the table has to *count. */
+int cq_sha256_layout(uint32_t* cells, size_t cap, size_t* count);
+/* Fills the CQ_SHA256_ADVICE_COLUMNS advice columns of the circuit for `blocks` chained 64-byte blocks on the context's
+ * stream: `msg_words` are the 16 * blocks big-endian words of the padded message (host memory), `cols_dev` device columns
+ * of `n` elements each; every row is written, Montgomery-encoded, the rows behind the
+ * (CQ_SHA256_BLOCK_REGIONS * blocks + CQ_SHA256_TAIL_REGIONS) * CQ_SHA256_REGION_ROWS the layout uses with zero.  The
+ * compression chain runs on the host (64 sequential rounds per block); a kernel expands its (a, e, W) words into the
+ * cells.  `digest` receives the eight words of SHA-256's output, which the last four regions hold.  CQ_ERR_ARG:
+ * table_bits outside [CQ_SHA256_MIN_TABLE_BITS, CQ_SHA256_MAX_TABLE_BITS], or n too small for the rows used. */
+int cq_sha256_synthesize_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* msg_words, size_t blocks, size_t n,
+                             uint64_t* const* cols_dev, uint32_t digest[8]);
+
 /* ---- harness RNG (not in the reference: its test draws from OsRng) ---------------------------------- */
 void cq_xoshiro256ss_seed(uint64_t seed, uint64_t state[4]);
 uint64_t cq_xoshiro256ss_next_u64(void* state /* uint64_t[4] */);

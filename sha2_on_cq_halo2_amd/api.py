@@ -16,3 +16,4 @@ from ._marshal import (FAIL_GATE, FAIL_GATE_POISONED, FAIL_LOOKUP, FAIL_PERMUTAT
 from .context import Context, DevBuf, rccl_unique_id  # noqa: F401
 from .params import EvaluationDomain, G2Srs, ParamsKZG, StaticTable, TableConfig  # noqa: F401
 from .proving_key import ProvingKey, WitnessError, WitnessFailure, _lower_plonk  # noqa: F401
+from .sha256_circuit import Sha256Circuit  # noqa: F401  (last: its constructor reaches sha_circuit, which imports this module)

@@ -1,0 +1,222 @@
+// SHA-256 compression circuit: witness synthesis.  The compression chain (64 sequential rounds per block, a few
+// microseconds per block) runs on the host and leaves four words per region -- a_r, e_r, W_r and what kind of region it
+// is; the kernel below expands them into the 18 advice columns, one thread per row: every cell is a bit field of a word
+// that a handful of xors and additions of the region's and its neighbours' (a, e, W) give, placed by the layout table of
+// sha256_layout.hpp.  The work is the 18 x n Montgomery encodings and their stores (151 MB at k = 18).
+#include <utility>
+#include <vector>
+
+#include "cq.hpp"
+#include "ctx.hpp"
+#include "sha256_layout.hpp"
+#include "tablehash.hpp"
+
+namespace cq {
+
+// region kinds (Sha256Region::meta, low byte; the round number sits above it)
+constexpr uint32_t SHA_RG_ROUND = 1;  // a compression round: the additions that give a_r and e_r, the copy of K_r
+constexpr uint32_t SHA_RG_SCHED = 2;  // rounds 16 .. 63: W_r is a schedule word
+constexpr uint32_t SHA_RG_CHAIN = 4;  // incoming state of a block after the first, or the digest: H + (a .. h)
+constexpr uint32_t SHA_RG_F3 = 8;     // Maj and Ch are laid out (the two regions before this one hold state words)
+
+struct Sha256Region {
+  uint32_t a, e, w, meta;
+};
+
+struct Sha256Cols {
+  Fr* p[CQ_SHA256_ADVICE_COLUMNS];
+};
+
+#define SHA256_K_VALUES \
+  0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be, \
+  0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, \
+  0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85, \
+  0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, \
+  0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, \
+  0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2
+static const uint32_t SHA256_K_HOST[64] = {SHA256_K_VALUES};
+__constant__ const uint32_t SHA256_K_DEV[64] = {SHA256_K_VALUES};
+static const uint32_t SHA256_IV[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+
+#define SHA_HD __host__ __device__ __forceinline__
+static SHA_HD uint32_t rotr(uint32_t x, uint32_t n) { return (x >> n) | (x << (32 - n)); }
+static SHA_HD uint32_t xor3(uint32_t x, uint32_t y, uint32_t z) { return x ^ y ^ z; }
+static SHA_HD uint32_t maj3(uint32_t x, uint32_t y, uint32_t z) { return (x & y) | (x & z) | (y & z); }
+static SHA_HD uint32_t big_sigma0(uint32_t a) { return xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)); }
+static SHA_HD uint32_t big_sigma1(uint32_t e) { return xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)); }
+static SHA_HD uint32_t small_sigma0(uint32_t w) { return xor3(rotr(w, 7), rotr(w, 18), w >> 3); }
+static SHA_HD uint32_t small_sigma1(uint32_t w) { return xor3(rotr(w, 17), rotr(w, 19), w >> 10); }
+static SHA_HD uint32_t ch3(uint32_t e, uint32_t f, uint32_t g) { return (e & f) | (~e & g); }
+
+// bit i -> bit 2i of a 32-bit word
+static __device__ __forceinline__ uint64_t spread32(uint32_t w) {
+  uint64_t x = w;
+  x = (x | (x << 16)) & 0x0000ffff0000ffffull;
+  x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
+  x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
+  x = (x | (x << 2)) & 0x3333333333333333ull;
+  x = (x | (x << 1)) & 0x5555555555555555ull;
+  return x;
+}
+
+// cell I of the layout table, if it sits in row r: the bit field of its word, and the spread form where the cell has one.
+// The table entry is a compile-time constant, so `src` and `out` are only ever indexed by constants and stay in registers.
+template <uint32_t I>
+static __device__ __forceinline__ void sha256_place(const uint32_t (&src)[CQ_SHA256_SRC_COUNT], uint64_t (&out)[CQ_SHA256_ADVICE_COLUMNS],
+                                                    uint32_t r, uint32_t table_bits) {
+  constexpr Sha256Cell c = SHA256_CELLS[I];
+  static_assert(c.kind < CQ_SHA256_SRC_COUNT && c.row < CQ_SHA256_REGION_ROWS, "layout table: word or row out of range");
+  static_assert(c.column + (c.form == CQ_SHA256_FORM_PAIR ? 1 : 0) < CQ_SHA256_ADVICE_COLUMNS, "layout table: column out of range");
+  if (c.row != r) return;
+  const uint32_t off = c.offset + c.per_table_bits * table_bits;
+  const uint32_t len = c.len ? c.len : table_bits;
+  const uint32_t field = off < 32 ? (src[c.kind] >> off) & (len < 32 ? (1u << len) - 1 : 0xffffffffu) : 0;
+  out[c.column] = c.form == CQ_SHA256_FORM_SPREAD ? spread32(field) : field;
+  if (c.form == CQ_SHA256_FORM_PAIR) out[c.column + 1] = spread32(field);
+}
+template <uint32_t... I>
+static __device__ __forceinline__ void sha256_place_all(const uint32_t (&src)[CQ_SHA256_SRC_COUNT], uint64_t (&out)[CQ_SHA256_ADVICE_COLUMNS],
+                                                        uint32_t r, uint32_t table_bits, std::integer_sequence<uint32_t, I...>) {
+  (sha256_place<I>(src, out, r, table_bits), ...);
+}
+
+// the row's cell of every column, Montgomery-encoded; a fold over the columns, because a loop the compiler declines to
+// unroll would index `out` at run time and send it to scratch memory
+template <uint32_t... I>
+static __device__ __forceinline__ void sha256_store_all(const Sha256Cols& cols, const uint64_t (&out)[CQ_SHA256_ADVICE_COLUMNS], uint32_t row,
+                                                        std::integer_sequence<uint32_t, I...>) {
+  (st(cols.p[I] + row, out[I] ? Fr::from_u64(out[I]) : Fr::zero()), ...);
+}
+
+// One thread per row.  `regions` holds `nregions` entries; rows behind them are written as zero.  Every index below is
+// guarded by the region kind the host sets and by the region index itself.
+__global__ __launch_bounds__(256) void sha256_expand_kernel(const Sha256Region* __restrict__ regions, uint32_t nregions, uint32_t n,
+                                                            uint32_t table_bits, Sha256Cols cols) {
+  const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n) return;
+  const uint32_t g = row / CQ_SHA256_REGION_ROWS, r = row % CQ_SHA256_REGION_ROWS;
+  uint64_t out[CQ_SHA256_ADVICE_COLUMNS];
+  CQ_UNROLL for (uint32_t i = 0; i < CQ_SHA256_ADVICE_COLUMNS; i++) out[i] = 0;
+  if (g < nregions) {
+    const Sha256Region cur = regions[g];
+    const uint32_t kind = cur.meta & 0xffu;
+    uint32_t src[CQ_SHA256_SRC_COUNT];
+    CQ_UNROLL for (uint32_t i = 0; i < CQ_SHA256_SRC_COUNT; i++) src[i] = 0;
+    src[CQ_SHA256_SRC_A] = cur.a;
+    src[CQ_SHA256_SRC_E] = cur.e;
+    src[CQ_SHA256_SRC_W] = cur.w;
+    src[CQ_SHA256_SRC_S0_EVEN] = big_sigma0(cur.a);
+    src[CQ_SHA256_SRC_S0_ODD] = maj3(rotr(cur.a, 2), rotr(cur.a, 13), rotr(cur.a, 22));
+    src[CQ_SHA256_SRC_S1_EVEN] = big_sigma1(cur.e);
+    src[CQ_SHA256_SRC_S1_ODD] = maj3(rotr(cur.e, 6), rotr(cur.e, 11), rotr(cur.e, 25));
+    src[CQ_SHA256_SRC_G0_EVEN] = small_sigma0(cur.w);
+    src[CQ_SHA256_SRC_G0_ODD] = maj3(rotr(cur.w, 7), rotr(cur.w, 18), cur.w >> 3);
+    src[CQ_SHA256_SRC_G1_EVEN] = small_sigma1(cur.w);
+    src[CQ_SHA256_SRC_G1_ODD] = maj3(rotr(cur.w, 17), rotr(cur.w, 19), cur.w >> 10);
+    if ((kind & SHA_RG_F3) && g >= 2) {
+      const Sha256Region p1 = regions[g - 1], p2 = regions[g - 2];
+      src[CQ_SHA256_SRC_MAJ_EVEN] = xor3(cur.a, p1.a, p2.a);
+      src[CQ_SHA256_SRC_MAJ_ODD] = maj3(cur.a, p1.a, p2.a);
+      src[CQ_SHA256_SRC_CHP_EVEN] = cur.e ^ p1.e;
+      src[CQ_SHA256_SRC_CHP_ODD] = cur.e & p1.e;
+      src[CQ_SHA256_SRC_CHQ_EVEN] = ~cur.e ^ p2.e;
+      src[CQ_SHA256_SRC_CHQ_ODD] = ~cur.e & p2.e;
+      src[CQ_SHA256_SRC_CH] = ch3(cur.e, p1.e, p2.e);
+    }
+    if ((kind & SHA_RG_ROUND) && g >= 4) {
+      const Sha256Region p1 = regions[g - 1], p2 = regions[g - 2], p3 = regions[g - 3], p4 = regions[g - 4];
+      const uint32_t k = SHA256_K_DEV[(cur.meta >> 8) & 63u];
+      const uint64_t t1 = (uint64_t)p4.e + big_sigma1(p1.e) + ch3(p1.e, p2.e, p3.e) + k + cur.w;
+      src[CQ_SHA256_SRC_K] = k;
+      src[CQ_SHA256_SRC_CARRY_E] = (uint32_t)((t1 + p4.a) >> 32);
+      src[CQ_SHA256_SRC_CARRY_A] = (uint32_t)((t1 + big_sigma0(p1.a) + maj3(p1.a, p2.a, p3.a)) >> 32);
+    }
+    if ((kind & SHA_RG_SCHED) && g >= 16)
+      src[CQ_SHA256_SRC_CARRY_W] = (uint32_t)(((uint64_t)small_sigma1(regions[g - 2].w) + regions[g - 7].w +
+                                               small_sigma0(regions[g - 15].w) + regions[g - 16].w) >> 32);
+    if ((kind & SHA_RG_CHAIN) && g >= CQ_SHA256_BLOCK_REGIONS) {
+      const Sha256Region h = regions[g - CQ_SHA256_BLOCK_REGIONS], v = regions[g - 4];
+      src[CQ_SHA256_SRC_CARRY_A] = (uint32_t)(((uint64_t)h.a + v.a) >> 32);
+      src[CQ_SHA256_SRC_CARRY_E] = (uint32_t)(((uint64_t)h.e + v.e) >> 32);
+    }
+    sha256_place_all(src, out, r, table_bits, std::make_integer_sequence<uint32_t, SHA256_NUM_CELLS>{});
+  }
+  sha256_store_all(cols, out, row, std::make_integer_sequence<uint32_t, CQ_SHA256_ADVICE_COLUMNS>{});
+}
+
+// the compression chain: the (a, e, W) words and the kind of every region, and the digest
+static void sha256_regions(const uint32_t* msg, size_t blocks, std::vector<Sha256Region>& rg, uint32_t digest[8]) {
+  uint32_t h[8];
+  for (int i = 0; i < 8; i++) h[i] = SHA256_IV[i];
+  rg.reserve(blocks * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS);
+  auto state_regions = [&](bool chained) {  // a_-4 .. a_-1 = d, c, b, a and e_-4 .. e_-1 = h, g, f, e
+    for (uint32_t i = 0; i < 4; i++) rg.push_back({h[3 - i], h[7 - i], 0, (chained ? SHA_RG_CHAIN : 0) | (i >= 2 ? SHA_RG_F3 : 0)});
+  };
+  for (size_t b = 0; b < blocks; b++) {
+    state_regions(b > 0);
+    uint32_t w[64];
+    for (int t = 0; t < 16; t++) w[t] = msg[16 * b + t];
+    for (int t = 16; t < 64; t++) w[t] = small_sigma1(w[t - 2]) + w[t - 7] + small_sigma0(w[t - 15]) + w[t - 16];
+    uint32_t s[8];
+    for (int i = 0; i < 8; i++) s[i] = h[i];
+    for (uint32_t t = 0; t < 64; t++) {
+      const uint32_t t1 = s[7] + big_sigma1(s[4]) + ch3(s[4], s[5], s[6]) + SHA256_K_HOST[t] + w[t];
+      const uint32_t t2 = big_sigma0(s[0]) + maj3(s[0], s[1], s[2]);
+      for (int i = 7; i > 0; i--) s[i] = s[i - 1];
+      s[4] += t1;
+      s[0] = t1 + t2;
+      rg.push_back({s[0], s[4], w[t], SHA_RG_ROUND | SHA_RG_F3 | (t >= 16 ? SHA_RG_SCHED : 0) | t << 8});
+    }
+    for (int i = 0; i < 8; i++) h[i] += s[i];
+  }
+  state_regions(true);
+  for (int i = 0; i < 8; i++) digest[i] = h[i];
+}
+
+int sha256_synthesize(cq_ctx* c, uint32_t table_bits, const uint32_t* msg_words, size_t blocks, uint32_t n, const Sha256Cols& cols,
+                      uint32_t digest[8]) {
+  std::vector<Sha256Region> rg;
+  sha256_regions(msg_words, blocks, rg, digest);
+  if (rg.size() * CQ_SHA256_REGION_ROWS > n) return c->fail(CQ_ERR_ARG, "sha256: the blocks do not fit the rows");
+  static_assert(sizeof(Sha256Region) == 16, "four words per region");
+  void* dev;
+  int rc = c->ensure_scratch(Scratch::EntryA, rg.size() * sizeof(Sha256Region), &dev);
+  if (rc != CQ_OK) return rc;
+  CQ_HIP(c, hipMemcpyAsync(dev, rg.data(), rg.size() * sizeof(Sha256Region), hipMemcpyHostToDevice, c->stream));
+  CQ_HIP(c, hipStreamSynchronize(c->stream));  // `rg` is pageable and goes away with this call
+  sha256_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha256Region*)dev, (uint32_t)rg.size(), n, table_bits, cols);
+  return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "sha256_expand launch failed");
+}
+
+}  // namespace cq
+
+using namespace cq;
+
+extern "C" {
+
+int cq_sha256_layout(uint32_t* cells, size_t cap, size_t* count) {
+  if (!count || (cap && !cells)) return CQ_ERR_ARG;
+  *count = SHA256_NUM_CELLS;
+  for (size_t i = 0; i < cap && i < SHA256_NUM_CELLS; i++) {
+    const Sha256Cell& s = SHA256_CELLS[i];
+    const uint32_t words[CQ_SHA256_CELL_WORDS] = {s.kind, s.form, s.column, s.row, s.offset, s.per_table_bits, s.len};
+    for (uint32_t j = 0; j < CQ_SHA256_CELL_WORDS; j++) cells[i * CQ_SHA256_CELL_WORDS + j] = words[j];
+  }
+  return CQ_OK;
+}
+
+int cq_sha256_synthesize_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* msg_words, size_t blocks, size_t n,
+                             uint64_t* const* cols_dev, uint32_t digest[8]) {
+  if (!c || !msg_words || !cols_dev || !digest || blocks == 0 || n > 0x7fffffffull || blocks > n) return CQ_ERR_ARG;
+  if (table_bits < CQ_SHA256_MIN_TABLE_BITS || table_bits > CQ_SHA256_MAX_TABLE_BITS)
+    return c->fail(CQ_ERR_ARG, "sha256: table_bits outside the range the pieces fit");
+  CQ_HIP(c, hipSetDevice(c->device));
+  Sha256Cols sc;
+  for (uint32_t i = 0; i < CQ_SHA256_ADVICE_COLUMNS; i++) {
+    if (!cols_dev[i]) return c->fail(CQ_ERR_ARG, "sha256: null column");
+    sc.p[i] = (Fr*)cols_dev[i];
+  }
+  return sha256_synthesize(c, table_bits, msg_words, blocks, (uint32_t)n, sc, digest);
+}
+
+}  // extern "C"
