@@ -729,7 +729,7 @@ int cq_permute_expression_pair_dev(cq_ctx* ctx, uint32_t k, uint32_t usable, con
                                    uint64_t* permuted_input_dev, uint64_t* permuted_table_dev);
 /* ---- the other heavy stages of create_proof on their own: with the calls above, every stage of a general circuit's
  * proof can be swapped in one by one (INTEGRATION.md has the whole call sequence).  They run the code cq_create_proof*
- * runs for the same stage (prover.hip), on the key's domain, window tables and scratch buffers.  Shapes: n = 2^k,
+ * runs for the same stage (prover_stages.hip), on the key's domain, window tables and scratch buffers.  Shapes: n = 2^k,
  * ext = 2^extended_k, bf = blinding_factors, S = permutation sets = ceil(permutation columns / (cs_degree - 2)),
  * PL = legacy lookups of `pk` in cs.lookups order; field elements in Montgomery form, 4 limbs.  A sharded key
  * (cq_pk_set_sharding world > 1) is CQ_ERR_ARG for all four, as for cq_pk_check_witness.

@@ -6,7 +6,7 @@
 //                       by EvaluationDomain::divide_by_vanishing_poly (poly/domain.rs:319-338)
 //   cq_permute_expression_pair_dev = permute_expression_pair of the legacy lookup argument (plonk/lookup/prover.rs:400-502)
 // They run the same kernels as cq_create_proof (prover.hip), without its cross-round overlap.
-// The remaining heavy stages are entry points onto the very functions ProofRun's stages call (prover.hip, stage_*); here
+// The remaining heavy stages are entry points onto the very functions ProofRun's stages call (prover_stages.hip, stage_*); here
 // are their argument checks:
 //   cq_permutation_commit_dev    = permutation::Argument::commit        (plonk/permutation/prover.rs:47-198)
 //   cq_lookup_commit_product_dev = lookup::Permuted::commit_product     (plonk/lookup/prover.rs:173-318)
@@ -24,12 +24,6 @@
 #include "prover.hpp"
 
 using namespace cq;
-
-#define CQ_TRY(x)                 \
-  do {                            \
-    int _rc = (x);                \
-    if (_rc != CQ_OK) return _rc; \
-  } while (0)
 
 namespace {
 

@@ -308,7 +308,7 @@ int rccl_bcast_parts(cq_ctx* c, const BcastPart* parts, size_t nparts, hipStream
 }
 
 // Both collectives on the context's communicator with patterns every rank can check, issued the way the sharded prover
-// issues them (prover.hip): an all-gather on the main stream; then grouped broadcasts on the SIDE stream, ordered behind
+// issues them (Commit::end in prover_support.hip, sharded_transform in prover.hip): an all-gather on the main stream; then grouped broadcasts on the SIDE stream, ordered behind
 // an event of the main stream (AuxFork) and followed by more side-stream work; an all-gather on the main stream while
 // those are in flight -- two streams, one communicator, the same issue order on every rank --; the main stream joins
 // the side stream last.  What cq_ctx_comm_selftest runs.

@@ -148,7 +148,7 @@ struct cq_pk : cq_pk_desc {
   // has static lookups and the table fits a bucket set): [0] = g_to_lagrange of (identity, g[0 .. n-1)), [1] = the same of
   // (identity, b0_g1_bound), so that  [b_0] = sum_i b(w^i) * b_row_bases[0][i]  and  [p] = sum_i b(w^i) * b_row_bases[1][i]
   // -- coefficient 0 of b meets the identity, which is the division by X.  b takes one value per table row, so both are
-  // short MSMs over per-table-row sums of these bases (prover.hip, round 2).
+  // short MSMs over per-table-row sums of these bases (prover_lookup.hip, round 2).
   cq::G1Affine* b_row_bases[2] = {nullptr, nullptr};
   cq::Fr* l_active_row = nullptr;       // extended coset
   // ---- general PLONK part (null for a CQ-only circuit) ----

@@ -33,7 +33,7 @@ enum class Scratch {
   PolyTmp,      // poly.hip eval / kate, plonk.hip prefix_product partials, for one call each
   ProverArena,  // create_proof_dev's arena, for the whole proof
   ProverStage,  // create_proof_dev's resident receive staging or its legacy-lookup staging (never both: resident sharding
-                // requires no legacy lookups); capi_rounds.hip's stand-alone rounds, which a proof never calls; prover.hip's
+                // requires no legacy lookups); capi_rounds.hip's stand-alone rounds, which a proof never calls; prover_stages.hip's
                 // stand-alone stages (stage_permutation_commit: the inverted denominators; stage_evaluate_h: the cosets and
                 // the challenges; stage_multiopen: the opener's buffers; stage_lookup_commit_product takes none), each for
                 // its own call only.  They are public entry points that call no other entry point and that create_proof_dev
@@ -66,7 +66,7 @@ struct cq_ctx {
   std::string err;
   std::vector<std::unique_ptr<cq::NttTables>> ntt_cache;
   cq::GrowBuf scratch[(int)cq::Scratch::Count];
-  cq::GrowBuf pinned;  // a proof's pinned host staging: the random polynomial's words, blinding rows (prover.hip)
+  cq::GrowBuf pinned;  // a proof's pinned host staging: the random polynomial's words, blinding rows (prover.hip, advice_phase)
   uint32_t msm_c = 0;  // 0 = automatic window size
   uint32_t msm_table_c = 0;  // caller's override of the window width of precomputed tables (cq_msm_set_table_window); 0 = by array length
   bool msm_precompute = true;  // build per-window tables for resident SRS arrays
@@ -177,14 +177,14 @@ struct cq_ctx {
   }
   // Second compute stream (lowest priority).  An MSM ends in latency-bound kernels (partial-sum combines, row /
   // column sums, weighted sums) that leave most of the GPU idle; the prover uses that time for transforms whose
-  // inputs are already fixed (prover.hip, AuxFork).  msm_run records `msm_tail_event` right after its accumulate
+  // inputs are already fixed (prover_run.hpp, AuxFork).  msm_run records `msm_tail_event` right after its accumulate
   // kernel; work on `aux_stream` starts there; `aux_done` orders the main stream after it.  While the prover has
   // `stream` pointed at the side stream, NTTs take their scratch from Scratch::NttAux (domain.hip) and a bucket-sum launch
   // its workspace from Scratch::MsmWorkAux (msm.hip).
   // msm_tail_event / msm_tail_seq belong to the MAIN stream's launches: an MSM launched on a side stream (the prover's
   // bucket-sum launch, msm.hip) neither records the event nor bumps the number, so a fork still orders itself after the
   // main-stream launch it runs beside.  `b_sums_done` is recorded behind a proof's last bucket-sum launch; round 2 makes the
-  // main stream wait for it before its first reader of the sums (prover.hip).
+  // main stream wait for it before its first reader of the sums (prover_lookup.hip, round2_commit).
   hipStream_t aux_stream = nullptr;
   hipEvent_t msm_tail_event = nullptr, aux_done = nullptr, b_sums_done = nullptr;
   uint64_t msm_tail_seq = 0;
@@ -284,4 +284,11 @@ struct cq_ctx {
   do {                                                      \
     hipError_t _e = (call);                                 \
     if (_e != hipSuccess) return (ctx)->hip_fail(_e, #call); \
+  } while (0)
+
+// passes on any status but CQ_OK
+#define CQ_TRY(x)                 \
+  do {                            \
+    int _rc = (x);                \
+    if (_rc != CQ_OK) return _rc; \
   } while (0)

@@ -63,7 +63,7 @@ static int run(cq_ctx* c, uint32_t log_n, const Fr& omega, const Fr* in, Fr* out
   const NttTables* tb = c->tables_for(log_n, omega, &rc);
   if (!tb) return rc;
   const size_t n = (size_t)1 << log_n;
-  // on the side stream (AuxFork, prover.hip) a buffer of its own; elsewhere the caller waits for this transform
+  // on the side stream (AuxFork, prover_run.hpp) a buffer of its own; elsewhere the caller waits for this transform
   const bool aux = c->aux_stream && c->stream == c->aux_stream;
   void* scr;
   if ((rc = c->ensure_scratch(aux ? Scratch::NttAux : Scratch::Ntt, (size_t)2 * io.batch * n * sizeof(Fr), &scr)) != CQ_OK) return rc;

@@ -1,8 +1,9 @@
 // HIP-free unit over the host-side glue of the prover -- the worker pool (hostpool.hpp), the jump-ahead bulk form of the
 // harness RNG (xoshiro.hpp), the transcript hash (blake2b.hpp) -- built by tests/test_sanitizers_cpu.py with
 // -fsanitize=thread and with -fsanitize=address,undefined.  The threading patterns are the prover's own
-// (csrc/prover.hip): a helper thread drawing the random polynomial chunk by chunk THROUGH the pool while the main thread
-// submits jobs to the same pool and waits for them (f by linearity, MSM folds); batch lanes = several such main threads.
+// (csrc/prover_support.hip RandomPolyDrawer, csrc/prover_lookup.hip cq_round1): a helper thread drawing the random
+// polynomial chunk by chunk THROUGH the pool while the main thread submits jobs to the same pool and waits for them
+// (f by linearity, MSM folds); batch lanes = several such main threads.
 #include <atomic>
 #include <cstdio>
 #include <cstring>
@@ -126,7 +127,7 @@ int main() {
       HostPool p(4);
       std::atomic<int> n{0};
       HostPool::Ticket t = p.submit(64, [&](size_t) { n.fetch_add(1); });
-      p.wait(t);  // (a job's frame must outlive it: the prover always waits -- PoolJoin in prover.hip)
+      p.wait(t);  // (a job's frame must outlive it: the prover always waits -- PoolJoin in prover_lookup.hip)
       EXPECT(n.load() == 64);
     }
   }

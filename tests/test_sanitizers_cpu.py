@@ -2,7 +2,7 @@
   * oracle/cq_oracle.c built with -fsanitize=address,undefined (`make -C oracle asan`) under the oracle's own tests
     (C vs Python agreement on fields, MSM, FFT, a full create_proof, the pairing);
   * the prover's HIP-free host glue (worker pool, jump-ahead RNG fill, transcript hash; tests/host/host_stress.cpp) under
-    -fsanitize=thread and -fsanitize=address,undefined, in the threading patterns csrc/prover.hip uses.
+    -fsanitize=thread and -fsanitize=address,undefined, in the threading patterns csrc/prover_support.hip and csrc/prover_lookup.hip use.
 Any sanitizer report fails the test (halt_on_error / non-zero exit)."""
 import hashlib
 import os
