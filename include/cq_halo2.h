@@ -875,6 +875,24 @@ int cq_sha256_layout(uint32_t* cells, size_t cap, size_t* count);
  * table_bits outside [CQ_SHA256_MIN_TABLE_BITS, CQ_SHA256_MAX_TABLE_BITS], or n too small for the rows used. */
 int cq_sha256_synthesize_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* msg_words, size_t blocks, size_t n,
                              uint64_t* const* cols_dev, uint32_t digest[8]);
+/* Several compression chains ("segments") one behind another in the same columns, wired to each other: segment j takes
+ * CQ_SHA256_BLOCK_REGIONS * seg_blocks[j] + CQ_SHA256_TAIL_REGIONS regions directly behind segment j - 1, and its first
+ * block starts from the IV.  `sources` holds one word per message word, 16 per block, in row order over all segments
+ * (16 * sum(seg_blocks) words): a value below CQ_SHA256_SOURCE_DIGEST is an index into `words_dev`, a device array of
+ * `words_len` 32-bit words (private words and constants alike); CQ_SHA256_SOURCE_DIGEST + 8 * s + i is digest word i of
+ * segment s, which must come before the segment that reads it.  `digests_dev` (device, 8 * segments words) receives every
+ * segment's digest.  All of it is validated on the host before anything is launched: CQ_ERR_ARG -- with the segment and
+ * the word in cq_last_error -- for a block count of zero, rows that do not fit n, an index outside `words_dev`, a
+ * reference to the segment itself or a later one, or table_bits out of range; nothing is written then.
+ * The chains run on the device: a segment's level is 0 if it reads no digest, else one more than the highest level it
+ * reads; one launch per level in ascending order, one lane per segment, then the expansion kernel of
+ * cq_sha256_synthesize_dev over all rows (rows behind the last segment: zero).  Everything is queued on the context's
+ * stream and nothing waits for it: `words_dev` must stay as it is, and `digests_dev` is good, once the stream has got
+ * there.  A one-segment description gives the columns cq_sha256_synthesize_dev gives for the same words. */
+#define CQ_SHA256_SOURCE_DIGEST 2147483648u
+int cq_sha256_synthesize_segments_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
+                                      const uint32_t* sources, const uint32_t* words_dev, size_t words_len, size_t n,
+                                      uint64_t* const* cols_dev, uint32_t* digests_dev);
 
 /* ---- harness RNG (not in the reference: its test draws from OsRng) ---------------------------------- */
 void cq_xoshiro256ss_seed(uint64_t seed, uint64_t state[4]);

@@ -59,9 +59,10 @@ void cq_ctx_destroy(cq_ctx* c) {
   cq::comm_rccl_destroy(c);
   for (const cq::GrowBuf& b : c->scratch)
     if (b.ptr) hipFree(b.ptr);
-  for (const cq::GrowBuf* b : {&c->pinned, &c->pinned_msm, &c->pinned_small, &c->pinned_comm})
+  for (const cq::GrowBuf* b : {&c->pinned, &c->pinned_msm, &c->pinned_small, &c->pinned_comm, &c->pinned_sha})
     if (b->ptr) hipHostFree(b->ptr);
   if (c->comm_event) hipEventDestroy(c->comm_event);
+  if (c->sha_staged) hipEventDestroy(c->sha_staged);
   for (auto& g : c->graphs) hipGraphExecDestroy(g.exec);
   if (c->prof_entries) hipHostFree(c->prof_entries);
   if (c->copy_done) hipEventDestroy(c->copy_done);

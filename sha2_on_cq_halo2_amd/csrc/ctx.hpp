@@ -22,10 +22,11 @@ enum class Scratch {
                 // input, capi_msm.hip (multiexp scalars, params set-up temp, validate flag), capi_g2.hip scalars, capi_cq.hip
                 // (table config, static table), pk.hip (keygen and write temps; PkStreamReader's verdict words or validity
                 // flag, from its begin() to its finish()), comm.hip self-test, the verdict words of the Processed conversions
-                // (serde.hip entry points, params / G2 SRS readers).  Nothing they call takes an entry buffer
+                // (serde.hip entry points, params / G2 SRS readers), sha256.hip's region words.  Nothing they call takes an
+                // entry buffer
   EntryB,       // the second buffer of the same entry points (outputs, bases, pk.hip's permutation mapping, the staged compressed
                 // bytes of the Processed params / pk / G2 SRS readers and writers, the two G2 points of a params set-up or full
-                // stream); also g1_fft's twiddles: its callers (g1_to_lagrange,
+                // stream), sha256.hip's lane and source tables of a segment synthesis; also g1_fft's twiddles: its callers (g1_to_lagrange,
                 // fk_table_quotients) run under entry points that hold neither entry buffer
   MsmWork,      // msm_multi.hip, msm.hip (msm_bucket_sums): the workspace of one MSM launch on any stream but a side stream;
                 // those launches follow one another on `stream`
@@ -277,6 +278,11 @@ struct cq_ctx {
   int ensure_pinned_comm(size_t bytes, void** out) { return grow(pinned_comm, bytes, 65536, true, out); }
   cq::GrowBuf pinned_msm;  // MSM results (kept apart from `pinned`, which stages RNG words)
   int ensure_pinned_msm(size_t bytes, void** out) { return grow(pinned_msm, bytes, 65536, true, out); }
+  // sha256.hip, cq_sha256_synthesize_segments_dev: the pinned staging of a call's lane and source tables, and the event
+  // behind their upload -- the next call waits for that copy alone, not for the stream, before it overwrites the staging
+  cq::GrowBuf pinned_sha;
+  hipEvent_t sha_staged = nullptr;
+  int ensure_pinned_sha(size_t bytes, void** out) { return grow(pinned_sha, bytes, 65536, true, out); }
   const cq::NttTables* tables_for(uint32_t log_n, const cq::Fr& omega, int* rc);
 };
 

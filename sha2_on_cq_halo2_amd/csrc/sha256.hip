@@ -3,6 +3,11 @@
 // is; the kernel below expands them into the 18 advice columns, one thread per row: every cell is a bit field of a word
 // that a handful of xors and additions of the region's and its neighbours' (a, e, W) give, placed by the layout table of
 // sha256_layout.hpp.  The work is the 18 x n Montgomery encodings and their stores (151 MB at k = 18).
+// Wired segments (cq_sha256_synthesize_segments_dev, further down): several chains whose message words may be digest words
+// of earlier chains.  There the chains run on the device, one lane per segment and one launch per dependency level, and
+// leave the same four words per region for the same expansion kernel.
+#include <cstring>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -36,7 +41,8 @@ struct Sha256Cols {
   0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2
 static const uint32_t SHA256_K_HOST[64] = {SHA256_K_VALUES};
 __constant__ const uint32_t SHA256_K_DEV[64] = {SHA256_K_VALUES};
-static const uint32_t SHA256_IV[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+#define SHA256_IV_VALUES 0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19
+static const uint32_t SHA256_IV[8] = {SHA256_IV_VALUES};
 
 #define SHA_HD __host__ __device__ __forceinline__
 static SHA_HD uint32_t rotr(uint32_t x, uint32_t n) { return (x >> n) | (x << (32 - n)); }
@@ -188,6 +194,145 @@ int sha256_synthesize(cq_ctx* c, uint32_t table_bits, const uint32_t* msg_words,
   return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "sha256_expand launch failed");
 }
 
+// ---- wired segments: the compression chains on the device ------------------------------------------------------------
+
+// One chain of a level's launch: where its regions and its 16 * blocks word sources start, and which segment it is.
+struct Sha256Lane {
+  uint32_t first_region, blocks, first_source, segment;
+};
+
+static __device__ __forceinline__ void sha256_put(Sha256Region* p, uint32_t a, uint32_t e, uint32_t w, uint32_t meta) {
+  *reinterpret_cast<uint4*>(p) = make_uint4(a, e, w, meta);
+}
+
+// a_-4 .. a_-1 = d, c, b, a and e_-4 .. e_-1 = h, g, f, e, as sha256_regions' state_regions lays them out
+static __device__ __forceinline__ void sha256_put_state(Sha256Region* out, const uint32_t (&h)[8], uint32_t chain) {
+  sha256_put(out + 0, h[3], h[7], 0, chain);
+  sha256_put(out + 1, h[2], h[6], 0, chain);
+  sha256_put(out + 2, h[1], h[5], 0, chain | SHA_RG_F3);
+  sha256_put(out + 3, h[0], h[4], 0, chain | SHA_RG_F3);
+}
+
+// Message word I of a block: a word of the caller's buffer or a digest word an earlier level's launch stored.  The host
+// has checked every source against both arrays' lengths.
+template <uint32_t I>
+static __device__ __forceinline__ void sha256_fetch(uint32_t (&w)[16], const uint32_t* src, const uint32_t* words, const uint32_t* digests) {
+  const uint32_t s = src[I];
+  w[I] = *((s & CQ_SHA256_SOURCE_DIGEST) ? digests + (s & (CQ_SHA256_SOURCE_DIGEST - 1)) : words + s);
+}
+
+// Round T0 + I on the 16-word rolling schedule and the state (a .. h), and its region.  I is a compile-time constant, so
+// `w` and `s` are only ever indexed by constants and stay in registers; T0, the group's first round, may be a loop variable.
+template <bool SCHED, uint32_t I>
+static __device__ __forceinline__ void sha256_step(uint32_t (&s)[8], uint32_t (&w)[16], uint32_t t0, Sha256Region* out) {
+  if (SCHED) w[I] += small_sigma1(w[(I + 14) & 15]) + w[(I + 9) & 15] + small_sigma0(w[(I + 1) & 15]);
+  const uint32_t t1 = s[7] + big_sigma1(s[4]) + ch3(s[4], s[5], s[6]) + SHA256_K_DEV[t0 + I] + w[I];
+  const uint32_t t2 = big_sigma0(s[0]) + maj3(s[0], s[1], s[2]);
+  s[7] = s[6], s[6] = s[5], s[5] = s[4], s[4] = s[3] + t1;
+  s[3] = s[2], s[2] = s[1], s[1] = s[0], s[0] = t1 + t2;
+  sha256_put(out + t0 + I, s[0], s[4], w[I], SHA_RG_ROUND | SHA_RG_F3 | (SCHED ? SHA_RG_SCHED : 0) | (t0 + I) << 8);
+}
+template <bool SCHED, uint32_t... I>
+static __device__ __forceinline__ void sha256_steps(uint32_t (&s)[8], uint32_t (&w)[16], uint32_t t0, Sha256Region* out,
+                                                    std::integer_sequence<uint32_t, I...>) {
+  (sha256_step<SCHED, I>(s, w, t0, out), ...);
+}
+template <uint32_t... I>
+static __device__ __forceinline__ void sha256_fetch_all(uint32_t (&w)[16], const uint32_t* src, const uint32_t* words, const uint32_t* digests,
+                                                        std::integer_sequence<uint32_t, I...>) {
+  (sha256_fetch<I>(w, src, words, digests), ...);
+}
+
+// One lane per segment of one level: what sha256_regions does for one message, with the message words gathered through
+// `sources`.  A chain is 64 dependent rounds per block, so the launch is latency-bound: one wave per workgroup spreads a
+// level's segments over the CUs.  Lanes of a wave may differ in their block counts.  `digests` is read (earlier levels)
+// and written (this lane's segment), hence neither const nor restrict.
+__global__ __launch_bounds__(64) void sha256_chain_kernel(const Sha256Lane* __restrict__ lanes, uint32_t nlanes,
+                                                          const uint32_t* __restrict__ sources, const uint32_t* words, uint32_t* digests,
+                                                          Sha256Region* __restrict__ regions) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nlanes) return;
+  const Sha256Lane lane = lanes[i];
+  using Seq16 = std::make_integer_sequence<uint32_t, 16>;
+  uint32_t h[8] = {SHA256_IV_VALUES};
+  Sha256Region* out = regions + lane.first_region;
+  const uint32_t* src = sources + lane.first_source;
+  for (uint32_t b = 0; b < lane.blocks; b++, out += CQ_SHA256_BLOCK_REGIONS, src += 16) {
+    sha256_put_state(out, h, b ? SHA_RG_CHAIN : 0);
+    uint32_t w[16], s[8] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]};
+    sha256_fetch_all(w, src, words, digests, Seq16{});
+    sha256_steps<false>(s, w, 0, out + 4, Seq16{});
+    for (uint32_t t0 = 16; t0 < 64; t0 += 16) sha256_steps<true>(s, w, t0, out + 4, Seq16{});
+    h[0] += s[0], h[1] += s[1], h[2] += s[2], h[3] += s[3];
+    h[4] += s[4], h[5] += s[5], h[6] += s[6], h[7] += s[7];
+  }
+  sha256_put_state(out, h, SHA_RG_CHAIN);
+  uint32_t* d = digests + 8 * (size_t)lane.segment;
+  d[0] = h[0], d[1] = h[1], d[2] = h[2], d[3] = h[3], d[4] = h[4], d[5] = h[5], d[6] = h[6], d[7] = h[7];
+}
+
+// Validates the description, then queues the tables' upload, one chain launch per level and the expansion.  Nothing here
+// waits for the stream; the staging is pinned, and only the previous call's copy out of it is waited for.
+int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* sources,
+                               const uint32_t* words_dev, size_t words_len, uint32_t n, const Sha256Cols& cols, uint32_t* digests_dev) {
+  const uint64_t max_regions = n / CQ_SHA256_REGION_ROWS;
+  uint64_t regions = 0, blocks = 0;
+  for (size_t j = 0; j < segments; j++) {
+    if (seg_blocks[j] == 0) return c->fail(CQ_ERR_ARG, "sha256: segment " + std::to_string(j) + " has no block");
+    blocks += seg_blocks[j];
+    regions += (uint64_t)seg_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS;
+    if (regions > max_regions) return c->fail(CQ_ERR_ARG, "sha256: the segments up to segment " + std::to_string(j) + " do not fit the rows");
+  }
+  std::vector<uint32_t> level(segments, 0), level_count;
+  for (size_t j = 0, at = 0; j < segments; j++)
+    for (size_t t = 0; t < 16 * (size_t)seg_blocks[j]; t++, at++) {
+      const uint32_t s = sources[at];
+      auto where = [&] { return "sha256: segment " + std::to_string(j) + ", word " + std::to_string(t); };
+      if (s & CQ_SHA256_SOURCE_DIGEST) {
+        const size_t ref = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3;
+        if (ref >= j) return c->fail(CQ_ERR_ARG, where() + " reads the digest of segment " + std::to_string(ref) + ", which does not come before it");
+        if (level[ref] + 1 > level[j]) level[j] = level[ref] + 1;
+      } else if (s >= words_len) {
+        return c->fail(CQ_ERR_ARG, where() + " reads word " + std::to_string(s) + " of a buffer of " + std::to_string(words_len));
+      }
+    }
+  for (uint32_t l : level) {
+    if (l >= level_count.size()) level_count.resize(l + 1, 0);
+    level_count[l]++;
+  }
+  std::vector<uint32_t> level_first(level_count.size(), 0);
+  for (size_t l = 1; l < level_count.size(); l++) level_first[l] = level_first[l - 1] + level_count[l - 1];
+
+  static_assert(sizeof(Sha256Region) == 16 && sizeof(Sha256Lane) == 16, "four words each");
+  const size_t lanes_bytes = segments * sizeof(Sha256Lane), tables_bytes = lanes_bytes + 16 * blocks * sizeof(uint32_t);
+  void *pin, *dev_regions, *dev_tables;
+  CQ_TRY(c->ensure_pinned_sha(tables_bytes, &pin));
+  CQ_TRY(c->ensure_scratch(Scratch::EntryA, regions * sizeof(Sha256Region), &dev_regions));
+  CQ_TRY(c->ensure_scratch(Scratch::EntryB, tables_bytes, &dev_tables));
+  if (!c->sha_staged) CQ_HIP(c, hipEventCreateWithFlags(&c->sha_staged, hipEventDisableTiming));
+  CQ_HIP(c, hipEventSynchronize(c->sha_staged));  // the previous call's copy out of `pin` (at once if there was none)
+  Sha256Lane* lanes = (Sha256Lane*)pin;
+  std::vector<uint32_t> next = level_first;
+  uint32_t first_region = 0, first_source = 0;
+  for (size_t j = 0; j < segments; j++) {  // lanes in level order, segments of one level in row order
+    lanes[next[level[j]]++] = {first_region, seg_blocks[j], first_source, (uint32_t)j};
+    first_region += seg_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS;
+    first_source += 16 * seg_blocks[j];
+  }
+  memcpy((char*)pin + lanes_bytes, sources, 16 * blocks * sizeof(uint32_t));
+  CQ_HIP(c, hipMemcpyAsync(dev_tables, pin, tables_bytes, hipMemcpyHostToDevice, c->stream));
+  CQ_HIP(c, hipEventRecord(c->sha_staged, c->stream));
+  const Sha256Lane* dev_lanes = (const Sha256Lane*)dev_tables;
+  const uint32_t* dev_sources = (const uint32_t*)((const char*)dev_tables + lanes_bytes);
+  for (size_t l = 0; l < level_count.size(); l++) {
+    sha256_chain_kernel<<<(level_count[l] + 63) / 64, 64, 0, c->stream>>>(dev_lanes + level_first[l], level_count[l], dev_sources, words_dev,
+                                                                         digests_dev, (Sha256Region*)dev_regions);
+    if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_chain launch failed");
+  }
+  sha256_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha256Region*)dev_regions, (uint32_t)regions, n, table_bits, cols);
+  return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "sha256_expand launch failed");
+}
+
 }  // namespace cq
 
 using namespace cq;
@@ -217,6 +362,24 @@ int cq_sha256_synthesize_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* msg
     sc.p[i] = (Fr*)cols_dev[i];
   }
   return sha256_synthesize(c, table_bits, msg_words, blocks, (uint32_t)n, sc, digest);
+}
+
+int cq_sha256_synthesize_segments_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
+                                      const uint32_t* sources, const uint32_t* words_dev, size_t words_len, size_t n,
+                                      uint64_t* const* cols_dev, uint32_t* digests_dev) {
+  if (!c) return CQ_ERR_ARG;
+  if (!seg_blocks || !sources || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull || (!words_dev && words_len) ||
+      words_len > CQ_SHA256_SOURCE_DIGEST)
+    return c->fail(CQ_ERR_ARG, "sha256: null array, no segment, or a length out of range");
+  if (table_bits < CQ_SHA256_MIN_TABLE_BITS || table_bits > CQ_SHA256_MAX_TABLE_BITS)
+    return c->fail(CQ_ERR_ARG, "sha256: table_bits outside the range the pieces fit");
+  CQ_HIP(c, hipSetDevice(c->device));
+  Sha256Cols sc;
+  for (uint32_t i = 0; i < CQ_SHA256_ADVICE_COLUMNS; i++) {
+    if (!cols_dev[i]) return c->fail(CQ_ERR_ARG, "sha256: null column");
+    sc.p[i] = (Fr*)cols_dev[i];
+  }
+  return sha256_synthesize_segments(c, table_bits, seg_blocks, segments, sources, words_dev, words_len, (uint32_t)n, sc, digests_dev);
 }
 
 }  // extern "C"

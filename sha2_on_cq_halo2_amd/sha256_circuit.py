@@ -202,15 +202,25 @@ def _constraint_system(tb: int, dense, spread):
 
 
 def _assign_fixed(k, blocks, tb, cs, adv, fcol, inst, cells, word) -> Description:
-    n, X = 1 << k, adv[2 * PAIRS]
+    n = 1 << k
     rows = rows_for(blocks)
     usable = n - (cs.blinding_factors() + 1)
     if rows > usable:
         raise ValueError(f"{blocks} blocks need {rows} rows, 2^{k} has {usable} usable")
     fixed = {name: np.zeros(n, dtype=np.uint64) for name in FIXED}
+    copies = []
+    _assign_segment(fixed, copies, 0, blocks, 0, tb, adv, fcol, inst, cells, word)
+    return Description(cs, adv, fcol, fixed, inst, copies, cells, tb, blocks, k)
+
+
+def _assign_segment(fixed, copies, first_region, blocks, public, tb, adv, fcol, inst, cells, word):
+    """The fixed cells and the copies of one chain of `blocks` blocks whose regions start at `first_region`: selectors and
+    scales, the round constants, the IV on its first four regions (no q_chain before its second block), and -- where
+    `public` is not None -- the copies of instance rows 8 * public .. 8 * public + 7 to the digest words of its tail."""
+    X = adv[2 * PAIRS]
     regions = BLOCK_REGIONS * blocks + TAIL_REGIONS
     g = np.arange(regions)
-    in_block, base = g % BLOCK_REGIONS, g * REGION_ROWS
+    in_block, base = g % BLOCK_REGIONS, (first_region + g) * REGION_ROWS
     is_tail = g >= BLOCK_REGIONS * blocks
     is_round = (in_block >= 4) & ~is_tail
     fixed["q_all"][base] = 1
@@ -222,7 +232,6 @@ def _assign_fixed(k, blocks, tb, cs, adv, fcol, inst, cells, word) -> Descriptio
         if c.form == FORM_PAIR:
             _, ln = _field_of(c, tb)
             fixed[f"scale{c.column // 2}"][base + c.row] = 1 << (tb - ln) if c.len else 1
-    copies = []
     krow = word[(SRC["K"], FORM_WORD)].row
     arow, erow = word[(SRC["A"], FORM_WORD)].row, word[(SRC["E"], FORM_WORD)].row
     kvals = np.array(K256, dtype=np.uint64)
@@ -230,19 +239,24 @@ def _assign_fixed(k, blocks, tb, cs, adv, fcol, inst, cells, word) -> Descriptio
     fixed["const"][rb + krow] = kvals[(in_block[is_round] - 4)]
     copies += [((fcol["const"], int(r) + krow), (X, int(r) + krow)) for r in rb]
     for i in range(4):  # region i of the first block holds a_(i-4) = H[3 - i] and e_(i-4) = H[7 - i]
+        head = int(base[i])
         for row, val in ((arow, IV256[3 - i]), (erow, IV256[7 - i])):
-            fixed["const"][REGION_ROWS * i + row] = val
-            copies.append(((fcol["const"], REGION_ROWS * i + row), (X, REGION_ROWS * i + row)))
-        tail = REGION_ROWS * (BLOCK_REGIONS * blocks + i)
-        copies.append(((inst, 3 - i), (X, tail + arow)))
-        copies.append(((inst, 7 - i), (X, tail + erow)))
-    return Description(cs, adv, fcol, fixed, inst, copies, cells, tb, blocks, k)
+            fixed["const"][head + row] = val
+            copies.append(((fcol["const"], head + row), (X, head + row)))
+        if public is not None:
+            tail = int(base[BLOCK_REGIONS * blocks + i])
+            copies.append(((inst, 8 * public + 3 - i), (X, tail + arow)))
+            copies.append(((inst, 8 * public + 7 - i), (X, tail + erow)))
+
+
+def usable_rows(k: int, table_bits: int = 12) -> int:
+    """The rows of 2^k a circuit may use: all but the blinding rows and the one behind them."""
+    return (1 << k) - (_constraint_system(table_bits, "dense", "spread")[0].blinding_factors() + 1)
 
 
 def max_blocks(k: int, table_bits: int = 12) -> int:
     """The largest block count whose rows fit the usable rows of 2^k."""
-    usable = (1 << k) - (_constraint_system(table_bits, "dense", "spread")[0].blinding_factors() + 1)
-    return (usable // REGION_ROWS - TAIL_REGIONS) // BLOCK_REGIONS
+    return (usable_rows(k, table_bits) // REGION_ROWS - TAIL_REGIONS) // BLOCK_REGIONS
 
 
 def _mont_column(vals: np.ndarray) -> np.ndarray:
@@ -251,50 +265,63 @@ def _mont_column(vals: np.ndarray) -> np.ndarray:
     return np.stack([fr_to_mont(int(u)) for u in uniq])[inv.reshape(-1)]
 
 
+def _build_key(self, ctx: Context, k: int, table_bits: int, setup: str, seed: int, make_description):
+    """What every SHA-256 circuit object holds: the params, the two static tables, the description
+    (`make_description(dense, spread)`), the proving key built from it and the 18 device columns."""
+    from .sha_circuit import small_to_mont, spread16, srs_powers_dev
+
+    self.ctx, self.k, self.table_bits, self.seed = ctx, k, table_bits, seed
+    n, N = 1 << k, 1 << table_bits
+    self.n = n
+    self.srs = None
+    idx = np.arange(N)
+    if setup == "powers":  # the powers [s^i]_1 stand in for a ceremony file: s appears here and nowhere below
+        count = max(n, N)
+        self.srs = srs_powers_dev(ctx, seed * 0x9E3779B97F4A7C15 + 12345, count)
+        self.params = ParamsKZG.from_powers(ctx, k, self.srs)
+        self.cfg = TableConfig.from_srs(ctx, N, self.srs, srs_len=count)
+        self.dense = StaticTable.new_fk(ctx, small_to_mont(idx), srs_dev=self.srs)
+        self.spread = StaticTable.new_fk(ctx, small_to_mont(spread16(idx)), srs_dev=self.srs)
+    else:
+        if setup != "toxic":
+            raise ValueError(f"setup: 'toxic' or 'powers', not {setup!r}")
+        s = fr_to_mont(seed * 0x9E3779B97F4A7C15 + 12345)
+        self.params = ParamsKZG.setup_from_toxic_waste(ctx, k, s)
+        self.cfg = TableConfig.setup_from_toxic_waste(ctx, N, s)
+        self.dense = StaticTable.setup_from_toxic_waste(ctx, small_to_mont(idx), s)
+        self.spread = StaticTable.setup_from_toxic_waste(ctx, small_to_mont(spread16(idx)), s)
+    self.description = d = make_description(self.dense, self.spread)
+    self.cs = d.cs
+    asm = GP.PermutationAssembly(ctx.lib, n, d.cs.permutation_columns)
+    for (lc, lr), (rc, rr) in d.copies:
+        asm.copy(lc, lr, rc, rr)
+    self.vk_repr = 0x534841323536 + k
+    self.pk = ProvingKey(ctx, self.params, k, 0, [], self.cfg, self.params.g_dev + 64, fr_to_mont(self.vk_repr), cs=d.cs,
+                         fixed=[_mont_column(d.fixed[name]) for name in FIXED], permutation=asm.mapping)
+    self.cols = [ctx.alloc(n * 32) for _ in range(ADVICE_COLUMNS)]
+
+
+def _close_key(self):
+    for o in [self.pk] + list(self.cols) + [self.dense, self.spread, self.cfg, self.params] + ([self.srs] if self.srs is not None else []):
+        o.close()
+
+
 class Sha256Circuit:
     """Proving key and GPU witness synthesis for SHA-256 over exactly `blocks` padded blocks at 2^k rows.  One key
-    proves one message length; there is no variable-length selection."""
+    proves one message length; there is no variable-length selection (several messages, a hash of a hash or a Merkle
+    root in one proof: sha256_segments.py)."""
 
     rows_per_block = BLOCK_REGIONS * REGION_ROWS
 
     def __init__(self, ctx: Context, k: int, blocks: int | None = None, table_bits: int = 12, setup: str = "toxic",
                  seed: int = 0x5348413243515F):
-        from .sha_circuit import small_to_mont, spread16, srs_powers_dev
-
         if blocks is None:
             blocks = max_blocks(k, table_bits)
         if blocks < 1:
             raise ValueError(f"2^{k} rows hold no block ({rows_for(1)} rows are needed)")
-        self.ctx, self.k, self.blocks, self.table_bits, self.seed = ctx, k, blocks, table_bits, seed
-        n, N = 1 << k, 1 << table_bits
-        self.n = n
-        self.srs = None
-        idx = np.arange(N)
-        if setup == "powers":  # the powers [s^i]_1 stand in for a ceremony file: s appears here and nowhere below
-            count = max(n, N)
-            self.srs = srs_powers_dev(ctx, seed * 0x9E3779B97F4A7C15 + 12345, count)
-            self.params = ParamsKZG.from_powers(ctx, k, self.srs)
-            self.cfg = TableConfig.from_srs(ctx, N, self.srs, srs_len=count)
-            self.dense = StaticTable.new_fk(ctx, small_to_mont(idx), srs_dev=self.srs)
-            self.spread = StaticTable.new_fk(ctx, small_to_mont(spread16(idx)), srs_dev=self.srs)
-        else:
-            if setup != "toxic":
-                raise ValueError(f"setup: 'toxic' or 'powers', not {setup!r}")
-            s = fr_to_mont(seed * 0x9E3779B97F4A7C15 + 12345)
-            self.params = ParamsKZG.setup_from_toxic_waste(ctx, k, s)
-            self.cfg = TableConfig.setup_from_toxic_waste(ctx, N, s)
-            self.dense = StaticTable.setup_from_toxic_waste(ctx, small_to_mont(idx), s)
-            self.spread = StaticTable.setup_from_toxic_waste(ctx, small_to_mont(spread16(idx)), s)
-        self.description = d = describe(k, blocks, table_bits, self.dense, self.spread)
-        self.cs = d.cs
-        asm = GP.PermutationAssembly(ctx.lib, n, d.cs.permutation_columns)
-        for (lc, lr), (rc, rr) in d.copies:
-            asm.copy(lc, lr, rc, rr)
-        self.vk_repr = 0x534841323536 + k
-        self.pk = ProvingKey(ctx, self.params, k, 0, [], self.cfg, self.params.g_dev + 64, fr_to_mont(self.vk_repr), cs=d.cs,
-                             fixed=[_mont_column(d.fixed[name]) for name in FIXED], permutation=asm.mapping)
+        self.blocks = blocks
+        _build_key(self, ctx, k, table_bits, setup, seed, lambda dense, spread: describe(k, blocks, table_bits, dense, spread))
         self.rows = rows_for(blocks)
-        self.cols = [ctx.alloc(n * 32) for _ in range(ADVICE_COLUMNS)]
         self.digest_words = None
 
     # ---- host side ----
@@ -334,6 +361,4 @@ class Sha256Circuit:
         cols, inst = self.synthesize(message)
         return self.pk.create_proof_dev([c.ptr for c in cols], seed=seed, instances=inst), self.digest
 
-    def close(self):
-        for o in [self.pk] + list(self.cols) + [self.dense, self.spread, self.cfg, self.params] + ([self.srs] if self.srs is not None else []):
-            o.close()
+    close = _close_key

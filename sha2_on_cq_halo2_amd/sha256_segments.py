@@ -1,0 +1,291 @@
+"""Wired multi-segment SHA-256 circuits: several compression chains ("segments") one behind another in the columns of
+the SHA-256 compression circuit, tied to each other and to constants by copy constraints ("Wired SHA-256
+segments").
+
+A plan says, for every message word of every segment, where the word comes from -- a private value, a constant, or a
+digest word of an earlier segment -- and which segments' digests are public.  The constraint system is the one of
+sha256_circuit.py, gate for gate; only the fixed columns and the copies differ.  The witness is synthesised on the GPU
+by `cq_sha256_synthesize_segments_dev`, which runs the chains level by level on the device.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import struct
+from typing import NamedTuple
+
+import numpy as np
+
+from . import sha256_circuit as SC
+from ._lib import constants
+from ._marshal import FR_MODULUS
+from .context import Context
+
+SOURCE_DIGEST = constants()["CQ_SHA256_SOURCE_DIGEST"]
+
+
+class Private(NamedTuple):
+    """A message word the prover chooses: no constraint ties it to anything."""
+
+
+class Const(NamedTuple):
+    """A message word pinned to `value` through the `const` fixed column."""
+
+    value: int
+
+
+class DigestWord(NamedTuple):
+    """A message word tied to digest word `word` of the earlier segment `segment`."""
+
+    segment: int
+    word: int
+
+
+class Segment(NamedTuple):
+    """One compression chain from the IV: `blocks` blocks and the source of each of its 16 * blocks message words."""
+
+    blocks: int
+    sources: tuple
+
+
+class Plan(NamedTuple):
+    """Segments in row order, and the segments whose digests are the instance: rows 8p .. 8p + 7 for public[p]."""
+
+    segments: tuple
+    public: tuple
+
+
+PRIVATE = Private()
+PAD_64_BYTES = (Const(0x80000000),) + (Const(0),) * 14 + (Const(512),)  # the second block of a 64-byte message
+
+
+def batch(blocks_list) -> Plan:
+    """Independent messages of the given block counts: every word private, every digest public."""
+    segs = tuple(Segment(b, (PRIVATE,) * (16 * b)) for b in blocks_list)
+    return Plan(segs, tuple(range(len(segs))))
+
+
+def double_sha256(blocks: int) -> Plan:
+    """SHA-256d: a private message of `blocks` blocks, then the one-block hash of its digest, whose padding is pinned;
+    only the second digest is public."""
+    second = tuple(DigestWord(0, i) for i in range(8)) + (Const(0x80000000),) + (Const(0),) * 6 + (Const(256),)
+    return Plan((Segment(blocks, (PRIVATE,) * (16 * blocks)), Segment(1, second)), (1,))
+
+
+def merkle_tree(depth: int) -> Plan:
+    """The root over 2^depth private 32-byte leaves: every node hashes left || right (64 bytes, two blocks, the second
+    one pinned padding); nodes level by level, the 2^(depth - 1) nodes over the leaves first; only the root is public."""
+    if depth < 1:
+        raise ValueError("a Merkle tree has at least two leaves (depth >= 1)")
+    segs, below = [], None
+    for level in range(depth):
+        first = len(segs)
+        for i in range(1 << (depth - 1 - level)):
+            if level == 0:
+                children = (PRIVATE,) * 16
+            else:
+                children = tuple(DigestWord(below + 2 * i + side, w) for side in (0, 1) for w in range(8))
+            segs.append(Segment(2, children + PAD_64_BYTES))
+        below = first
+    return Plan(tuple(segs), (len(segs) - 1,))
+
+
+def rows_for(plan: Plan) -> int:
+    return sum(SC.rows_for(s.blocks) for s in plan.segments)
+
+
+def first_regions(plan: Plan):
+    """The first region of every segment."""
+    out, at = [], 0
+    for s in plan.segments:
+        out.append(at)
+        at += SC.BLOCK_REGIONS * s.blocks + SC.TAIL_REGIONS
+    return out
+
+
+def _check_plan(plan: Plan):
+    if not plan.segments:
+        raise ValueError("a plan has at least one segment")
+    for j, seg in enumerate(plan.segments):
+        if seg.blocks < 1 or len(seg.sources) != 16 * seg.blocks:
+            raise ValueError(f"segment {j}: {seg.blocks} blocks and {len(seg.sources)} word sources (16 per block, at least one block)")
+        for t, src in enumerate(seg.sources):
+            if isinstance(src, DigestWord):
+                if not 0 <= src.segment < j:
+                    raise ValueError(f"segment {j}, word {t}: the digest of segment {src.segment} does not come before it")
+                if not 0 <= src.word < 8:
+                    raise ValueError(f"segment {j}, word {t}: a digest has words 0 .. 7, not {src.word}")
+            elif isinstance(src, Const):
+                if not 0 <= src.value < 1 << 32:
+                    raise ValueError(f"segment {j}, word {t}: the constant {src.value} is no 32-bit word")
+            elif not isinstance(src, Private):
+                raise ValueError(f"segment {j}, word {t}: a source is Private, Const or DigestWord, not {src!r}")
+    if not plan.public or len(set(plan.public)) != len(plan.public) or not all(0 <= p < len(plan.segments) for p in plan.public):
+        raise ValueError(f"public segments {plan.public!r}: at least one, each an index below {len(plan.segments)}, none twice")
+
+
+def describe(k: int, plan: Plan, table_bits: int = 12, dense="dense", spread="spread") -> SC.Description:
+    """The constraint system of sha256_circuit.describe with the fixed columns and copies of `plan`; `blocks` is the
+    tuple of the segments' block counts.  ValueError for a plan that is malformed or does not fit 2^k rows."""
+    if not SC.MIN_TABLE_BITS <= table_bits <= SC.MAX_TABLE_BITS:
+        raise ValueError(f"table_bits must be in [{SC.MIN_TABLE_BITS}, {SC.MAX_TABLE_BITS}]: the widest piece has {SC.MIN_TABLE_BITS} bits")
+    _check_plan(plan)
+    cs, adv, fcol, inst, cells, word = SC._constraint_system(table_bits, dense, spread)
+    n, X = 1 << k, adv[2 * SC.PAIRS]
+    rows, usable = rows_for(plan), n - (cs.blinding_factors() + 1)
+    if max(rows, 8 * len(plan.public)) > usable:
+        raise ValueError(f"{len(plan.segments)} segments need {rows} rows and {8 * len(plan.public)} instance rows, 2^{k} has {usable} usable")
+    fixed = {name: np.zeros(n, dtype=np.uint64) for name in SC.FIXED}
+    copies = []
+    firsts = first_regions(plan)
+    public = {s: p for p, s in enumerate(plan.public)}
+    arow, erow, wrow = (word[(SC.SRC[s], SC.FORM_WORD)].row for s in "AEW")
+    for j, seg in enumerate(plan.segments):
+        SC._assign_segment(fixed, copies, firsts[j], seg.blocks, public.get(j), table_bits, adv, fcol, inst, cells, word)
+        for t, src in enumerate(seg.sources):
+            w_cell = SC.REGION_ROWS * (firsts[j] + SC.BLOCK_REGIONS * (t // 16) + 4 + t % 16) + wrow
+            if isinstance(src, Const):
+                fixed["const"][w_cell] = src.value
+                copies.append(((fcol["const"], w_cell), (X, w_cell)))
+            elif isinstance(src, DigestWord):  # tail region 3 - i % 4 holds digest word i: its A row for i < 4, its E row otherwise
+                s = plan.segments[src.segment]
+                tail = SC.REGION_ROWS * (firsts[src.segment] + SC.BLOCK_REGIONS * s.blocks + 3 - src.word % 4)
+                copies.append(((X, tail + (arow if src.word < 4 else erow)), (X, w_cell)))
+    return SC.Description(cs, adv, fcol, fixed, inst, copies, cells, table_bits, tuple(s.blocks for s in plan.segments), k)
+
+
+def _words_to_mont(words) -> np.ndarray:
+    """32-bit words -> uint64[len, 4] Montgomery limbs (a batch has thousands of instance words: one bytes join, no
+    array per word)."""
+    r = (1 << 256) % FR_MODULUS
+    return np.frombuffer(b"".join((int(w) * r % FR_MODULUS).to_bytes(32, "little") for w in words), dtype=np.uint64).reshape(-1, 4).copy()
+
+
+def _digest_words(message: bytes):
+    return list(struct.unpack(">8I", message))
+
+
+class Sha256SegmentsCircuit:
+    """Proving key and GPU witness synthesis for a plan of wired SHA-256 segments at 2^k rows.  A key fixes the plan:
+    the number of segments, their block counts, their wiring and which digests are public.
+
+    `values` (synthesize, check, assert_satisfied, prove) is one sequence per segment: the segment's Private words in
+    word order.  Private words are unconstrained -- a private message's padding included, exactly as in Sha256Circuit:
+    the circuit proves the compression of the words it is given, not that they are a padded message.  Const words and
+    DigestWord wirings are constrained."""
+
+    def __init__(self, ctx: Context, k: int, plan: Plan, table_bits: int = 12, setup: str = "toxic", seed: int = 0x5348413243515F):
+        self.plan = plan
+        SC._build_key(self, ctx, k, table_bits, setup, seed, lambda dense, spread: describe(k, plan, table_bits, dense, spread))
+        self.rows = rows_for(plan)
+        # the word buffer: the distinct constants, then every Private word in (segment, word) order
+        consts = sorted({s.value for seg in plan.segments for s in seg.sources if isinstance(s, Const)})
+        at_const = {v: i for i, v in enumerate(consts)}
+        self._consts = np.array(consts, dtype=np.uint32)
+        self._private_counts = [sum(isinstance(s, Private) for s in seg.sources) for seg in plan.segments]
+        sources, nxt = [], len(consts)
+        for seg in plan.segments:
+            for s in seg.sources:
+                if isinstance(s, Private):
+                    sources.append(nxt)
+                    nxt += 1
+                else:
+                    sources.append(at_const[s.value] if isinstance(s, Const) else SOURCE_DIGEST + 8 * s.segment + s.word)
+        self._sources = np.array(sources, dtype=np.uint32)
+        self._seg_blocks = np.array([seg.blocks for seg in plan.segments], dtype=np.uint32)
+        self._words_len = nxt
+        self._words = ctx.alloc(4 * max(nxt, 1))
+        self._digests = ctx.alloc(32 * len(plan.segments))
+        self.digest_words = self.instances = None
+
+    # ---- witness ----
+    def _values(self, values):
+        return values
+
+    def synthesize(self, values):
+        """Uploads the word buffer, fills the advice columns on the GPU (cq_sha256_synthesize_segments_dev) and downloads the
+        digests; returns (device columns, instances)."""
+        ctx, values = self.ctx, [np.asarray(v, dtype=np.uint32).reshape(-1) for v in self._values(values)]
+        if [len(v) for v in values] != self._private_counts:
+            raise ValueError(f"private words per segment: {self._private_counts}, not {[len(v) for v in values]}")
+        self._words.upload(np.concatenate([self._consts] + values))
+        arr = (C.c_void_p * SC.ADVICE_COLUMNS)(*[c.ptr for c in self.cols])
+        ctx._chk(ctx.lib.cq_sha256_synthesize_segments_dev(ctx.h, self.table_bits, self._seg_blocks.ctypes.data, len(self._seg_blocks),
+                                                           self._sources.ctypes.data, self._words.ptr, self._words_len, self.n, arr,
+                                                           self._digests.ptr))
+        self.digest_words = self._digests.download((len(self._seg_blocks), 8), np.uint32).tolist()
+        self.instances = [_words_to_mont([x for p in self.plan.public for x in self.digest_words[p]])]
+        return self.cols, self.instances
+
+    @property
+    def digests(self):
+        """The digests of the public segments of the last synthesis, 32 big-endian bytes each, in instance order."""
+        return [struct.pack(">8I", *self.digest_words[p]) for p in self.plan.public]
+
+    def _result(self):
+        return self.digests
+
+    def check(self, values, max_failures: int = 64):
+        cols, inst = self.synthesize(values)
+        return self.pk.check_witness([c.ptr for c in cols], instances=inst, max_failures=max_failures)
+
+    def assert_satisfied(self, values):
+        cols, inst = self.synthesize(values)
+        self.pk.assert_satisfied([c.ptr for c in cols], instances=inst)
+
+    def prove(self, values, seed: int = 1):
+        """(proof bytes, public digests): create_proof with the public segments' digest words as the public inputs."""
+        cols, inst = self.synthesize(values)
+        return self.pk.create_proof_dev([c.ptr for c in cols], seed=seed, instances=inst), self._result()
+
+    def close(self):
+        for o in (self._words, self._digests):
+            o.close()
+        SC._close_key(self)
+
+
+class Sha256BatchCircuit(Sha256SegmentsCircuit):
+    """Several independent messages in one proof, message j of exactly blocks_list[j] padded blocks; every digest is
+    public.  The methods take the list of messages (bytes) and pad them here: the padding is private words like the rest
+    of a message and is not constrained."""
+
+    def __init__(self, ctx: Context, k: int, blocks_list, **kw):
+        super().__init__(ctx, k, batch(blocks_list), **kw)
+
+    def _values(self, messages):
+        if len(messages) != len(self.plan.segments):
+            raise ValueError(f"{len(self.plan.segments)} messages, not {len(messages)}")
+        return [SC.pad(m, seg.blocks) for m, seg in zip(messages, self.plan.segments)]
+
+
+class Sha256dCircuit(Sha256SegmentsCircuit):
+    """SHA-256(SHA-256(message)) for a message of exactly `blocks` padded blocks; the double digest is public, the inner one
+    is not.  The methods take the message (bytes) and pad it here: that padding is private and not constrained; the second
+    hash's input is wired to the first digest and its padding is pinned."""
+
+    def __init__(self, ctx: Context, k: int, blocks: int, **kw):
+        super().__init__(ctx, k, double_sha256(blocks), **kw)
+
+    def _values(self, message):
+        return [SC.pad(message, self.plan.segments[0].blocks), []]
+
+    def _result(self):
+        return self.digests[0]
+
+
+class Sha256MerkleCircuit(Sha256SegmentsCircuit):
+    """The SHA-256 Merkle root over 2^depth private 32-byte leaves (node = SHA-256(left || right)); the root is public.
+    The methods take the list of leaves.  Every node's children are wired and its padding block is pinned, so nothing but
+    the leaves is free."""
+
+    def __init__(self, ctx: Context, k: int, depth: int, **kw):
+        self.depth = depth
+        super().__init__(ctx, k, merkle_tree(depth), **kw)
+
+    def _values(self, leaves):
+        if len(leaves) != 1 << self.depth or any(len(leaf) != 32 for leaf in leaves):
+            raise ValueError(f"{1 << self.depth} leaves of 32 bytes each")
+        pairs = 1 << (self.depth - 1)
+        return [_digest_words(leaves[2 * i]) + _digest_words(leaves[2 * i + 1]) for i in range(pairs)] + [[]] * (pairs - 1)
+
+    def _result(self):
+        return self.digests[0]

@@ -5,7 +5,14 @@ holds; next to them the proof of `ShaPlonkWorkload` at the same k, in the same p
 Every timed call ends in a stream synchronise (synthesize: an explicit one here), so a host clock around it measures
 the whole thing.
 
-    python tools/sha256_perf.py [--sizes 14,18] [--reps 15] [--warmup 3]
+With --segments-k K (0 = off): the wired-segment circuits at 2^K rows -- `Sha256BatchCircuit` of as many one-block
+messages as fit and `Sha256MerkleCircuit` of the largest depth that fits: synthesize (word upload, the entry point with
+its device compression chains, digest download), check and proof; beside the batch, `Sha256Circuit.synthesize` (the host
+compression chain) at the same total block count.  Then a sweep over the segment count at 2^K rows, entry point against
+entry point with no key: cq_sha256_synthesize_segments_dev on c one-block segments whose words are already on the
+device, and cq_sha256_synthesize_dev on one message of c blocks, each followed by a stream synchronise.
+
+    python tools/sha256_perf.py [--sizes 14,18] [--segments-k 18] [--sweep 1,2,4,...] [--reps 15] [--warmup 3]
 """
 import argparse
 import json
@@ -28,9 +35,92 @@ def median_ms(fn, reps, warmup):
     return round(statistics.median(ts), 3), [round(min(ts), 3), round(max(ts), 3)]
 
 
+def timed(row, legs, reps, warmup):
+    for name, fn in legs:
+        row[name], row[name + "_range"] = median_ms(fn, reps, warmup)
+
+
+def segment_legs(ctx, k, sweep, reps, warmup):
+    import ctypes as C
+    import hashlib
+
+    import numpy as np
+
+    from sha2_on_cq_halo2_amd import sha256_circuit as SC
+    from sha2_on_cq_halo2_amd.api import Sha256BatchCircuit, Sha256Circuit, Sha256MerkleCircuit
+
+    usable = SC.usable_rows(k)
+    count = usable // SC.rows_for(1)
+    depth = (usable // SC.rows_for(2) + 1).bit_length() - 1  # 2^depth - 1 two-block nodes
+    messages = [bytes((i + j) % 251 for i in range(55 - j % 7)) for j in range(count)]
+    leaves = [hashlib.sha256(bytes([i % 256, i // 256])).digest() for i in range(1 << depth)]
+    for name, make, arg, shape in (("Sha256BatchCircuit", lambda: Sha256BatchCircuit(ctx, k, [1] * count), messages, {"segments": count, "blocks": count, "levels": 1}),
+                                   ("Sha256MerkleCircuit", lambda: Sha256MerkleCircuit(ctx, k, depth), leaves,
+                                    {"depth": depth, "segments": (1 << depth) - 1, "blocks": 2 * ((1 << depth) - 1), "levels": depth})):
+        t0 = time.perf_counter()
+        c = make()
+        row = {"circuit": name, "k": k, **shape, "rows": c.rows, "keygen_s": round(time.perf_counter() - t0, 2)}
+        assert c.check(arg) == (0, [])
+        ptrs, seed = [b.ptr for b in c.cols], [0]
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+
+        def call():  # the entry point alone: the word buffer of the last synthesize is still on the device
+            ctx._chk(ctx.lib.cq_sha256_synthesize_segments_dev(ctx.h, c.table_bits, c._seg_blocks.ctypes.data, len(c._seg_blocks), c._sources.ctypes.data,
+                                                               c._words.ptr, c._words_len, c.n, arr, c._digests.ptr))
+            ctx.sync()
+
+        def prove():
+            seed[0] += 1
+            c.pk.create_proof_dev(ptrs, seed=seed[0], instances=c.instances)
+
+        timed(row, (("synthesize_ms", lambda: c.synthesize(arg)), ("synthesize_call_ms", call),
+                    ("check_ms", lambda: c.pk.check_witness(ptrs, instances=c.instances, max_failures=0)), ("proof_ms", prove)), reps, warmup)
+        c.close()
+        if name == "Sha256BatchCircuit":  # the host-chain path at the same total block count, same process
+            one = Sha256Circuit(ctx, k, count)
+            msg = bytes(i % 251 for i in range(64 * count - 9))
+
+            def host():
+                one.synthesize(msg)
+                ctx.sync()
+
+            timed(row, (("sha256circuit_same_blocks_synthesize_ms", host),), reps, warmup)
+            row["synthesize_vs_host_chain"] = round(row["synthesize_ms"] / row["sha256circuit_same_blocks_synthesize_ms"], 3)
+            row["synthesize_call_vs_host_chain"] = round(row["synthesize_call_ms"] / row["sha256circuit_same_blocks_synthesize_ms"], 3)
+            one.close()
+        print(json.dumps(row), flush=True)
+    # the sweep: no key, one set of columns
+    n = 1 << k
+    cols = [ctx.alloc(32 * n) for _ in range(SC.ADVICE_COLUMNS)]
+    arr = (C.c_void_p * len(cols))(*[b.ptr for b in cols])
+    words = np.array(SC.pad(bytes(i % 251 for i in range(64 * count - 9))), dtype=np.uint32)
+    words_dev, digests_dev, digest = ctx.to_device(words), ctx.alloc(32 * count), (C.c_uint32 * 8)()
+    for c_ in (int(x) for x in sweep.split(",")):
+        c_ = min(c_, count)
+        blocks, sources = np.ones(c_, dtype=np.uint32), np.arange(16 * c_, dtype=np.uint32)
+
+        def device():
+            ctx._chk(ctx.lib.cq_sha256_synthesize_segments_dev(ctx.h, 12, blocks.ctypes.data, c_, sources.ctypes.data, words_dev.ptr, len(words), n, arr,
+                                                               digests_dev.ptr))
+            ctx.sync()
+
+        def host():
+            ctx._chk(ctx.lib.cq_sha256_synthesize_dev(ctx.h, 12, words.ctypes.data, c_, n, arr, digest))
+            ctx.sync()
+
+        row = {"sweep": "one-block segments (device chains) vs one message of as many blocks (host chain)", "k": k, "count": c_}
+        timed(row, (("segments_call_ms", device), ("host_chain_call_ms", host)), reps, warmup)
+        row["ratio"] = round(row["segments_call_ms"] / row["host_chain_call_ms"], 3)
+        print(json.dumps(row), flush=True)
+    for b in cols + [words_dev, digests_dev]:
+        b.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="14,18")
+    ap.add_argument("--segments-k", type=int, default=0)
+    ap.add_argument("--sweep", default="1,2,4,8,16,32,64,128,256,512")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args()
@@ -42,7 +132,7 @@ def main():
     from sha2_on_cq_halo2_amd.sha_circuit import ShaPlonkWorkload
 
     ctx = Context(0)
-    for k in (int(s) for s in args.sizes.split(",")):
+    for k in (int(s) for s in args.sizes.split(",") if s):
         t0 = time.perf_counter()
         c = Sha256Circuit(ctx, k)
         keygen_s = time.perf_counter() - t0
@@ -68,6 +158,8 @@ def main():
         row["sha_plonk_workload_proof_ms"], row["sha_plonk_workload_proof_ms_range"] = median_ms(lambda: wl.prove(seed=3), args.reps, args.warmup)
         wl.close()
         print(json.dumps(row), flush=True)
+    if args.segments_k:
+        segment_legs(ctx, args.segments_k, args.sweep, args.reps, args.warmup)
     ctx.close()
 
 
