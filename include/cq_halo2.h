@@ -893,6 +893,26 @@ int cq_sha256_synthesize_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* m
 int cq_sha256_synthesize_segments_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
                                       const uint32_t* sources, const uint32_t* words_dev, size_t words_len, size_t n,
                                       uint64_t* const* cols_dev, uint32_t* digests_dev);
+/* The same with message words that are a choice between two operands under a private bit (DESIGN.md "Choice-wired message
+ * words").  A source value CQ_SHA256_SOURCE_CHOICE + c (the digest flag is tested first) means entry c of `choices`, a host
+ * array of `n_choices` entries of four words {bit, zero, one, 0}: `bit` is an index into `words_dev` of a word that is 0 or
+ * 1; `zero` and `one` are plain sources -- a word index or a digest reference -- and the message word is `one` if the bit
+ * word is not zero, else `zero`.  Every entry must be referenced by exactly one message word, whose region it then belongs
+ * to: after the expansion a kernel writes the zero operand, the one operand and the bit word as given (a bit word that is
+ * neither 0 nor 1 is the witness checker's finding, not an error here) to rows CQ_SHA256_CHOICE_ROW_ZERO / _ONE / _BIT of
+ * that region in advice column CQ_SHA256_ADVICE_COLUMNS - 1, which the expansion leaves zero.  A segment's level also
+ * counts the digests its choices read.  With n_choices > 0, words_len must not exceed CQ_SHA256_SOURCE_CHOICE.
+ * CQ_ERR_ARG, besides the cases above and again before anything is queued: a choice index >= n_choices, an entry
+ * referenced twice or never, a bit or operand index outside `words_dev`, a digest operand of the segment itself or a
+ * later one.  n_choices = 0 (`choices` may be NULL) is cq_sha256_synthesize_segments_dev exactly. */
+#define CQ_SHA256_SOURCE_CHOICE 1073741824u
+#define CQ_SHA256_CHOICE_WORDS 4
+#define CQ_SHA256_CHOICE_ROW_ZERO 4
+#define CQ_SHA256_CHOICE_ROW_ONE 5
+#define CQ_SHA256_CHOICE_ROW_BIT 6
+int cq_sha256_synthesize_choices_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
+                                     const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* words_dev,
+                                     size_t words_len, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev);
 
 /* ---- harness RNG (not in the reference: its test draws from OsRng) ---------------------------------- */
 void cq_xoshiro256ss_seed(uint64_t seed, uint64_t state[4]);

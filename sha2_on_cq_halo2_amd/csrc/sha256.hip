@@ -6,6 +6,9 @@
 // Wired segments (cq_sha256_synthesize_segments_dev, further down): several chains whose message words may be digest words
 // of earlier chains.  There the chains run on the device, one lane per segment and one launch per dependency level, and
 // leave the same four words per region for the same expansion kernel.
+// Choices (cq_sha256_synthesize_choices_dev): a message word may be one of two operands under a private bit.  The chain
+// kernel's fetch takes the operand the bit selects, and a small kernel behind the expansion writes both operands and the
+// bit into three cells of the word's region that the layout leaves free.
 #include <cstring>
 #include <string>
 #include <utility>
@@ -213,12 +216,31 @@ static __device__ __forceinline__ void sha256_put_state(Sha256Region* out, const
   sha256_put(out + 3, h[0], h[4], 0, chain | SHA_RG_F3);
 }
 
-// Message word I of a block: a word of the caller's buffer or a digest word an earlier level's launch stored.  The host
-// has checked every source against both arrays' lengths.
-template <uint32_t I>
-static __device__ __forceinline__ void sha256_fetch(uint32_t (&w)[16], const uint32_t* src, const uint32_t* words, const uint32_t* digests) {
+// A plain source: a word of the caller's buffer or a digest word an earlier level's launch stored.  The host has checked
+// every source against both arrays' lengths.
+static __device__ __forceinline__ uint32_t sha256_load(uint32_t s, const uint32_t* words, const uint32_t* digests) {
+  return *((s & CQ_SHA256_SOURCE_DIGEST) ? digests + (s & (CQ_SHA256_SOURCE_DIGEST - 1)) : words + s);
+}
+
+// One entry of the choice table as the device sees it: the bit's index in the word buffer, the two operands (plain
+// sources), and -- filled in by the host -- the region of the message word that refers to the entry.
+struct Sha256Choice {
+  uint32_t bit, zero, one, region;
+};
+
+// Message word I of a block.  With CHOICES a source may name an entry of `choices`: the bit and both operands are read and
+// the word is `bit ? one : zero`; without, the fetch is a plain source's and `choices` is not looked at.
+template <bool CHOICES, uint32_t I>
+static __device__ __forceinline__ void sha256_fetch(uint32_t (&w)[16], const uint32_t* src, const Sha256Choice* choices, const uint32_t* words,
+                                                    const uint32_t* digests) {
   const uint32_t s = src[I];
-  w[I] = *((s & CQ_SHA256_SOURCE_DIGEST) ? digests + (s & (CQ_SHA256_SOURCE_DIGEST - 1)) : words + s);
+  if (CHOICES && !(s & CQ_SHA256_SOURCE_DIGEST) && s >= CQ_SHA256_SOURCE_CHOICE) {
+    const uint4 c = *reinterpret_cast<const uint4*>(choices + (s - CQ_SHA256_SOURCE_CHOICE));
+    const uint32_t bit = words[c.x], zero = sha256_load(c.y, words, digests), one = sha256_load(c.z, words, digests);
+    w[I] = bit ? one : zero;
+  } else {
+    w[I] = sha256_load(s, words, digests);
+  }
 }
 
 // Round T0 + I on the 16-word rolling schedule and the state (a .. h), and its region.  I is a compile-time constant, so
@@ -237,19 +259,21 @@ static __device__ __forceinline__ void sha256_steps(uint32_t (&s)[8], uint32_t (
                                                     std::integer_sequence<uint32_t, I...>) {
   (sha256_step<SCHED, I>(s, w, t0, out), ...);
 }
-template <uint32_t... I>
-static __device__ __forceinline__ void sha256_fetch_all(uint32_t (&w)[16], const uint32_t* src, const uint32_t* words, const uint32_t* digests,
-                                                        std::integer_sequence<uint32_t, I...>) {
-  (sha256_fetch<I>(w, src, words, digests), ...);
+template <bool CHOICES, uint32_t... I>
+static __device__ __forceinline__ void sha256_fetch_all(uint32_t (&w)[16], const uint32_t* src, const Sha256Choice* choices, const uint32_t* words,
+                                                        const uint32_t* digests, std::integer_sequence<uint32_t, I...>) {
+  (sha256_fetch<CHOICES, I>(w, src, choices, words, digests), ...);
 }
 
 // One lane per segment of one level: what sha256_regions does for one message, with the message words gathered through
 // `sources`.  A chain is 64 dependent rounds per block, so the launch is latency-bound: one wave per workgroup spreads a
 // level's segments over the CUs.  Lanes of a wave may differ in their block counts.  `digests` is read (earlier levels)
-// and written (this lane's segment), hence neither const nor restrict.
+// and written (this lane's segment), hence neither const nor restrict.  CHOICES: whether the launch's sources may name
+// entries of `choices` (sha256_fetch); a plan without choices runs the instantiation whose fetch knows nothing of them.
+template <bool CHOICES>
 __global__ __launch_bounds__(64) void sha256_chain_kernel(const Sha256Lane* __restrict__ lanes, uint32_t nlanes,
-                                                          const uint32_t* __restrict__ sources, const uint32_t* words, uint32_t* digests,
-                                                          Sha256Region* __restrict__ regions) {
+                                                          const uint32_t* __restrict__ sources, const Sha256Choice* __restrict__ choices,
+                                                          const uint32_t* words, uint32_t* digests, Sha256Region* __restrict__ regions) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nlanes) return;
   const Sha256Lane lane = lanes[i];
@@ -260,7 +284,7 @@ __global__ __launch_bounds__(64) void sha256_chain_kernel(const Sha256Lane* __re
   for (uint32_t b = 0; b < lane.blocks; b++, out += CQ_SHA256_BLOCK_REGIONS, src += 16) {
     sha256_put_state(out, h, b ? SHA_RG_CHAIN : 0);
     uint32_t w[16], s[8] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]};
-    sha256_fetch_all(w, src, words, digests, Seq16{});
+    sha256_fetch_all<CHOICES>(w, src, choices, words, digests, Seq16{});
     sha256_steps<false>(s, w, 0, out + 4, Seq16{});
     for (uint32_t t0 = 16; t0 < 64; t0 += 16) sha256_steps<true>(s, w, t0, out + 4, Seq16{});
     h[0] += s[0], h[1] += s[1], h[2] += s[2], h[3] += s[3];
@@ -271,10 +295,30 @@ __global__ __launch_bounds__(64) void sha256_chain_kernel(const Sha256Lane* __re
   d[0] = h[0], d[1] = h[1], d[2] = h[2], d[3] = h[3], d[4] = h[4], d[5] = h[5], d[6] = h[6], d[7] = h[7];
 }
 
-// Validates the description, then queues the tables' upload, one chain launch per level and the expansion.  Nothing here
-// waits for the stream; the staging is pinned, and only the previous call's copy out of it is waited for.
+// One thread per choice entry, after the expansion (which wrote these cells as zero) on the same stream: the operand taken
+// for bit 0, the one taken for bit 1 and the bit word as given, in rows CQ_SHA256_CHOICE_ROW_* of the entry's region in
+// column Y.  Every digest is final by now.  The host has checked the entry's indices and set its region, which lies
+// below n / CQ_SHA256_REGION_ROWS.
+__global__ __launch_bounds__(64) void sha256_choice_fill_kernel(const Sha256Choice* __restrict__ choices, uint32_t nchoices,
+                                                                const uint32_t* __restrict__ words, const uint32_t* __restrict__ digests,
+                                                                Fr* __restrict__ y) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nchoices) return;
+  const uint4 c = *reinterpret_cast<const uint4*>(choices + i);
+  const uint32_t bit = words[c.x], zero = sha256_load(c.y, words, digests), one = sha256_load(c.z, words, digests);
+  Fr* cell = y + (size_t)c.w * CQ_SHA256_REGION_ROWS;
+  st(cell + CQ_SHA256_CHOICE_ROW_ZERO, zero ? Fr::from_u64(zero) : Fr::zero());
+  st(cell + CQ_SHA256_CHOICE_ROW_ONE, one ? Fr::from_u64(one) : Fr::zero());
+  st(cell + CQ_SHA256_CHOICE_ROW_BIT, bit ? Fr::from_u64(bit) : Fr::zero());
+}
+
+// Validates the description, then queues the tables' upload, one chain launch per level, the expansion and -- with
+// choices -- the fill of their cells.  Nothing here waits for the stream; the staging is pinned, and only the previous
+// call's copy out of it is waited for.  n_choices = 0 is the description without choices: a source at or above
+// CQ_SHA256_SOURCE_CHOICE is then a word index like any other.
 int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* sources,
-                               const uint32_t* words_dev, size_t words_len, uint32_t n, const Sha256Cols& cols, uint32_t* digests_dev) {
+                               const uint32_t* choices, size_t n_choices, const uint32_t* words_dev, size_t words_len, uint32_t n,
+                               const Sha256Cols& cols, uint32_t* digests_dev) {
   const uint64_t max_regions = n / CQ_SHA256_REGION_ROWS;
   uint64_t regions = 0, blocks = 0;
   for (size_t j = 0; j < segments; j++) {
@@ -284,18 +328,42 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
     if (regions > max_regions) return c->fail(CQ_ERR_ARG, "sha256: the segments up to segment " + std::to_string(j) + " do not fit the rows");
   }
   std::vector<uint32_t> level(segments, 0), level_count;
-  for (size_t j = 0, at = 0; j < segments; j++)
+  std::vector<uint32_t> choice_region(n_choices, UINT32_MAX);  // the region of the word that refers to the entry, once one does
+  uint32_t seg_region = 0;
+  for (size_t j = 0, at = 0; j < segments; seg_region += seg_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS, j++)
     for (size_t t = 0; t < 16 * (size_t)seg_blocks[j]; t++, at++) {
-      const uint32_t s = sources[at];
       auto where = [&] { return "sha256: segment " + std::to_string(j) + ", word " + std::to_string(t); };
-      if (s & CQ_SHA256_SOURCE_DIGEST) {
-        const size_t ref = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3;
-        if (ref >= j) return c->fail(CQ_ERR_ARG, where() + " reads the digest of segment " + std::to_string(ref) + ", which does not come before it");
-        if (level[ref] + 1 > level[j]) level[j] = level[ref] + 1;
-      } else if (s >= words_len) {
-        return c->fail(CQ_ERR_ARG, where() + " reads word " + std::to_string(s) + " of a buffer of " + std::to_string(words_len));
+      // a plain source, the word's own or a choice's operand: "" if it is good, and the segment's level follows a digest's
+      auto plain = [&](uint32_t s) -> std::string {
+        if (s & CQ_SHA256_SOURCE_DIGEST) {
+          const size_t ref = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3;
+          if (ref >= j) return " reads the digest of segment " + std::to_string(ref) + ", which does not come before it";
+          if (level[ref] + 1 > level[j]) level[j] = level[ref] + 1;
+        } else if (s >= words_len) {
+          return " reads word " + std::to_string(s) + " of a buffer of " + std::to_string(words_len);
+        }
+        return "";
+      };
+      const uint32_t s = sources[at];
+      std::string bad;
+      if (n_choices && !(s & CQ_SHA256_SOURCE_DIGEST) && s >= CQ_SHA256_SOURCE_CHOICE) {
+        const size_t e = s - CQ_SHA256_SOURCE_CHOICE;
+        if (e >= n_choices) return c->fail(CQ_ERR_ARG, where() + " reads choice " + std::to_string(e) + " of " + std::to_string(n_choices));
+        if (choice_region[e] != UINT32_MAX) return c->fail(CQ_ERR_ARG, where() + " reads choice " + std::to_string(e) + ", which another word reads already");
+        choice_region[e] = seg_region + (uint32_t)(t / 16) * CQ_SHA256_BLOCK_REGIONS + 4 + (uint32_t)(t % 16);
+        const uint32_t* entry = choices + CQ_SHA256_CHOICE_WORDS * e;
+        if (entry[0] >= words_len)
+          bad = "'s bit reads word " + std::to_string(entry[0]) + " of a buffer of " + std::to_string(words_len);
+        for (uint32_t o = 1; o <= 2 && bad.empty(); o++)
+          if (!(bad = plain(entry[o])).empty()) bad = std::string(o == 1 ? "'s zero operand" : "'s one operand") + bad;
+        if (!bad.empty()) bad = ", choice " + std::to_string(e) + bad;
+      } else {
+        bad = plain(s);
       }
+      if (!bad.empty()) return c->fail(CQ_ERR_ARG, where() + bad);
     }
+  for (size_t e = 0; e < n_choices; e++)
+    if (choice_region[e] == UINT32_MAX) return c->fail(CQ_ERR_ARG, "sha256: choice " + std::to_string(e) + " is read by no word");
   for (uint32_t l : level) {
     if (l >= level_count.size()) level_count.resize(l + 1, 0);
     level_count[l]++;
@@ -304,7 +372,10 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
   for (size_t l = 1; l < level_count.size(); l++) level_first[l] = level_first[l - 1] + level_count[l - 1];
 
   static_assert(sizeof(Sha256Region) == 16 && sizeof(Sha256Lane) == 16, "four words each");
-  const size_t lanes_bytes = segments * sizeof(Sha256Lane), tables_bytes = lanes_bytes + 16 * blocks * sizeof(uint32_t);
+  static_assert(sizeof(Sha256Choice) == CQ_SHA256_CHOICE_WORDS * sizeof(uint32_t), "an entry of the choice table as the header states it");
+  // lanes, sources, choices: each a multiple of 16 bytes, so the choice entries are aligned for their 16-byte loads
+  const size_t lanes_bytes = segments * sizeof(Sha256Lane), sources_bytes = 16 * blocks * sizeof(uint32_t);
+  const size_t tables_bytes = lanes_bytes + sources_bytes + n_choices * sizeof(Sha256Choice);
   void *pin, *dev_regions, *dev_tables;
   CQ_TRY(c->ensure_pinned_sha(tables_bytes, &pin));
   CQ_TRY(c->ensure_scratch(Scratch::EntryA, regions * sizeof(Sha256Region), &dev_regions));
@@ -319,18 +390,33 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
     first_region += seg_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS;
     first_source += 16 * seg_blocks[j];
   }
-  memcpy((char*)pin + lanes_bytes, sources, 16 * blocks * sizeof(uint32_t));
+  memcpy((char*)pin + lanes_bytes, sources, sources_bytes);
+  Sha256Choice* staged = (Sha256Choice*)((char*)pin + lanes_bytes + sources_bytes);
+  for (size_t e = 0; e < n_choices; e++)
+    staged[e] = {choices[CQ_SHA256_CHOICE_WORDS * e], choices[CQ_SHA256_CHOICE_WORDS * e + 1], choices[CQ_SHA256_CHOICE_WORDS * e + 2], choice_region[e]};
   CQ_HIP(c, hipMemcpyAsync(dev_tables, pin, tables_bytes, hipMemcpyHostToDevice, c->stream));
   CQ_HIP(c, hipEventRecord(c->sha_staged, c->stream));
   const Sha256Lane* dev_lanes = (const Sha256Lane*)dev_tables;
   const uint32_t* dev_sources = (const uint32_t*)((const char*)dev_tables + lanes_bytes);
+  const Sha256Choice* dev_choices = (const Sha256Choice*)((const char*)dev_sources + sources_bytes);
   for (size_t l = 0; l < level_count.size(); l++) {
-    sha256_chain_kernel<<<(level_count[l] + 63) / 64, 64, 0, c->stream>>>(dev_lanes + level_first[l], level_count[l], dev_sources, words_dev,
-                                                                         digests_dev, (Sha256Region*)dev_regions);
+    const uint32_t grid = (level_count[l] + 63) / 64;
+    if (n_choices)
+      sha256_chain_kernel<true><<<grid, 64, 0, c->stream>>>(dev_lanes + level_first[l], level_count[l], dev_sources, dev_choices, words_dev,
+                                                            digests_dev, (Sha256Region*)dev_regions);
+    else
+      sha256_chain_kernel<false><<<grid, 64, 0, c->stream>>>(dev_lanes + level_first[l], level_count[l], dev_sources, nullptr, words_dev,
+                                                             digests_dev, (Sha256Region*)dev_regions);
     if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_chain launch failed");
   }
   sha256_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha256Region*)dev_regions, (uint32_t)regions, n, table_bits, cols);
-  return hipGetLastError() == hipSuccess ? CQ_OK : c->fail(CQ_ERR_HIP, "sha256_expand launch failed");
+  if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_expand launch failed");
+  if (n_choices) {
+    sha256_choice_fill_kernel<<<((uint32_t)n_choices + 63) / 64, 64, 0, c->stream>>>(dev_choices, (uint32_t)n_choices, words_dev, digests_dev,
+                                                                                    cols.p[SHA256_COL_Y]);
+    if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_choice_fill launch failed");
+  }
+  return CQ_OK;
 }
 
 }  // namespace cq
@@ -364,13 +450,16 @@ int cq_sha256_synthesize_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* msg
   return sha256_synthesize(c, table_bits, msg_words, blocks, (uint32_t)n, sc, digest);
 }
 
-int cq_sha256_synthesize_segments_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
-                                      const uint32_t* sources, const uint32_t* words_dev, size_t words_len, size_t n,
-                                      uint64_t* const* cols_dev, uint32_t* digests_dev) {
+// both entry points below: the argument checks that need no description, then the host function
+static int sha256_segments_entry(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* sources,
+                                 const uint32_t* choices, size_t n_choices, const uint32_t* words_dev, size_t words_len, size_t n,
+                                 uint64_t* const* cols_dev, uint32_t* digests_dev) {
   if (!c) return CQ_ERR_ARG;
   if (!seg_blocks || !sources || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull || (!words_dev && words_len) ||
       words_len > CQ_SHA256_SOURCE_DIGEST)
     return c->fail(CQ_ERR_ARG, "sha256: null array, no segment, or a length out of range");
+  if (n_choices && (!choices || words_len > CQ_SHA256_SOURCE_CHOICE || n_choices > n))
+    return c->fail(CQ_ERR_ARG, "sha256: null choice table, more choices than rows, or a word buffer that reaches the choice flag");
   if (table_bits < CQ_SHA256_MIN_TABLE_BITS || table_bits > CQ_SHA256_MAX_TABLE_BITS)
     return c->fail(CQ_ERR_ARG, "sha256: table_bits outside the range the pieces fit");
   CQ_HIP(c, hipSetDevice(c->device));
@@ -379,7 +468,20 @@ int cq_sha256_synthesize_segments_dev(cq_ctx* c, uint32_t table_bits, const uint
     if (!cols_dev[i]) return c->fail(CQ_ERR_ARG, "sha256: null column");
     sc.p[i] = (Fr*)cols_dev[i];
   }
-  return sha256_synthesize_segments(c, table_bits, seg_blocks, segments, sources, words_dev, words_len, (uint32_t)n, sc, digests_dev);
+  return sha256_synthesize_segments(c, table_bits, seg_blocks, segments, sources, choices, n_choices, words_dev, words_len, (uint32_t)n, sc,
+                                    digests_dev);
+}
+
+int cq_sha256_synthesize_segments_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
+                                      const uint32_t* sources, const uint32_t* words_dev, size_t words_len, size_t n,
+                                      uint64_t* const* cols_dev, uint32_t* digests_dev) {
+  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, nullptr, 0, words_dev, words_len, n, cols_dev, digests_dev);
+}
+
+int cq_sha256_synthesize_choices_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
+                                     const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* words_dev,
+                                     size_t words_len, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
+  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, choices, n_choices, words_dev, words_len, n, cols_dev, digests_dev);
 }
 
 }  // extern "C"

@@ -46,6 +46,11 @@ GATES = ("a_word", "a_spread", "e_word", "e_spread", "w_word", "Sigma0_even_odd"
          "chq_even_odd", "ch_word", "e_add", "a_add", "w_add", "chain_a", "chain_e")
 # fixed columns in allocation order
 FIXED = ("q_all", "q_f3", "q_round", "q_sched", "q_chain") + tuple(f"scale{j}" for j in range(PAIRS)) + ("const",)
+# the choice variant of the constraint system (plans with a Choice word, sha256_segments.py): one selector behind `const`,
+# two gates behind the others, and three cells in the rows column Y leaves free in a region
+GATES_CHOICE = GATES + ("choice", "choice_bit")
+FIXED_CHOICE = FIXED + ("q_choice",)
+CHOICE_ROW_ZERO, CHOICE_ROW_ONE, CHOICE_ROW_BIT = (_CQ["CQ_SHA256_CHOICE_ROW_" + s] for s in ("ZERO", "ONE", "BIT"))
 
 
 class Cell(NamedTuple):
@@ -87,8 +92,9 @@ def pad(message: bytes, blocks: int | None = None):
 
 
 class Description(NamedTuple):
-    """The circuit without a device: constraint system, fixed columns (integers, by FIXED name), copy constraints
-    ((column, row), (column, row)) and the instance rows' sources."""
+    """The circuit without a device: constraint system, fixed columns (integers, by name; `fixed_names` is their
+    allocation order: FIXED, or FIXED_CHOICE for the choice variant), copy constraints ((column, row), (column, row)) and
+    the instance rows' sources."""
 
     cs: GP.ConstraintSystem
     advice: list
@@ -100,6 +106,7 @@ class Description(NamedTuple):
     table_bits: int
     blocks: int
     k: int
+    fixed_names: tuple = FIXED
 
 
 def _field_of(cell: Cell, tb: int):
@@ -117,14 +124,16 @@ def describe(k: int, blocks: int, table_bits: int = 12, dense="dense", spread="s
     return _assign_fixed(k, blocks, table_bits, cs, adv, fcol, inst, cells, word)
 
 
-def _constraint_system(tb: int, dense, spread):
+def _constraint_system(tb: int, dense, spread, choice: bool = False):
+    """`choice`: the variant for plans with choice-wired message words -- the fixed column `q_choice`, equality on column
+    Y and the gates `choice` and `choice_bit`; everything else is the plain system, built by the same lines."""
     cells = layout()
     cs = GP.ConstraintSystem()
     adv = [cs.advice_column() for _ in range(ADVICE_COLUMNS)]
-    fcol = {name: cs.fixed_column() for name in FIXED}
+    fcol = {name: cs.fixed_column() for name in (FIXED_CHOICE if choice else FIXED)}
     inst = cs.instance_column()
-    X = adv[2 * PAIRS]
-    for c in (X, fcol["const"], inst):
+    X, Y = adv[2 * PAIRS], adv[2 * PAIRS + 1]
+    for c in (X, fcol["const"], inst) + ((Y,) if choice else ()):
         cs.enable_equality(c)
 
     pieces = {s: sorted((c for c in cells if c.kind == s and c.form == FORM_PAIR and c.len), key=lambda c: c.offset) for s in SRC.values()}
@@ -190,8 +199,15 @@ def _constraint_system(tb: int, dense, spread):
     polys["w_add"] = sel["q_sched"] * (w("W") + carry("CARRY_W") - w("G1_EVEN", back=2) - w("W", back=7) - w("G0_EVEN", back=15) - w("W", back=16))
     for name, s in (("a", "A"), ("e", "E")):  # H + (a .. h): the same slot one block and four regions back
         polys["chain_" + name] = sel["q_chain"] * (w(s) + carry("CARRY_" + s) - w(s, back=BLOCK_REGIONS) - w(s, back=4))
-    assert tuple(polys) != () and set(polys) == set(GATES)
-    for name in GATES:
+    if choice:  # W = x + d * (y - x) with d boolean: x, y, d in the rows of Y that no layout cell uses
+        assert not any(c.column == Y.index and c.row in (CHOICE_ROW_ZERO, CHOICE_ROW_ONE, CHOICE_ROW_BIT) for c in cells)
+        q_choice = cs.query_fixed(fcol["q_choice"])
+        x, y, d = (cs.query_advice(Y, r) for r in (CHOICE_ROW_ZERO, CHOICE_ROW_ONE, CHOICE_ROW_BIT))
+        polys["choice"] = q_choice * (w("W") - x - d * (y - x))
+        polys["choice_bit"] = q_choice * (d * (GP.Expression.constant(1) - d))
+    gates = GATES_CHOICE if choice else GATES
+    assert tuple(polys) != () and set(polys) == set(gates)
+    for name in gates:
         cs.create_gate(name, [polys[name]])
     # lookups 0 .. 7: (dense_j, spread_j) in (dense, spread); 8 .. 15: dense_j * scale_j in dense -- the length check
     for j in range(PAIRS):
@@ -297,7 +313,7 @@ def _build_key(self, ctx: Context, k: int, table_bits: int, setup: str, seed: in
         asm.copy(lc, lr, rc, rr)
     self.vk_repr = 0x534841323536 + k
     self.pk = ProvingKey(ctx, self.params, k, 0, [], self.cfg, self.params.g_dev + 64, fr_to_mont(self.vk_repr), cs=d.cs,
-                         fixed=[_mont_column(d.fixed[name]) for name in FIXED], permutation=asm.mapping)
+                         fixed=[_mont_column(d.fixed[name]) for name in d.fixed_names], permutation=asm.mapping)
     self.cols = [ctx.alloc(n * 32) for _ in range(ADVICE_COLUMNS)]
 
 
@@ -308,8 +324,8 @@ def _close_key(self):
 
 class Sha256Circuit:
     """Proving key and GPU witness synthesis for SHA-256 over exactly `blocks` padded blocks at 2^k rows.  One key
-    proves one message length; there is no variable-length selection (several messages, a hash of a hash or a Merkle
-    root in one proof: sha256_segments.py)."""
+    proves one message length; there is no variable-length selection (several messages, a hash of a hash, a Merkle root
+    over private leaves or Merkle membership of one leaf in one proof: sha256_segments.py)."""
 
     rows_per_block = BLOCK_REGIONS * REGION_ROWS
 

@@ -2,10 +2,12 @@
 the SHA-256 compression circuit, tied to each other and to constants by copy constraints ("Wired SHA-256
 segments").
 
-A plan says, for every message word of every segment, where the word comes from -- a private value, a constant, or a
-digest word of an earlier segment -- and which segments' digests are public.  The constraint system is the one of
-sha256_circuit.py, gate for gate; only the fixed columns and the copies differ.  The witness is synthesised on the GPU
-by `cq_sha256_synthesize_segments_dev`, which runs the chains level by level on the device.
+A plan says, for every message word of every segment, where the word comes from -- a private value, a constant, a
+digest word of an earlier segment, a shared private word, or a choice between two of the latter under a private bit --
+and which segments' digests are public.  The constraint system is the one of sha256_circuit.py, gate for gate; only the
+fixed columns and the copies differ -- and, for a plan with a choice, one selector and two gates (DESIGN.md,
+"Choice-wired message words").  The witness is synthesised on the GPU by `cq_sha256_synthesize_segments_dev`
+(`cq_sha256_synthesize_choices_dev` for a plan with a choice), which runs the chains level by level on the device.
 """
 from __future__ import annotations
 
@@ -20,7 +22,7 @@ from ._lib import constants
 from ._marshal import FR_MODULUS
 from .context import Context
 
-SOURCE_DIGEST = constants()["CQ_SHA256_SOURCE_DIGEST"]
+SOURCE_DIGEST, SOURCE_CHOICE = (constants()["CQ_SHA256_SOURCE_" + s] for s in ("DIGEST", "CHOICE"))
 
 
 class Private(NamedTuple):
@@ -38,6 +40,22 @@ class DigestWord(NamedTuple):
 
     segment: int
     word: int
+
+
+class Var(NamedTuple):
+    """Shared private 32-bit word number `index` of the plan: it may stand in several places -- as a message word or as
+    an operand of a Choice -- and all its cells are tied by copies."""
+
+    index: int
+
+
+class Choice(NamedTuple):
+    """A message word that equals `one` if private bit number `bit` of the plan is 1, else `zero`; each operand is a Var
+    or a DigestWord of an earlier segment.  One bit may steer many choices."""
+
+    bit: int
+    zero: tuple
+    one: tuple
 
 
 class Segment(NamedTuple):
@@ -89,6 +107,50 @@ def merkle_tree(depth: int) -> Plan:
     return Plan(tuple(segs), (len(segs) - 1,))
 
 
+def merkle_path(depth: int, paths: int = 1, leaf_blocks: int | None = None, public_leaf: bool = False) -> Plan:
+    """Membership of a leaf under a Merkle root, `paths` independent times: per path `depth` two-block segments bottom-up,
+    the second block pinned padding.  At level l, word t < 8 is Choice(bit, cur_t, sib_t) and word 8 + t is
+    Choice(bit, sib_t, cur_t) under the one bit of that level and path (bit depth * p + l): the running node is the left
+    half for bit 0, the right half for bit 1.  sib_t is a Var; cur_t is the digest of the level below, and at level 0 a
+    Var holding the 32-byte leaf -- or, with `leaf_blocks`, the digest of a private segment of that many blocks laid before
+    the path (public iff `public_leaf`).  A path's vars: the leaf's 8 (without `leaf_blocks`), then 8 per level.  Every
+    path's top segment is public; instance order per path: the leaf digest if public, then the root."""
+    if depth < 1 or paths < 1:
+        raise ValueError("a Merkle path has at least one level (depth >= 1), a plan at least one path")
+    if public_leaf and leaf_blocks is None:
+        raise ValueError("public_leaf: the leaf digest of a leaf_blocks segment; a 32-byte leaf is a private Var")
+    segs, public, var = [], [], 0
+    for p in range(paths):
+        if leaf_blocks is None:
+            cur = tuple(Var(var + t) for t in range(8))
+            var += 8
+        else:
+            cur = tuple(DigestWord(len(segs), t) for t in range(8))
+            if public_leaf:
+                public.append(len(segs))
+            segs.append(Segment(leaf_blocks, (PRIVATE,) * (16 * leaf_blocks)))
+        for level in range(depth):
+            bit, sib = depth * p + level, tuple(Var(var + t) for t in range(8))
+            var += 8
+            words = tuple(Choice(bit, c, s) for c, s in zip(cur, sib)) + tuple(Choice(bit, s, c) for c, s in zip(cur, sib))
+            cur = tuple(DigestWord(len(segs), t) for t in range(8))
+            segs.append(Segment(2, words + PAD_64_BYTES))
+        public.append(len(segs) - 1)
+    return Plan(tuple(segs), tuple(public))
+
+
+def has_choice(plan: Plan) -> bool:
+    return any(isinstance(s, Choice) for seg in plan.segments for s in seg.sources)
+
+
+def shared_counts(plan: Plan):
+    """(vars, bits) of the plan: one more than the largest index used, 0 if none is."""
+    srcs = [s for seg in plan.segments for s in seg.sources]
+    operands = [o for s in srcs if isinstance(s, Choice) for o in (s.zero, s.one)]
+    return (max([v.index + 1 for v in srcs + operands if isinstance(v, Var)], default=0),
+            max([s.bit + 1 for s in srcs if isinstance(s, Choice)], default=0))
+
+
 def rows_for(plan: Plan) -> int:
     return sum(SC.rows_for(s.blocks) for s in plan.segments)
 
@@ -105,20 +167,37 @@ def first_regions(plan: Plan):
 def _check_plan(plan: Plan):
     if not plan.segments:
         raise ValueError("a plan has at least one segment")
+
+    def digest_word(j, t, src, what=""):
+        if not 0 <= src.segment < j:
+            raise ValueError(f"segment {j}, word {t}: the digest of segment {src.segment}{what} does not come before it")
+        if not 0 <= src.word < 8:
+            raise ValueError(f"segment {j}, word {t}: a digest has words 0 .. 7, not {src.word}")
+
     for j, seg in enumerate(plan.segments):
         if seg.blocks < 1 or len(seg.sources) != 16 * seg.blocks:
             raise ValueError(f"segment {j}: {seg.blocks} blocks and {len(seg.sources)} word sources (16 per block, at least one block)")
         for t, src in enumerate(seg.sources):
             if isinstance(src, DigestWord):
-                if not 0 <= src.segment < j:
-                    raise ValueError(f"segment {j}, word {t}: the digest of segment {src.segment} does not come before it")
-                if not 0 <= src.word < 8:
-                    raise ValueError(f"segment {j}, word {t}: a digest has words 0 .. 7, not {src.word}")
+                digest_word(j, t, src)
+            elif isinstance(src, Var):
+                if src.index < 0:
+                    raise ValueError(f"segment {j}, word {t}: the var index {src.index} is negative")
+            elif isinstance(src, Choice):
+                if src.bit < 0:
+                    raise ValueError(f"segment {j}, word {t}: the bit index {src.bit} is negative")
+                for name, o in (("zero", src.zero), ("one", src.one)):
+                    if isinstance(o, DigestWord):
+                        digest_word(j, t, o, f" (the {name} operand)")
+                    elif not isinstance(o, Var):
+                        raise ValueError(f"segment {j}, word {t}: the {name} operand of a choice is a Var or a DigestWord, not {o!r}")
+                    elif o.index < 0:
+                        raise ValueError(f"segment {j}, word {t}: the var index {o.index} of the {name} operand is negative")
             elif isinstance(src, Const):
                 if not 0 <= src.value < 1 << 32:
                     raise ValueError(f"segment {j}, word {t}: the constant {src.value} is no 32-bit word")
             elif not isinstance(src, Private):
-                raise ValueError(f"segment {j}, word {t}: a source is Private, Const or DigestWord, not {src!r}")
+                raise ValueError(f"segment {j}, word {t}: a source is Private, Const, DigestWord, Var or Choice, not {src!r}")
     if not plan.public or len(set(plan.public)) != len(plan.public) or not all(0 <= p < len(plan.segments) for p in plan.public):
         raise ValueError(f"public segments {plan.public!r}: at least one, each an index below {len(plan.segments)}, none twice")
 
@@ -129,28 +208,53 @@ def describe(k: int, plan: Plan, table_bits: int = 12, dense="dense", spread="sp
     if not SC.MIN_TABLE_BITS <= table_bits <= SC.MAX_TABLE_BITS:
         raise ValueError(f"table_bits must be in [{SC.MIN_TABLE_BITS}, {SC.MAX_TABLE_BITS}]: the widest piece has {SC.MIN_TABLE_BITS} bits")
     _check_plan(plan)
-    cs, adv, fcol, inst, cells, word = SC._constraint_system(table_bits, dense, spread)
-    n, X = 1 << k, adv[2 * SC.PAIRS]
+    choice = has_choice(plan)
+    names = SC.FIXED_CHOICE if choice else SC.FIXED
+    cs, adv, fcol, inst, cells, word = SC._constraint_system(table_bits, dense, spread, choice)
+    n, X, Y = 1 << k, adv[2 * SC.PAIRS], adv[2 * SC.PAIRS + 1]
     rows, usable = rows_for(plan), n - (cs.blinding_factors() + 1)
     if max(rows, 8 * len(plan.public)) > usable:
         raise ValueError(f"{len(plan.segments)} segments need {rows} rows and {8 * len(plan.public)} instance rows, 2^{k} has {usable} usable")
-    fixed = {name: np.zeros(n, dtype=np.uint64) for name in SC.FIXED}
+    fixed = {name: np.zeros(n, dtype=np.uint64) for name in names}
     copies = []
     firsts = first_regions(plan)
     public = {s: p for p, s in enumerate(plan.public)}
     arow, erow, wrow = (word[(SC.SRC[s], SC.FORM_WORD)].row for s in "AEW")
+
+    def tail_cell(src):  # tail region 3 - i % 4 holds digest word i: its A row for i < 4, its E row otherwise
+        s = plan.segments[src.segment]
+        tail = SC.REGION_ROWS * (firsts[src.segment] + SC.BLOCK_REGIONS * s.blocks + 3 - src.word % 4)
+        return X, tail + (arow if src.word < 4 else erow)
+
+    # the cells of the choices' digest operands, of every var and of every bit, in (segment, word, zero-then-one) order
+    digest_cells, var_cells, bit_cells = [], {}, {}
     for j, seg in enumerate(plan.segments):
         SC._assign_segment(fixed, copies, firsts[j], seg.blocks, public.get(j), table_bits, adv, fcol, inst, cells, word)
         for t, src in enumerate(seg.sources):
-            w_cell = SC.REGION_ROWS * (firsts[j] + SC.BLOCK_REGIONS * (t // 16) + 4 + t % 16) + wrow
+            base = SC.REGION_ROWS * (firsts[j] + SC.BLOCK_REGIONS * (t // 16) + 4 + t % 16)
+            w_cell = base + wrow
             if isinstance(src, Const):
                 fixed["const"][w_cell] = src.value
                 copies.append(((fcol["const"], w_cell), (X, w_cell)))
-            elif isinstance(src, DigestWord):  # tail region 3 - i % 4 holds digest word i: its A row for i < 4, its E row otherwise
-                s = plan.segments[src.segment]
-                tail = SC.REGION_ROWS * (firsts[src.segment] + SC.BLOCK_REGIONS * s.blocks + 3 - src.word % 4)
-                copies.append(((X, tail + (arow if src.word < 4 else erow)), (X, w_cell)))
-    return SC.Description(cs, adv, fcol, fixed, inst, copies, cells, table_bits, tuple(s.blocks for s in plan.segments), k)
+            elif isinstance(src, DigestWord):
+                copies.append((tail_cell(src), (X, w_cell)))
+            elif isinstance(src, Var):
+                var_cells.setdefault(src.index, []).append((X, w_cell))
+            elif isinstance(src, Choice):
+                fixed["q_choice"][base] = 1
+                for o, row in ((src.zero, SC.CHOICE_ROW_ZERO), (src.one, SC.CHOICE_ROW_ONE)):
+                    if isinstance(o, DigestWord):
+                        digest_cells.append((tail_cell(o), (Y, base + row)))
+                    else:
+                        var_cells.setdefault(o.index, []).append((Y, base + row))
+                bit_cells.setdefault(src.bit, []).append((Y, base + SC.CHOICE_ROW_BIT))
+    # behind the segments' own copies: every digest operand to its tail cell, then every later cell of a var to the var's
+    # first cell (vars in ascending index), then the same for every bit
+    copies += digest_cells
+    for shared in (var_cells, bit_cells):
+        for i in sorted(shared):
+            copies += [(shared[i][0], cell) for cell in shared[i][1:]]
+    return SC.Description(cs, adv, fcol, fixed, inst, copies, cells, table_bits, tuple(s.blocks for s in plan.segments), k, names)
 
 
 def _words_to_mont(words) -> np.ndarray:
@@ -171,29 +275,42 @@ class Sha256SegmentsCircuit:
     `values` (synthesize, check, assert_satisfied, prove) is one sequence per segment: the segment's Private words in
     word order.  Private words are unconstrained -- a private message's padding included, exactly as in Sha256Circuit:
     the circuit proves the compression of the words it is given, not that they are a padded message.  Const words and
-    DigestWord wirings are constrained."""
+    DigestWord wirings are constrained.  `shared` holds the plan's Var words by index and `bits` its bits (each 0 or 1);
+    a Choice word is constrained to the operand its bit selects."""
 
     def __init__(self, ctx: Context, k: int, plan: Plan, table_bits: int = 12, setup: str = "toxic", seed: int = 0x5348413243515F):
         self.plan = plan
         SC._build_key(self, ctx, k, table_bits, setup, seed, lambda dense, spread: describe(k, plan, table_bits, dense, spread))
         self.rows = rows_for(plan)
-        # the word buffer: the distinct constants, then every Private word in (segment, word) order
+        # the word buffer: the distinct constants, then every Private word in (segment, word) order, the vars, the bits
         consts = sorted({s.value for seg in plan.segments for s in seg.sources if isinstance(s, Const)})
         at_const = {v: i for i, v in enumerate(consts)}
         self._consts = np.array(consts, dtype=np.uint32)
         self._private_counts = [sum(isinstance(s, Private) for s in seg.sources) for seg in plan.segments]
-        sources, nxt = [], len(consts)
+        self._shared_counts = nvars, nbits = shared_counts(plan)
+        first_var = len(consts) + sum(self._private_counts)
+        first_bit = first_var + nvars
+
+        def plain(s):
+            return first_var + s.index if isinstance(s, Var) else SOURCE_DIGEST + 8 * s.segment + s.word
+
+        sources, choices, nxt = [], [], len(consts)
         for seg in plan.segments:
             for s in seg.sources:
                 if isinstance(s, Private):
                     sources.append(nxt)
                     nxt += 1
+                elif isinstance(s, Choice):  # entry c of the choice table: {bit, zero, one, 0}
+                    sources.append(SOURCE_CHOICE + len(choices))
+                    choices.append((first_bit + s.bit, plain(s.zero), plain(s.one), 0))
                 else:
-                    sources.append(at_const[s.value] if isinstance(s, Const) else SOURCE_DIGEST + 8 * s.segment + s.word)
+                    sources.append(at_const[s.value] if isinstance(s, Const) else plain(s))
+        assert nxt == first_var
         self._sources = np.array(sources, dtype=np.uint32)
+        self._choices = np.array(choices, dtype=np.uint32).reshape(-1, 4)
         self._seg_blocks = np.array([seg.blocks for seg in plan.segments], dtype=np.uint32)
-        self._words_len = nxt
-        self._words = ctx.alloc(4 * max(nxt, 1))
+        self._words_len = first_bit + nbits
+        self._words = ctx.alloc(4 * max(self._words_len, 1))
         self._digests = ctx.alloc(32 * len(plan.segments))
         self.digest_words = self.instances = None
 
@@ -201,17 +318,37 @@ class Sha256SegmentsCircuit:
     def _values(self, values):
         return values
 
-    def synthesize(self, values):
-        """Uploads the word buffer, fills the advice columns on the GPU (cq_sha256_synthesize_segments_dev) and downloads the
-        digests; returns (device columns, instances)."""
-        ctx, values = self.ctx, [np.asarray(v, dtype=np.uint32).reshape(-1) for v in self._values(values)]
+    def _inputs(self, values, shared, bits):
+        """What a front end's methods take -> (values, shared, bits) of the plan."""
+        return self._values(values), shared, bits
+
+    def _call(self, arr):
+        """The entry point alone, on the word buffer as it is on the device: the one with choices only for a plan that has some."""
+        ctx = self.ctx
+        if len(self._choices):
+            ctx._chk(ctx.lib.cq_sha256_synthesize_choices_dev(ctx.h, self.table_bits, self._seg_blocks.ctypes.data, len(self._seg_blocks),
+                                                              self._sources.ctypes.data, self._choices.ctypes.data, len(self._choices),
+                                                              self._words.ptr, self._words_len, self.n, arr, self._digests.ptr))
+        else:
+            ctx._chk(ctx.lib.cq_sha256_synthesize_segments_dev(ctx.h, self.table_bits, self._seg_blocks.ctypes.data, len(self._seg_blocks),
+                                                               self._sources.ctypes.data, self._words.ptr, self._words_len, self.n, arr,
+                                                               self._digests.ptr))
+
+    def synthesize(self, values, shared=(), bits=()):
+        """Uploads the word buffer, fills the advice columns on the GPU (cq_sha256_synthesize_segments_dev, or
+        cq_sha256_synthesize_choices_dev for a plan with choices) and downloads the digests; returns (device columns,
+        instances)."""
+        values, shared, bits = self._inputs(values, shared, bits)
+        values = [np.asarray(v, dtype=np.uint32).reshape(-1) for v in values]
         if [len(v) for v in values] != self._private_counts:
             raise ValueError(f"private words per segment: {self._private_counts}, not {[len(v) for v in values]}")
-        self._words.upload(np.concatenate([self._consts] + values))
-        arr = (C.c_void_p * SC.ADVICE_COLUMNS)(*[c.ptr for c in self.cols])
-        ctx._chk(ctx.lib.cq_sha256_synthesize_segments_dev(ctx.h, self.table_bits, self._seg_blocks.ctypes.data, len(self._seg_blocks),
-                                                           self._sources.ctypes.data, self._words.ptr, self._words_len, self.n, arr,
-                                                           self._digests.ptr))
+        if any(not 0 <= int(w) < 1 << 32 for w in shared) or any(int(b) not in (0, 1) for b in bits):
+            raise ValueError("shared words are 32-bit words, bits are 0 or 1")
+        if (len(shared), len(bits)) != self._shared_counts:
+            raise ValueError(f"(shared words, bits): {self._shared_counts}, not {(len(shared), len(bits))}")
+        tail = [np.array([int(x) for x in part], dtype=np.uint32) for part in (shared, bits)]
+        self._words.upload(np.concatenate([self._consts] + values + tail))
+        self._call((C.c_void_p * SC.ADVICE_COLUMNS)(*[c.ptr for c in self.cols]))
         self.digest_words = self._digests.download((len(self._seg_blocks), 8), np.uint32).tolist()
         self.instances = [_words_to_mont([x for p in self.plan.public for x in self.digest_words[p]])]
         return self.cols, self.instances
@@ -224,17 +361,17 @@ class Sha256SegmentsCircuit:
     def _result(self):
         return self.digests
 
-    def check(self, values, max_failures: int = 64):
-        cols, inst = self.synthesize(values)
+    def check(self, values, shared=(), bits=(), max_failures: int = 64):
+        cols, inst = self.synthesize(values, shared, bits)
         return self.pk.check_witness([c.ptr for c in cols], instances=inst, max_failures=max_failures)
 
-    def assert_satisfied(self, values):
-        cols, inst = self.synthesize(values)
+    def assert_satisfied(self, values, shared=(), bits=()):
+        cols, inst = self.synthesize(values, shared, bits)
         self.pk.assert_satisfied([c.ptr for c in cols], instances=inst)
 
-    def prove(self, values, seed: int = 1):
+    def prove(self, values, shared=(), bits=(), seed: int = 1):
         """(proof bytes, public digests): create_proof with the public segments' digest words as the public inputs."""
-        cols, inst = self.synthesize(values)
+        cols, inst = self.synthesize(values, shared, bits)
         return self.pk.create_proof_dev([c.ptr for c in cols], seed=seed, instances=inst), self._result()
 
     def close(self):
@@ -289,3 +426,47 @@ class Sha256MerkleCircuit(Sha256SegmentsCircuit):
 
     def _result(self):
         return self.digests[0]
+
+
+class Sha256MerklePathCircuit(Sha256SegmentsCircuit):
+    """Membership under a SHA-256 Merkle root (node = SHA-256(left || right)): `paths` independent paths of `depth` levels;
+    every root is public, the leaf, its position and the siblings are private.  The methods take, per path,
+    (leaf, index, siblings): the 32-byte leaf -- with `leaf_blocks` the message of exactly that many padded blocks whose
+    digest is the leaf, public iff `public_leaf` -- the leaf's index in [0, 2^depth), whose bit l says whether the running
+    node is the right half at level l, and the `depth` 32-byte siblings bottom-up.  The siblings, the direction bits and
+    a 32-byte leaf are constrained to nothing but the hashes they enter; a `leaf_blocks` message's padding is private
+    words, as in Sha256BatchCircuit."""
+
+    def __init__(self, ctx: Context, k: int, depth: int, paths: int = 1, leaf_blocks: int | None = None, public_leaf: bool = False, **kw):
+        self.depth, self.paths, self.leaf_blocks = depth, paths, leaf_blocks
+        super().__init__(ctx, k, merkle_path(depth, paths, leaf_blocks, public_leaf), **kw)
+
+    def _inputs(self, items, shared=(), bits=()):
+        if shared or bits:
+            raise ValueError("a Merkle path takes (leaf, index, siblings) per path and nothing else")
+        if len(items) != self.paths:
+            raise ValueError(f"{self.paths} paths, not {len(items)}")
+        values, shared, bits = [], [], []
+        for leaf, index, siblings in items:
+            if not 0 <= index < 1 << self.depth or len(siblings) != self.depth or any(len(s) != 32 for s in siblings):
+                raise ValueError(f"an index below 2^{self.depth} and {self.depth} siblings of 32 bytes each")
+            if self.leaf_blocks is None:
+                if len(leaf) != 32:
+                    raise ValueError("a leaf of 32 bytes")
+                shared += _digest_words(leaf)
+            else:
+                values.append(SC.pad(leaf, self.leaf_blocks))
+            values += [[]] * self.depth
+            for level, sibling in enumerate(siblings):
+                shared += _digest_words(sibling)
+                bits.append(index >> level & 1)
+        return values, shared, bits
+
+    @property
+    def roots(self):
+        """The roots of the last synthesis, one per path, 32 big-endian bytes each."""
+        per_path = len(self.plan.public) // self.paths  # the public segments of a path: its leaf digest if public, then its root
+        return self.digests[per_path - 1:: per_path]
+
+    def _result(self):
+        return self.roots

@@ -12,7 +12,12 @@ compression chain) at the same total block count.  Then a sweep over the segment
 entry point with no key: cq_sha256_synthesize_segments_dev on c one-block segments whose words are already on the
 device, and cq_sha256_synthesize_dev on one message of c blocks, each followed by a stream synchronise.
 
-    python tools/sha256_perf.py [--sizes 14,18] [--segments-k 18] [--sweep 1,2,4,...] [--reps 15] [--warmup 3]
+With --path-k K (0 = off): `Sha256MerklePathCircuit` of depth 32 with as many paths as 2^K rows hold, next to a plan of
+the same shape without choices -- per path a chain of 32 two-block segments, each wired to the one below by DigestWord
+alone -- through cq_sha256_synthesize_segments_dev: entry point + synchronise, the wrapper's synthesize, check and proof of
+both.  The difference of the two entry-point times is the choice fetch of the chain kernel plus the fill launch.
+
+    python tools/sha256_perf.py [--sizes 14,18] [--segments-k 18] [--path-k 18] [--sweep 1,2,4,...] [--reps 15] [--warmup 3]
 """
 import argparse
 import json
@@ -116,10 +121,63 @@ def segment_legs(ctx, k, sweep, reps, warmup):
         b.close()
 
 
+def path_legs(ctx, k, reps, warmup, depth=32):
+    import ctypes as C
+    import hashlib
+    import struct
+
+    from sha2_on_cq_halo2_amd import sha256_circuit as SC
+    from sha2_on_cq_halo2_amd import sha256_segments as SS
+    from sha2_on_cq_halo2_amd.api import Sha256MerklePathCircuit, Sha256SegmentsCircuit
+
+    paths = SC.usable_rows(k) // (depth * SC.rows_for(2))
+    assert paths >= 1, f"2^{k} rows hold no path of depth {depth}"
+    node = lambda *key: hashlib.sha256(bytes(key)).digest()
+    items = [(node(p), (0x9E3779B9 * (p + 1)) % (1 << depth), [node(p, level) for level in range(depth)]) for p in range(paths)]
+    # the same shape without a choice: the left half wired to the segment below, the right half private
+    upper = tuple(SS.DigestWord(0, t) for t in range(8)) + (SS.PRIVATE,) * 8
+    segs = []
+    for p in range(paths):
+        for level in range(depth):
+            words = tuple(w._replace(segment=len(segs) - 1) if isinstance(w, SS.DigestWord) else w for w in upper) if level else (SS.PRIVATE,) * 16
+            segs.append(SS.Segment(2, words + SS.PAD_64_BYTES))
+    wired = SS.Plan(tuple(segs), tuple(depth * (p + 1) - 1 for p in range(paths)))
+    words_of = lambda data: list(struct.unpack(f">{len(data) // 4}I", data))
+    wired_values = [w for leaf, _, siblings in items for w in [words_of(leaf + siblings[0])] + [words_of(s) for s in siblings[1:]]]
+    rows = []
+    for name, make, arg in (("Sha256MerklePathCircuit", lambda: Sha256MerklePathCircuit(ctx, k, depth, paths), items),
+                            ("DigestWord chains, same shape, no choice", lambda: Sha256SegmentsCircuit(ctx, k, wired), wired_values)):
+        t0 = time.perf_counter()
+        c = make()
+        row = {"circuit": name, "k": k, "depth": depth, "paths": paths, "segments": len(c.plan.segments), "levels": depth, "rows": c.rows,
+               "choices": len(c._choices), "keygen_s": round(time.perf_counter() - t0, 2)}
+        assert c.check(arg) == (0, [])
+        ptrs, seed = [b.ptr for b in c.cols], [0]
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+
+        def call():  # the entry point alone: the word buffer of the last synthesize is still on the device
+            c._call(arr)
+            ctx.sync()
+
+        def prove():
+            seed[0] += 1
+            c.pk.create_proof_dev(ptrs, seed=seed[0], instances=c.instances)
+
+        timed(row, (("synthesize_ms", lambda: c.synthesize(arg)), ("synthesize_call_ms", call),
+                    ("check_ms", lambda: c.pk.check_witness(ptrs, instances=c.instances, max_failures=0)), ("proof_ms", prove)), reps, warmup)
+        c.close()
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    print(json.dumps({"choice_cost": "entry point + sync, with choices minus without", "k": k,
+                      "synthesize_call_ms_difference": round(rows[0]["synthesize_call_ms"] - rows[1]["synthesize_call_ms"], 3),
+                      "proof_ms_difference": round(rows[0]["proof_ms"] - rows[1]["proof_ms"], 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="14,18")
     ap.add_argument("--segments-k", type=int, default=0)
+    ap.add_argument("--path-k", type=int, default=0)
     ap.add_argument("--sweep", default="1,2,4,8,16,32,64,128,256,512")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
@@ -160,6 +218,8 @@ def main():
         print(json.dumps(row), flush=True)
     if args.segments_k:
         segment_legs(ctx, args.segments_k, args.sweep, args.reps, args.warmup)
+    if args.path_k:
+        path_legs(ctx, args.path_k, args.reps, args.warmup)
     ctx.close()
 
 
