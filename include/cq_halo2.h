@@ -913,6 +913,43 @@ int cq_sha256_synthesize_segments_dev(cq_ctx* ctx, uint32_t table_bits, const ui
 int cq_sha256_synthesize_choices_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
                                      const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* words_dev,
                                      size_t words_len, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev);
+/* Messages of variable length with constrained padding (DESIGN.md "Variable-length messages"): segment j is a chain of
+ * seg_max_blocks[j] blocks that holds message j -- msg_lens[j] raw bytes at msg_bytes_dev + msg_offsets[j], a device buffer
+ * of msg_bytes_len bytes (no alignment is asked of it) -- padded on the device: 0x80, zeros, the bit length in the last two
+ * words of the first block that has room for them (the FINAL block), zero words behind it.  Behind the chains and the
+ * expansion of cq_sha256_synthesize_segments_dev a kernel writes the cells the padding gates read, which the expansion
+ * leaves zero: in a message-word region (rounds 0 .. 15) rows CQ_SHA256_VAR_ROW_M / _LEN / _C0 / _C1 of the last advice
+ * column (the word lies wholly inside the message; the running byte length; the two bits of 3 - (bytes of the message
+ * in the boundary word)), the bits' product in the dense and spread cells of pair slot CQ_SHA256_VAR_SLOT_PRODUCT, row 0,
+ * and the two 12-bit halves of the boundary word's message bytes in pair slot CQ_SHA256_VAR_SLOT_DATA, rows 0 and 1; in
+ * region CQ_SHA256_VAR_REGION_CARRY of a block the flag and the length the block starts from (rows _M, _LEN) and their
+ * factors; in regions CQ_SHA256_VAR_REGION_SUM + i (i < 8: digest word i) and CQ_SHA256_VAR_REGION_LENGTH rows
+ * CQ_SHA256_VAR_ROW_IN / _FLAG / _VALUE / _OUT (out = in + flag * value: the word selected so far, whether the block is
+ * the final one, the chaining value behind the block or the length); in region CQ_SHA256_VAR_REGION_FINAL rows _IN, _FLAG,
+ * _VALUE hold the flags of word 13 of the block before and of this block and their difference.  `digests_dev` (8 * segments
+ * words) receives the chaining value behind each message's final block: SHA-256 of the message.  Everything is validated
+ * on the host before anything is queued; CQ_ERR_ARG, with the segment in cq_last_error: table_bits below
+ * CQ_SHA256_VAR_MIN_TABLE_BITS or above CQ_SHA256_MAX_TABLE_BITS, a block count of zero, msg_lens[j] above
+ * 64 * seg_max_blocks[j] - 9, an offset or a length that leaves the buffer, rows that do not fit n.  Nothing waits for the
+ * stream: the buffer must stay as it is, and `digests_dev` is good, once the stream has got there. */
+#define CQ_SHA256_VAR_MIN_TABLE_BITS 12
+#define CQ_SHA256_VAR_ROW_M 4
+#define CQ_SHA256_VAR_ROW_LEN 5
+#define CQ_SHA256_VAR_ROW_C0 6
+#define CQ_SHA256_VAR_ROW_C1 7
+#define CQ_SHA256_VAR_SLOT_PRODUCT 6
+#define CQ_SHA256_VAR_SLOT_DATA 7
+#define CQ_SHA256_VAR_ROW_IN 4
+#define CQ_SHA256_VAR_ROW_FLAG 5
+#define CQ_SHA256_VAR_ROW_VALUE 6
+#define CQ_SHA256_VAR_ROW_OUT 7
+#define CQ_SHA256_VAR_REGION_CARRY 3
+#define CQ_SHA256_VAR_REGION_SUM 20
+#define CQ_SHA256_VAR_REGION_FINAL 28
+#define CQ_SHA256_VAR_REGION_LENGTH 29
+int cq_sha256_synthesize_varlen_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_max_blocks, size_t segments,
+                                    const uint8_t* msg_bytes_dev, size_t msg_bytes_len, const uint64_t* msg_offsets,
+                                    const uint64_t* msg_lens, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev);
 
 /* ---- harness RNG (not in the reference: its test draws from OsRng) ---------------------------------- */
 void cq_xoshiro256ss_seed(uint64_t seed, uint64_t state[4]);

@@ -19,3 +19,4 @@ from .proving_key import ProvingKey, WitnessError, WitnessFailure, _lower_plonk 
 from .sha256_circuit import Sha256Circuit  # noqa: F401  (last: its constructor reaches sha_circuit, which imports this module)
 from .sha256_segments import (Sha256BatchCircuit, Sha256dCircuit, Sha256MerkleCircuit, Sha256MerklePathCircuit,  # noqa: F401
                               Sha256SegmentsCircuit)
+from .sha256_varlen import Sha256VarCircuit  # noqa: F401

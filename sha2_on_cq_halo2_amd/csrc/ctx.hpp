@@ -26,7 +26,7 @@ enum class Scratch {
                 // entry buffer
   EntryB,       // the second buffer of the same entry points (outputs, bases, pk.hip's permutation mapping, the staged compressed
                 // bytes of the Processed params / pk / G2 SRS readers and writers, the two G2 points of a params set-up or full
-                // stream), sha256.hip's lane and source tables of a segment synthesis; also g1_fft's twiddles: its callers (g1_to_lagrange,
+                // stream), sha256.hip's lane and source tables of a segment synthesis (and, behind them, a variable-length synthesis' padded words); also g1_fft's twiddles: its callers (g1_to_lagrange,
                 // fk_table_quotients) run under entry points that hold neither entry buffer
   MsmWork,      // msm_multi.hip, msm.hip (msm_bucket_sums): the workspace of one MSM launch on any stream but a side stream;
                 // those launches follow one another on `stream`

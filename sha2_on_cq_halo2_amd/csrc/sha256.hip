@@ -9,6 +9,8 @@
 // Choices (cq_sha256_synthesize_choices_dev): a message word may be one of two operands under a private bit.  The chain
 // kernel's fetch takes the operand the bit selects, and a small kernel behind the expansion writes both operands and the
 // bit into three cells of the word's region that the layout leaves free.
+// Variable length (cq_sha256_synthesize_varlen_dev): raw bytes are padded on the device into the word buffer the plain
+// chain kernel reads, and a kernel behind the expansion writes the flags, lengths and selection cells the padding gates read.
 #include <cstring>
 #include <string>
 #include <utility>
@@ -419,6 +421,195 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
   return CQ_OK;
 }
 
+// ---- messages of variable length: padding on the device, and the cells its gates read --------------------------------
+
+// One message of a variable-length synthesis: where its raw bytes start in the caller's buffer and how many there are.
+struct Sha256VarMsg {
+  uint64_t offset;
+  uint32_t len, unused;
+};
+
+// The segment that holds word `word` of the word buffer: lanes are in segment order there and lane j's words start at
+// first_source, ascending, lane 0's at 0; `word` lies below the buffer's end.
+static __device__ __forceinline__ uint32_t sha256_var_segment(const Sha256Lane* __restrict__ lanes, uint32_t nlanes, uint32_t word) {
+  uint32_t lo = 0, hi = nlanes;  // lanes[lo].first_source <= word < lanes[hi].first_source (hi = nlanes: the end)
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (lanes[mid].first_source <= word) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// the index of a message's final block: the first with room for 0x80 and the 64-bit length behind the data
+static SHA_HD uint32_t sha256_var_final_block(uint32_t len) { return (len + 8) / 64; }
+
+// One thread per word of the word buffer (16 per block of every segment, segment after segment): the big-endian word of
+// the padded message -- data bytes, 0x80, zeros, the bit length in word 15 of the final block -- and zero behind the
+// final block.  A byte is loaded only below the message's length, which the host has checked against the buffer.
+__global__ __launch_bounds__(256) void sha256_pad_kernel(const Sha256Lane* __restrict__ lanes, const Sha256VarMsg* __restrict__ msgs,
+                                                         uint32_t nlanes, uint32_t nwords, const uint8_t* __restrict__ bytes,
+                                                         uint32_t* __restrict__ words) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nwords) return;
+  const uint32_t j = sha256_var_segment(lanes, nlanes, i);
+  const uint32_t t = i - lanes[j].first_source, len = msgs[j].len, last = 16 * sha256_var_final_block(len) + 15;
+  const uint8_t* src = bytes + msgs[j].offset;
+  uint32_t w = 0;
+  if (t == last) {
+    w = 8 * len;
+  } else if (t < last) {
+    CQ_UNROLL for (uint32_t k = 0; k < 4; k++) {
+      const uint32_t pos = 4 * t + k;
+      const uint32_t byte = pos < len ? src[pos] : (pos == len ? 0x80u : 0u);
+      w |= byte << (24 - 8 * k);
+    }
+  }
+  words[i] = w;
+}
+
+static __device__ __forceinline__ void sha256_var_put(Fr* cell, uint64_t v) { st(cell, v ? Fr::from_u64(v) : Fr::zero()); }
+
+// The flag and the running length of word g (16 * block + word) of a message of `len` bytes whose final block is `fb`:
+// the word lies wholly inside the message; the bytes of the message up to and with the word -- zero behind the final block,
+// where the length a block starts from is cleared.
+static __device__ __forceinline__ uint32_t sha256_var_m(uint32_t g, uint32_t len) { return 4 * (g + 1) <= len ? 1u : 0u; }
+static __device__ __forceinline__ uint32_t sha256_var_len(uint32_t g, uint32_t len, uint32_t fb) {
+  return g / 16 > fb ? 0u : min(4 * (g + 1), len);
+}
+
+// 32 threads per block of every segment, after the expansion (which wrote these cells as zero) on the same stream; a
+// thread's role is its index among the 32.  0 .. 15: the message-word region of that word -- flag, length, and in the
+// boundary word the two bits, their product and the halves of its data bytes.  16: the block's carry-in region.
+// 17 .. 24: the region that adds digest word (role - 17) of the chaining value behind the block, if the block is final,
+// to the word selected so far; the last block's sum goes to `digests`, over the chain kernel's digest.  25: the final
+// flag.  26: the same sum for the length.  The host has checked that every region of every lane lies below
+// n / CQ_SHA256_REGION_ROWS; `regions` is what the chain kernel left.
+__global__ __launch_bounds__(256) void sha256_varlen_fill_kernel(const Sha256Lane* __restrict__ lanes, const Sha256VarMsg* __restrict__ msgs,
+                                                                 uint32_t nlanes, uint32_t nblocks, const Sha256Region* __restrict__ regions,
+                                                                 Sha256Cols cols, uint32_t* __restrict__ digests) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t gb = i / 32, role = i % 32;
+  if (gb >= nblocks || role > 26) return;
+  const uint32_t j = sha256_var_segment(lanes, nlanes, 16 * gb);
+  const Sha256Lane lane = lanes[j];
+  const uint32_t b = gb - lane.first_source / 16, len = msgs[j].len, fb = sha256_var_final_block(len);
+  const uint32_t block_region = lane.first_region + b * CQ_SHA256_BLOCK_REGIONS;
+  Fr* const y = cols.p[SHA256_COL_Y];
+  const uint32_t m13_before = b ? sha256_var_m(16 * b - 3, len) : 1u, m13 = sha256_var_m(16 * b + 13, len);
+  if (role < 16) {
+    const uint32_t g = 16 * b + role;
+    const size_t row = (size_t)(block_region + 4 + role) * CQ_SHA256_REGION_ROWS;
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_M, sha256_var_m(g, len));
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_LEN, sha256_var_len(g, len, fb));
+    if (g == len / 4) {  // the boundary word: r = len % 4 bytes of the message, 0x80, zeros
+      const uint32_t r = len % 4, s = 3 - r, c0 = s & 1, c1 = s >> 1;
+      const uint32_t data = r ? regions[block_region + 4 + role].w >> (32 - 8 * r) : 0;
+      const uint32_t d0 = data & 0xfffu, d1 = data >> 12;
+      sha256_var_put(y + row + CQ_SHA256_VAR_ROW_C0, c0);
+      sha256_var_put(y + row + CQ_SHA256_VAR_ROW_C1, c1);
+      sha256_var_put(cols.p[2 * CQ_SHA256_VAR_SLOT_PRODUCT] + row, c0 & c1);  // a bit is its own spread form
+      sha256_var_put(cols.p[2 * CQ_SHA256_VAR_SLOT_PRODUCT + 1] + row, c0 & c1);
+      sha256_var_put(cols.p[2 * CQ_SHA256_VAR_SLOT_DATA] + row, d0);
+      sha256_var_put(cols.p[2 * CQ_SHA256_VAR_SLOT_DATA + 1] + row, spread32(d0));
+      sha256_var_put(cols.p[2 * CQ_SHA256_VAR_SLOT_DATA] + row + 1, d1);
+      sha256_var_put(cols.p[2 * CQ_SHA256_VAR_SLOT_DATA + 1] + row + 1, spread32(d1));
+    }
+  } else if (role == 16) {
+    const size_t row = (size_t)(block_region + CQ_SHA256_VAR_REGION_CARRY) * CQ_SHA256_REGION_ROWS;
+    const uint32_t len15 = b ? sha256_var_len(16 * b - 1, len, fb) : 0u;
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_M, b ? sha256_var_m(16 * b - 1, len) : 1u);
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_LEN, len15 * (b ? m13_before : 0u));
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_VALUE, len15);
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_OUT, b ? m13_before : 0u);
+  } else if (role == 25) {
+    const size_t row = (size_t)(block_region + CQ_SHA256_VAR_REGION_FINAL) * CQ_SHA256_REGION_ROWS;
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_IN, m13_before);
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_FLAG, m13);
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_VALUE, m13_before - m13);
+  } else {
+    // digest word w of the chaining value behind block c: state region 3 - w % 4 of block c + 1 (or of the tail)
+    auto chaining = [&](uint32_t c, uint32_t w) {
+      const Sha256Region h = regions[lane.first_region + (c + 1) * CQ_SHA256_BLOCK_REGIONS + 3 - w % 4];
+      return w < 4 ? h.a : h.e;
+    };
+    const bool is_len = role == 26;
+    const uint32_t w = role - 17;
+    const size_t row = (size_t)(block_region + (is_len ? CQ_SHA256_VAR_REGION_LENGTH : CQ_SHA256_VAR_REGION_SUM + w)) * CQ_SHA256_REGION_ROWS;
+    // the final block lies inside the lane (the host has checked the length against the block count)
+    const uint32_t selected = is_len ? len : chaining(fb, w);
+    const uint32_t out = b >= fb ? selected : 0u;
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_IN, b > fb ? selected : 0u);
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_FLAG, b == fb ? 1u : 0u);
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_VALUE, is_len ? sha256_var_len(16 * b + 15, len, fb) : chaining(b, w));
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_OUT, out);
+    if (!is_len && b + 1 == lane.blocks) digests[8 * (size_t)lane.segment + w] = out;
+  }
+}
+
+// Validates the messages against their segments, the buffer and the rows, then queues: the upload of the lane, message and
+// source tables (pinned staging, as sha256_synthesize_segments), the padding into the word buffer, one launch of the plain
+// chain kernel over all segments (a padded message reads no digest: every segment has level 0, and its sources are its own
+// words in order), the expansion, and the fill of the padding gates' cells.  Nothing here waits for the stream.
+int sha256_synthesize_varlen(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_max_blocks, size_t segments, const uint8_t* bytes_dev,
+                             size_t bytes_len, const uint64_t* offsets, const uint64_t* lens, uint32_t n, const Sha256Cols& cols,
+                             uint32_t* digests_dev) {
+  const uint64_t max_regions = n / CQ_SHA256_REGION_ROWS;
+  uint64_t regions = 0, blocks = 0;
+  for (size_t j = 0; j < segments; j++) {
+    auto seg = [&] { return "sha256: segment " + std::to_string(j); };
+    if (seg_max_blocks[j] == 0) return c->fail(CQ_ERR_ARG, seg() + " has no block");
+    blocks += seg_max_blocks[j];
+    regions += (uint64_t)seg_max_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS;
+    if (regions > max_regions) return c->fail(CQ_ERR_ARG, "sha256: the segments up to segment " + std::to_string(j) + " do not fit the rows");
+    // n < 2^31 bounds the blocks, so 64 * blocks stays far below 2^29 and 8 * length is a 32-bit word
+    if (lens[j] > 64 * (uint64_t)seg_max_blocks[j] - 9)
+      return c->fail(CQ_ERR_ARG, seg() + ": a message of " + std::to_string(lens[j]) + " bytes does not pad to " +
+                                     std::to_string(seg_max_blocks[j]) + " blocks or fewer");
+    if (offsets[j] > bytes_len || lens[j] > bytes_len - offsets[j])
+      return c->fail(CQ_ERR_ARG, seg() + ": bytes " + std::to_string(offsets[j]) + " .. " + std::to_string(offsets[j]) + " + " +
+                                     std::to_string(lens[j]) + " leave a buffer of " + std::to_string(bytes_len));
+  }
+  static_assert(sizeof(Sha256VarMsg) == 16, "four words");
+  const size_t lanes_bytes = segments * sizeof(Sha256Lane), msgs_bytes = segments * sizeof(Sha256VarMsg);
+  const size_t nwords = 16 * blocks, words_bytes = nwords * sizeof(uint32_t);
+  const size_t tables_bytes = lanes_bytes + msgs_bytes + words_bytes;  // the sources: one index per word
+  void *pin, *dev_regions, *dev_tables;
+  CQ_TRY(c->ensure_pinned_sha(tables_bytes, &pin));
+  CQ_TRY(c->ensure_scratch(Scratch::EntryA, regions * sizeof(Sha256Region), &dev_regions));
+  CQ_TRY(c->ensure_scratch(Scratch::EntryB, tables_bytes + words_bytes, &dev_tables));  // behind the tables: the word buffer
+  if (!c->sha_staged) CQ_HIP(c, hipEventCreateWithFlags(&c->sha_staged, hipEventDisableTiming));
+  CQ_HIP(c, hipEventSynchronize(c->sha_staged));  // the previous call's copy out of `pin` (at once if there was none)
+  Sha256Lane* lanes = (Sha256Lane*)pin;
+  Sha256VarMsg* msgs = (Sha256VarMsg*)((char*)pin + lanes_bytes);
+  uint32_t* sources = (uint32_t*)((char*)pin + lanes_bytes + msgs_bytes);
+  uint32_t first_region = 0, first_source = 0;
+  for (size_t j = 0; j < segments; j++) {
+    lanes[j] = {first_region, seg_max_blocks[j], first_source, (uint32_t)j};
+    msgs[j] = {offsets[j], (uint32_t)lens[j], 0};
+    first_region += seg_max_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS;
+    first_source += 16 * seg_max_blocks[j];
+  }
+  for (size_t i = 0; i < nwords; i++) sources[i] = (uint32_t)i;
+  CQ_HIP(c, hipMemcpyAsync(dev_tables, pin, tables_bytes, hipMemcpyHostToDevice, c->stream));
+  CQ_HIP(c, hipEventRecord(c->sha_staged, c->stream));
+  const Sha256Lane* dev_lanes = (const Sha256Lane*)dev_tables;
+  const Sha256VarMsg* dev_msgs = (const Sha256VarMsg*)((const char*)dev_tables + lanes_bytes);
+  const uint32_t* dev_sources = (const uint32_t*)((const char*)dev_msgs + msgs_bytes);
+  uint32_t* dev_words = (uint32_t*)((char*)dev_tables + tables_bytes);
+  sha256_pad_kernel<<<((uint32_t)nwords + 255) / 256, 256, 0, c->stream>>>(dev_lanes, dev_msgs, (uint32_t)segments, (uint32_t)nwords, bytes_dev,
+                                                                          dev_words);
+  if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_pad launch failed");
+  sha256_chain_kernel<false><<<((uint32_t)segments + 63) / 64, 64, 0, c->stream>>>(dev_lanes, (uint32_t)segments, dev_sources, nullptr, dev_words,
+                                                                                  digests_dev, (Sha256Region*)dev_regions);
+  if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_chain launch failed");
+  sha256_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha256Region*)dev_regions, (uint32_t)regions, n, table_bits, cols);
+  if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_expand launch failed");
+  sha256_varlen_fill_kernel<<<(uint32_t)((32 * blocks + 255) / 256), 256, 0, c->stream>>>(dev_lanes, dev_msgs, (uint32_t)segments, (uint32_t)blocks,
+                                                                                         (const Sha256Region*)dev_regions, cols, digests_dev);
+  if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_varlen_fill launch failed");
+  return CQ_OK;
+}
+
 }  // namespace cq
 
 using namespace cq;
@@ -482,6 +673,25 @@ int cq_sha256_synthesize_choices_dev(cq_ctx* c, uint32_t table_bits, const uint3
                                      const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* words_dev,
                                      size_t words_len, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
   return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, choices, n_choices, words_dev, words_len, n, cols_dev, digests_dev);
+}
+
+int cq_sha256_synthesize_varlen_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_max_blocks, size_t segments,
+                                    const uint8_t* msg_bytes_dev, size_t msg_bytes_len, const uint64_t* msg_offsets,
+                                    const uint64_t* msg_lens, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
+  if (!c) return CQ_ERR_ARG;
+  if (!seg_max_blocks || !msg_offsets || !msg_lens || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull ||
+      (!msg_bytes_dev && msg_bytes_len))
+    return c->fail(CQ_ERR_ARG, "sha256: null array, no segment, or a length out of range");
+  if (table_bits < CQ_SHA256_VAR_MIN_TABLE_BITS || table_bits > CQ_SHA256_MAX_TABLE_BITS)
+    return c->fail(CQ_ERR_ARG, "sha256: table_bits outside the range the 12-bit halves of a boundary word's bytes fit");
+  CQ_HIP(c, hipSetDevice(c->device));
+  Sha256Cols sc;
+  for (uint32_t i = 0; i < CQ_SHA256_ADVICE_COLUMNS; i++) {
+    if (!cols_dev[i]) return c->fail(CQ_ERR_ARG, "sha256: null column");
+    sc.p[i] = (Fr*)cols_dev[i];
+  }
+  return sha256_synthesize_varlen(c, table_bits, seg_max_blocks, segments, msg_bytes_dev, msg_bytes_len, msg_offsets, msg_lens, (uint32_t)n,
+                                  sc, digests_dev);
 }
 
 }  // extern "C"

@@ -51,6 +51,13 @@ FIXED = ("q_all", "q_f3", "q_round", "q_sched", "q_chain") + tuple(f"scale{j}" f
 GATES_CHOICE = GATES + ("choice", "choice_bit")
 FIXED_CHOICE = FIXED + ("q_choice",)
 CHOICE_ROW_ZERO, CHOICE_ROW_ONE, CHOICE_ROW_BIT = (_CQ["CQ_SHA256_CHOICE_ROW_" + s] for s in ("ZERO", "ONE", "BIT"))
+# the variable-length variant (sha256_varlen.py): six selectors behind `const`, thirteen gates behind the others, equality
+# on column Y; its cells sit in rows 4 .. 7 of Y, in pair slot 7 of rows 0 and 1, and -- in a message-word region, whose
+# schedule carry nothing reads -- in the carry's slot ("Variable-length messages")
+GATES_VARLEN = GATES + ("var_m_bool", "var_b_bool", "var_c0_bool", "var_c1_bool", "var_c_product", "var_len", "var_boundary",
+                        "var_pad_zero", "var_length_word", "var_last_final", "var_carry", "var_final", "var_select")
+FIXED_VARLEN = FIXED + ("q_vpad", "q_vlength", "q_vlast", "q_vcarry", "q_vfinal", "q_vsum")
+VAR = {name[len("CQ_SHA256_VAR_"):]: v for name, v in _CQ.items() if name.startswith("CQ_SHA256_VAR_")}
 
 
 class Cell(NamedTuple):
@@ -124,16 +131,20 @@ def describe(k: int, blocks: int, table_bits: int = 12, dense="dense", spread="s
     return _assign_fixed(k, blocks, table_bits, cs, adv, fcol, inst, cells, word)
 
 
-def _constraint_system(tb: int, dense, spread, choice: bool = False):
+def _constraint_system(tb: int, dense, spread, choice: bool = False, varlen: bool = False):
     """`choice`: the variant for plans with choice-wired message words -- the fixed column `q_choice`, equality on column
-    Y and the gates `choice` and `choice_bit`; everything else is the plain system, built by the same lines."""
+    Y and the gates `choice` and `choice_bit`; everything else is the plain system, built by the same lines.  `varlen`:
+    the variant for messages of variable length -- the selectors of FIXED_VARLEN, equality on Y and the gates of
+    GATES_VARLEN; the two variants do not combine."""
+    if choice and varlen:
+        raise ValueError("a variable-length segment does not combine with choice-wired words")
     cells = layout()
     cs = GP.ConstraintSystem()
     adv = [cs.advice_column() for _ in range(ADVICE_COLUMNS)]
-    fcol = {name: cs.fixed_column() for name in (FIXED_CHOICE if choice else FIXED)}
+    fcol = {name: cs.fixed_column() for name in (FIXED_CHOICE if choice else FIXED_VARLEN if varlen else FIXED)}
     inst = cs.instance_column()
     X, Y = adv[2 * PAIRS], adv[2 * PAIRS + 1]
-    for c in (X, fcol["const"], inst) + ((Y,) if choice else ()):
+    for c in (X, fcol["const"], inst) + ((Y,) if choice or varlen else ()):
         cs.enable_equality(c)
 
     pieces = {s: sorted((c for c in cells if c.kind == s and c.form == FORM_PAIR and c.len), key=lambda c: c.offset) for s in SRC.values()}
@@ -205,7 +216,9 @@ def _constraint_system(tb: int, dense, spread, choice: bool = False):
         x, y, d = (cs.query_advice(Y, r) for r in (CHOICE_ROW_ZERO, CHOICE_ROW_ONE, CHOICE_ROW_BIT))
         polys["choice"] = q_choice * (w("W") - x - d * (y - x))
         polys["choice_bit"] = q_choice * (d * (GP.Expression.constant(1) - d))
-    gates = GATES_CHOICE if choice else GATES
+    if varlen:
+        _varlen_gates(cs, polys, cells, adv, fcol, w)
+    gates = GATES_CHOICE if choice else GATES_VARLEN if varlen else GATES
     assert tuple(polys) != () and set(polys) == set(gates)
     for name in gates:
         cs.create_gate(name, [polys[name]])
@@ -215,6 +228,51 @@ def _constraint_system(tb: int, dense, spread, choice: bool = False):
     for j in range(PAIRS):
         cs.lookup_static(f"length{j}", [(cs.query_advice(adv[2 * j]) * cs.query_fixed(fcol[f"scale{j}"]), dense)])
     return cs, adv, fcol, inst, cells, word
+
+
+def _varlen_gates(cs, polys, cells, adv, fcol, w):
+    """The gates of GATES_VARLEN into `polys` ("Variable-length messages").  In the region of message word g,
+    column Y: m_g (the word lies wholly inside the message), len_g (the message's bytes up to and with the word) and two
+    bits c0, c1; e = c0 * c1 in the schedule carry's slot; d0, d1, the 12-bit halves of D, in pair slot 7 of rows 0 and 1.
+    The cells of word g - 1 are one region up -- for word 0 of a block in the block's carry-in region.  b_g = m_(g-1) - m_g
+    marks the boundary word, which holds r = 3 - c0 - 2 c1 bytes of the message (the integer D), 0x80 and zeros:
+    W = 2^(8 (3 - r)) * (256 D + 128).  Every gate is anchored on row 0 of its region and has degree <= 4; Y is read at no
+    rotation beyond two regions up."""
+    Y = adv[2 * PAIRS + 1]
+    free = {(Y.index, r) for r in range(4, REGION_ROWS)} | {(2 * VAR["SLOT_DATA"], r) for r in (0, 1)}
+    assert not any((c.column, c.row) in free for c in cells), "the layout uses a cell of the variable-length gates"
+    assert (2 * VAR["SLOT_PRODUCT"], 0) == next((c.column, c.row) for c in cells if c.kind == SRC["CARRY_W"])
+
+    def y(row, regions_back=0):
+        return cs.query_advice(Y, row - REGION_ROWS * regions_back)
+
+    q_pad, q_length, q_last, q_carry, q_final, q_sum = (cs.query_fixed(fcol[name]) for name in FIXED_VARLEN[len(FIXED):])
+    q_word = q_pad + q_length  # words 0 .. 14 and word 15: every message-word region
+    one = GP.Expression.constant(1)
+    m, ln, c0, c1 = (y(VAR["ROW_" + s]) for s in ("M", "LEN", "C0", "C1"))
+    m_prev, len_prev, m_13 = y(VAR["ROW_M"], 1), y(VAR["ROW_LEN"], 1), y(VAR["ROW_M"], 2)
+    e = cs.query_advice(adv[2 * VAR["SLOT_PRODUCT"]], 0)
+    d0, d1 = (cs.query_advice(adv[2 * VAR["SLOT_DATA"]], r) for r in (0, 1))
+    b = m_prev - m
+    u = one + c0 * 255 + c1 * 65535 + e * (255 * 65535)  # (1 + 255 c0)(1 + 65535 c1) = 2^(8 (c0 + 2 c1))
+    polys["var_m_bool"] = q_word * (m * (one - m))
+    polys["var_b_bool"] = q_word * (b * (one - b))
+    polys["var_c0_bool"] = q_word * (c0 * (one - c0))
+    polys["var_c1_bool"] = q_word * (c1 * (one - c1))
+    polys["var_c_product"] = q_word * (e - c0 * c1)
+    polys["var_len"] = q_word * (ln - len_prev - m * 4 - b * (GP.Expression.constant(3) - c0 - c1 * 2))
+    polys["var_boundary"] = q_word * (b * (w("W") - u * (d0 * 256 + d1 * (256 << 12) + GP.Expression.constant(128))))
+    polys["var_pad_zero"] = q_pad * ((one - m_prev) * w("W"))  # behind the boundary word: zero, words 0 .. 14
+    # word 15 behind the boundary: the bit length if word 13 is not message (this block is the final one: behind it the
+    # carried length is zero, and so is this word), else zero (the boundary is word 14, the next block is final)
+    polys["var_length_word"] = q_length * ((one - m_prev) * (w("W") - (ln * 8) * (one - m_13)))
+    polys["var_last_final"] = q_last * m  # word 13 of the last block is no message word: some block is final
+    row = {s: y(VAR["ROW_" + s]) for s in ("IN", "FLAG", "VALUE", "OUT")}
+    # carry-in region of a block after the first: the length it starts from = the length behind the block before (VALUE)
+    # times that block's m_13 (OUT) -- zero behind the final block
+    polys["var_carry"] = q_carry * (y(VAR["ROW_LEN"]) - row["VALUE"] * row["OUT"])
+    polys["var_final"] = q_final * (row["VALUE"] - row["IN"] + row["FLAG"])  # fin = m_13 of the block before - m_13
+    polys["var_select"] = q_sum * (row["OUT"] - row["IN"] - row["FLAG"] * row["VALUE"])
 
 
 def _assign_fixed(k, blocks, tb, cs, adv, fcol, inst, cells, word) -> Description:
@@ -325,7 +383,8 @@ def _close_key(self):
 class Sha256Circuit:
     """Proving key and GPU witness synthesis for SHA-256 over exactly `blocks` padded blocks at 2^k rows.  One key
     proves one message length; there is no variable-length selection (several messages, a hash of a hash, a Merkle root
-    over private leaves or Merkle membership of one leaf in one proof: sha256_segments.py)."""
+    over private leaves or Merkle membership of one leaf in one proof: sha256_segments.py; any length under one key, with
+    the padding constrained: sha256_varlen.py)."""
 
     rows_per_block = BLOCK_REGIONS * REGION_ROWS
 

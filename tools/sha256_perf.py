@@ -17,7 +17,11 @@ the same shape without choices -- per path a chain of 32 two-block segments, eac
 alone -- through cq_sha256_synthesize_segments_dev: entry point + synchronise, the wrapper's synthesize, check and proof of
 both.  The difference of the two entry-point times is the choice fetch of the chain kernel plus the fill launch.
 
-    python tools/sha256_perf.py [--sizes 14,18] [--segments-k 18] [--path-k 18] [--sweep 1,2,4,...] [--reps 15] [--warmup 3]
+With --varlen-k K (0 = off): `Sha256VarCircuit` over segments of 1, 2, 4, 8 blocks in turn, as many as 2^K rows hold, with
+messages of mixed lengths (raw bytes in, padded on the device), next to `Sha256BatchCircuit` at the same block counts, whose
+messages fill their segments: the wrapper's synthesize, the entry point + synchronise, check and proof of both.
+
+    python tools/sha256_perf.py [--sizes 14,18] [--segments-k 18] [--path-k 18] [--varlen-k 18] [--sweep 1,2,4,...] [--reps 15] [--warmup 3]
 """
 import argparse
 import json
@@ -173,11 +177,52 @@ def path_legs(ctx, k, reps, warmup, depth=32):
                       "proof_ms_difference": round(rows[0]["proof_ms"] - rows[1]["proof_ms"], 3)}), flush=True)
 
 
+def varlen_legs(ctx, k, reps, warmup):
+    import ctypes as C
+    import hashlib
+
+    from sha2_on_cq_halo2_amd import sha256_circuit as SC
+    from sha2_on_cq_halo2_amd.api import Sha256BatchCircuit, Sha256VarCircuit
+
+    blocks_list, rows, usable = [], 0, SC.usable_rows(k)
+    while rows + SC.rows_for((1, 2, 4, 8)[len(blocks_list) % 4]) <= usable:  # segments of 1, 2, 4, 8 blocks in turn
+        blocks_list.append((1, 2, 4, 8)[len(blocks_list) % 4])
+        rows += SC.rows_for(blocks_list[-1])
+    # mixed lengths: every fourth message fills its segment, the others end anywhere in it (the empty message included)
+    lengths = [64 * b - 9 if j % 4 == 3 else (0x9E3779B1 * j) % (64 * b - 8) for j, b in enumerate(blocks_list)]
+    mixed = [bytes((i + j) % 251 for i in range(n_)) for j, n_ in enumerate(lengths)]
+    full = [bytes((i + j) % 251 for i in range(64 * b - 9)) for j, b in enumerate(blocks_list)]  # what a fixed-length batch takes
+    for name, make, arg in (("Sha256VarCircuit", lambda: Sha256VarCircuit(ctx, k, blocks_list), mixed),
+                            ("Sha256BatchCircuit, same block counts", lambda: Sha256BatchCircuit(ctx, k, blocks_list), full)):
+        t0 = time.perf_counter()
+        c = make()
+        row = {"circuit": name, "k": k, "segments": len(blocks_list), "blocks": sum(blocks_list), "rows": c.rows,
+               "message_bytes": sum(len(m) for m in arg), "fixed_columns": c.cs.num_fixed_columns, "gates": len(c.cs.gates),
+               "proof_bytes": c.pk.proof_size, "keygen_s": round(time.perf_counter() - t0, 2)}
+        assert c.check(arg) == (0, []) and c.digests == [hashlib.sha256(m).digest() for m in arg]
+        ptrs, seed = [b.ptr for b in c.cols], [0]
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+
+        def call():  # the entry point alone: the bytes (or words) of the last synthesize are still on the device
+            c._call(arr)
+            ctx.sync()
+
+        def prove():
+            seed[0] += 1
+            c.pk.create_proof_dev(ptrs, seed=seed[0], instances=c.instances)
+
+        timed(row, (("synthesize_ms", lambda: c.synthesize(arg)), ("synthesize_call_ms", call),
+                    ("check_ms", lambda: c.pk.check_witness(ptrs, instances=c.instances, max_failures=0)), ("proof_ms", prove)), reps, warmup)
+        c.close()
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="14,18")
     ap.add_argument("--segments-k", type=int, default=0)
     ap.add_argument("--path-k", type=int, default=0)
+    ap.add_argument("--varlen-k", type=int, default=0)
     ap.add_argument("--sweep", default="1,2,4,8,16,32,64,128,256,512")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
@@ -220,6 +265,8 @@ def main():
         segment_legs(ctx, args.segments_k, args.sweep, args.reps, args.warmup)
     if args.path_k:
         path_legs(ctx, args.path_k, args.reps, args.warmup)
+    if args.varlen_k:
+        varlen_legs(ctx, args.varlen_k, args.reps, args.warmup)
     ctx.close()
 
 
