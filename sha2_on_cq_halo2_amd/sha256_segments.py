@@ -257,6 +257,63 @@ def describe(k: int, plan: Plan, table_bits: int = 12, dense="dense", spread="sp
     return SC.Description(cs, adv, fcol, fixed, inst, copies, cells, table_bits, tuple(s.blocks for s in plan.segments), k, names)
 
 
+class Lowered(NamedTuple):
+    """A plan as the entry points take it: the arrays of cq_sha256_synthesize_segments_dev / _choices_dev and the shape
+    of the word buffer they index -- the distinct constants, then every Private word in (segment, word) order, then the
+    vars, then the bits."""
+
+    seg_blocks: np.ndarray      # uint32[segments]
+    sources: np.ndarray         # uint32[16 * blocks]: a word index, SOURCE_DIGEST + 8 * segment + word, or SOURCE_CHOICE + entry
+    choices: np.ndarray         # uint32[entries, 4]: {bit, zero, one, 0}, bit a word index, the operands plain sources
+    consts: np.ndarray          # uint32: the head of the word buffer
+    words_len: int
+    private_counts: list        # Private words per segment
+    shared_counts: tuple        # (vars, bits)
+
+
+def lower(plan: Plan) -> Lowered:
+    """The plan's sources as indices into its word buffer; needs no key and no device."""
+    consts = sorted({s.value for seg in plan.segments for s in seg.sources if isinstance(s, Const)})
+    at_const = {v: i for i, v in enumerate(consts)}
+    private_counts = [sum(isinstance(s, Private) for s in seg.sources) for seg in plan.segments]
+    nvars, nbits = shared_counts(plan)
+    first_var = len(consts) + sum(private_counts)
+    first_bit = first_var + nvars
+
+    def plain(s):
+        return first_var + s.index if isinstance(s, Var) else SOURCE_DIGEST + 8 * s.segment + s.word
+
+    sources, choices, nxt = [], [], len(consts)
+    for seg in plan.segments:
+        for s in seg.sources:
+            if isinstance(s, Private):
+                sources.append(nxt)
+                nxt += 1
+            elif isinstance(s, Choice):  # entry c of the choice table: {bit, zero, one, 0}
+                sources.append(SOURCE_CHOICE + len(choices))
+                choices.append((first_bit + s.bit, plain(s.zero), plain(s.one), 0))
+            else:
+                sources.append(at_const[s.value] if isinstance(s, Const) else plain(s))
+    assert nxt == first_var
+    return Lowered(np.array([seg.blocks for seg in plan.segments], dtype=np.uint32), np.array(sources, dtype=np.uint32),
+                   np.array(choices, dtype=np.uint32).reshape(-1, 4), np.array(consts, dtype=np.uint32), first_bit + nbits,
+                   private_counts, (nvars, nbits))
+
+
+def word_buffer(low: Lowered, values, shared=(), bits=()) -> np.ndarray:
+    """The word buffer of a lowered plan for one witness: `values` per segment its Private words in word order, `shared`
+    the Var words by index, `bits` the bits.  ValueError for counts that are not the plan's or values out of range."""
+    values = [np.asarray(v, dtype=np.uint32).reshape(-1) for v in values]
+    if [len(v) for v in values] != low.private_counts:
+        raise ValueError(f"private words per segment: {low.private_counts}, not {[len(v) for v in values]}")
+    if any(not 0 <= int(w) < 1 << 32 for w in shared) or any(int(b) not in (0, 1) for b in bits):
+        raise ValueError("shared words are 32-bit words, bits are 0 or 1")
+    if (len(shared), len(bits)) != low.shared_counts:
+        raise ValueError(f"(shared words, bits): {low.shared_counts}, not {(len(shared), len(bits))}")
+    tail = [np.array([int(x) for x in part], dtype=np.uint32) for part in (shared, bits)]
+    return np.concatenate([low.consts] + values + tail)
+
+
 def _words_to_mont(words) -> np.ndarray:
     """32-bit words -> uint64[len, 4] Montgomery limbs (a batch has thousands of instance words: one bytes join, no
     array per word)."""
@@ -282,34 +339,8 @@ class Sha256SegmentsCircuit:
         self.plan = plan
         SC._build_key(self, ctx, k, table_bits, setup, seed, lambda dense, spread: describe(k, plan, table_bits, dense, spread))
         self.rows = rows_for(plan)
-        # the word buffer: the distinct constants, then every Private word in (segment, word) order, the vars, the bits
-        consts = sorted({s.value for seg in plan.segments for s in seg.sources if isinstance(s, Const)})
-        at_const = {v: i for i, v in enumerate(consts)}
-        self._consts = np.array(consts, dtype=np.uint32)
-        self._private_counts = [sum(isinstance(s, Private) for s in seg.sources) for seg in plan.segments]
-        self._shared_counts = nvars, nbits = shared_counts(plan)
-        first_var = len(consts) + sum(self._private_counts)
-        first_bit = first_var + nvars
-
-        def plain(s):
-            return first_var + s.index if isinstance(s, Var) else SOURCE_DIGEST + 8 * s.segment + s.word
-
-        sources, choices, nxt = [], [], len(consts)
-        for seg in plan.segments:
-            for s in seg.sources:
-                if isinstance(s, Private):
-                    sources.append(nxt)
-                    nxt += 1
-                elif isinstance(s, Choice):  # entry c of the choice table: {bit, zero, one, 0}
-                    sources.append(SOURCE_CHOICE + len(choices))
-                    choices.append((first_bit + s.bit, plain(s.zero), plain(s.one), 0))
-                else:
-                    sources.append(at_const[s.value] if isinstance(s, Const) else plain(s))
-        assert nxt == first_var
-        self._sources = np.array(sources, dtype=np.uint32)
-        self._choices = np.array(choices, dtype=np.uint32).reshape(-1, 4)
-        self._seg_blocks = np.array([seg.blocks for seg in plan.segments], dtype=np.uint32)
-        self._words_len = first_bit + nbits
+        self._lowered = low = lower(plan)
+        self._seg_blocks, self._sources, self._choices, self._words_len = low.seg_blocks, low.sources, low.choices, low.words_len
         self._words = ctx.alloc(4 * max(self._words_len, 1))
         self._digests = ctx.alloc(32 * len(plan.segments))
         self.digest_words = self.instances = None
@@ -339,15 +370,7 @@ class Sha256SegmentsCircuit:
         cq_sha256_synthesize_choices_dev for a plan with choices) and downloads the digests; returns (device columns,
         instances)."""
         values, shared, bits = self._inputs(values, shared, bits)
-        values = [np.asarray(v, dtype=np.uint32).reshape(-1) for v in values]
-        if [len(v) for v in values] != self._private_counts:
-            raise ValueError(f"private words per segment: {self._private_counts}, not {[len(v) for v in values]}")
-        if any(not 0 <= int(w) < 1 << 32 for w in shared) or any(int(b) not in (0, 1) for b in bits):
-            raise ValueError("shared words are 32-bit words, bits are 0 or 1")
-        if (len(shared), len(bits)) != self._shared_counts:
-            raise ValueError(f"(shared words, bits): {self._shared_counts}, not {(len(shared), len(bits))}")
-        tail = [np.array([int(x) for x in part], dtype=np.uint32) for part in (shared, bits)]
-        self._words.upload(np.concatenate([self._consts] + values + tail))
+        self._words.upload(word_buffer(self._lowered, values, shared, bits))
         self._call((C.c_void_p * SC.ADVICE_COLUMNS)(*[c.ptr for c in self.cols]))
         self.digest_words = self._digests.download((len(self._seg_blocks), 8), np.uint32).tolist()
         self.instances = [_words_to_mont([x for p in self.plan.public for x in self.digest_words[p]])]
