@@ -7,7 +7,8 @@ value derived from them (interpolants, vanishing products, exact divisions) is i
 order, so insertion order is used here.
 
 Parity status: "parity unpinned" against Rust (no golden proof; `plonk_api.rs` only checks acceptance); pinned
-from the verifier side in `tests/test_oracle_plonk.py`.
+from the verifier side in `tests/test_oracle_plonk.py`, and for arbitrary queries (64 rotation sets, sets of 8 points,
+n = 2^12 and 2^13, challenges 0, 1 and p - 1) in `tests/test_multiopen_shapes_cpu.py`.
 """
 from __future__ import annotations
 

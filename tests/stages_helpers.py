@@ -9,10 +9,13 @@ from oracle.poly import eval_polynomial, kate_division, msm_affine
 P = B.R_MOD
 
 
-def gwc_prove(tr, n, queries, polys, g):
+def gwc_prove(tr, n, queries, polys, g, commit=None):
     """queries: [(key, point, eval)] in order; polys: key -> coefficients (<= n); g: the SRS.  Per distinct point in
     first-seen order (gwc.rs:36-61): poly_batch = sum_i v^i p_i, eval_batch = sum_i v^i e_i over the point's queries
-    (:62-78), the witness (poly_batch - eval_batch) / (X - point) (:80) and its commitment (:85)."""
+    (:62-78), the witness (poly_batch - eval_batch) / (X - point) (:80) and its commitment (:85).  commit(poly) replaces
+    the MSM over g[: n - 1] (g may then be None): `trapdoor_commit` for large n, a scalar for the verifier identities."""
+    if commit is None:
+        commit = lambda w: msm_affine(w, g[: n - 1])
     v = tr.squeeze_challenge_scalar()
     points = []
     for _, pt, _ in queries:
@@ -28,7 +31,7 @@ def gwc_prove(tr, n, queries, polys, g):
             pv = pv * v % P
         batch[0] = (batch[0] - eval_batch) % P
         w = kate_division(batch, pt)
-        tr.write_point(msm_affine(w, g[: n - 1]))
+        tr.write_point(commit(w))
     return v
 
 
@@ -54,6 +57,35 @@ class RecordingTranscript:
         pt = B.points_from_mont_limbs(affine.reshape(1, 8))[0]
         self.points.append(pt)
         self.tr.write_point(pt)
+
+
+class ScriptedTranscript:
+    """No hash: hands out the given challenges in order and records what is written, so a test chooses y, v, u itself.
+    Both faces: squeeze_challenge_scalar / write_point for the oracle's provers (ints and whatever their `commit`
+    returns), squeeze / write for cq_multiopen_dev's callbacks (Montgomery limbs, as RecordingTranscript converts them)."""
+
+    def __init__(self, challenges):
+        self.script, self.challenges, self.points = list(challenges), [], []
+
+    def squeeze_challenge_scalar(self):
+        c = self.script[len(self.challenges)]  # an IndexError here fails the device call: more squeezes than scripted
+        self.challenges.append(c)
+        return c
+
+    def write_point(self, pt):
+        self.points.append(pt)
+
+    def squeeze(self):
+        return B.to_mont_limbs([self.squeeze_challenge_scalar()])[0]
+
+    def write(self, affine):
+        self.write_point(B.points_from_mont_limbs(affine.reshape(1, 8))[0])
+
+
+def trapdoor_commit(s):
+    """commit(p) = p(s) G: what the MSM over the powers [s^i]_1 of `setup_from_toxic_waste(k, s)` gives, in one scalar
+    multiplication (tests/test_multiopen_shapes_cpu.py checks the two against each other once)."""
+    return lambda poly: B.g1_mul(B.G1_GEN, eval_polynomial(poly, s))
 
 
 def reference_transcript():
