@@ -913,6 +913,19 @@ int cq_sha256_synthesize_segments_dev(cq_ctx* ctx, uint32_t table_bits, const ui
 int cq_sha256_synthesize_choices_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
                                      const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* words_dev,
                                      size_t words_len, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev);
+/* The same with segments that start from a wired state instead of the IV (DESIGN.md "Wired initial states").
+ * `init_sources` is a host array of 8 entries per segment, H[0..7] of the state the segment's first block starts from: an
+ * entry is CQ_SHA256_SOURCE_IV (tested before the digest flag) for the IV's word of that position, or a plain source -- a
+ * word index or a digest reference.  A segment's level also counts the digests its initial words read: a segment whose
+ * only dependency is its initial state still runs one level behind its producer.  CQ_ERR_ARG, besides the cases above and
+ * again before anything is queued, with "segment j, initial word i" in cq_last_error: a digest of the segment itself or a
+ * later one, an index outside `words_dev`, and -- with n_choices > 0 -- a value at or above CQ_SHA256_SOURCE_CHOICE (a
+ * choice is no initial word).  init_sources = NULL is cq_sha256_synthesize_choices_dev exactly. */
+#define CQ_SHA256_SOURCE_IV 4294967295u
+int cq_sha256_synthesize_states_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
+                                    const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* init_sources,
+                                    const uint32_t* words_dev, size_t words_len, size_t n, uint64_t* const* cols_dev,
+                                    uint32_t* digests_dev);
 /* Messages of variable length with constrained padding (DESIGN.md "Variable-length messages"): segment j is a chain of
  * seg_max_blocks[j] blocks that holds message j -- msg_lens[j] raw bytes at msg_bytes_dev + msg_offsets[j], a device buffer
  * of msg_bytes_len bytes (no alignment is asked of it) -- padded on the device: 0x80, zeros, the bit length in the last two
@@ -950,6 +963,16 @@ int cq_sha256_synthesize_choices_dev(cq_ctx* ctx, uint32_t table_bits, const uin
 int cq_sha256_synthesize_varlen_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_max_blocks, size_t segments,
                                     const uint8_t* msg_bytes_dev, size_t msg_bytes_len, const uint64_t* msg_offsets,
                                     const uint64_t* msg_lens, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev);
+/* The same continued from a state: segment j starts from the eight words at init_states_dev + 8 j (device, 8 * segments
+ * words) instead of the IV, after base_lens[j] bytes (host) that the state has absorbed already.  The padding's length word
+ * is the bit length of base_lens[j] + msg_lens[j]; every running-length cell, the carry-in of the first block and the
+ * selected length count from the base.  CQ_ERR_ARG, besides the cases above, with the segment in cq_last_error: a base that
+ * is no multiple of 64, or base_lens[j] + 64 * seg_max_blocks[j] above 2^29 (the bit length is the 32-bit word 15 of the
+ * final block; word 14 is zero).  All-IV states with bases of zero give cq_sha256_synthesize_varlen_dev's columns. */
+int cq_sha256_synthesize_varlen_from_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_max_blocks, size_t segments,
+                                         const uint8_t* msg_bytes_dev, size_t msg_bytes_len, const uint64_t* msg_offsets,
+                                         const uint64_t* msg_lens, const uint32_t* init_states_dev, const uint64_t* base_lens, size_t n,
+                                         uint64_t* const* cols_dev, uint32_t* digests_dev);
 
 /* ---- harness RNG (not in the reference: its test draws from OsRng) ---------------------------------- */
 void cq_xoshiro256ss_seed(uint64_t seed, uint64_t state[4]);

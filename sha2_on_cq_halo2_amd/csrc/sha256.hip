@@ -11,6 +11,8 @@
 // bit into three cells of the word's region that the layout leaves free.
 // Variable length (cq_sha256_synthesize_varlen_dev): raw bytes are padded on the device into the word buffer the plain
 // chain kernel reads, and a kernel behind the expansion writes the flags, lengths and selection cells the padding gates read.
+// Wired states (cq_sha256_synthesize_states_dev, cq_sha256_synthesize_varlen_from_dev): a segment's chain may start from
+// eight gathered words instead of the IV; the chain kernel's INIT instantiations fetch them as they fetch a message word.
 #include <cstring>
 #include <string>
 #include <utility>
@@ -267,20 +269,39 @@ static __device__ __forceinline__ void sha256_fetch_all(uint32_t (&w)[16], const
   (sha256_fetch<CHOICES, I>(w, src, choices, words, digests), ...);
 }
 
+// Word I of the state a lane's chain starts from: the IV's on the sentinel, else a plain source -- read from `init_words`,
+// which is the word buffer or a buffer of states of its own.  I is a compile-time constant, so `h` stays in registers.
+template <uint32_t I>
+static __device__ __forceinline__ void sha256_fetch_init(uint32_t (&h)[8], uint32_t s, const uint32_t* init_words, const uint32_t* digests) {
+  if (s != CQ_SHA256_SOURCE_IV) h[I] = sha256_load(s, init_words, digests);
+}
+
 // One lane per segment of one level: what sha256_regions does for one message, with the message words gathered through
 // `sources`.  A chain is 64 dependent rounds per block, so the launch is latency-bound: one wave per workgroup spreads a
 // level's segments over the CUs.  Lanes of a wave may differ in their block counts.  `digests` is read (earlier levels)
 // and written (this lane's segment), hence neither const nor restrict.  CHOICES: whether the launch's sources may name
 // entries of `choices` (sha256_fetch); a plan without choices runs the instantiation whose fetch knows nothing of them.
-template <bool CHOICES>
+// INIT: whether the chains may start from other states than the IV -- `init_sources` then holds 8 entries per segment
+// (32 bytes, aligned to 16), each CQ_SHA256_SOURCE_IV or a plain source into `init_words` / `digests`, checked by the
+// host like a message word's; lanes of one wave may mix the two.  Without INIT neither pointer is looked at.
+template <bool CHOICES, bool INIT>
 __global__ __launch_bounds__(64) void sha256_chain_kernel(const Sha256Lane* __restrict__ lanes, uint32_t nlanes,
                                                           const uint32_t* __restrict__ sources, const Sha256Choice* __restrict__ choices,
-                                                          const uint32_t* words, uint32_t* digests, Sha256Region* __restrict__ regions) {
+                                                          const uint32_t* words, uint32_t* digests, Sha256Region* __restrict__ regions,
+                                                          const uint32_t* __restrict__ init_sources, const uint32_t* init_words) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nlanes) return;
   const Sha256Lane lane = lanes[i];
   using Seq16 = std::make_integer_sequence<uint32_t, 16>;
   uint32_t h[8] = {SHA256_IV_VALUES};
+  if (INIT) {
+    const uint4* is = reinterpret_cast<const uint4*>(init_sources + 8 * (size_t)lane.segment);
+    const uint4 lo = is[0], hi = is[1];
+    sha256_fetch_init<0>(h, lo.x, init_words, digests), sha256_fetch_init<1>(h, lo.y, init_words, digests);
+    sha256_fetch_init<2>(h, lo.z, init_words, digests), sha256_fetch_init<3>(h, lo.w, init_words, digests);
+    sha256_fetch_init<4>(h, hi.x, init_words, digests), sha256_fetch_init<5>(h, hi.y, init_words, digests);
+    sha256_fetch_init<6>(h, hi.z, init_words, digests), sha256_fetch_init<7>(h, hi.w, init_words, digests);
+  }
   Sha256Region* out = regions + lane.first_region;
   const uint32_t* src = sources + lane.first_source;
   for (uint32_t b = 0; b < lane.blocks; b++, out += CQ_SHA256_BLOCK_REGIONS, src += 16) {
@@ -295,6 +316,20 @@ __global__ __launch_bounds__(64) void sha256_chain_kernel(const Sha256Lane* __re
   sha256_put_state(out, h, SHA_RG_CHAIN);
   uint32_t* d = digests + 8 * (size_t)lane.segment;
   d[0] = h[0], d[1] = h[1], d[2] = h[2], d[3] = h[3], d[4] = h[4], d[5] = h[5], d[6] = h[6], d[7] = h[7];
+}
+
+// the chain launch of one level: the instantiation that knows no more than the description needs
+static void sha256_launch_chain(cq_ctx* c, bool choices, bool init, uint32_t grid, const Sha256Lane* lanes, uint32_t nlanes, const uint32_t* sources,
+                                const Sha256Choice* dev_choices, const uint32_t* words, uint32_t* digests, Sha256Region* regions,
+                                const uint32_t* init_sources, const uint32_t* init_words) {
+  if (choices && init)
+    sha256_chain_kernel<true, true><<<grid, 64, 0, c->stream>>>(lanes, nlanes, sources, dev_choices, words, digests, regions, init_sources, init_words);
+  else if (choices)
+    sha256_chain_kernel<true, false><<<grid, 64, 0, c->stream>>>(lanes, nlanes, sources, dev_choices, words, digests, regions, nullptr, nullptr);
+  else if (init)
+    sha256_chain_kernel<false, true><<<grid, 64, 0, c->stream>>>(lanes, nlanes, sources, nullptr, words, digests, regions, init_sources, init_words);
+  else
+    sha256_chain_kernel<false, false><<<grid, 64, 0, c->stream>>>(lanes, nlanes, sources, nullptr, words, digests, regions, nullptr, nullptr);
 }
 
 // One thread per choice entry, after the expansion (which wrote these cells as zero) on the same stream: the operand taken
@@ -317,10 +352,11 @@ __global__ __launch_bounds__(64) void sha256_choice_fill_kernel(const Sha256Choi
 // Validates the description, then queues the tables' upload, one chain launch per level, the expansion and -- with
 // choices -- the fill of their cells.  Nothing here waits for the stream; the staging is pinned, and only the previous
 // call's copy out of it is waited for.  n_choices = 0 is the description without choices: a source at or above
-// CQ_SHA256_SOURCE_CHOICE is then a word index like any other.
+// CQ_SHA256_SOURCE_CHOICE is then a word index like any other.  init_sources = nullptr is the description whose segments
+// all start from the IV; otherwise it holds 8 entries per segment, CQ_SHA256_SOURCE_IV or a plain source.
 int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* sources,
-                               const uint32_t* choices, size_t n_choices, const uint32_t* words_dev, size_t words_len, uint32_t n,
-                               const Sha256Cols& cols, uint32_t* digests_dev) {
+                               const uint32_t* choices, size_t n_choices, const uint32_t* init_sources, const uint32_t* words_dev,
+                               size_t words_len, uint32_t n, const Sha256Cols& cols, uint32_t* digests_dev) {
   const uint64_t max_regions = n / CQ_SHA256_REGION_ROWS;
   uint64_t regions = 0, blocks = 0;
   for (size_t j = 0; j < segments; j++) {
@@ -332,7 +368,22 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
   std::vector<uint32_t> level(segments, 0), level_count;
   std::vector<uint32_t> choice_region(n_choices, UINT32_MAX);  // the region of the word that refers to the entry, once one does
   uint32_t seg_region = 0;
-  for (size_t j = 0, at = 0; j < segments; seg_region += seg_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS, j++)
+  for (size_t j = 0, at = 0; j < segments; seg_region += seg_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS, j++) {
+    for (size_t i = 0; init_sources && i < 8; i++) {  // the state the chain starts from: the IV's word or a plain source
+      const uint32_t s = init_sources[8 * j + i];
+      std::string bad;
+      if (s == CQ_SHA256_SOURCE_IV) continue;
+      if (s & CQ_SHA256_SOURCE_DIGEST) {
+        const size_t ref = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3;
+        if (ref >= j) bad = " reads the digest of segment " + std::to_string(ref) + ", which does not come before it";
+        else if (level[ref] + 1 > level[j]) level[j] = level[ref] + 1;
+      } else if (n_choices && s >= CQ_SHA256_SOURCE_CHOICE) {
+        bad = " is a choice, which an initial word cannot be";
+      } else if (s >= words_len) {
+        bad = " reads word " + std::to_string(s) + " of a buffer of " + std::to_string(words_len);
+      }
+      if (!bad.empty()) return c->fail(CQ_ERR_ARG, "sha256: segment " + std::to_string(j) + ", initial word " + std::to_string(i) + bad);
+    }
     for (size_t t = 0; t < 16 * (size_t)seg_blocks[j]; t++, at++) {
       auto where = [&] { return "sha256: segment " + std::to_string(j) + ", word " + std::to_string(t); };
       // a plain source, the word's own or a choice's operand: "" if it is good, and the segment's level follows a digest's
@@ -364,6 +415,7 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
       }
       if (!bad.empty()) return c->fail(CQ_ERR_ARG, where() + bad);
     }
+  }
   for (size_t e = 0; e < n_choices; e++)
     if (choice_region[e] == UINT32_MAX) return c->fail(CQ_ERR_ARG, "sha256: choice " + std::to_string(e) + " is read by no word");
   for (uint32_t l : level) {
@@ -375,9 +427,11 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
 
   static_assert(sizeof(Sha256Region) == 16 && sizeof(Sha256Lane) == 16, "four words each");
   static_assert(sizeof(Sha256Choice) == CQ_SHA256_CHOICE_WORDS * sizeof(uint32_t), "an entry of the choice table as the header states it");
-  // lanes, sources, choices: each a multiple of 16 bytes, so the choice entries are aligned for their 16-byte loads
+  // lanes, sources, choices, initial sources: each a multiple of 16 bytes, so the choice entries and a segment's eight
+  // initial sources are aligned for their 16-byte loads
   const size_t lanes_bytes = segments * sizeof(Sha256Lane), sources_bytes = 16 * blocks * sizeof(uint32_t);
-  const size_t tables_bytes = lanes_bytes + sources_bytes + n_choices * sizeof(Sha256Choice);
+  const size_t choices_bytes = n_choices * sizeof(Sha256Choice), init_bytes = init_sources ? 8 * segments * sizeof(uint32_t) : 0;
+  const size_t tables_bytes = lanes_bytes + sources_bytes + choices_bytes + init_bytes;
   void *pin, *dev_regions, *dev_tables;
   CQ_TRY(c->ensure_pinned_sha(tables_bytes, &pin));
   CQ_TRY(c->ensure_scratch(Scratch::EntryA, regions * sizeof(Sha256Region), &dev_regions));
@@ -396,19 +450,16 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
   Sha256Choice* staged = (Sha256Choice*)((char*)pin + lanes_bytes + sources_bytes);
   for (size_t e = 0; e < n_choices; e++)
     staged[e] = {choices[CQ_SHA256_CHOICE_WORDS * e], choices[CQ_SHA256_CHOICE_WORDS * e + 1], choices[CQ_SHA256_CHOICE_WORDS * e + 2], choice_region[e]};
+  if (init_sources) memcpy((char*)pin + lanes_bytes + sources_bytes + choices_bytes, init_sources, init_bytes);
   CQ_HIP(c, hipMemcpyAsync(dev_tables, pin, tables_bytes, hipMemcpyHostToDevice, c->stream));
   CQ_HIP(c, hipEventRecord(c->sha_staged, c->stream));
   const Sha256Lane* dev_lanes = (const Sha256Lane*)dev_tables;
   const uint32_t* dev_sources = (const uint32_t*)((const char*)dev_tables + lanes_bytes);
   const Sha256Choice* dev_choices = (const Sha256Choice*)((const char*)dev_sources + sources_bytes);
+  const uint32_t* dev_init = (const uint32_t*)((const char*)dev_choices + choices_bytes);
   for (size_t l = 0; l < level_count.size(); l++) {
-    const uint32_t grid = (level_count[l] + 63) / 64;
-    if (n_choices)
-      sha256_chain_kernel<true><<<grid, 64, 0, c->stream>>>(dev_lanes + level_first[l], level_count[l], dev_sources, dev_choices, words_dev,
-                                                            digests_dev, (Sha256Region*)dev_regions);
-    else
-      sha256_chain_kernel<false><<<grid, 64, 0, c->stream>>>(dev_lanes + level_first[l], level_count[l], dev_sources, nullptr, words_dev,
-                                                             digests_dev, (Sha256Region*)dev_regions);
+    sha256_launch_chain(c, n_choices != 0, init_sources != nullptr, (level_count[l] + 63) / 64, dev_lanes + level_first[l], level_count[l],
+                        dev_sources, dev_choices, words_dev, digests_dev, (Sha256Region*)dev_regions, dev_init, words_dev);
     if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_chain launch failed");
   }
   sha256_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha256Region*)dev_regions, (uint32_t)regions, n, table_bits, cols);
@@ -423,10 +474,11 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
 
 // ---- messages of variable length: padding on the device, and the cells its gates read --------------------------------
 
-// One message of a variable-length synthesis: where its raw bytes start in the caller's buffer and how many there are.
+// One message of a variable-length synthesis: where its raw bytes start in the caller's buffer, how many there are, and
+// the bytes absorbed before them (a multiple of 64; zero unless the chain continues from a state).
 struct Sha256VarMsg {
   uint64_t offset;
-  uint32_t len, unused;
+  uint32_t len, base;
 };
 
 // The segment that holds word `word` of the word buffer: lanes are in segment order there and lane j's words start at
@@ -444,8 +496,8 @@ static __device__ __forceinline__ uint32_t sha256_var_segment(const Sha256Lane* 
 static SHA_HD uint32_t sha256_var_final_block(uint32_t len) { return (len + 8) / 64; }
 
 // One thread per word of the word buffer (16 per block of every segment, segment after segment): the big-endian word of
-// the padded message -- data bytes, 0x80, zeros, the bit length in word 15 of the final block -- and zero behind the
-// final block.  A byte is loaded only below the message's length, which the host has checked against the buffer.
+// the padded message -- data bytes, 0x80, zeros, the bit length of base + len bytes in word 15 of the final block (the
+// host has checked that it is a 32-bit word) -- and zero behind the final block.  A byte is loaded only below the message's length, which the host has checked against the buffer.
 __global__ __launch_bounds__(256) void sha256_pad_kernel(const Sha256Lane* __restrict__ lanes, const Sha256VarMsg* __restrict__ msgs,
                                                          uint32_t nlanes, uint32_t nwords, const uint8_t* __restrict__ bytes,
                                                          uint32_t* __restrict__ words) {
@@ -456,7 +508,7 @@ __global__ __launch_bounds__(256) void sha256_pad_kernel(const Sha256Lane* __res
   const uint8_t* src = bytes + msgs[j].offset;
   uint32_t w = 0;
   if (t == last) {
-    w = 8 * len;
+    w = 8 * (msgs[j].base + len);
   } else if (t < last) {
     CQ_UNROLL for (uint32_t k = 0; k < 4; k++) {
       const uint32_t pos = 4 * t + k;
@@ -471,10 +523,10 @@ static __device__ __forceinline__ void sha256_var_put(Fr* cell, uint64_t v) { st
 
 // The flag and the running length of word g (16 * block + word) of a message of `len` bytes whose final block is `fb`:
 // the word lies wholly inside the message; the bytes of the message up to and with the word -- zero behind the final block,
-// where the length a block starts from is cleared.
+// where the length a block starts from is cleared.  The length counts from `base`, the bytes absorbed before the message.
 static __device__ __forceinline__ uint32_t sha256_var_m(uint32_t g, uint32_t len) { return 4 * (g + 1) <= len ? 1u : 0u; }
-static __device__ __forceinline__ uint32_t sha256_var_len(uint32_t g, uint32_t len, uint32_t fb) {
-  return g / 16 > fb ? 0u : min(4 * (g + 1), len);
+static __device__ __forceinline__ uint32_t sha256_var_len(uint32_t g, uint32_t len, uint32_t fb, uint32_t base) {
+  return g / 16 > fb ? 0u : base + min(4 * (g + 1), len);
 }
 
 // 32 threads per block of every segment, after the expansion (which wrote these cells as zero) on the same stream; a
@@ -492,7 +544,7 @@ __global__ __launch_bounds__(256) void sha256_varlen_fill_kernel(const Sha256Lan
   if (gb >= nblocks || role > 26) return;
   const uint32_t j = sha256_var_segment(lanes, nlanes, 16 * gb);
   const Sha256Lane lane = lanes[j];
-  const uint32_t b = gb - lane.first_source / 16, len = msgs[j].len, fb = sha256_var_final_block(len);
+  const uint32_t b = gb - lane.first_source / 16, len = msgs[j].len, base = msgs[j].base, fb = sha256_var_final_block(len);
   const uint32_t block_region = lane.first_region + b * CQ_SHA256_BLOCK_REGIONS;
   Fr* const y = cols.p[SHA256_COL_Y];
   const uint32_t m13_before = b ? sha256_var_m(16 * b - 3, len) : 1u, m13 = sha256_var_m(16 * b + 13, len);
@@ -500,7 +552,7 @@ __global__ __launch_bounds__(256) void sha256_varlen_fill_kernel(const Sha256Lan
     const uint32_t g = 16 * b + role;
     const size_t row = (size_t)(block_region + 4 + role) * CQ_SHA256_REGION_ROWS;
     sha256_var_put(y + row + CQ_SHA256_VAR_ROW_M, sha256_var_m(g, len));
-    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_LEN, sha256_var_len(g, len, fb));
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_LEN, sha256_var_len(g, len, fb, base));
     if (g == len / 4) {  // the boundary word: r = len % 4 bytes of the message, 0x80, zeros
       const uint32_t r = len % 4, s = 3 - r, c0 = s & 1, c1 = s >> 1;
       const uint32_t data = r ? regions[block_region + 4 + role].w >> (32 - 8 * r) : 0;
@@ -516,9 +568,9 @@ __global__ __launch_bounds__(256) void sha256_varlen_fill_kernel(const Sha256Lan
     }
   } else if (role == 16) {
     const size_t row = (size_t)(block_region + CQ_SHA256_VAR_REGION_CARRY) * CQ_SHA256_REGION_ROWS;
-    const uint32_t len15 = b ? sha256_var_len(16 * b - 1, len, fb) : 0u;
+    const uint32_t len15 = b ? sha256_var_len(16 * b - 1, len, fb, base) : 0u;
     sha256_var_put(y + row + CQ_SHA256_VAR_ROW_M, b ? sha256_var_m(16 * b - 1, len) : 1u);
-    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_LEN, len15 * (b ? m13_before : 0u));
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_LEN, b ? len15 * m13_before : base);
     sha256_var_put(y + row + CQ_SHA256_VAR_ROW_VALUE, len15);
     sha256_var_put(y + row + CQ_SHA256_VAR_ROW_OUT, b ? m13_before : 0u);
   } else if (role == 25) {
@@ -536,11 +588,11 @@ __global__ __launch_bounds__(256) void sha256_varlen_fill_kernel(const Sha256Lan
     const uint32_t w = role - 17;
     const size_t row = (size_t)(block_region + (is_len ? CQ_SHA256_VAR_REGION_LENGTH : CQ_SHA256_VAR_REGION_SUM + w)) * CQ_SHA256_REGION_ROWS;
     // the final block lies inside the lane (the host has checked the length against the block count)
-    const uint32_t selected = is_len ? len : chaining(fb, w);
+    const uint32_t selected = is_len ? base + len : chaining(fb, w);
     const uint32_t out = b >= fb ? selected : 0u;
     sha256_var_put(y + row + CQ_SHA256_VAR_ROW_IN, b > fb ? selected : 0u);
     sha256_var_put(y + row + CQ_SHA256_VAR_ROW_FLAG, b == fb ? 1u : 0u);
-    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_VALUE, is_len ? sha256_var_len(16 * b + 15, len, fb) : chaining(b, w));
+    sha256_var_put(y + row + CQ_SHA256_VAR_ROW_VALUE, is_len ? sha256_var_len(16 * b + 15, len, fb, base) : chaining(b, w));
     sha256_var_put(y + row + CQ_SHA256_VAR_ROW_OUT, out);
     if (!is_len && b + 1 == lane.blocks) digests[8 * (size_t)lane.segment + w] = out;
   }
@@ -550,9 +602,12 @@ __global__ __launch_bounds__(256) void sha256_varlen_fill_kernel(const Sha256Lan
 // source tables (pinned staging, as sha256_synthesize_segments), the padding into the word buffer, one launch of the plain
 // chain kernel over all segments (a padded message reads no digest: every segment has level 0, and its sources are its own
 // words in order), the expansion, and the fill of the padding gates' cells.  Nothing here waits for the stream.
+// init_states_dev = nullptr: every chain starts from the IV after no byte.  Otherwise segment j starts from the eight words
+// at init_states_dev + 8 j after base_lens[j] bytes: the chain launch is the INIT instantiation with the identity for its
+// initial sources, which rides behind the word sources in the same upload.
 int sha256_synthesize_varlen(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_max_blocks, size_t segments, const uint8_t* bytes_dev,
-                             size_t bytes_len, const uint64_t* offsets, const uint64_t* lens, uint32_t n, const Sha256Cols& cols,
-                             uint32_t* digests_dev) {
+                             size_t bytes_len, const uint64_t* offsets, const uint64_t* lens, const uint32_t* init_states_dev,
+                             const uint64_t* base_lens, uint32_t n, const Sha256Cols& cols, uint32_t* digests_dev) {
   const uint64_t max_regions = n / CQ_SHA256_REGION_ROWS;
   uint64_t regions = 0, blocks = 0;
   for (size_t j = 0; j < segments; j++) {
@@ -568,11 +623,19 @@ int sha256_synthesize_varlen(cq_ctx* c, uint32_t table_bits, const uint32_t* seg
     if (offsets[j] > bytes_len || lens[j] > bytes_len - offsets[j])
       return c->fail(CQ_ERR_ARG, seg() + ": bytes " + std::to_string(offsets[j]) + " .. " + std::to_string(offsets[j]) + " + " +
                                      std::to_string(lens[j]) + " leave a buffer of " + std::to_string(bytes_len));
+    // the bit length of base + length is the 32-bit word 15 of the final block: the total stays below 2^29 bytes
+    if (base_lens && base_lens[j] % 64)
+      return c->fail(CQ_ERR_ARG, seg() + ": a base of " + std::to_string(base_lens[j]) + " bytes is no multiple of 64");
+    if (base_lens && (base_lens[j] > (1ull << 29) || base_lens[j] + 64 * (uint64_t)seg_max_blocks[j] > (1ull << 29)))
+      return c->fail(CQ_ERR_ARG, seg() + ": a base of " + std::to_string(base_lens[j]) + " bytes and " + std::to_string(seg_max_blocks[j]) +
+                                     " blocks reach past 2^29 bytes");
   }
   static_assert(sizeof(Sha256VarMsg) == 16, "four words");
   const size_t lanes_bytes = segments * sizeof(Sha256Lane), msgs_bytes = segments * sizeof(Sha256VarMsg);
   const size_t nwords = 16 * blocks, words_bytes = nwords * sizeof(uint32_t);
-  const size_t tables_bytes = lanes_bytes + msgs_bytes + words_bytes;  // the sources: one index per word
+  const size_t init_bytes = init_states_dev ? 8 * segments * sizeof(uint32_t) : 0;
+  // the sources: one index per word; each part a multiple of 16 bytes
+  const size_t tables_bytes = lanes_bytes + msgs_bytes + words_bytes + init_bytes;
   void *pin, *dev_regions, *dev_tables;
   CQ_TRY(c->ensure_pinned_sha(tables_bytes, &pin));
   CQ_TRY(c->ensure_scratch(Scratch::EntryA, regions * sizeof(Sha256Region), &dev_regions));
@@ -585,11 +648,12 @@ int sha256_synthesize_varlen(cq_ctx* c, uint32_t table_bits, const uint32_t* seg
   uint32_t first_region = 0, first_source = 0;
   for (size_t j = 0; j < segments; j++) {
     lanes[j] = {first_region, seg_max_blocks[j], first_source, (uint32_t)j};
-    msgs[j] = {offsets[j], (uint32_t)lens[j], 0};
+    msgs[j] = {offsets[j], (uint32_t)lens[j], base_lens ? (uint32_t)base_lens[j] : 0u};
     first_region += seg_max_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS;
     first_source += 16 * seg_max_blocks[j];
   }
   for (size_t i = 0; i < nwords; i++) sources[i] = (uint32_t)i;
+  for (size_t i = 0; i < init_bytes / sizeof(uint32_t); i++) sources[nwords + i] = (uint32_t)i;
   CQ_HIP(c, hipMemcpyAsync(dev_tables, pin, tables_bytes, hipMemcpyHostToDevice, c->stream));
   CQ_HIP(c, hipEventRecord(c->sha_staged, c->stream));
   const Sha256Lane* dev_lanes = (const Sha256Lane*)dev_tables;
@@ -599,8 +663,8 @@ int sha256_synthesize_varlen(cq_ctx* c, uint32_t table_bits, const uint32_t* seg
   sha256_pad_kernel<<<((uint32_t)nwords + 255) / 256, 256, 0, c->stream>>>(dev_lanes, dev_msgs, (uint32_t)segments, (uint32_t)nwords, bytes_dev,
                                                                           dev_words);
   if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_pad launch failed");
-  sha256_chain_kernel<false><<<((uint32_t)segments + 63) / 64, 64, 0, c->stream>>>(dev_lanes, (uint32_t)segments, dev_sources, nullptr, dev_words,
-                                                                                  digests_dev, (Sha256Region*)dev_regions);
+  sha256_launch_chain(c, false, init_states_dev != nullptr, ((uint32_t)segments + 63) / 64, dev_lanes, (uint32_t)segments, dev_sources, nullptr,
+                      dev_words, digests_dev, (Sha256Region*)dev_regions, dev_sources + nwords, init_states_dev);
   if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_chain launch failed");
   sha256_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha256Region*)dev_regions, (uint32_t)regions, n, table_bits, cols);
   if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_expand launch failed");
@@ -641,10 +705,10 @@ int cq_sha256_synthesize_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* msg
   return sha256_synthesize(c, table_bits, msg_words, blocks, (uint32_t)n, sc, digest);
 }
 
-// both entry points below: the argument checks that need no description, then the host function
+// the three entry points below: the argument checks that need no description, then the host function
 static int sha256_segments_entry(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* sources,
-                                 const uint32_t* choices, size_t n_choices, const uint32_t* words_dev, size_t words_len, size_t n,
-                                 uint64_t* const* cols_dev, uint32_t* digests_dev) {
+                                 const uint32_t* choices, size_t n_choices, const uint32_t* init_sources, const uint32_t* words_dev,
+                                 size_t words_len, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
   if (!c) return CQ_ERR_ARG;
   if (!seg_blocks || !sources || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull || (!words_dev && words_len) ||
       words_len > CQ_SHA256_SOURCE_DIGEST)
@@ -659,25 +723,35 @@ static int sha256_segments_entry(cq_ctx* c, uint32_t table_bits, const uint32_t*
     if (!cols_dev[i]) return c->fail(CQ_ERR_ARG, "sha256: null column");
     sc.p[i] = (Fr*)cols_dev[i];
   }
-  return sha256_synthesize_segments(c, table_bits, seg_blocks, segments, sources, choices, n_choices, words_dev, words_len, (uint32_t)n, sc,
-                                    digests_dev);
+  return sha256_synthesize_segments(c, table_bits, seg_blocks, segments, sources, choices, n_choices, init_sources, words_dev, words_len,
+                                    (uint32_t)n, sc, digests_dev);
 }
 
 int cq_sha256_synthesize_segments_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
                                       const uint32_t* sources, const uint32_t* words_dev, size_t words_len, size_t n,
                                       uint64_t* const* cols_dev, uint32_t* digests_dev) {
-  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, nullptr, 0, words_dev, words_len, n, cols_dev, digests_dev);
+  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, nullptr, 0, nullptr, words_dev, words_len, n, cols_dev, digests_dev);
 }
 
 int cq_sha256_synthesize_choices_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
                                      const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* words_dev,
                                      size_t words_len, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
-  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, choices, n_choices, words_dev, words_len, n, cols_dev, digests_dev);
+  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, choices, n_choices, nullptr, words_dev, words_len, n, cols_dev,
+                               digests_dev);
 }
 
-int cq_sha256_synthesize_varlen_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_max_blocks, size_t segments,
-                                    const uint8_t* msg_bytes_dev, size_t msg_bytes_len, const uint64_t* msg_offsets,
-                                    const uint64_t* msg_lens, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
+int cq_sha256_synthesize_states_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
+                                    const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* init_sources,
+                                    const uint32_t* words_dev, size_t words_len, size_t n, uint64_t* const* cols_dev,
+                                    uint32_t* digests_dev) {
+  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, choices, n_choices, init_sources, words_dev, words_len, n, cols_dev,
+                               digests_dev);
+}
+
+// both entry points below: the argument checks that need no message, then the host function
+static int sha256_varlen_entry(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_max_blocks, size_t segments, const uint8_t* msg_bytes_dev,
+                               size_t msg_bytes_len, const uint64_t* msg_offsets, const uint64_t* msg_lens, const uint32_t* init_states_dev,
+                               const uint64_t* base_lens, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
   if (!c) return CQ_ERR_ARG;
   if (!seg_max_blocks || !msg_offsets || !msg_lens || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull ||
       (!msg_bytes_dev && msg_bytes_len))
@@ -690,8 +764,24 @@ int cq_sha256_synthesize_varlen_dev(cq_ctx* c, uint32_t table_bits, const uint32
     if (!cols_dev[i]) return c->fail(CQ_ERR_ARG, "sha256: null column");
     sc.p[i] = (Fr*)cols_dev[i];
   }
-  return sha256_synthesize_varlen(c, table_bits, seg_max_blocks, segments, msg_bytes_dev, msg_bytes_len, msg_offsets, msg_lens, (uint32_t)n,
-                                  sc, digests_dev);
+  return sha256_synthesize_varlen(c, table_bits, seg_max_blocks, segments, msg_bytes_dev, msg_bytes_len, msg_offsets, msg_lens, init_states_dev,
+                                  base_lens, (uint32_t)n, sc, digests_dev);
+}
+
+int cq_sha256_synthesize_varlen_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_max_blocks, size_t segments,
+                                    const uint8_t* msg_bytes_dev, size_t msg_bytes_len, const uint64_t* msg_offsets,
+                                    const uint64_t* msg_lens, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
+  return sha256_varlen_entry(c, table_bits, seg_max_blocks, segments, msg_bytes_dev, msg_bytes_len, msg_offsets, msg_lens, nullptr, nullptr, n,
+                             cols_dev, digests_dev);
+}
+
+int cq_sha256_synthesize_varlen_from_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_max_blocks, size_t segments,
+                                         const uint8_t* msg_bytes_dev, size_t msg_bytes_len, const uint64_t* msg_offsets,
+                                         const uint64_t* msg_lens, const uint32_t* init_states_dev, const uint64_t* base_lens, size_t n,
+                                         uint64_t* const* cols_dev, uint32_t* digests_dev) {
+  if (c && (!init_states_dev || !base_lens)) return c->fail(CQ_ERR_ARG, "sha256: null initial states or base lengths");
+  return sha256_varlen_entry(c, table_bits, seg_max_blocks, segments, msg_bytes_dev, msg_bytes_len, msg_offsets, msg_lens, init_states_dev,
+                             base_lens, n, cols_dev, digests_dev);
 }
 
 }  // extern "C"

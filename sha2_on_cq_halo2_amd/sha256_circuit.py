@@ -287,10 +287,13 @@ def _assign_fixed(k, blocks, tb, cs, adv, fcol, inst, cells, word) -> Descriptio
     return Description(cs, adv, fcol, fixed, inst, copies, cells, tb, blocks, k)
 
 
-def _assign_segment(fixed, copies, first_region, blocks, public, tb, adv, fcol, inst, cells, word):
+def _assign_segment(fixed, copies, first_region, blocks, public, tb, adv, fcol, inst, cells, word, init=None):
     """The fixed cells and the copies of one chain of `blocks` blocks whose regions start at `first_region`: selectors and
-    scales, the round constants, the IV on its first four regions (no q_chain before its second block), and -- where
-    `public` is not None -- the copies of instance rows 8 * public .. 8 * public + 7 to the digest words of its tail."""
+    scales, the round constants, the state it starts from on its first four regions (no q_chain before its second block),
+    and -- where `public` is not None -- the copies of instance rows 8 * public .. 8 * public + 7 to the digest words of its
+    tail.  `init`: H[0..7] of that state, each a constant pinned through `const` or None for a cell the caller ties (or
+    leaves free) itself; the default is the IV."""
+    init = IV256 if init is None else init
     X = adv[2 * PAIRS]
     regions = BLOCK_REGIONS * blocks + TAIL_REGIONS
     g = np.arange(regions)
@@ -314,7 +317,9 @@ def _assign_segment(fixed, copies, first_region, blocks, public, tb, adv, fcol, 
     copies += [((fcol["const"], int(r) + krow), (X, int(r) + krow)) for r in rb]
     for i in range(4):  # region i of the first block holds a_(i-4) = H[3 - i] and e_(i-4) = H[7 - i]
         head = int(base[i])
-        for row, val in ((arow, IV256[3 - i]), (erow, IV256[7 - i])):
+        for row, val in ((arow, init[3 - i]), (erow, init[7 - i])):
+            if val is None:
+                continue
             fixed["const"][head + row] = val
             copies.append(((fcol["const"], head + row), (X, head + row)))
         if public is not None:

@@ -8,6 +8,9 @@ and which segments' digests are public.  The constraint system is the one of sha
 fixed columns and the copies differ -- and, for a plan with a choice, one selector and two gates (DESIGN.md,
 "Choice-wired message words").  The witness is synthesised on the GPU by `cq_sha256_synthesize_segments_dev`
 (`cq_sha256_synthesize_choices_dev` for a plan with a choice), which runs the chains level by level on the device.
+
+A segment may also start from a state other than the IV (`Segment.init`, DESIGN.md "Wired initial states"): eight sources
+for H[0..7], tied by the same kinds of copies; such a plan is synthesised by `cq_sha256_synthesize_states_dev`.
 """
 from __future__ import annotations
 
@@ -22,7 +25,8 @@ from ._lib import constants
 from ._marshal import FR_MODULUS
 from .context import Context
 
-SOURCE_DIGEST, SOURCE_CHOICE = (constants()["CQ_SHA256_SOURCE_" + s] for s in ("DIGEST", "CHOICE"))
+SOURCE_DIGEST, SOURCE_CHOICE, SOURCE_IV = (constants()["CQ_SHA256_SOURCE_" + s] for s in ("DIGEST", "CHOICE", "IV"))
+IV224 = (0xC1059ED8, 0x367CD507, 0x3070DD17, 0xF70E5939, 0xFFC00B31, 0x68581511, 0x64F98FA7, 0xBEFA4FA4)  # FIPS 180-4, 5.3.2
 
 
 class Private(NamedTuple):
@@ -59,17 +63,23 @@ class Choice(NamedTuple):
 
 
 class Segment(NamedTuple):
-    """One compression chain from the IV: `blocks` blocks and the source of each of its 16 * blocks message words."""
+    """One compression chain: `blocks` blocks and the source of each of its 16 * blocks message words.  `init` is the state
+    its first block starts from: None for the IV, else 8 sources for H[0..7], each a Const, Private, Var or a DigestWord of
+    an earlier segment (no Choice)."""
 
     blocks: int
     sources: tuple
+    init: tuple | None = None
 
 
 class Plan(NamedTuple):
-    """Segments in row order, and the segments whose digests are the instance: rows 8p .. 8p + 7 for public[p]."""
+    """Segments in row order, and the segments whose digests are the instance: rows 8p .. 8p + 7 for public[p].
+    `public_init`: segments (each with an `init`) whose 8 initial words are public too, behind all the digests: instance
+    row 8 * len(public) + 8q + i holds initial word i of segment public_init[q]."""
 
     segments: tuple
     public: tuple
+    public_init: tuple = ()
 
 
 PRIVATE = Private()
@@ -139,13 +149,31 @@ def merkle_path(depth: int, paths: int = 1, leaf_blocks: int | None = None, publ
     return Plan(tuple(segs), tuple(public))
 
 
+def midstate(blocks: int) -> Plan:
+    """Compressing `blocks` private blocks takes the public state H_in to the public state H_out: one segment, every
+    message word and every initial word Private, the digest (instance rows 0 .. 7) and the initial state (rows 8 .. 15)
+    public.  Nothing says the blocks are padded or where a message ends: it is the link of a chain of proofs."""
+    return Plan((Segment(blocks, (PRIVATE,) * (16 * blocks), (PRIVATE,) * 8),), (0,), (0,))
+
+
+def sha224(blocks: int) -> Plan:
+    """SHA-224 of a private message of exactly `blocks` padded blocks: SHA-256's compression from the SHA-224 initial
+    value, pinned as constants.  The public digest has 8 words as in every plan; words 0 .. 6 are the SHA-224 digest, and
+    word 7, which SHA-224 drops, stays public too -- a verifier compares the first seven and may ignore the eighth."""
+    return Plan((Segment(blocks, (PRIVATE,) * (16 * blocks), tuple(Const(v) for v in IV224)),), (0,))
+
+
+def has_init(plan: Plan) -> bool:
+    return any(seg.init is not None for seg in plan.segments)
+
+
 def has_choice(plan: Plan) -> bool:
     return any(isinstance(s, Choice) for seg in plan.segments for s in seg.sources)
 
 
 def shared_counts(plan: Plan):
     """(vars, bits) of the plan: one more than the largest index used, 0 if none is."""
-    srcs = [s for seg in plan.segments for s in seg.sources]
+    srcs = [s for seg in plan.segments for s in tuple(seg.sources) + tuple(seg.init or ())]
     operands = [o for s in srcs if isinstance(s, Choice) for o in (s.zero, s.one)]
     return (max([v.index + 1 for v in srcs + operands if isinstance(v, Var)], default=0),
             max([s.bit + 1 for s in srcs if isinstance(s, Choice)], default=0))
@@ -169,14 +197,28 @@ def _check_plan(plan: Plan):
         raise ValueError("a plan has at least one segment")
 
     def digest_word(j, t, src, what=""):
+        where = t if isinstance(t, str) else f"word {t}"
         if not 0 <= src.segment < j:
-            raise ValueError(f"segment {j}, word {t}: the digest of segment {src.segment}{what} does not come before it")
+            raise ValueError(f"segment {j}, {where}: the digest of segment {src.segment}{what} does not come before it")
         if not 0 <= src.word < 8:
-            raise ValueError(f"segment {j}, word {t}: a digest has words 0 .. 7, not {src.word}")
+            raise ValueError(f"segment {j}, {where}: a digest has words 0 .. 7, not {src.word}")
 
     for j, seg in enumerate(plan.segments):
         if seg.blocks < 1 or len(seg.sources) != 16 * seg.blocks:
             raise ValueError(f"segment {j}: {seg.blocks} blocks and {len(seg.sources)} word sources (16 per block, at least one block)")
+        if seg.init is not None and len(seg.init) != 8:
+            raise ValueError(f"segment {j}: an initial state has 8 words, not {len(seg.init)}")
+        for i, src in enumerate(seg.init or ()):
+            if isinstance(src, DigestWord):
+                digest_word(j, f"initial word {i}", src)
+            elif isinstance(src, Var):
+                if src.index < 0:
+                    raise ValueError(f"segment {j}, initial word {i}: the var index {src.index} is negative")
+            elif isinstance(src, Const):
+                if not 0 <= src.value < 1 << 32:
+                    raise ValueError(f"segment {j}, initial word {i}: the constant {src.value} is no 32-bit word")
+            elif not isinstance(src, Private):
+                raise ValueError(f"segment {j}, initial word {i}: an initial word is Private, Const, DigestWord or Var, not {src!r}")
         for t, src in enumerate(seg.sources):
             if isinstance(src, DigestWord):
                 digest_word(j, t, src)
@@ -200,6 +242,9 @@ def _check_plan(plan: Plan):
                 raise ValueError(f"segment {j}, word {t}: a source is Private, Const, DigestWord, Var or Choice, not {src!r}")
     if not plan.public or len(set(plan.public)) != len(plan.public) or not all(0 <= p < len(plan.segments) for p in plan.public):
         raise ValueError(f"public segments {plan.public!r}: at least one, each an index below {len(plan.segments)}, none twice")
+    pi = tuple(plan.public_init)
+    if len(set(pi)) != len(pi) or not all(isinstance(q, int) and 0 <= q < len(plan.segments) and plan.segments[q].init is not None for q in pi):
+        raise ValueError(f"public_init segments {pi!r}: each an index below {len(plan.segments)} of a segment with an init, none twice")
 
 
 def describe(k: int, plan: Plan, table_bits: int = 12, dense="dense", spread="spread") -> SC.Description:
@@ -213,8 +258,9 @@ def describe(k: int, plan: Plan, table_bits: int = 12, dense="dense", spread="sp
     cs, adv, fcol, inst, cells, word = SC._constraint_system(table_bits, dense, spread, choice)
     n, X, Y = 1 << k, adv[2 * SC.PAIRS], adv[2 * SC.PAIRS + 1]
     rows, usable = rows_for(plan), n - (cs.blinding_factors() + 1)
-    if max(rows, 8 * len(plan.public)) > usable:
-        raise ValueError(f"{len(plan.segments)} segments need {rows} rows and {8 * len(plan.public)} instance rows, 2^{k} has {usable} usable")
+    instance_rows = 8 * (len(plan.public) + len(plan.public_init))
+    if max(rows, instance_rows) > usable:
+        raise ValueError(f"{len(plan.segments)} segments need {rows} rows and {instance_rows} instance rows, 2^{k} has {usable} usable")
     fixed = {name: np.zeros(n, dtype=np.uint64) for name in names}
     copies = []
     firsts = first_regions(plan)
@@ -228,8 +274,19 @@ def describe(k: int, plan: Plan, table_bits: int = 12, dense="dense", spread="sp
 
     # the cells of the choices' digest operands, of every var and of every bit, in (segment, word, zero-then-one) order
     digest_cells, var_cells, bit_cells = [], {}, {}
+    init_digest_cells, init_var_cells, init_public_cells = [], {}, []
     for j, seg in enumerate(plan.segments):
-        SC._assign_segment(fixed, copies, firsts[j], seg.blocks, public.get(j), table_bits, adv, fcol, inst, cells, word)
+        # a constant initial word is pinned where the IV's is, by the same lines; the others are tied behind everything else
+        pinned = None if seg.init is None else [s.value if isinstance(s, Const) else None for s in seg.init]
+        SC._assign_segment(fixed, copies, firsts[j], seg.blocks, public.get(j), table_bits, adv, fcol, inst, cells, word, pinned)
+        for i, src in enumerate(seg.init or ()):  # state word i: region 3 - i % 4 of the first block, A row for i < 4, else E row
+            cell = (X, SC.REGION_ROWS * (firsts[j] + 3 - i % 4) + (arow if i < 4 else erow))
+            if isinstance(src, DigestWord):
+                init_digest_cells.append((tail_cell(src), cell))
+            elif isinstance(src, Var):
+                init_var_cells.setdefault(src.index, []).append(cell)
+            if j in plan.public_init:
+                init_public_cells.append(((inst, 8 * len(plan.public) + 8 * plan.public_init.index(j) + i), cell))
         for t, src in enumerate(seg.sources):
             base = SC.REGION_ROWS * (firsts[j] + SC.BLOCK_REGIONS * (t // 16) + 4 + t % 16)
             w_cell = base + wrow
@@ -254,6 +311,14 @@ def describe(k: int, plan: Plan, table_bits: int = 12, dense="dense", spread="sp
     for shared in (var_cells, bit_cells):
         for i in sorted(shared):
             copies += [(shared[i][0], cell) for cell in shared[i][1:]]
+    # behind all of those, the initial states: every digest-wired state cell to its tail cell in (segment, word) order;
+    # then, vars in ascending index, every state cell of a var to the var's first cell (its first message or operand cell
+    # if it has one, else its first state cell); then the public initial words to their instance rows, in instance order
+    copies += init_digest_cells
+    for i in sorted(init_var_cells):
+        first, rest = (var_cells[i][0], init_var_cells[i]) if i in var_cells else (init_var_cells[i][0], init_var_cells[i][1:])
+        copies += [(first, cell) for cell in rest]
+    copies += sorted(init_public_cells, key=lambda c: c[0][1])
     return SC.Description(cs, adv, fcol, fixed, inst, copies, cells, table_bits, tuple(s.blocks for s in plan.segments), k, names)
 
 
@@ -267,15 +332,16 @@ class Lowered(NamedTuple):
     choices: np.ndarray         # uint32[entries, 4]: {bit, zero, one, 0}, bit a word index, the operands plain sources
     consts: np.ndarray          # uint32: the head of the word buffer
     words_len: int
-    private_counts: list        # Private words per segment
+    private_counts: list        # Private words per segment: its initial words' first, then its message words'
     shared_counts: tuple        # (vars, bits)
+    init_sources: np.ndarray = None  # uint32[8 * segments]: SOURCE_IV, a word index or SOURCE_DIGEST + 8 * segment + word
 
 
 def lower(plan: Plan) -> Lowered:
     """The plan's sources as indices into its word buffer; needs no key and no device."""
-    consts = sorted({s.value for seg in plan.segments for s in seg.sources if isinstance(s, Const)})
+    consts = sorted({s.value for seg in plan.segments for s in tuple(seg.sources) + tuple(seg.init or ()) if isinstance(s, Const)})
     at_const = {v: i for i, v in enumerate(consts)}
-    private_counts = [sum(isinstance(s, Private) for s in seg.sources) for seg in plan.segments]
+    private_counts = [sum(isinstance(s, Private) for s in tuple(seg.init or ()) + tuple(seg.sources)) for seg in plan.segments]
     nvars, nbits = shared_counts(plan)
     first_var = len(consts) + sum(private_counts)
     first_bit = first_var + nvars
@@ -283,8 +349,16 @@ def lower(plan: Plan) -> Lowered:
     def plain(s):
         return first_var + s.index if isinstance(s, Var) else SOURCE_DIGEST + 8 * s.segment + s.word
 
-    sources, choices, nxt = [], [], len(consts)
+    sources, choices, init_sources, nxt = [], [], [], len(consts)
     for seg in plan.segments:
+        for s in seg.init or (None,) * 8:  # a segment's Private initial words come before its Private message words
+            if s is None:
+                init_sources.append(SOURCE_IV)
+            elif isinstance(s, Private):
+                init_sources.append(nxt)
+                nxt += 1
+            else:
+                init_sources.append(at_const[s.value] if isinstance(s, Const) else plain(s))
         for s in seg.sources:
             if isinstance(s, Private):
                 sources.append(nxt)
@@ -297,7 +371,7 @@ def lower(plan: Plan) -> Lowered:
     assert nxt == first_var
     return Lowered(np.array([seg.blocks for seg in plan.segments], dtype=np.uint32), np.array(sources, dtype=np.uint32),
                    np.array(choices, dtype=np.uint32).reshape(-1, 4), np.array(consts, dtype=np.uint32), first_bit + nbits,
-                   private_counts, (nvars, nbits))
+                   private_counts, (nvars, nbits), np.array(init_sources, dtype=np.uint32))
 
 
 def word_buffer(low: Lowered, values, shared=(), bits=()) -> np.ndarray:
@@ -330,7 +404,8 @@ class Sha256SegmentsCircuit:
     the number of segments, their block counts, their wiring and which digests are public.
 
     `values` (synthesize, check, assert_satisfied, prove) is one sequence per segment: the segment's Private words in
-    word order.  Private words are unconstrained -- a private message's padding included, exactly as in Sha256Circuit:
+    word order -- for a segment with an `init`, its Private initial words first.  With `public_init` the instance is the
+    public digests' words, then the public initial states' words.  Private words are unconstrained -- a private message's padding included, exactly as in Sha256Circuit:
     the circuit proves the compression of the words it is given, not that they are a padded message.  Const words and
     DigestWord wirings are constrained.  `shared` holds the plan's Var words by index and `bits` its bits (each 0 or 1);
     a Choice word is constrained to the operand its bit selects."""
@@ -341,9 +416,10 @@ class Sha256SegmentsCircuit:
         self.rows = rows_for(plan)
         self._lowered = low = lower(plan)
         self._seg_blocks, self._sources, self._choices, self._words_len = low.seg_blocks, low.sources, low.choices, low.words_len
+        self._init_sources = low.init_sources if has_init(plan) else None
         self._words = ctx.alloc(4 * max(self._words_len, 1))
         self._digests = ctx.alloc(32 * len(plan.segments))
-        self.digest_words = self.instances = None
+        self.digest_words = self.instances = self.init_words = self.instance_words = None
 
     # ---- witness ----
     def _values(self, values):
@@ -353,10 +429,17 @@ class Sha256SegmentsCircuit:
         """What a front end's methods take -> (values, shared, bits) of the plan."""
         return self._values(values), shared, bits
 
-    def _call(self, arr):
-        """The entry point alone, on the word buffer as it is on the device: the one with choices only for a plan that has some."""
+    def _call(self, arr, words_ptr=None, digests_ptr=None):
+        """The entry point alone, on the word buffer as it is on the device (`words_ptr`, `digests_ptr`: other device arrays
+        than the circuit's own): the one with choices only for a plan that has some, the one with states only for a plan
+        with an `init`."""
         ctx = self.ctx
-        if len(self._choices):
+        if self._init_sources is not None:
+            ctx._chk(ctx.lib.cq_sha256_synthesize_states_dev(ctx.h, self.table_bits, self._seg_blocks.ctypes.data, len(self._seg_blocks),
+                                                             self._sources.ctypes.data, self._choices.ctypes.data if len(self._choices) else None,
+                                                             len(self._choices), self._init_sources.ctypes.data, words_ptr or self._words.ptr,
+                                                             self._words_len, self.n, arr, digests_ptr or self._digests.ptr))
+        elif len(self._choices):
             ctx._chk(ctx.lib.cq_sha256_synthesize_choices_dev(ctx.h, self.table_bits, self._seg_blocks.ctypes.data, len(self._seg_blocks),
                                                               self._sources.ctypes.data, self._choices.ctypes.data, len(self._choices),
                                                               self._words.ptr, self._words_len, self.n, arr, self._digests.ptr))
@@ -366,14 +449,23 @@ class Sha256SegmentsCircuit:
                                                                self._digests.ptr))
 
     def synthesize(self, values, shared=(), bits=()):
-        """Uploads the word buffer, fills the advice columns on the GPU (cq_sha256_synthesize_segments_dev, or
-        cq_sha256_synthesize_choices_dev for a plan with choices) and downloads the digests; returns (device columns,
-        instances)."""
+        """Uploads the word buffer, fills the advice columns on the GPU (cq_sha256_synthesize_segments_dev,
+        cq_sha256_synthesize_choices_dev for a plan with choices, cq_sha256_synthesize_states_dev for one with an initial
+        state) and downloads the digests; returns (device columns, instances)."""
         values, shared, bits = self._inputs(values, shared, bits)
-        self._words.upload(word_buffer(self._lowered, values, shared, bits))
+        words = word_buffer(self._lowered, values, shared, bits)
+        self._words.upload(words)
+        return self._finish(words)
+
+    def _finish(self, words):
+        """The entry point on the word buffer as it is on the device (`words`: its host copy), then the instances."""
         self._call((C.c_void_p * SC.ADVICE_COLUMNS)(*[c.ptr for c in self.cols]))
         self.digest_words = self._digests.download((len(self._seg_blocks), 8), np.uint32).tolist()
-        self.instances = [_words_to_mont([x for p in self.plan.public for x in self.digest_words[p]])]
+        flat = [x for d in self.digest_words for x in d]
+        self.init_words = [[int(flat[s - SOURCE_DIGEST] if s & SOURCE_DIGEST else words[s]) for s in self._lowered.init_sources[8 * q: 8 * q + 8]]
+                           for q in self.plan.public_init]
+        self.instance_words = [x for p in self.plan.public for x in self.digest_words[p]] + [x for ws in self.init_words for x in ws]
+        self.instances = [_words_to_mont(self.instance_words)]
         return self.cols, self.instances
 
     @property
@@ -430,6 +522,57 @@ class Sha256dCircuit(Sha256SegmentsCircuit):
 
     def _result(self):
         return self.digests[0]
+
+
+class Sha256MidstateCircuit(Sha256SegmentsCircuit):
+    """`blocks` private 64-byte blocks take the public chaining value H_in to the public chaining value H_out (the plan
+    `midstate`): instance rows 0 .. 7 are H_out, rows 8 .. 15 H_in.  The methods take (h_in, data): 8 words and exactly
+    64 * blocks bytes; nothing is padded.  A proof says nothing about where H_in comes from: a verifier links it to the
+    IV or to the H_out of another proof (sha256_stream.link)."""
+
+    def __init__(self, ctx: Context, k: int, blocks: int, **kw):
+        super().__init__(ctx, k, midstate(blocks), **kw)
+
+    def _values(self, item):
+        h_in, data = item
+        blocks = self.plan.segments[0].blocks
+        if len(h_in) != 8 or len(data) != 64 * blocks:
+            raise ValueError(f"a state of 8 words and {64 * blocks} bytes of data")
+        return [[int(x) for x in h_in] + list(struct.unpack(f">{16 * blocks}I", bytes(data)))]
+
+    def synthesize_dev(self, words_ptr: int, digests_ptr: int, h_in):
+        """The synthesis on a word buffer that is on the device already -- 8 state words, then the 16 * blocks message words
+        -- with the digest stored to `digests_ptr` (8 words): a chain of syntheses hands H_out on as the next H_in without a
+        copy.  `h_in` is the host's copy of the state, for the instance."""
+        ctx = self.ctx
+        self._call((C.c_void_p * SC.ADVICE_COLUMNS)(*[c.ptr for c in self.cols]), words_ptr, digests_ptr)
+        out = np.empty(8, dtype=np.uint32)
+        ctx._chk(ctx.lib.cq_dev_download(ctx.h, out.ctypes.data, digests_ptr, out.nbytes))
+        self.digest_words, self.init_words = [out.tolist()], [[int(x) for x in h_in]]
+        self.instance_words = self.digest_words[0] + self.init_words[0]
+        self.instances = [_words_to_mont(self.instance_words)]
+        return self.cols, self.instances
+
+    @property
+    def h_out(self):
+        return self.digest_words[0]
+
+    def _result(self):
+        return self.instance_words
+
+
+class Sha224Circuit(Sha256SegmentsCircuit):
+    """SHA-224 of a message of exactly `blocks` padded blocks (the plan `sha224`): the methods take the message and pad it
+    here, as Sha256BatchCircuit does.  All 8 words of the final state are public; the SHA-224 digest is the first 28 bytes."""
+
+    def __init__(self, ctx: Context, k: int, blocks: int, **kw):
+        super().__init__(ctx, k, sha224(blocks), **kw)
+
+    def _values(self, message):
+        return [SC.pad(message, self.plan.segments[0].blocks)]
+
+    def _result(self):
+        return self.digests[0][:28]
 
 
 class Sha256MerkleCircuit(Sha256SegmentsCircuit):

@@ -21,7 +21,16 @@ With --varlen-k K (0 = off): `Sha256VarCircuit` over segments of 1, 2, 4, 8 bloc
 messages of mixed lengths (raw bytes in, padded on the device), next to `Sha256BatchCircuit` at the same block counts, whose
 messages fill their segments: the wrapper's synthesize, the entry point + synchronise, check and proof of both.
 
-    python tools/sha256_perf.py [--sizes 14,18] [--segments-k 18] [--path-k 18] [--varlen-k 18] [--sweep 1,2,4,...] [--reps 15] [--warmup 3]
+With --states-k K (0 = off): as many one-block segments as 2^K rows hold, no key, words on the device: the entry point + a
+synchronise through cq_sha256_synthesize_segments_dev, through cq_sha256_synthesize_states_dev with init_sources = NULL,
+with all-IV initial sources, and with every segment's state eight Private words of the buffer.
+
+With --stream-k K (0 = off): a 1 MiB message through `Sha256Stream` with bodies and a tail of as many blocks as 2^K rows
+hold: the whole `prove` (one median over --reps runs would take minutes: 3 runs), per proof and in total, next to
+`Sha256Circuit`'s proof at the same K.
+
+    python tools/sha256_perf.py [--sizes 14,18] [--segments-k 18] [--path-k 18] [--varlen-k 18] [--states-k 18] [--stream-k 18]
+                                [--sweep 1,2,4,...] [--reps 15] [--warmup 3]
 """
 import argparse
 import json
@@ -217,12 +226,78 @@ def varlen_legs(ctx, k, reps, warmup):
         print(json.dumps(row), flush=True)
 
 
+def states_legs(ctx, k, reps, warmup):
+    import ctypes as C
+
+    import numpy as np
+
+    from sha2_on_cq_halo2_amd import sha256_circuit as SC
+    from sha2_on_cq_halo2_amd import sha256_segments as SS
+
+    n, count = 1 << k, SC.usable_rows(k) // SC.rows_for(1)
+    cols = [ctx.alloc(32 * n) for _ in range(SC.ADVICE_COLUMNS)]
+    arr = (C.c_void_p * len(cols))(*[b.ptr for b in cols])
+    words = np.arange(24 * count, dtype=np.uint32) * np.uint32(0x9E3779B1)  # per segment 8 state words, then 16 message words
+    words_dev, digests_dev = ctx.to_device(words), ctx.alloc(32 * count)
+    blocks = np.ones(count, dtype=np.uint32)
+    sources = (24 * np.arange(count, dtype=np.uint32)[:, None] + 8 + np.arange(16, dtype=np.uint32)).reshape(-1).copy()
+    iv = np.full(8 * count, SS.SOURCE_IV, dtype=np.uint32)
+    wired = (24 * np.arange(count, dtype=np.uint32)[:, None] + np.arange(8, dtype=np.uint32)).reshape(-1).copy()
+
+    def old():
+        ctx._chk(ctx.lib.cq_sha256_synthesize_segments_dev(ctx.h, 12, blocks.ctypes.data, count, sources.ctypes.data, words_dev.ptr, len(words), n, arr,
+                                                           digests_dev.ptr))
+        ctx.sync()
+
+    def states(init):
+        def call():
+            ctx._chk(ctx.lib.cq_sha256_synthesize_states_dev(ctx.h, 12, blocks.ctypes.data, count, sources.ctypes.data, None, 0,
+                                                             None if init is None else init.ctypes.data, words_dev.ptr, len(words), n, arr,
+                                                             digests_dev.ptr))
+            ctx.sync()
+        return call
+
+    row = {"states": "entry point + sync, one-block segments, no key", "k": k, "segments": count}
+    timed(row, (("segments_dev_ms", old), ("states_dev_null_ms", states(None)), ("states_dev_all_iv_ms", states(iv)),
+                ("states_dev_private_states_ms", states(wired)), ("segments_dev_again_ms", old)), reps, warmup)
+    print(json.dumps(row), flush=True)
+    for b in cols + [words_dev, digests_dev]:
+        b.close()
+
+
+def stream_legs(ctx, k, reps, warmup):
+    import hashlib
+
+    from sha2_on_cq_halo2_amd import sha256_circuit as SC
+    from sha2_on_cq_halo2_amd.api import Sha256Circuit, Sha256Stream, link
+
+    blocks = SC.max_blocks(k)
+    t0 = time.perf_counter()
+    s = Sha256Stream(ctx, k, blocks, k, blocks)
+    keygen_s = time.perf_counter() - t0
+    msg = bytes((i * 7 + i // 251) % 256 for i in range(1 << 20))
+    out = s.prove(msg)
+    assert link([inst for _, inst in out], blocks, blocks) == (hashlib.sha256(msg).digest(), len(msg))
+    row = {"circuit": "Sha256Stream", "k": k, "body_blocks": blocks, "tail_max_blocks": blocks, "message_bytes": len(msg), "proofs": len(out),
+           "proof_bytes": [s.body.pk.proof_size, s.tail.pk.proof_size], "keygen_s": round(keygen_s, 2)}
+    row["prove_total_ms"], row["prove_total_ms_range"] = median_ms(lambda: s.prove(msg), 3, 1)
+    row["per_proof_ms"] = round(row["prove_total_ms"] / len(out), 3)
+    s.close()
+    c = Sha256Circuit(ctx, k)
+    one = bytes(i % 251 for i in range(64 * c.blocks - 9))
+    row["sha256circuit_prove_ms"], row["sha256circuit_prove_ms_range"] = median_ms(lambda: c.prove(one), reps, warmup)
+    c.close()
+    print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="14,18")
     ap.add_argument("--segments-k", type=int, default=0)
     ap.add_argument("--path-k", type=int, default=0)
     ap.add_argument("--varlen-k", type=int, default=0)
+    ap.add_argument("--states-k", type=int, default=0)
+    ap.add_argument("--stream-k", type=int, default=0)
     ap.add_argument("--sweep", default="1,2,4,8,16,32,64,128,256,512")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
@@ -267,6 +342,10 @@ def main():
         path_legs(ctx, args.path_k, args.reps, args.warmup)
     if args.varlen_k:
         varlen_legs(ctx, args.varlen_k, args.reps, args.warmup)
+    if args.states_k:
+        states_legs(ctx, args.states_k, args.reps, args.warmup)
+    if args.stream_k:
+        stream_legs(ctx, args.stream_k, args.reps, args.warmup)
     ctx.close()
 
 
