@@ -926,6 +926,27 @@ int cq_sha256_synthesize_states_dev(cq_ctx* ctx, uint32_t table_bits, const uint
                                     const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* init_sources,
                                     const uint32_t* words_dev, size_t words_len, size_t n, uint64_t* const* cols_dev,
                                     uint32_t* digests_dev);
+/* The same with message words that are the XOR of two plain sources (DESIGN.md "XOR-wired message words").  `xors` is a
+ * host array of `n_xors` units of CQ_SHA256_XOR_WORDS words {x, y, 0, 0}: x and y are plain sources -- a word index or a
+ * digest reference to a segment that exists; no unit's result and no choice.  `digests_dev` holds 8 * segments + n_xors
+ * words: word 8 * segments + u receives x ^ y of unit u, and a message word reads it through the source value
+ * CQ_SHA256_SOURCE_DIGEST + 8 * segments + u (a message word's own source only: not an operand of a choice, not an initial
+ * word).  Any number of message words may read one unit, none included.  Unit u takes CQ_SHA256_XOR_REGIONS regions
+ * directly behind the last segment's tail, regions R + 2u and R + 2u + 1 (R: the segments' regions): the first holds
+ * e = x and nothing else, the second e = y and W = x ^ y, with the Ch cells of two consecutive e words that the expansion
+ * lays out for it.  A unit is ready at level 0 if it reads no digest, else one level above the highest level it reads; a
+ * segment that reads a unit runs at or above the unit's level.  Per level one launch computes that level's units before
+ * the level's chains, and one more behind the last level those over its digests; then the expansion runs once over all
+ * regions.  CQ_ERR_ARG, besides the cases above and again before anything is queued, naming the unit (and segment and
+ * word for a reader): an operand index outside `words_dev`, a digest operand of a segment that does not exist, a reader
+ * in segment j of a unit with a digest operand of segment >= j, a unit index >= n_xors, an area that does not fit n.
+ * n_xors = 0 (`xors` may be NULL) is cq_sha256_synthesize_states_dev exactly. */
+#define CQ_SHA256_XOR_WORDS 4
+#define CQ_SHA256_XOR_REGIONS 2
+int cq_sha256_synthesize_xors_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
+                                  const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* init_sources,
+                                  const uint32_t* xors, size_t n_xors, const uint32_t* words_dev, size_t words_len, size_t n,
+                                  uint64_t* const* cols_dev, uint32_t* digests_dev);
 /* Messages of variable length with constrained padding (DESIGN.md "Variable-length messages"): segment j is a chain of
  * seg_max_blocks[j] blocks that holds message j -- msg_lens[j] raw bytes at msg_bytes_dev + msg_offsets[j], a device buffer
  * of msg_bytes_len bytes (no alignment is asked of it) -- padded on the device: 0x80, zeros, the bit length in the last two

@@ -17,7 +17,7 @@ from .context import Context, DevBuf, rccl_unique_id  # noqa: F401
 from .params import EvaluationDomain, G2Srs, ParamsKZG, StaticTable, TableConfig  # noqa: F401
 from .proving_key import ProvingKey, WitnessError, WitnessFailure, _lower_plonk  # noqa: F401
 from .sha256_circuit import Sha256Circuit  # noqa: F401  (last: its constructor reaches sha_circuit, which imports this module)
-from .sha256_segments import (Sha224Circuit, Sha256BatchCircuit, Sha256dCircuit, Sha256MerkleCircuit, Sha256MerklePathCircuit,  # noqa: F401
-                              Sha256MidstateCircuit, Sha256SegmentsCircuit)
+from .sha256_segments import (HmacSha256Circuit, Sha224Circuit, Sha256BatchCircuit, Sha256dCircuit, Sha256MerkleCircuit,  # noqa: F401
+                              Sha256MerklePathCircuit, Sha256MidstateCircuit, Sha256SegmentsCircuit)
 from .sha256_varlen import Sha256VarCircuit  # noqa: F401
 from .sha256_stream import Sha256Stream, link  # noqa: F401

@@ -13,6 +13,10 @@
 // chain kernel reads, and a kernel behind the expansion writes the flags, lengths and selection cells the padding gates read.
 // Wired states (cq_sha256_synthesize_states_dev, cq_sha256_synthesize_varlen_from_dev): a segment's chain may start from
 // eight gathered words instead of the IV; the chain kernel's INIT instantiations fetch them as they fetch a message word.
+// XOR units (cq_sha256_synthesize_xors_dev): a message word may be the XOR of two plain sources.  A small kernel per level
+// computes the units that are ready, stores each result behind the segments' digests -- where a message word's fetch finds
+// it like a digest word -- and leaves two regions per unit behind the last segment for the same expansion kernel.
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <utility>
@@ -349,14 +353,39 @@ __global__ __launch_bounds__(64) void sha256_choice_fill_kernel(const Sha256Choi
   st(cell + CQ_SHA256_CHOICE_ROW_BIT, bit ? Fr::from_u64(bit) : Fr::zero());
 }
 
+// One XOR unit as the device sees it: its two operands (plain sources), the word of `digests` that takes the result,
+// and -- both filled in by the host -- the first of the unit's two regions.
+struct Sha256XorUnit {
+  uint32_t x, y, result, region;
+};
+
+// One thread per unit of one level, before the level's chains on the same stream: both operands through sha256_load (the
+// digests they may read are earlier levels'), the result word, and the unit's two regions: e = x alone, then e = y with
+// W = x ^ y under SHA_RG_F3, whose CHP_EVEN word the expansion computes as this region's e xor the one before.  `digests`
+// is read and written, hence neither const nor restrict.  The host has checked every operand against both arrays'
+// lengths and that region + 1 lies below n / CQ_SHA256_REGION_ROWS.
+__global__ __launch_bounds__(64) void sha256_xor_kernel(const Sha256XorUnit* __restrict__ units, uint32_t nunits, const uint32_t* words,
+                                                        uint32_t* digests, Sha256Region* __restrict__ regions) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nunits) return;
+  const uint4 u = *reinterpret_cast<const uint4*>(units + i);
+  const uint32_t x = sha256_load(u.x, words, digests), y = sha256_load(u.y, words, digests);
+  digests[u.z] = x ^ y;
+  sha256_put(regions + u.w, 0, x, 0, 0);
+  sha256_put(regions + u.w + 1, 0, y, x ^ y, SHA_RG_F3);
+}
+
 // Validates the description, then queues the tables' upload, one chain launch per level, the expansion and -- with
 // choices -- the fill of their cells.  Nothing here waits for the stream; the staging is pinned, and only the previous
 // call's copy out of it is waited for.  n_choices = 0 is the description without choices: a source at or above
 // CQ_SHA256_SOURCE_CHOICE is then a word index like any other.  init_sources = nullptr is the description whose segments
 // all start from the IV; otherwise it holds 8 entries per segment, CQ_SHA256_SOURCE_IV or a plain source.
+// n_xors = 0 is the description without XOR units: a digest reference at or above 8 * segments then names a segment that
+// does not exist.  Otherwise such a reference in a message word's own source names unit (index - 8 * segments) of `xors`,
+// whose result the level's XOR launch stores at that word of `digests_dev` before the chains that read it run.
 int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* sources,
-                               const uint32_t* choices, size_t n_choices, const uint32_t* init_sources, const uint32_t* words_dev,
-                               size_t words_len, uint32_t n, const Sha256Cols& cols, uint32_t* digests_dev) {
+                               const uint32_t* choices, size_t n_choices, const uint32_t* init_sources, const uint32_t* xors, size_t n_xors,
+                               const uint32_t* words_dev, size_t words_len, uint32_t n, const Sha256Cols& cols, uint32_t* digests_dev) {
   const uint64_t max_regions = n / CQ_SHA256_REGION_ROWS;
   uint64_t regions = 0, blocks = 0;
   for (size_t j = 0; j < segments; j++) {
@@ -365,6 +394,20 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
     regions += (uint64_t)seg_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS;
     if (regions > max_regions) return c->fail(CQ_ERR_ARG, "sha256: the segments up to segment " + std::to_string(j) + " do not fit the rows");
   }
+  if (regions + CQ_SHA256_XOR_REGIONS * (uint64_t)n_xors > max_regions)
+    return c->fail(CQ_ERR_ARG, "sha256: the area of " + std::to_string(n_xors) + " xor units behind the segments does not fit the rows");
+  for (size_t u = 0; u < n_xors; u++)  // the operands: plain sources, a digest's of a segment that exists (no unit's result)
+    for (uint32_t o = 0; o < 2; o++) {
+      const uint32_t s = xors[CQ_SHA256_XOR_WORDS * u + o];
+      std::string bad;
+      if (s & CQ_SHA256_SOURCE_DIGEST) {
+        const size_t ref = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3;
+        if (ref >= segments) bad = " reads the digest of segment " + std::to_string(ref) + " of " + std::to_string(segments);
+      } else if (s >= words_len) {
+        bad = " reads word " + std::to_string(s) + " of a buffer of " + std::to_string(words_len);
+      }
+      if (!bad.empty()) return c->fail(CQ_ERR_ARG, "sha256: xor unit " + std::to_string(u) + (o ? ", operand y" : ", operand x") + bad);
+    }
   std::vector<uint32_t> level(segments, 0), level_count;
   std::vector<uint32_t> choice_region(n_choices, UINT32_MAX);  // the region of the word that refers to the entry, once one does
   uint32_t seg_region = 0;
@@ -410,6 +453,13 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
         for (uint32_t o = 1; o <= 2 && bad.empty(); o++)
           if (!(bad = plain(entry[o])).empty()) bad = std::string(o == 1 ? "'s zero operand" : "'s one operand") + bad;
         if (!bad.empty()) bad = ", choice " + std::to_string(e) + bad;
+      } else if (n_xors && (s & CQ_SHA256_SOURCE_DIGEST) && (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >= 8 * segments) {
+        // a unit's result: the unit's digest operands come before this segment, and the segment runs at or above the unit's level
+        const size_t u = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) - 8 * segments;
+        if (u >= n_xors) return c->fail(CQ_ERR_ARG, where() + " reads xor unit " + std::to_string(u) + " of " + std::to_string(n_xors));
+        for (uint32_t o = 0; o < 2 && bad.empty(); o++)
+          if (!(bad = plain(xors[CQ_SHA256_XOR_WORDS * u + o])).empty())
+            bad = ", xor unit " + std::to_string(u) + (o ? ", operand y" : ", operand x") + bad;
       } else {
         bad = plain(s);
       }
@@ -424,17 +474,32 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
   }
   std::vector<uint32_t> level_first(level_count.size(), 0);
   for (size_t l = 1; l < level_count.size(); l++) level_first[l] = level_first[l - 1] + level_count[l - 1];
+  // a unit is ready at level 0 if it reads no digest, else one level above the highest level it reads: at most one level
+  // behind the last chain launch.  Every segment's level is final by now, whether or not a word reads the unit.
+  std::vector<uint32_t> xor_level(n_xors, 0), xor_count(n_xors ? level_count.size() + 1 : 0, 0);
+  for (size_t u = 0; u < n_xors; u++) {
+    for (uint32_t o = 0; o < 2; o++) {
+      const uint32_t s = xors[CQ_SHA256_XOR_WORDS * u + o];
+      if (s & CQ_SHA256_SOURCE_DIGEST) xor_level[u] = std::max(xor_level[u], level[(s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3] + 1);
+    }
+    xor_count[xor_level[u]]++;
+  }
+  std::vector<uint32_t> xor_first(xor_count.size(), 0);
+  for (size_t l = 1; l < xor_count.size(); l++) xor_first[l] = xor_first[l - 1] + xor_count[l - 1];
 
-  static_assert(sizeof(Sha256Region) == 16 && sizeof(Sha256Lane) == 16, "four words each");
+  static_assert(sizeof(Sha256Region) == 16 && sizeof(Sha256Lane) == 16 && sizeof(Sha256XorUnit) == 16, "four words each");
+  static_assert(sizeof(Sha256XorUnit) == CQ_SHA256_XOR_WORDS * sizeof(uint32_t), "an entry of the xor table as the header states it");
   static_assert(sizeof(Sha256Choice) == CQ_SHA256_CHOICE_WORDS * sizeof(uint32_t), "an entry of the choice table as the header states it");
-  // lanes, sources, choices, initial sources: each a multiple of 16 bytes, so the choice entries and a segment's eight
-  // initial sources are aligned for their 16-byte loads
+  // lanes, sources, choices, initial sources, xor units: each a multiple of 16 bytes, so the choice entries, a segment's
+  // eight initial sources and the units are aligned for their 16-byte loads
   const size_t lanes_bytes = segments * sizeof(Sha256Lane), sources_bytes = 16 * blocks * sizeof(uint32_t);
   const size_t choices_bytes = n_choices * sizeof(Sha256Choice), init_bytes = init_sources ? 8 * segments * sizeof(uint32_t) : 0;
-  const size_t tables_bytes = lanes_bytes + sources_bytes + choices_bytes + init_bytes;
+  const size_t xors_bytes = n_xors * sizeof(Sha256XorUnit);
+  const size_t tables_bytes = lanes_bytes + sources_bytes + choices_bytes + init_bytes + xors_bytes;
+  const uint64_t all_regions = regions + CQ_SHA256_XOR_REGIONS * (uint64_t)n_xors;  // the units' regions lie behind the last tail
   void *pin, *dev_regions, *dev_tables;
   CQ_TRY(c->ensure_pinned_sha(tables_bytes, &pin));
-  CQ_TRY(c->ensure_scratch(Scratch::EntryA, regions * sizeof(Sha256Region), &dev_regions));
+  CQ_TRY(c->ensure_scratch(Scratch::EntryA, all_regions * sizeof(Sha256Region), &dev_regions));
   CQ_TRY(c->ensure_scratch(Scratch::EntryB, tables_bytes, &dev_tables));
   if (!c->sha_staged) CQ_HIP(c, hipEventCreateWithFlags(&c->sha_staged, hipEventDisableTiming));
   CQ_HIP(c, hipEventSynchronize(c->sha_staged));  // the previous call's copy out of `pin` (at once if there was none)
@@ -451,18 +516,32 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
   for (size_t e = 0; e < n_choices; e++)
     staged[e] = {choices[CQ_SHA256_CHOICE_WORDS * e], choices[CQ_SHA256_CHOICE_WORDS * e + 1], choices[CQ_SHA256_CHOICE_WORDS * e + 2], choice_region[e]};
   if (init_sources) memcpy((char*)pin + lanes_bytes + sources_bytes + choices_bytes, init_sources, init_bytes);
+  Sha256XorUnit* units = (Sha256XorUnit*)((char*)pin + lanes_bytes + sources_bytes + choices_bytes + init_bytes);
+  std::vector<uint32_t> next_unit = xor_first;
+  for (size_t u = 0; u < n_xors; u++)  // units in level order; unit u keeps its result word and its regions whatever its level
+    units[next_unit[xor_level[u]]++] = {xors[CQ_SHA256_XOR_WORDS * u], xors[CQ_SHA256_XOR_WORDS * u + 1], (uint32_t)(8 * segments + u),
+                                        (uint32_t)(regions + CQ_SHA256_XOR_REGIONS * u)};
   CQ_HIP(c, hipMemcpyAsync(dev_tables, pin, tables_bytes, hipMemcpyHostToDevice, c->stream));
   CQ_HIP(c, hipEventRecord(c->sha_staged, c->stream));
   const Sha256Lane* dev_lanes = (const Sha256Lane*)dev_tables;
   const uint32_t* dev_sources = (const uint32_t*)((const char*)dev_tables + lanes_bytes);
   const Sha256Choice* dev_choices = (const Sha256Choice*)((const char*)dev_sources + sources_bytes);
   const uint32_t* dev_init = (const uint32_t*)((const char*)dev_choices + choices_bytes);
+  const Sha256XorUnit* dev_units = (const Sha256XorUnit*)((const char*)dev_init + init_bytes);
+  auto launch_xors = [&](size_t l) {  // the units that are ready at level l, if there are any
+    if (l >= xor_count.size() || !xor_count[l]) return true;
+    sha256_xor_kernel<<<(xor_count[l] + 63) / 64, 64, 0, c->stream>>>(dev_units + xor_first[l], xor_count[l], words_dev, digests_dev,
+                                                                     (Sha256Region*)dev_regions);
+    return hipGetLastError() == hipSuccess;
+  };
   for (size_t l = 0; l < level_count.size(); l++) {
+    if (!launch_xors(l)) return c->fail(CQ_ERR_HIP, "sha256_xor launch failed");
     sha256_launch_chain(c, n_choices != 0, init_sources != nullptr, (level_count[l] + 63) / 64, dev_lanes + level_first[l], level_count[l],
                         dev_sources, dev_choices, words_dev, digests_dev, (Sha256Region*)dev_regions, dev_init, words_dev);
     if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_chain launch failed");
   }
-  sha256_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha256Region*)dev_regions, (uint32_t)regions, n, table_bits, cols);
+  if (!launch_xors(level_count.size())) return c->fail(CQ_ERR_HIP, "sha256_xor launch failed");  // units over the last level's digests
+  sha256_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha256Region*)dev_regions, (uint32_t)all_regions, n, table_bits, cols);
   if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha256_expand launch failed");
   if (n_choices) {
     sha256_choice_fill_kernel<<<((uint32_t)n_choices + 63) / 64, 64, 0, c->stream>>>(dev_choices, (uint32_t)n_choices, words_dev, digests_dev,
@@ -705,16 +784,17 @@ int cq_sha256_synthesize_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* msg
   return sha256_synthesize(c, table_bits, msg_words, blocks, (uint32_t)n, sc, digest);
 }
 
-// the three entry points below: the argument checks that need no description, then the host function
+// the four entry points below: the argument checks that need no description, then the host function
 static int sha256_segments_entry(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* sources,
-                                 const uint32_t* choices, size_t n_choices, const uint32_t* init_sources, const uint32_t* words_dev,
-                                 size_t words_len, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
+                                 const uint32_t* choices, size_t n_choices, const uint32_t* init_sources, const uint32_t* xors, size_t n_xors,
+                                 const uint32_t* words_dev, size_t words_len, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
   if (!c) return CQ_ERR_ARG;
   if (!seg_blocks || !sources || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull || (!words_dev && words_len) ||
       words_len > CQ_SHA256_SOURCE_DIGEST)
     return c->fail(CQ_ERR_ARG, "sha256: null array, no segment, or a length out of range");
   if (n_choices && (!choices || words_len > CQ_SHA256_SOURCE_CHOICE || n_choices > n))
     return c->fail(CQ_ERR_ARG, "sha256: null choice table, more choices than rows, or a word buffer that reaches the choice flag");
+  if (n_xors && (!xors || n_xors > n)) return c->fail(CQ_ERR_ARG, "sha256: null xor table, or more xor units than rows");
   if (table_bits < CQ_SHA256_MIN_TABLE_BITS || table_bits > CQ_SHA256_MAX_TABLE_BITS)
     return c->fail(CQ_ERR_ARG, "sha256: table_bits outside the range the pieces fit");
   CQ_HIP(c, hipSetDevice(c->device));
@@ -723,29 +803,38 @@ static int sha256_segments_entry(cq_ctx* c, uint32_t table_bits, const uint32_t*
     if (!cols_dev[i]) return c->fail(CQ_ERR_ARG, "sha256: null column");
     sc.p[i] = (Fr*)cols_dev[i];
   }
-  return sha256_synthesize_segments(c, table_bits, seg_blocks, segments, sources, choices, n_choices, init_sources, words_dev, words_len,
-                                    (uint32_t)n, sc, digests_dev);
+  return sha256_synthesize_segments(c, table_bits, seg_blocks, segments, sources, choices, n_choices, init_sources, xors, n_xors, words_dev,
+                                    words_len, (uint32_t)n, sc, digests_dev);
 }
 
 int cq_sha256_synthesize_segments_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
                                       const uint32_t* sources, const uint32_t* words_dev, size_t words_len, size_t n,
                                       uint64_t* const* cols_dev, uint32_t* digests_dev) {
-  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, nullptr, 0, nullptr, words_dev, words_len, n, cols_dev, digests_dev);
+  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, nullptr, 0, nullptr, nullptr, 0, words_dev, words_len, n, cols_dev,
+                               digests_dev);
 }
 
 int cq_sha256_synthesize_choices_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
                                      const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* words_dev,
                                      size_t words_len, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
-  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, choices, n_choices, nullptr, words_dev, words_len, n, cols_dev,
-                               digests_dev);
+  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, choices, n_choices, nullptr, nullptr, 0, words_dev, words_len, n,
+                               cols_dev, digests_dev);
 }
 
 int cq_sha256_synthesize_states_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
                                     const uint32_t* sources, const uint32_t* choices, size_t n_choices, const uint32_t* init_sources,
                                     const uint32_t* words_dev, size_t words_len, size_t n, uint64_t* const* cols_dev,
                                     uint32_t* digests_dev) {
-  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, choices, n_choices, init_sources, words_dev, words_len, n, cols_dev,
-                               digests_dev);
+  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, choices, n_choices, init_sources, nullptr, 0, words_dev, words_len, n,
+                               cols_dev, digests_dev);
+}
+
+int cq_sha256_synthesize_xors_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* sources,
+                                  const uint32_t* choices, size_t n_choices, const uint32_t* init_sources, const uint32_t* xors,
+                                  size_t n_xors, const uint32_t* words_dev, size_t words_len, size_t n, uint64_t* const* cols_dev,
+                                  uint32_t* digests_dev) {
+  return sha256_segments_entry(c, table_bits, seg_blocks, segments, sources, choices, n_choices, init_sources, xors, n_xors, words_dev, words_len,
+                               n, cols_dev, digests_dev);
 }
 
 // both entry points below: the argument checks that need no message, then the host function

@@ -58,6 +58,12 @@ GATES_VARLEN = GATES + ("var_m_bool", "var_b_bool", "var_c0_bool", "var_c1_bool"
                         "var_pad_zero", "var_length_word", "var_last_final", "var_carry", "var_final", "var_select")
 FIXED_VARLEN = FIXED + ("q_vpad", "q_vlength", "q_vlast", "q_vcarry", "q_vfinal", "q_vsum")
 VAR = {name[len("CQ_SHA256_VAR_"):]: v for name, v in _CQ.items() if name.startswith("CQ_SHA256_VAR_")}
+# the XOR variant (plans with an Xor word, sha256_segments.py): one selector behind `const`, one gate behind the others; a
+# unit is XOR_REGIONS regions behind the last segment, and the gate reads cells the layout has already (DESIGN.md,
+# "XOR-wired message words")
+GATES_XOR = GATES + ("xor_word",)
+FIXED_XOR = FIXED + ("q_xor",)
+XOR_REGIONS, XOR_WORDS = _CQ["CQ_SHA256_XOR_REGIONS"], _CQ["CQ_SHA256_XOR_WORDS"]
 
 
 class Cell(NamedTuple):
@@ -131,17 +137,20 @@ def describe(k: int, blocks: int, table_bits: int = 12, dense="dense", spread="s
     return _assign_fixed(k, blocks, table_bits, cs, adv, fcol, inst, cells, word)
 
 
-def _constraint_system(tb: int, dense, spread, choice: bool = False, varlen: bool = False):
+def _constraint_system(tb: int, dense, spread, choice: bool = False, varlen: bool = False, xor: bool = False):
     """`choice`: the variant for plans with choice-wired message words -- the fixed column `q_choice`, equality on column
     Y and the gates `choice` and `choice_bit`; everything else is the plain system, built by the same lines.  `varlen`:
     the variant for messages of variable length -- the selectors of FIXED_VARLEN, equality on Y and the gates of
-    GATES_VARLEN; the two variants do not combine."""
+    GATES_VARLEN.  `xor`: the variant for plans with XOR-wired message words -- the fixed column `q_xor` and the gate
+    `xor_word`.  The variants do not combine."""
     if choice and varlen:
         raise ValueError("a variable-length segment does not combine with choice-wired words")
+    if xor and (choice or varlen):
+        raise ValueError("XOR-wired words do not combine with choice-wired words or a variable-length segment")
     cells = layout()
     cs = GP.ConstraintSystem()
     adv = [cs.advice_column() for _ in range(ADVICE_COLUMNS)]
-    fcol = {name: cs.fixed_column() for name in (FIXED_CHOICE if choice else FIXED_VARLEN if varlen else FIXED)}
+    fcol = {name: cs.fixed_column() for name in (FIXED_CHOICE if choice else FIXED_VARLEN if varlen else FIXED_XOR if xor else FIXED)}
     inst = cs.instance_column()
     X, Y = adv[2 * PAIRS], adv[2 * PAIRS + 1]
     for c in (X, fcol["const"], inst) + ((Y,) if choice or varlen else ()):
@@ -218,7 +227,9 @@ def _constraint_system(tb: int, dense, spread, choice: bool = False, varlen: boo
         polys["choice_bit"] = q_choice * (d * (GP.Expression.constant(1) - d))
     if varlen:
         _varlen_gates(cs, polys, cells, adv, fcol, w)
-    gates = GATES_CHOICE if choice else GATES_VARLEN if varlen else GATES
+    if xor:  # W = e_r ^ e_(r-1): under q_f3 `chp_even_odd` makes the CHP_EVEN chunks the even bits of spread(e_r) + spread(e_(r-1))
+        polys["xor_word"] = cs.query_fixed(fcol["q_xor"]) * (w("W") - from_chunks("CHP_EVEN"))
+    gates = GATES_CHOICE if choice else GATES_VARLEN if varlen else GATES_XOR if xor else GATES
     assert tuple(polys) != () and set(polys) == set(gates)
     for name in gates:
         cs.create_gate(name, [polys[name]])
@@ -227,6 +238,8 @@ def _constraint_system(tb: int, dense, spread, choice: bool = False, varlen: boo
         cs.lookup_static(f"pair{j}", [(adv[2 * j], dense), (adv[2 * j + 1], spread)])
     for j in range(PAIRS):
         cs.lookup_static(f"length{j}", [(cs.query_advice(adv[2 * j]) * cs.query_fixed(fcol[f"scale{j}"]), dense)])
+    if xor:  # the gate adds three dense cells of row 6 and one fixed column to the queries, nothing to the blinding rows or the degree
+        assert (cs.blinding_factors(), cs.degree()) == (20, 4)
     return cs, adv, fcol, inst, cells, word
 
 

@@ -11,6 +11,10 @@ fixed columns and the copies differ -- and, for a plan with a choice, one select
 
 A segment may also start from a state other than the IV (`Segment.init`, DESIGN.md "Wired initial states"): eight sources
 for H[0..7], tied by the same kinds of copies; such a plan is synthesised by `cq_sha256_synthesize_states_dev`.
+
+A message word may also be the XOR of two sources (`Xor`, DESIGN.md "XOR-wired message words"): every distinct Xor is a
+unit of two regions behind the last segment, one selector and one gate are added, and the plan is synthesised by
+`cq_sha256_synthesize_xors_dev`.  `hmac_sha256` / `HmacSha256Circuit` build HMAC-SHA-256 from it.
 """
 from __future__ import annotations
 
@@ -62,10 +66,18 @@ class Choice(NamedTuple):
     one: tuple
 
 
+class Xor(NamedTuple):
+    """A message word that equals `x` XOR `y`; each operand is a Const, a Var or a DigestWord of an earlier segment.  Equal
+    Xors are one unit: any number of message words may read it.  A plan with an Xor holds no Choice."""
+
+    x: tuple
+    y: tuple
+
+
 class Segment(NamedTuple):
     """One compression chain: `blocks` blocks and the source of each of its 16 * blocks message words.  `init` is the state
     its first block starts from: None for the IV, else 8 sources for H[0..7], each a Const, Private, Var or a DigestWord of
-    an earlier segment (no Choice)."""
+    an earlier segment (no Choice, no Xor)."""
 
     blocks: int
     sources: tuple
@@ -163,6 +175,38 @@ def sha224(blocks: int) -> Plan:
     return Plan((Segment(blocks, (PRIVATE,) * (16 * blocks), tuple(Const(v) for v in IV224)),), (0,))
 
 
+HMAC_IPAD, HMAC_OPAD = 0x36363636, 0x5C5C5C5C
+
+
+def hmac_sha256(key_bytes: int, message_bytes: int, commit_key: bool = False) -> Plan:
+    """HMAC-SHA-256 (RFC 2104) of a private message of `message_bytes` bytes under a private key of `key_bytes` <= 64 bytes,
+    both multiples of 4: tag = H((K' ^ opad) || H((K' ^ ipad) || m)), K' the key padded with zeros to 64 bytes.  The key is
+    Var 0 .. key_bytes / 4 - 1.  Segment 0, the inner hash: words t < key_bytes / 4 are Xor(Var(t), Const(ipad)), the rest of
+    the key block Const(ipad) -- a zero key byte xor ipad -- then the message words, Private, then the padding of a
+    64 + message_bytes byte message, Const word for word.  Segment 1, the outer hash, two blocks: the key block with opad,
+    the inner digest, the pinned padding of a 96-byte message.  Its digest, the tag, is public.  `commit_key`: a third segment
+    hashes the key Vars under pinned padding and its digest is public too, behind the tag: "the key whose SHA-256 is C"."""
+    if key_bytes % 4 or message_bytes % 4 or not 0 <= key_bytes <= 64 or message_bytes < 0:
+        raise ValueError(f"hmac_sha256: a key of {key_bytes} bytes and a message of {message_bytes}: both are multiples of 4, the key at "
+                         "most 64 bytes (a longer key is hashed first, any byte length needs the variable-length circuit)")
+    key = tuple(Var(t) for t in range(key_bytes // 4))
+
+    def key_block(pad):
+        return tuple(Xor(v, Const(pad)) for v in key) + (Const(pad),) * (16 - len(key))
+
+    def padding(total_bytes):  # the words behind the data of a message of that many bytes: 0x80, zeros, the bit length
+        return tuple(Const(w) for w in SC.pad(bytes(total_bytes))[total_bytes // 4:])
+
+    inner = key_block(HMAC_IPAD) + (PRIVATE,) * (message_bytes // 4) + padding(64 + message_bytes)
+    outer = key_block(HMAC_OPAD) + tuple(DigestWord(0, i) for i in range(8)) + padding(96)
+    segs = [Segment(len(inner) // 16, inner), Segment(2, outer)]
+    if commit_key:
+        committed = key + padding(key_bytes)
+        segs.append(Segment(len(committed) // 16, committed))
+    assert segs[0].blocks == 1 + -(-(message_bytes + 9) // 64)
+    return Plan(tuple(segs), (1, 2) if commit_key else (1,))
+
+
 def has_init(plan: Plan) -> bool:
     return any(seg.init is not None for seg in plan.segments)
 
@@ -171,16 +215,32 @@ def has_choice(plan: Plan) -> bool:
     return any(isinstance(s, Choice) for seg in plan.segments for s in seg.sources)
 
 
+def xor_units(plan: Plan):
+    """The plan's XOR units: its distinct Xor words in the order of their first use, by (segment, word)."""
+    return list(dict.fromkeys(s for seg in plan.segments for s in seg.sources if isinstance(s, Xor)))
+
+
+def has_xor(plan: Plan) -> bool:
+    return any(isinstance(s, Xor) for seg in plan.segments for s in seg.sources)
+
+
 def shared_counts(plan: Plan):
     """(vars, bits) of the plan: one more than the largest index used, 0 if none is."""
     srcs = [s for seg in plan.segments for s in tuple(seg.sources) + tuple(seg.init or ())]
-    operands = [o for s in srcs if isinstance(s, Choice) for o in (s.zero, s.one)]
+    operands = [o for s in srcs if isinstance(s, Choice) for o in (s.zero, s.one)] + [o for s in srcs if isinstance(s, Xor) for o in (s.x, s.y)]
     return (max([v.index + 1 for v in srcs + operands if isinstance(v, Var)], default=0),
             max([s.bit + 1 for s in srcs if isinstance(s, Choice)], default=0))
 
 
 def rows_for(plan: Plan) -> int:
-    return sum(SC.rows_for(s.blocks) for s in plan.segments)
+    """The rows the plan uses: its segments one behind another, then SC.XOR_REGIONS regions per XOR unit."""
+    return sum(SC.rows_for(s.blocks) for s in plan.segments) + SC.XOR_REGIONS * SC.REGION_ROWS * len(xor_units(plan))
+
+
+def xor_first_region(plan: Plan) -> int:
+    """The first region of the XOR area: the one directly behind the last segment's tail.  Unit u takes regions
+    SC.XOR_REGIONS * u (e = x) and SC.XOR_REGIONS * u + 1 (e = y, W = x ^ y) from there."""
+    return sum(SC.BLOCK_REGIONS * s.blocks + SC.TAIL_REGIONS for s in plan.segments)
 
 
 def first_regions(plan: Plan):
@@ -235,11 +295,26 @@ def _check_plan(plan: Plan):
                         raise ValueError(f"segment {j}, word {t}: the {name} operand of a choice is a Var or a DigestWord, not {o!r}")
                     elif o.index < 0:
                         raise ValueError(f"segment {j}, word {t}: the var index {o.index} of the {name} operand is negative")
+            elif isinstance(src, Xor):
+                for name, o in (("x", src.x), ("y", src.y)):
+                    if isinstance(o, DigestWord):
+                        digest_word(j, t, o, f" (the {name} operand)")
+                    elif isinstance(o, Var):
+                        if o.index < 0:
+                            raise ValueError(f"segment {j}, word {t}: the var index {o.index} of the {name} operand is negative")
+                    elif isinstance(o, Const):
+                        if not 0 <= o.value < 1 << 32:
+                            raise ValueError(f"segment {j}, word {t}: the constant {o.value} of the {name} operand is no 32-bit word")
+                    else:
+                        raise ValueError(f"segment {j}, word {t}: the {name} operand of an xor is a Const, a Var or a DigestWord, not {o!r}")
             elif isinstance(src, Const):
                 if not 0 <= src.value < 1 << 32:
                     raise ValueError(f"segment {j}, word {t}: the constant {src.value} is no 32-bit word")
             elif not isinstance(src, Private):
-                raise ValueError(f"segment {j}, word {t}: a source is Private, Const, DigestWord, Var or Choice, not {src!r}")
+                raise ValueError(f"segment {j}, word {t}: a source is Private, Const, DigestWord, Var, Choice or Xor, not {src!r}")
+    if has_xor(plan) and has_choice(plan):
+        j, t = next((j, t) for j, seg in enumerate(plan.segments) for t, s in enumerate(seg.sources) if isinstance(s, Choice))
+        raise ValueError(f"segment {j}, word {t}: a Choice in a plan that holds an Xor -- the two variants do not combine")
     if not plan.public or len(set(plan.public)) != len(plan.public) or not all(0 <= p < len(plan.segments) for p in plan.public):
         raise ValueError(f"public segments {plan.public!r}: at least one, each an index below {len(plan.segments)}, none twice")
     pi = tuple(plan.public_init)
@@ -253,14 +328,15 @@ def describe(k: int, plan: Plan, table_bits: int = 12, dense="dense", spread="sp
     if not SC.MIN_TABLE_BITS <= table_bits <= SC.MAX_TABLE_BITS:
         raise ValueError(f"table_bits must be in [{SC.MIN_TABLE_BITS}, {SC.MAX_TABLE_BITS}]: the widest piece has {SC.MIN_TABLE_BITS} bits")
     _check_plan(plan)
-    choice = has_choice(plan)
-    names = SC.FIXED_CHOICE if choice else SC.FIXED
-    cs, adv, fcol, inst, cells, word = SC._constraint_system(table_bits, dense, spread, choice)
+    choice, units = has_choice(plan), xor_units(plan)
+    names = SC.FIXED_CHOICE if choice else SC.FIXED_XOR if units else SC.FIXED
+    cs, adv, fcol, inst, cells, word = SC._constraint_system(table_bits, dense, spread, choice, xor=bool(units))
     n, X, Y = 1 << k, adv[2 * SC.PAIRS], adv[2 * SC.PAIRS + 1]
     rows, usable = rows_for(plan), n - (cs.blinding_factors() + 1)
     instance_rows = 8 * (len(plan.public) + len(plan.public_init))
     if max(rows, instance_rows) > usable:
-        raise ValueError(f"{len(plan.segments)} segments need {rows} rows and {instance_rows} instance rows, 2^{k} has {usable} usable")
+        area = f" and {len(units)} xor units" if units else ""
+        raise ValueError(f"{len(plan.segments)} segments{area} need {rows} rows and {instance_rows} instance rows, 2^{k} has {usable} usable")
     fixed = {name: np.zeros(n, dtype=np.uint64) for name in names}
     copies = []
     firsts = first_regions(plan)
@@ -275,6 +351,7 @@ def describe(k: int, plan: Plan, table_bits: int = 12, dense="dense", spread="sp
     # the cells of the choices' digest operands, of every var and of every bit, in (segment, word, zero-then-one) order
     digest_cells, var_cells, bit_cells = [], {}, {}
     init_digest_cells, init_var_cells, init_public_cells = [], {}, []
+    xor_first, xor_readers = xor_first_region(plan), []  # every reader's W cell, tied to its unit's, in (segment, word) order
     for j, seg in enumerate(plan.segments):
         # a constant initial word is pinned where the IV's is, by the same lines; the others are tied behind everything else
         pinned = None if seg.init is None else [s.value if isinstance(s, Const) else None for s in seg.init]
@@ -305,6 +382,8 @@ def describe(k: int, plan: Plan, table_bits: int = 12, dense="dense", spread="sp
                     else:
                         var_cells.setdefault(o.index, []).append((Y, base + row))
                 bit_cells.setdefault(src.bit, []).append((Y, base + SC.CHOICE_ROW_BIT))
+            elif isinstance(src, Xor):
+                xor_readers.append(((X, SC.REGION_ROWS * (xor_first + SC.XOR_REGIONS * units.index(src) + 1) + wrow), (X, w_cell)))
     # behind the segments' own copies: every digest operand to its tail cell, then every later cell of a var to the var's
     # first cell (vars in ascending index), then the same for every bit
     copies += digest_cells
@@ -319,13 +398,39 @@ def describe(k: int, plan: Plan, table_bits: int = 12, dense="dense", spread="sp
         first, rest = (var_cells[i][0], init_var_cells[i]) if i in var_cells else (init_var_cells[i][0], init_var_cells[i][1:])
         copies += [(first, cell) for cell in rest]
     copies += sorted(init_public_cells, key=lambda c: c[0][1])
+    # behind all of those, the XOR area.  Unit u: region xor_first + 2u holds e = x under q_all; the next one e = y and
+    # W = x ^ y under q_all, q_f3 and q_xor; scales in both as _assign_segment sets them.  Copies, all in X: (1) unit after
+    # unit, x then y, a Const operand's E cell to `const` and a DigestWord operand's E cell to its tail cell; (2) vars in
+    # ascending index: every operand cell of the var to the var's first cell -- its first message cell if it has one, else
+    # its first state cell, else its first operand cell; (3) every reader's W cell to its unit's W cell
+    xor_var_cells = {}
+    for u, unit in enumerate(units):
+        for o, region in ((unit.x, xor_first + SC.XOR_REGIONS * u), (unit.y, xor_first + SC.XOR_REGIONS * u + 1)):
+            base = SC.REGION_ROWS * region
+            fixed["q_all"][base] = 1
+            for c in cells:
+                if c.form == SC.FORM_PAIR:
+                    fixed[f"scale{c.column // 2}"][base + c.row] = 1 << (table_bits - SC._field_of(c, table_bits)[1]) if c.len else 1
+            if isinstance(o, Const):
+                fixed["const"][base + erow] = o.value
+                copies.append(((fcol["const"], base + erow), (X, base + erow)))
+            elif isinstance(o, DigestWord):
+                copies.append((tail_cell(o), (X, base + erow)))
+            else:
+                xor_var_cells.setdefault(o.index, []).append((X, base + erow))
+        fixed["q_f3"][base] = fixed["q_xor"][base] = 1  # `base`: the unit's second region
+    for i in sorted(xor_var_cells):
+        own = var_cells.get(i) or init_var_cells.get(i)
+        first, rest = (own[0], xor_var_cells[i]) if own else (xor_var_cells[i][0], xor_var_cells[i][1:])
+        copies += [(first, cell) for cell in rest]
+    copies += xor_readers
     return SC.Description(cs, adv, fcol, fixed, inst, copies, cells, table_bits, tuple(s.blocks for s in plan.segments), k, names)
 
 
 class Lowered(NamedTuple):
-    """A plan as the entry points take it: the arrays of cq_sha256_synthesize_segments_dev / _choices_dev and the shape
-    of the word buffer they index -- the distinct constants, then every Private word in (segment, word) order, then the
-    vars, then the bits."""
+    """A plan as the entry points take it: the arrays of cq_sha256_synthesize_segments_dev / _choices_dev / _states_dev /
+    _xors_dev and the shape of the word buffer they index -- the distinct constants, then every Private word in (segment,
+    word) order, then the vars, then the bits."""
 
     seg_blocks: np.ndarray      # uint32[segments]
     sources: np.ndarray         # uint32[16 * blocks]: a word index, SOURCE_DIGEST + 8 * segment + word, or SOURCE_CHOICE + entry
@@ -335,11 +440,14 @@ class Lowered(NamedTuple):
     private_counts: list        # Private words per segment: its initial words' first, then its message words'
     shared_counts: tuple        # (vars, bits)
     init_sources: np.ndarray = None  # uint32[8 * segments]: SOURCE_IV, a word index or SOURCE_DIGEST + 8 * segment + word
+    xors: np.ndarray = None     # uint32[units, 4]: {x, y, 0, 0}, plain sources; a reader's source is SOURCE_DIGEST + 8 * segments + unit
 
 
 def lower(plan: Plan) -> Lowered:
     """The plan's sources as indices into its word buffer; needs no key and no device."""
-    consts = sorted({s.value for seg in plan.segments for s in tuple(seg.sources) + tuple(seg.init or ()) if isinstance(s, Const)})
+    units = xor_units(plan)
+    consts = sorted({s.value for seg in plan.segments for s in tuple(seg.sources) + tuple(seg.init or ()) if isinstance(s, Const)} |
+                    {o.value for unit in units for o in unit if isinstance(o, Const)})
     at_const = {v: i for i, v in enumerate(consts)}
     private_counts = [sum(isinstance(s, Private) for s in tuple(seg.init or ()) + tuple(seg.sources)) for seg in plan.segments]
     nvars, nbits = shared_counts(plan)
@@ -347,8 +455,11 @@ def lower(plan: Plan) -> Lowered:
     first_bit = first_var + nvars
 
     def plain(s):
+        if isinstance(s, Const):
+            return at_const[s.value]
         return first_var + s.index if isinstance(s, Var) else SOURCE_DIGEST + 8 * s.segment + s.word
 
+    at_unit = {unit: SOURCE_DIGEST + 8 * len(plan.segments) + u for u, unit in enumerate(units)}
     sources, choices, init_sources, nxt = [], [], [], len(consts)
     for seg in plan.segments:
         for s in seg.init or (None,) * 8:  # a segment's Private initial words come before its Private message words
@@ -366,12 +477,16 @@ def lower(plan: Plan) -> Lowered:
             elif isinstance(s, Choice):  # entry c of the choice table: {bit, zero, one, 0}
                 sources.append(SOURCE_CHOICE + len(choices))
                 choices.append((first_bit + s.bit, plain(s.zero), plain(s.one), 0))
+            elif isinstance(s, Xor):  # the unit's result word, behind the segments' digests
+                sources.append(at_unit[s])
             else:
                 sources.append(at_const[s.value] if isinstance(s, Const) else plain(s))
     assert nxt == first_var
+    xors = [(plain(unit.x), plain(unit.y), 0, 0) for unit in units]
     return Lowered(np.array([seg.blocks for seg in plan.segments], dtype=np.uint32), np.array(sources, dtype=np.uint32),
                    np.array(choices, dtype=np.uint32).reshape(-1, 4), np.array(consts, dtype=np.uint32), first_bit + nbits,
-                   private_counts, (nvars, nbits), np.array(init_sources, dtype=np.uint32))
+                   private_counts, (nvars, nbits), np.array(init_sources, dtype=np.uint32),
+                   np.array(xors, dtype=np.uint32).reshape(-1, SC.XOR_WORDS))
 
 
 def word_buffer(low: Lowered, values, shared=(), bits=()) -> np.ndarray:
@@ -417,8 +532,9 @@ class Sha256SegmentsCircuit:
         self._lowered = low = lower(plan)
         self._seg_blocks, self._sources, self._choices, self._words_len = low.seg_blocks, low.sources, low.choices, low.words_len
         self._init_sources = low.init_sources if has_init(plan) else None
+        self._xors = low.xors
         self._words = ctx.alloc(4 * max(self._words_len, 1))
-        self._digests = ctx.alloc(32 * len(plan.segments))
+        self._digests = ctx.alloc(32 * len(plan.segments) + 4 * len(low.xors))  # behind the digests: every XOR unit's result word
         self.digest_words = self.instances = self.init_words = self.instance_words = None
 
     # ---- witness ----
@@ -432,9 +548,15 @@ class Sha256SegmentsCircuit:
     def _call(self, arr, words_ptr=None, digests_ptr=None):
         """The entry point alone, on the word buffer as it is on the device (`words_ptr`, `digests_ptr`: other device arrays
         than the circuit's own): the one with choices only for a plan that has some, the one with states only for a plan
-        with an `init`."""
+        with an `init`, the one with XOR units only for a plan with an Xor."""
         ctx = self.ctx
-        if self._init_sources is not None:
+        if len(self._xors):
+            ctx._chk(ctx.lib.cq_sha256_synthesize_xors_dev(ctx.h, self.table_bits, self._seg_blocks.ctypes.data, len(self._seg_blocks),
+                                                           self._sources.ctypes.data, None, 0,
+                                                           None if self._init_sources is None else self._init_sources.ctypes.data,
+                                                           self._xors.ctypes.data, len(self._xors), words_ptr or self._words.ptr, self._words_len,
+                                                           self.n, arr, digests_ptr or self._digests.ptr))
+        elif self._init_sources is not None:
             ctx._chk(ctx.lib.cq_sha256_synthesize_states_dev(ctx.h, self.table_bits, self._seg_blocks.ctypes.data, len(self._seg_blocks),
                                                              self._sources.ctypes.data, self._choices.ctypes.data if len(self._choices) else None,
                                                              len(self._choices), self._init_sources.ctypes.data, words_ptr or self._words.ptr,
@@ -636,3 +758,54 @@ class Sha256MerklePathCircuit(Sha256SegmentsCircuit):
 
     def _result(self):
         return self.roots
+
+
+class HmacSha256Circuit(Sha256SegmentsCircuit):
+    """HMAC-SHA-256 of a private message of exactly `message_bytes` bytes under a private key of exactly `key_bytes` <= 64
+    bytes, both multiples of 4 (the plan `hmac_sha256`); the tag is public, with `commit_key` SHA-256(key) too.  The methods
+    take (key, message) as bytes.  Forced: the key block's zero padding and both pads (Const words and Xor units), the
+    message's padding, the wiring of the inner digest into the outer hash, and that both hashes -- and the commitment -- use
+    one key.  Not offered: keys above 64 bytes (a Plan with DigestWord operands a user can write) and byte lengths that
+    are no multiple of 4 (the variable-length variant, which does not combine with plan variants)."""
+
+    def __init__(self, ctx: Context, k: int, key_bytes: int, message_bytes: int, commit_key: bool = False, **kw):
+        self.key_bytes, self.message_bytes, self.commit_key = key_bytes, message_bytes, commit_key
+        super().__init__(ctx, k, hmac_sha256(key_bytes, message_bytes, commit_key), **kw)
+
+    def _inputs(self, item, shared=(), bits=()):
+        if shared or bits:
+            raise ValueError("an HMAC takes (key, message) and nothing else")
+        key, message = (bytes(x) for x in item)
+        if (len(key), len(message)) != (self.key_bytes, self.message_bytes):
+            raise ValueError(f"a key of {self.key_bytes} bytes and a message of {self.message_bytes}, not {len(key)} and {len(message)}")
+        words = lambda data: list(struct.unpack(f">{len(data) // 4}I", data))
+        return [words(message)] + [[]] * (len(self.plan.segments) - 1), words(key), []
+
+    def synthesize(self, key, message):
+        return super().synthesize((key, message))
+
+    def check(self, key, message, max_failures: int = 64):
+        cols, inst = self.synthesize(key, message)
+        return self.pk.check_witness([c.ptr for c in cols], instances=inst, max_failures=max_failures)
+
+    def assert_satisfied(self, key, message):
+        cols, inst = self.synthesize(key, message)
+        self.pk.assert_satisfied([c.ptr for c in cols], instances=inst)
+
+    def prove(self, key, message, seed: int = 1):
+        """(proof bytes, tag): the public inputs are the tag's words, then with `commit_key` those of SHA-256(key)."""
+        cols, inst = self.synthesize(key, message)
+        return self.pk.create_proof_dev([c.ptr for c in cols], seed=seed, instances=inst), self.tag()
+
+    def tag(self) -> bytes:
+        """The tag of the last synthesis, 32 bytes."""
+        return self.digests[0]
+
+    def key_commitment(self) -> bytes:
+        """SHA-256(key) of the last synthesis (`commit_key` only)."""
+        if not self.commit_key:
+            raise ValueError("the circuit was built without commit_key")
+        return self.digests[1]
+
+    def _result(self):
+        return self.tag()

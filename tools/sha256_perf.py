@@ -29,7 +29,11 @@ With --stream-k K (0 = off): a 1 MiB message through `Sha256Stream` with bodies 
 hold: the whole `prove` (one median over --reps runs would take minutes: 3 runs), per proof and in total, next to
 `Sha256Circuit`'s proof at the same K.
 
-    python tools/sha256_perf.py [--sizes 14,18] [--segments-k 18] [--path-k 18] [--varlen-k 18] [--states-k 18] [--stream-k 18]
+With --hmac-k K (0 = off): as many independent HMAC-SHA-256 (32-byte key, one message block) as 2^K rows hold in one plan
+with XOR-wired key blocks: cq_sha256_synthesize_xors_dev + synchronise with no key, beside the same plan with the Xor words
+as Private words through cq_sha256_synthesize_states_dev; then the wrapper's synthesize, check and proof.
+
+    python tools/sha256_perf.py [--sizes 14,18] [--segments-k 18] [--path-k 18] [--varlen-k 18] [--states-k 18] [--stream-k 18] [--hmac-k 18]
                                 [--sweep 1,2,4,...] [--reps 15] [--warmup 3]
 """
 import argparse
@@ -265,6 +269,90 @@ def states_legs(ctx, k, reps, warmup):
         b.close()
 
 
+def hmac_legs(ctx, k, reps, warmup):
+    import ctypes as C
+    import hashlib
+    import hmac
+
+    import numpy as np
+
+    from sha2_on_cq_halo2_amd import sha256_circuit as SC
+    from sha2_on_cq_halo2_amd import sha256_segments as SS
+    from sha2_on_cq_halo2_amd.api import Sha256SegmentsCircuit
+
+    key_bytes, message_bytes = 32, 52  # one message block behind the key block
+    one = SS.hmac_sha256(key_bytes, message_bytes)
+    count, nvars = SC.usable_rows(k) // SS.rows_for(one), key_bytes // 4
+
+    def moved(s, i, strip):  # HMAC i of the plan: its own vars and segments; `strip`: the Xor words as Private words
+        if isinstance(s, SS.Xor):
+            return SS.PRIVATE if strip else SS.Xor(moved(s.x, i, strip), moved(s.y, i, strip))
+        if isinstance(s, SS.Var):
+            return SS.Var(s.index + nvars * i)
+        return SS.DigestWord(s.segment + 2 * i, s.word) if isinstance(s, SS.DigestWord) else s
+
+    def repeated(strip):
+        segs = tuple(SS.Segment(seg.blocks, tuple(moved(s, i, strip) for s in seg.sources)) for i in range(count) for seg in one.segments)
+        return SS.Plan(segs, tuple(2 * i + 1 for i in range(count)))
+
+    keys = [hashlib.sha256(b"key %d" % i).digest() for i in range(count)]
+    messages = [bytes((i + 3 * j) % 256 for j in range(message_bytes)) for i in range(count)]
+    words = lambda data: list(np.frombuffer(data, dtype=">u4"))
+    n = 1 << k
+    cols = [ctx.alloc(32 * n) for _ in range(SC.ADVICE_COLUMNS)]
+    arr = (C.c_void_p * len(cols))(*[b.ptr for b in cols])
+    row = {"hmac": "independent HMAC-SHA-256, 32-byte key, 52-byte message", "k": k, "hmacs": count, "segments": 2 * count, "blocks": 4 * count,
+           "xor_units": 2 * nvars * count, "rows": count * SS.rows_for(one)}
+    legs = []
+    for strip in (False, True):
+        plan = repeated(strip)
+        low = SS.lower(plan)
+        if strip:  # the key block's words are private words, in word order before the message's
+            values = [x for i in range(count) for x in ([w ^ SS.HMAC_IPAD for w in words(keys[i])] + words(messages[i]), [w ^ SS.HMAC_OPAD for w in words(keys[i])])]
+            buf = SS.word_buffer(low, values)
+        else:
+            buf = SS.word_buffer(low, [x for i in range(count) for x in (words(messages[i]), [])], [w for key in keys for w in words(key)])
+        words_dev, digests_dev = ctx.to_device(buf), ctx.alloc(32 * len(low.seg_blocks) + 4 * len(low.xors))
+
+        def call(low=low, words_dev=words_dev, digests_dev=digests_dev, strip=strip):
+            if strip:
+                ctx._chk(ctx.lib.cq_sha256_synthesize_states_dev(ctx.h, 12, low.seg_blocks.ctypes.data, len(low.seg_blocks), low.sources.ctypes.data,
+                                                                 None, 0, None, words_dev.ptr, low.words_len, n, arr, digests_dev.ptr))
+            else:
+                ctx._chk(ctx.lib.cq_sha256_synthesize_xors_dev(ctx.h, 12, low.seg_blocks.ctypes.data, len(low.seg_blocks), low.sources.ctypes.data,
+                                                               None, 0, None, low.xors.ctypes.data, len(low.xors), words_dev.ptr, low.words_len, n,
+                                                               arr, digests_dev.ptr))
+            ctx.sync()
+
+        call()
+        tags = digests_dev.download((2 * count, 8), np.uint32)[1::2].astype(">u4")
+        assert [t.tobytes() for t in tags] == [hmac.new(key, m, "sha256").digest() for key, m in zip(keys, messages)]
+        legs.append(("states_dev_private_key_blocks_ms" if strip else "xors_dev_ms", call))
+    timed(row, legs + [("xors_dev_again_ms", legs[0][1])], reps, warmup)
+    for b in cols:
+        b.close()
+    t0 = time.perf_counter()
+    c = Sha256SegmentsCircuit(ctx, k, repeated(False))
+    row["keygen_s"] = round(time.perf_counter() - t0, 2)
+    values, shared = [x for i in range(count) for x in (words(messages[i]), [])], [w for key in keys for w in words(key)]
+    assert c.check(values, shared) == (0, [])
+    ptrs, seed = [b.ptr for b in c.cols], [0]
+
+    def prove():
+        seed[0] += 1
+        c.pk.create_proof_dev(ptrs, seed=seed[0], instances=c.instances)
+
+    def synthesize():
+        c.synthesize(values, shared)
+        ctx.sync()
+
+    timed(row, (("synthesize_ms", synthesize), ("check_ms", lambda: c.pk.check_witness(ptrs, instances=c.instances, max_failures=0)),
+                ("proof_ms", prove)), reps, warmup)
+    row["proof_bytes"] = c.pk.proof_size
+    c.close()
+    print(json.dumps(row), flush=True)
+
+
 def stream_legs(ctx, k, reps, warmup):
     import hashlib
 
@@ -298,6 +386,7 @@ def main():
     ap.add_argument("--varlen-k", type=int, default=0)
     ap.add_argument("--states-k", type=int, default=0)
     ap.add_argument("--stream-k", type=int, default=0)
+    ap.add_argument("--hmac-k", type=int, default=0)
     ap.add_argument("--sweep", default="1,2,4,8,16,32,64,128,256,512")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
@@ -346,6 +435,8 @@ def main():
         states_legs(ctx, args.states_k, args.reps, args.warmup)
     if args.stream_k:
         stream_legs(ctx, args.stream_k, args.reps, args.warmup)
+    if args.hmac_k:
+        hmac_legs(ctx, args.hmac_k, args.reps, args.warmup)
     ctx.close()
 
 
