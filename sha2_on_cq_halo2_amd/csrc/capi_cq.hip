@@ -230,17 +230,8 @@ size_t cq_pk_proof_size(const cq_pk* pk) {
   if (!pk) return 0;
   const size_t L = pk->lookups.size(), S = pk->perm_sets();
   // one opening witness per distinct evaluation point (gwc/prover.rs:42-91)
-  std::vector<int32_t> rots{0};
-  auto seen = [&](int32_t r) {
-    if (std::find(rots.begin(), rots.end(), r) == rots.end()) rots.push_back(r);
-  };
-  for (auto& q : pk->advice_queries) seen(q.second);
-  for (auto& q : pk->fixed_queries) seen(q.second);
   const size_t PL = pk->legacy.size();
-  if (S || PL) seen(1);
-  if (PL) seen(-1);
-  if (S > 1) seen(-(int32_t)(pk->bf + 1));
-  const size_t openings = pk->opener == CQ_OPENER_SHPLONK ? 2 : rots.size();
+  const size_t openings = pk->opener == CQ_OPENER_SHPLONK ? 2 : pk->opening_rotations().size();
   const size_t points = pk->num_advice + 2 * L + 3 * PL + S + 5 * L + 1 + pk->domain->quotient_poly_degree + openings;
   const size_t scalars = pk->advice_queries.size() + pk->fixed_queries.size() + 1 + pk->perm_columns.size() + (S ? 3 * S - 1 : 0) + 3 * L + 5 * PL;
   return 32 * (points + scalars);

@@ -46,6 +46,26 @@ struct cq_pk_desc {
     const size_t chunk = cs_degree - 2;
     return (perm_columns.size() + chunk - 1) / chunk;
   }
+  // The multi-open groups queries by their POINT (gwc.rs:36-61, shplonk.rs:56-133), and omega^rot x is the same point for
+  // every rotation of one residue modulo 2^k: the representative in [-n/2, n/2) stands for all of them.
+  int32_t point_rotation(int32_t rot) const {
+    const int64_t n = (int64_t)1 << k, r = (((int64_t)rot % n) + n) % n;
+    return (int32_t)(r >= (n + 1) / 2 ? r - n : r);
+  }
+  // the distinct points the proof opens at, as rotations of x: one GWC witness each, one evaluation batch each
+  std::vector<int32_t> opening_rotations() const {
+    std::vector<int32_t> rots{0};
+    auto seen = [&](int32_t rot) {
+      const int32_t r = point_rotation(rot);
+      if (std::find(rots.begin(), rots.end(), r) == rots.end()) rots.push_back(r);
+    };
+    for (auto& q : advice_queries) seen(q.second);
+    for (auto& q : fixed_queries) seen(q.second);
+    if (perm_sets() || !legacy.empty()) seen(1);
+    if (!legacy.empty()) seen(-1);
+    if (perm_sets() > 1) seen(-(int32_t)(bf + 1));
+    return rots;
+  }
 };
 
 namespace cq {

@@ -380,8 +380,8 @@ struct ProofRun {
   uint32_t phase_of(size_t a) const { return pk->advice_phase.empty() ? 0u : pk->advice_phase[a]; }
   Fr* plk_buf(size_t l, int which) const { return B.plk + (l * 5 + which) * n; }  // 0 A, 1 S, 2 a', 3 s', 4 z
   Fr point_of(int32_t rot) const { return rot >= 0 ? x * dom->omega.pow_u64((uint64_t)rot) : x * dom->omega_inv.pow_u64((uint64_t)(-(int64_t)rot)); }  // rotate_omega (domain.rs:414-424)
-  size_t add_query(const Fr* p, size_t len, int32_t rot) {
-    qs.push_back({p, (uint32_t)len, rot, -1, Fr::zero()});
+  size_t add_query(const Fr* p, size_t len, int32_t rot) {  // rotations that name one point become one rotation (pk.hpp)
+    qs.push_back({p, (uint32_t)len, pk->point_rotation(rot), -1, Fr::zero()});
     return qs.size() - 1;
   }
   // this rank holds f_l and b_l of lookup l: every lookup in the replicated flow, the owned range under resident sharding

@@ -33,19 +33,6 @@ G1Jac jac_from_limbs(const uint64_t* l) {
   return {Fq::from_limbs64(l), Fq::from_limbs64(l + 4), Fq::from_limbs64(l + 8)};
 }
 
-std::vector<int32_t> opening_rotations(const cq_pk* pk) {
-  std::vector<int32_t> rots{0};
-  auto seen = [&](int32_t r) {
-    if (std::find(rots.begin(), rots.end(), r) == rots.end()) rots.push_back(r);
-  };
-  for (auto& q : pk->advice_queries) seen(q.second);
-  for (auto& q : pk->fixed_queries) seen(q.second);
-  if (pk->perm_sets() || !pk->legacy.empty()) seen(1);
-  if (!pk->legacy.empty()) seen(-1);
-  if (pk->perm_sets() > 1) seen(-(int32_t)(pk->bf + 1));
-  return rots;
-}
-
 }  // namespace
 
 bool host_trace_enabled() {
@@ -161,7 +148,7 @@ void carve(const cq_pk* pk, Arena& ar, Buffers& b) {
   const bool general = pk->general();
   size_t wsum = 0;
   for (auto& lk : pk->lookups) wsum += lk.cols.size();
-  const size_t npts = opening_rotations(pk).size();
+  const size_t npts = pk->opening_rotations().size();
   b.adv = ar.take(A * n);            // advice (lagrange -> coeff in place)
   // CQ-only single-phase circuits: the coefficient forms go to a buffer of their own, so that the transform can start
   // under the advice launch's tail while the Lagrange values are still needed (round 1 folds them into f)

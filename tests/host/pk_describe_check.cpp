@@ -2,7 +2,8 @@
 // pk_describe, pack_programs, pk_pack_programs) over one good description and the bad ones of tests/test_pk_build_gpu.py,
 // built with -fsanitize=address,undefined.  Every array is a heap block of exactly its length, so a read past an end is an
 // AddressSanitizer report.  The two functions pk.hpp takes from the rest of the library have stand-ins here.
-//   pk_describe_check   prints one line per case and "ok"; a wrong code, text, field or offset is exit status 1
+//   pk_describe_check   prints one line for the good description, one per refused one and "ok" (the descriptions at the
+//                       accepted limits print nothing); a wrong code, text, field or offset is exit status 1
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -47,14 +48,18 @@ struct Description {
   cq_plonk pl{};
   cq_circuit cs{};
   Description() {
-    for (uint32_t c = 0; c < PERM; c++)
+    identity_mapping(PERM);
+    fixed[0] = fixed[1] = constants.data();  // only their presence is looked at
+    pl.cs_degree = 5;
+    link();
+  }
+  void identity_mapping(uint32_t columns) {
+    mapping.clear();
+    for (uint32_t c = 0; c < columns; c++)
       for (uint32_t r = 0; r < N; r++) {
         mapping.push_back(c);
         mapping.push_back(r);
       }
-    fixed[0] = fixed[1] = constants.data();  // only their presence is looked at
-    pl.cs_degree = 5;
-    link();
   }
   void link() {  // after a vector was replaced
     pl.num_fixed = FIXED;
@@ -71,7 +76,7 @@ struct Description {
     pl.gate_programs = gate_words.data();
     pl.num_constants = 1;
     pl.constants = constants.data();
-    pl.num_perm_columns = PERM;
+    pl.num_perm_columns = (uint32_t)perm_kinds.size();
     pl.perm_column_kinds = perm_kinds.data();
     pl.perm_column_indices = perm_idx.data();
     pl.perm_mapping = mapping.data();
@@ -110,6 +115,17 @@ void rejected(const char* text, const std::function<void(Description&)>& spoil, 
   printf("%d %s\n", rc, err.c_str());
   expect(rc == CQ_ERR_ARG && err == text, text);
 }
+
+// describes `d` after `shape`, as pk.hip's driver does, and expects CQ_OK and `holds`; prints nothing
+void accepted(const char* what, const std::function<void(Description&)>& shape, const std::function<bool(Description&, cq_pk_desc&)>& holds) {
+  Description d;
+  shape(d);
+  d.link();
+  cq_pk_desc desc;
+  std::string err;
+  const int rc = cq::pk_describe(&d.cs, K, &d.table_rows, true, false, LIMITS, &desc, &err);
+  expect(rc == CQ_OK && err.empty() && holds(d, desc), what);
+}
 }  // namespace
 
 int main() {
@@ -140,6 +156,46 @@ int main() {
     d.pl.perm_mapping = nullptr;
     cq_pk_desc again;
     expect(cq::pk_describe(&d.cs, K, &d.table_rows, true, true, LIMITS, &again, &err) == CQ_OK, "description of a serialized key");
+  }
+  // the limits themselves are accepted: degree 3 and 18, 64 permutation columns, a legacy lookup 64 expressions wide
+  accepted("cs_degree 18", [](Description& d) { d.pl.cs_degree = 18; }, [](Description&, cq_pk_desc& desc) { return desc.cs_degree == 18 && desc.perm_sets() == 1; });
+  accepted("cs_degree 3", [](Description& d) { d.pl.cs_degree = 3; }, [](Description&, cq_pk_desc& desc) { return desc.cs_degree == 3 && desc.perm_sets() == PERM; });
+  const auto columns64 = [](Description& d) {
+    d.perm_kinds.clear();
+    d.perm_idx.clear();
+    for (uint32_t c = 0; c < 64; c++) {
+      d.perm_kinds.push_back(c % 3 == 2 ? CQ_COL_FIXED : CQ_COL_ADVICE);
+      d.perm_idx.push_back(c % 2);
+    }
+    d.identity_mapping(64);
+  };
+  accepted("64 permutation columns", columns64, [](Description&, cq_pk_desc& desc) {
+    return desc.perm_columns.size() == 64 && desc.perm_sets() == 22 && desc.perm_columns[63] == std::make_pair(CQ_COL_ADVICE, 1u);
+  });
+  accepted("64 permutation columns, one per set", [&](Description& d) { columns64(d); d.pl.cs_degree = 3; },
+           [](Description&, cq_pk_desc& desc) { return desc.perm_sets() == 64; });
+  accepted("legacy lookup 64 wide", [](Description& d) { d.legacy_widths[0] = 64; d.legacy_lens.assign(128, 1); d.legacy_words.assign(128, 0); },
+           [](Description& d, cq_pk_desc& desc) {
+             const cq::PkPrograms prog = cq::pk_pack_programs(&d.pl, &desc);
+             return desc.legacy.size() == 1 && desc.legacy[0].width == 64 && prog.legacy.size() == 256 && desc.legacy[0].in_off == 0 &&
+                    desc.legacy[0].tab_off == 128;
+           });
+  {  // opening points: rotations of one residue modulo 2^k are one point
+    cq_pk_desc desc;
+    desc.k = K;
+    const int32_t rots[][2] = {{0, 0}, {1, 1}, {-1, -1}, {15, 15}, {16, -16}, {-16, -16}, {17, -15}, {31, -1}, {-31, 1}, {32, 0}, {-33, -1}, {-6, -6}};
+    for (auto& r : rots) expect(desc.point_rotation(r[0]) == r[1], "point_rotation, k = 5");
+    desc.k = 3;
+    expect(desc.point_rotation(-6) == 2 && desc.point_rotation(4) == -4 && desc.point_rotation(3) == 3, "point_rotation, k = 3");
+    desc.k = 0;
+    expect(desc.point_rotation(5) == 0 && desc.point_rotation(-1) == 0, "point_rotation, k = 0");
+    desc.k = K;
+    desc.bf = 5;
+    desc.advice_queries = {{0, 0}, {1, -31}, {2, 16}, {0, -16}, {1, 1}};
+    desc.fixed_queries = {{0, 31}};
+    expect(desc.opening_rotations() == std::vector<int32_t>({0, 1, -16, -1}), "opening rotations without a permutation");
+    desc.perm_columns = {{CQ_COL_ADVICE, 0}, {CQ_COL_ADVICE, 1}};  // two sets at degree 3: x, omega x, omega^-6 x
+    expect(desc.opening_rotations() == std::vector<int32_t>({0, 1, -16, -1, -6}), "opening rotations with two product sets");
   }
   rejected("pk: circuit k differs from params k", [](Description&) {}, K + 1);
   rejected("pk: static lookups need a table config and b0_g1_bound", [](Description&) {}, K, false, true);

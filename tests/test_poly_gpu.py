@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 P = B.R_MOD
 
 
-@pytest.mark.parametrize("j,k", [(3, 3), (3, 5), (2, 4), (4, 6), (9, 7), (3, 11), (5, 12)])
+@pytest.mark.parametrize("j,k", [(3, 3), (3, 5), (2, 4), (4, 6), (9, 7), (3, 11), (5, 12), (17, 5), (18, 5), (18, 6)])
 def test_domain_transforms(ctx, j, k):
     from sha2_on_cq_halo2_amd import EvaluationDomain
 
