@@ -995,6 +995,43 @@ int cq_sha256_synthesize_varlen_from_dev(cq_ctx* ctx, uint32_t table_bits, const
                                          const uint64_t* msg_lens, const uint32_t* init_states_dev, const uint64_t* base_lens, size_t n,
                                          uint64_t* const* cols_dev, uint32_t* digests_dev);
 
+/* ---- SHA-512 / SHA-384 compression circuit: layout and witness synthesis (no counterpart in the reference) ------ */
+/* The 64-bit counterpart (sha2_on_cq_halo2_amd/sha512_circuit.py, DESIGN.md "SHA-512 and SHA-384 circuits"): the same
+ * CQ_SHA256_ADVICE_COLUMNS advice columns -- CQ_SHA256_PAIRS (dense, spread) pairs and two plain columns -- in regions
+ * of CQ_SHA512_REGION_ROWS rows.  A block of 128 bytes takes CQ_SHA512_BLOCK_REGIONS regions: four that hold the
+ * incoming state and one per round (80); CQ_SHA512_TAIL_REGIONS more after a message's last block hold its final state.
+ * Every cell is a bit field of one 64-bit word of its region, by the table of csrc/sha512_layout.hpp: the cell record,
+ * the CQ_SHA256_SRC_* word kinds and the CQ_SHA256_FORM_* forms are those of cq_sha256_layout, with these differences:
+ * a word has 64 bits, so a CQ_SHA256_FORM_SPREAD cell is a 128-bit value; an even / odd word has CQ_SHA512_CHUNKS chunks
+ * of table_bits bits, of which those that start at or above bit 64 hold zero (6, 5, 4 non-empty chunks at table_bits
+ * 11 .. 12, 13 .. 15 and 16); CQ_SHA256_SRC_CARRY_W is the carry of rounds 16 .. 79. */
+#define CQ_SHA512_REGION_ROWS 16
+#define CQ_SHA512_BLOCK_REGIONS 84
+#define CQ_SHA512_TAIL_REGIONS 4
+#define CQ_SHA512_MIN_TABLE_BITS 11
+#define CQ_SHA512_MAX_TABLE_BITS 16
+#define CQ_SHA512_CHUNKS 6
+#define CQ_SHA512_VARIANT_512 0 /* a segment starts from SHA-512's initial hash value */
+#define CQ_SHA512_VARIANT_384 1 /* ... from SHA-384's; the digest is the first six words of the final state */
+/* Host only: writes the first `cap` cells of the layout table to `cells` (CQ_SHA256_CELL_WORDS words each; may be NULL
+ * with cap = 0) and the number of cells the table has to *count. */
+int cq_sha512_layout(uint32_t* cells, size_t cap, size_t* count);
+/* Fills the CQ_SHA256_ADVICE_COLUMNS advice columns for `segments` independent messages one behind another: segment j
+ * takes CQ_SHA512_BLOCK_REGIONS * seg_blocks[j] + CQ_SHA512_TAIL_REGIONS regions directly behind segment j - 1 and starts
+ * from the initial hash value seg_variant[j] names (CQ_SHA512_VARIANT_*).  `msg_words` (host) are the big-endian 64-bit
+ * words of the padded messages back to back, 16 per block; `cols_dev` device columns of `n` elements each: every row
+ * below n is written, Montgomery-encoded, the rows behind the last segment's regions with zero; no row at or behind n is
+ * touched.  The compression chains run on the device, one lane per segment, and leave (a, e, W, kind) per region there
+ * for the expansion kernel, one thread per row; both are queued on the context's stream behind the words' upload, and the
+ * call waits for the stream once, at its end.  `digests_out` (host, 8 * segments words) receives every segment's final
+ * state, eight words whatever the variant.  All arguments are checked on the host before anything is launched:
+ * CQ_ERR_ARG -- with the segment in cq_last_error -- for table_bits outside [CQ_SHA512_MIN_TABLE_BITS,
+ * CQ_SHA512_MAX_TABLE_BITS], no segment, a block count of zero, a variant that is neither of the two, or n too small
+ * for the rows used; nothing is written then. */
+int cq_sha512_synthesize_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
+                             const uint32_t* seg_variant, const uint64_t* msg_words, size_t n, uint64_t* const* cols_dev,
+                             uint64_t* digests_out);
+
 /* ---- harness RNG (not in the reference: its test draws from OsRng) ---------------------------------- */
 void cq_xoshiro256ss_seed(uint64_t seed, uint64_t state[4]);
 uint64_t cq_xoshiro256ss_next_u64(void* state /* uint64_t[4] */);

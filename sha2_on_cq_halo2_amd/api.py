@@ -21,3 +21,4 @@ from .sha256_segments import (HmacSha256Circuit, Sha224Circuit, Sha256BatchCircu
                               Sha256MerklePathCircuit, Sha256MidstateCircuit, Sha256SegmentsCircuit)
 from .sha256_varlen import Sha256VarCircuit  # noqa: F401
 from .sha256_stream import Sha256Stream, link  # noqa: F401
+from .sha512_circuit import Sha384Circuit, Sha512BatchCircuit, Sha512Circuit  # noqa: F401

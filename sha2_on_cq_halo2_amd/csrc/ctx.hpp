@@ -22,11 +22,12 @@ enum class Scratch {
                 // input, capi_msm.hip (multiexp scalars, params set-up temp, validate flag), capi_g2.hip scalars, capi_cq.hip
                 // (table config, static table), pk.hip (keygen and write temps; PkStreamReader's verdict words or validity
                 // flag, from its begin() to its finish()), comm.hip self-test, the verdict words of the Processed conversions
-                // (serde.hip entry points, params / G2 SRS readers), sha256.hip's region words.  Nothing they call takes an
+                // (serde.hip entry points, params / G2 SRS readers), sha256.hip's and sha512.hip's region words.  Nothing they call takes an
                 // entry buffer
   EntryB,       // the second buffer of the same entry points (outputs, bases, pk.hip's permutation mapping, the staged compressed
                 // bytes of the Processed params / pk / G2 SRS readers and writers, the two G2 points of a params set-up or full
-                // stream), sha256.hip's lane and source tables of a segment synthesis (and, behind them, a variable-length synthesis' padded words); also g1_fft's twiddles: its callers (g1_to_lagrange,
+                // stream), sha256.hip's lane and source tables of a segment synthesis (and, behind them, a variable-length synthesis' padded words),
+                // sha512.hip's lanes, message words and digests; also g1_fft's twiddles: its callers (g1_to_lagrange,
                 // fk_table_quotients) run under entry points that hold neither entry buffer
   MsmWork,      // msm_multi.hip, msm.hip (msm_bucket_sums): the workspace of one MSM launch on any stream but a side stream;
                 // those launches follow one another on `stream`
