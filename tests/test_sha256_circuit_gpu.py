@@ -6,13 +6,11 @@ import numpy as np
 import pytest
 
 from oracle import bn254 as B
-from oracle import cq_prover as CP
-from oracle import cq_verifier as CV
-from oracle import plonk as PL
-from sha2_on_cq_halo2_amd import plonk as GP
 from sha2_on_cq_halo2_amd import sha256_circuit as SC
 from sha2_on_cq_halo2_amd.api import FAIL_GATE, FAIL_PERMUTATION, FAIL_STATIC_LOOKUP, Sha256Circuit, fr_to_mont
 from tests import sha256_circuit_model as M
+from tests.sha_oracle import verifier as _verifier
+from tests.sha_oracle import write_cell as _write
 
 pytestmark = pytest.mark.gpu
 SEED = 0x5348413243515F
@@ -70,11 +68,6 @@ def _cell(c, name, form=SC.FORM_PAIR, **where):
 
 def _read(c, column, row):
     return B.from_mont_limbs(c.cols[column].download((c.n, 4))[row: row + 1])[0]
-
-
-def _write(c, column, row, value):
-    v = np.ascontiguousarray(fr_to_mont(value), dtype=np.uint64)
-    c.ctx._chk(c.ctx.lib.cq_dev_upload(c.ctx.h, c.cols[column].ptr + 32 * row, v.ctypes.data, 32))
 
 
 def _findings(c, instances=None):
@@ -155,41 +148,6 @@ def test_a_wrong_witness_is_named(circuits):
     assert (FAIL_STATIC_LOOKUP, SC.PAIRS + p.column // 2, base + p.row) in found
     assert _gate("e_word", base) not in found and not any(f[0] == FAIL_STATIC_LOOKUP and f[1] < SC.PAIRS for f in found)
     assert all(f[2] in (base, base + p.row) for f in found)
-
-
-def _oracle_expr(e):
-    if e.op == "const":
-        return PL.const(e.a)
-    if e.op == "query":
-        return (PL.adv, PL.fix, PL.inst)[e.a.kind](e.a.index, e.b)
-    if e.op == "neg":
-        return PL.neg(_oracle_expr(e.a))
-    if e.op == "scale":
-        return PL.scale(_oracle_expr(e.a), e.b)
-    return (PL.add if e.op == "add" else PL.mul)(_oracle_expr(e.a), _oracle_expr(e.b))
-
-
-def _verifier(c, seed):
-    """The circuit's constraint system restated for the oracle's verifier -> verify(proof, digest words)."""
-    cs = c.cs
-    kinds = {GP.COL_ADVICE: PL.ADVICE, GP.COL_FIXED: PL.FIXED, GP.COL_INSTANCE: PL.INSTANCE}
-    names = {id(c.dense): "dense", id(c.spread): "spread"}
-    exprs = iter(cs._lookup_exprs)
-    lookups = [[(_oracle_expr(next(exprs)), names[id(t)]) for _, t in lk] for lk in cs.static_lookups]
-    queries = {PL.ADVICE: list(cs.advice_queries), PL.FIXED: list(cs.fixed_queries), PL.INSTANCE: list(cs.instance_queries)}
-    circ = CP.CqCircuit(c.k, cs.num_advice_columns, lookups, cs.num_fixed_columns, 1, [_oracle_expr(g) for g in cs.gates],
-                        [(kinds[col.kind], col.index) for col in cs.permutation_columns], queries)
-    assert circ.degree() == cs.degree() and circ.blinding_factors() == cs.blinding_factors()
-    s = (seed * 0x9E3779B97F4A7C15 + 12345) % B.R_MOD
-    N = 1 << c.table_bits
-    tv = {"dense": list(range(N)), "spread": [M.spread(i) for i in range(N)]}
-    fcm, pcm = c.pk.vk_commitments()
-
-    def verify(proof, digest_words):
-        return CV.verify_proof(proof, circ, c.vk_repr, s, tv, N, 1 << c.k, instances=[list(digest_words)],
-                               fixed_commitments=B.points_from_mont_limbs(fcm), perm_commitments=B.points_from_mont_limbs(pcm))
-
-    return verify
 
 
 @pytest.mark.parametrize("blocks", [1, 2])

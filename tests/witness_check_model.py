@@ -64,7 +64,10 @@ def evaluate(e, row, n, cell, challenges):
     if t == "add":
         return v_add(evaluate(e[1], row, n, cell, challenges), evaluate(e[2], row, n, cell, challenges))
     if t == "mul":
-        return v_mul(evaluate(e[1], row, n, cell, challenges), evaluate(e[2], row, n, cell, challenges))
+        a = evaluate(e[1], row, n, cell, challenges)
+        if a is not POISON and a == 0:  # zero times anything, poison included, is zero: a gate whose selector is off costs one query
+            return 0
+        return v_mul(a, evaluate(e[2], row, n, cell, challenges))
     if t == "scale":
         return v_scale(evaluate(e[1], row, n, cell, challenges), e[2])
     raise ValueError(t)
