@@ -1031,6 +1031,30 @@ int cq_sha512_layout(uint32_t* cells, size_t cap, size_t* count);
 int cq_sha512_synthesize_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
                              const uint32_t* seg_variant, const uint64_t* msg_words, size_t n, uint64_t* const* cols_dev,
                              uint64_t* digests_out);
+/* The same for segments wired to each other (sha2_on_cq_halo2_amd/sha512_segments.py, DESIGN.md "Wired SHA-512
+ * segments"): the 64-bit counterpart of cq_sha256_synthesize_states_dev without choices.  `sources` (host) holds one
+ * entry per message word, 16 per block, in row order over all segments: a value below CQ_SHA512_SOURCE_DIGEST is an index
+ * into `words_dev`, a device array of `words_len` 64-bit words (private words and constants alike);
+ * CQ_SHA512_SOURCE_DIGEST + 8 * s + i is word i of the final state of segment s, which must come before the segment that
+ * reads it -- all eight words are readable whatever the variant of s.  `init_sources` (host, 8 entries per segment, or NULL
+ * for the initial hash value everywhere) is H[0..7] of the state a segment's first block starts from: CQ_SHA512_SOURCE_IV
+ * (tested before the digest flag) for the word of seg_variant[j]'s initial hash value at that position, or a source as
+ * above.  `digests_dev` (device, 8 * segments words) receives every segment's final state.  A segment that reads no
+ * digest is of level 0, any other one level above the highest it reads -- through a message word or an initial word
+ * alike; the chains run one launch per level in ascending order, one lane per segment, then the expansion over all rows.
+ * Everything is queued on the context's stream and nothing waits for it: `words_dev` must stay as it is, and
+ * `digests_dev` is good, once the stream has got there.  All of it is validated on the host before anything is queued:
+ * CQ_ERR_ARG -- with "segment j, word t" or "segment j, initial word i" in cq_last_error where one is at fault -- for a
+ * null array, no segment, a block count of zero, a variant that is neither of the two, table_bits out of range, regions
+ * that do not fit n, a word index at or above words_len, a digest of the segment itself or a later one, and
+ * CQ_SHA512_SOURCE_IV among `sources`; nothing is written then.  A description whose words are all private and whose
+ * init_sources is NULL gives the columns and digests cq_sha512_synthesize_dev gives for the same words. */
+#define CQ_SHA512_SOURCE_DIGEST 2147483648u
+#define CQ_SHA512_SOURCE_IV 4294967295u
+int cq_sha512_synthesize_segments_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
+                                      const uint32_t* seg_variant, const uint32_t* sources, const uint32_t* init_sources,
+                                      const uint64_t* words_dev, size_t words_len, size_t n, uint64_t* const* cols_dev,
+                                      uint64_t* digests_dev);
 
 /* ---- harness RNG (not in the reference: its test draws from OsRng) ---------------------------------- */
 void cq_xoshiro256ss_seed(uint64_t seed, uint64_t state[4]);

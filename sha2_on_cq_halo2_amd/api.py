@@ -22,3 +22,6 @@ from .sha256_segments import (HmacSha256Circuit, Sha224Circuit, Sha256BatchCircu
 from .sha256_varlen import Sha256VarCircuit  # noqa: F401
 from .sha256_stream import Sha256Stream, link  # noqa: F401
 from .sha512_circuit import Sha384Circuit, Sha512BatchCircuit, Sha512Circuit  # noqa: F401
+# the plans of the wired SHA-512 segments: `batch`, `merkle_tree` and `midstate` are sha512_segments', not sha256_segments'
+from .sha512_segments import (Sha512_256Circuit, Sha512dCircuit, Sha512MerkleCircuit, Sha512MidstateCircuit, Sha512SegmentsCircuit,  # noqa: F401
+                              batch, double_sha512, merkle_tree, midstate, sha512_256)

@@ -5,9 +5,11 @@
 // is a bit field of a word that a handful of xors and additions of the region's and its neighbours' (a, e, W) give,
 // placed by the layout table of sha512_layout.hpp.  The spread form of a 64-bit word has 128 bits, so a cell value is two
 // 64-bit limbs until it is Montgomery-encoded.
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "cq.hpp"
 #include "ctx.hpp"
@@ -229,36 +231,70 @@ template <bool SCHED, uint32_t... I>
 static SHA_D void sha512_steps(uint64_t (&s)[8], uint64_t (&w)[16], uint32_t t0, Sha512Region* out, std::integer_sequence<uint32_t, I...>) {
   (sha512_step<SCHED, I>(s, w, t0, out), ...);
 }
-template <uint32_t... I>
-static SHA_D void sha512_fetch_all(uint64_t (&w)[16], const uint64_t* __restrict__ src, std::integer_sequence<uint32_t, I...>) {
-  ((w[I] = src[I]), ...);
+// A source of the wired form: a word of the caller's buffer or a word of a final state that an earlier level's launch
+// stored.  The host has checked every source against both arrays' lengths.
+static SHA_D uint64_t sha512_load(uint32_t s, const uint64_t* words, const uint64_t* digests) {
+  return *((s & CQ_SHA512_SOURCE_DIGEST) ? digests + (s & (CQ_SHA512_SOURCE_DIGEST - 1)) : words + s);
+}
+// The 16 message words of a block.  Unwired, `words` points at them; WIRED, `src` holds their 16 sources.  A fold over
+// constant indices, not a loop: `w` is only ever indexed by constants and stays in registers.
+template <bool WIRED, uint32_t... I>
+static SHA_D void sha512_fetch_all(uint64_t (&w)[16], const uint64_t* words, const uint32_t* src, const uint64_t* digests,
+                                   std::integer_sequence<uint32_t, I...>) {
+  if constexpr (WIRED)
+    ((w[I] = sha512_load(src[I], words, digests)), ...);
+  else
+    ((w[I] = words[I]), ...);
+}
+// Word I of the state a wired lane's chain starts from: the variant's own on the sentinel, else a source
+template <uint32_t I>
+static SHA_D void sha512_fetch_init(uint64_t (&h)[8], uint32_t s, const uint64_t* words, const uint64_t* digests) {
+  if (s != CQ_SHA512_SOURCE_IV) h[I] = sha512_load(s, words, digests);
 }
 
 // One lane per segment: the compression chain of one message, 80 dependent rounds per block, so the launch is
 // latency-bound: one wave per workgroup spreads the segments over the CUs.  Lanes of a wave may differ in their block
 // counts and their variants.  The host has checked that every lane's regions lie below n / CQ_SHA512_REGION_ROWS and its
 // words inside `words`.
-__global__ __launch_bounds__(64) void sha512_chain_kernel(const Sha512Lane* __restrict__ lanes, uint32_t nlanes, const uint64_t* __restrict__ words,
-                                                          uint64_t* __restrict__ digests, Sha512Region* __restrict__ regions) {
+// Unwired (cq_sha512_synthesize_dev): lane i is segment i, its message words lie at words + first_word, and neither
+// `sources` nor `init_sources` is looked at.  WIRED (cq_sha512_synthesize_segments_dev): the launch is one level's lanes;
+// a lane's segment sits above the variant bit of Sha512Lane::variant, its 16 * blocks sources at sources + first_word and
+// its eight initial sources (32 bytes, aligned to 16) at init_sources + 8 * segment; `digests` is read (earlier levels')
+// and written (this lane's segment).
+template <bool WIRED>
+__global__ __launch_bounds__(64) void sha512_chain_kernel(const Sha512Lane* __restrict__ lanes, uint32_t nlanes, const uint64_t* words,
+                                                          uint64_t* digests, Sha512Region* __restrict__ regions,
+                                                          const uint32_t* __restrict__ sources, const uint32_t* __restrict__ init_sources) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nlanes) return;
   const Sha512Lane lane = lanes[i];
   using Seq16 = std::make_integer_sequence<uint32_t, 16>;
+  const uint32_t segment = WIRED ? lane.variant >> 1 : i;
   const uint64_t* iv = SHA512_IV_DEV[lane.variant & 1u];
   uint64_t h[8] = {iv[0], iv[1], iv[2], iv[3], iv[4], iv[5], iv[6], iv[7]};
+  if constexpr (WIRED) {
+    const uint4* is = reinterpret_cast<const uint4*>(init_sources + 8 * (size_t)segment);
+    const uint4 lo = is[0], hi = is[1];
+    sha512_fetch_init<0>(h, lo.x, words, digests), sha512_fetch_init<1>(h, lo.y, words, digests);
+    sha512_fetch_init<2>(h, lo.z, words, digests), sha512_fetch_init<3>(h, lo.w, words, digests);
+    sha512_fetch_init<4>(h, hi.x, words, digests), sha512_fetch_init<5>(h, hi.y, words, digests);
+    sha512_fetch_init<6>(h, hi.z, words, digests), sha512_fetch_init<7>(h, hi.w, words, digests);
+  }
   Sha512Region* out = regions + lane.first_region;
-  const uint64_t* src = words + lane.first_word;
-  for (uint32_t b = 0; b < lane.blocks; b++, out += CQ_SHA512_BLOCK_REGIONS, src += 16) {
+  const uint64_t* msg = WIRED ? words : words + lane.first_word;
+  const uint32_t* src = WIRED ? sources + lane.first_word : nullptr;
+  for (uint32_t b = 0; b < lane.blocks; b++, out += CQ_SHA512_BLOCK_REGIONS) {
     sha512_put_state(out, h, b ? SHA512_RG_CHAIN : 0);
     uint64_t w[16], s[8] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]};
-    sha512_fetch_all(w, src, Seq16{});
+    sha512_fetch_all<WIRED>(w, msg, src, digests, Seq16{});
+    if (WIRED) src += 16; else msg += 16;
     sha512_steps<false>(s, w, 0, out + 4, Seq16{});
     for (uint32_t t0 = 16; t0 < 80; t0 += 16) sha512_steps<true>(s, w, t0, out + 4, Seq16{});
     h[0] += s[0], h[1] += s[1], h[2] += s[2], h[3] += s[3];
     h[4] += s[4], h[5] += s[5], h[6] += s[6], h[7] += s[7];
   }
   sha512_put_state(out, h, SHA512_RG_CHAIN);
-  uint64_t* d = digests + 8 * (size_t)i;
+  uint64_t* d = digests + 8 * (size_t)segment;
   d[0] = h[0], d[1] = h[1], d[2] = h[2], d[3] = h[3], d[4] = h[4], d[5] = h[5], d[6] = h[6], d[7] = h[7];
 }
 
@@ -298,14 +334,101 @@ int sha512_synthesize(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks
   const Sha512Lane* dev_lanes = (const Sha512Lane*)dev_tables;
   const uint64_t* dev_words = (const uint64_t*)((const char*)dev_tables + lanes_bytes);
   uint64_t* dev_digests = (uint64_t*)((char*)dev_tables + tables_bytes);
-  sha512_chain_kernel<<<((uint32_t)segments + 63) / 64, 64, 0, c->stream>>>(dev_lanes, (uint32_t)segments, dev_words, dev_digests,
-                                                                           (Sha512Region*)dev_regions);
+  sha512_chain_kernel<false><<<((uint32_t)segments + 63) / 64, 64, 0, c->stream>>>(dev_lanes, (uint32_t)segments, dev_words, dev_digests,
+                                                                                  (Sha512Region*)dev_regions, nullptr, nullptr);
   if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha512_chain launch failed");
   sha512_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha512Region*)dev_regions, (uint32_t)regions, n, table_bits, cols);
   if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha512_expand launch failed");
   CQ_HIP(c, hipMemcpyAsync((char*)pin + tables_bytes, dev_digests, digests_bytes, hipMemcpyDeviceToHost, c->stream));
   CQ_HIP(c, hipStreamSynchronize(c->stream));
   memcpy(digests_out, (const char*)pin + tables_bytes, digests_bytes);
+  return CQ_OK;
+}
+
+// Validates the description, then queues the tables' upload, one chain launch per level and the expansion on the context's
+// stream.  Nothing here waits for the stream: the staging is pinned, and only the previous call's copy out of it -- this
+// function's, sha512_synthesize's or a segment synthesis of sha256.hip's -- is waited for, through the event they share.
+// init_sources = nullptr is the description whose segments all start from their variant's initial hash value: the staged
+// table then holds the sentinel everywhere, so the kernel has one form.
+int sha512_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* seg_variant,
+                               const uint32_t* sources, const uint32_t* init_sources, const uint64_t* words_dev, size_t words_len, uint32_t n,
+                               const Sha512Cols& cols, uint64_t* digests_dev) {
+  const uint64_t max_regions = n / CQ_SHA512_REGION_ROWS;
+  uint64_t regions = 0, blocks = 0;
+  for (size_t j = 0; j < segments; j++) {
+    if (seg_blocks[j] == 0) return c->fail(CQ_ERR_ARG, "sha512: segment " + std::to_string(j) + " has no block");
+    if (seg_variant[j] != CQ_SHA512_VARIANT_512 && seg_variant[j] != CQ_SHA512_VARIANT_384)
+      return c->fail(CQ_ERR_ARG, "sha512: segment " + std::to_string(j) + " has variant " + std::to_string(seg_variant[j]));
+    blocks += seg_blocks[j];
+    regions += (uint64_t)seg_blocks[j] * CQ_SHA512_BLOCK_REGIONS + CQ_SHA512_TAIL_REGIONS;
+    if (regions > max_regions) return c->fail(CQ_ERR_ARG, "sha512: the segments up to segment " + std::to_string(j) + " do not fit the rows");
+  }
+  std::vector<uint32_t> level(segments, 0), level_count;
+  for (size_t j = 0, at = 0; j < segments; j++) {
+    // a source of segment j: "" if it is good, and the segment's level follows a digest's
+    auto check = [&](uint32_t s) -> std::string {
+      if (s == CQ_SHA512_SOURCE_IV) return " is the initial-value sentinel, which only an initial word can be";
+      if (s & CQ_SHA512_SOURCE_DIGEST) {
+        const size_t ref = (s & (CQ_SHA512_SOURCE_DIGEST - 1)) >> 3;
+        if (ref >= j) return " reads the digest of segment " + std::to_string(ref) + ", which does not come before it";
+        if (level[ref] + 1 > level[j]) level[j] = level[ref] + 1;
+      } else if (s >= words_len) {
+        return " reads word " + std::to_string(s) + " of a buffer of " + std::to_string(words_len);
+      }
+      return "";
+    };
+    for (size_t i = 0; init_sources && i < 8; i++) {
+      const uint32_t s = init_sources[8 * j + i];
+      if (s == CQ_SHA512_SOURCE_IV) continue;
+      const std::string bad = check(s);
+      if (!bad.empty()) return c->fail(CQ_ERR_ARG, "sha512: segment " + std::to_string(j) + ", initial word " + std::to_string(i) + bad);
+    }
+    for (size_t t = 0; t < 16 * (size_t)seg_blocks[j]; t++, at++) {
+      const std::string bad = check(sources[at]);
+      if (!bad.empty()) return c->fail(CQ_ERR_ARG, "sha512: segment " + std::to_string(j) + ", word " + std::to_string(t) + bad);
+    }
+  }
+  for (uint32_t l : level) {
+    if (l >= level_count.size()) level_count.resize(l + 1, 0);
+    level_count[l]++;
+  }
+  std::vector<uint32_t> level_first(level_count.size(), 0);
+  for (size_t l = 1; l < level_count.size(); l++) level_first[l] = level_first[l - 1] + level_count[l - 1];
+
+  // lanes, sources, initial sources: each a multiple of 16 bytes, so a segment's eight initial sources are aligned for
+  // their two 16-byte loads
+  const size_t lanes_bytes = segments * sizeof(Sha512Lane), sources_bytes = 16 * blocks * sizeof(uint32_t);
+  const size_t init_bytes = 8 * segments * sizeof(uint32_t), tables_bytes = lanes_bytes + sources_bytes + init_bytes;
+  void *pin, *dev_regions, *dev_tables;
+  if (c->sha_staged) CQ_HIP(c, hipEventSynchronize(c->sha_staged));  // the previous call's copy out of `pin`, before it may move
+  CQ_TRY(c->ensure_pinned_sha(tables_bytes, &pin));
+  CQ_TRY(c->ensure_scratch(Scratch::EntryA, regions * sizeof(Sha512Region), &dev_regions));
+  CQ_TRY(c->ensure_scratch(Scratch::EntryB, tables_bytes, &dev_tables));
+  if (!c->sha_staged) CQ_HIP(c, hipEventCreateWithFlags(&c->sha_staged, hipEventDisableTiming));
+  Sha512Lane* lanes = (Sha512Lane*)pin;
+  std::vector<uint32_t> next = level_first;
+  uint32_t first_region = 0, first_source = 0;
+  for (size_t j = 0; j < segments; j++) {  // lanes in level order, segments of one level in row order
+    lanes[next[level[j]]++] = {first_region, seg_blocks[j], first_source, (uint32_t)j << 1 | seg_variant[j]};
+    first_region += seg_blocks[j] * CQ_SHA512_BLOCK_REGIONS + CQ_SHA512_TAIL_REGIONS;
+    first_source += 16 * seg_blocks[j];
+  }
+  memcpy((char*)pin + lanes_bytes, sources, sources_bytes);
+  uint32_t* staged_init = (uint32_t*)((char*)pin + lanes_bytes + sources_bytes);
+  if (init_sources) memcpy(staged_init, init_sources, init_bytes);
+  else std::fill(staged_init, staged_init + 8 * segments, CQ_SHA512_SOURCE_IV);
+  CQ_HIP(c, hipMemcpyAsync(dev_tables, pin, tables_bytes, hipMemcpyHostToDevice, c->stream));
+  CQ_HIP(c, hipEventRecord(c->sha_staged, c->stream));
+  const Sha512Lane* dev_lanes = (const Sha512Lane*)dev_tables;
+  const uint32_t* dev_sources = (const uint32_t*)((const char*)dev_tables + lanes_bytes);
+  const uint32_t* dev_init = (const uint32_t*)((const char*)dev_sources + sources_bytes);
+  for (size_t l = 0; l < level_count.size(); l++) {
+    sha512_chain_kernel<true><<<(level_count[l] + 63) / 64, 64, 0, c->stream>>>(dev_lanes + level_first[l], level_count[l], words_dev, digests_dev,
+                                                                               (Sha512Region*)dev_regions, dev_sources, dev_init);
+    if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha512_chain launch failed");
+  }
+  sha512_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha512Region*)dev_regions, (uint32_t)regions, n, table_bits, cols);
+  if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha512_expand launch failed");
   return CQ_OK;
 }
 
@@ -340,6 +463,25 @@ int cq_sha512_synthesize_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg
     sc.p[i] = (Fr*)cols_dev[i];
   }
   return sha512_synthesize(c, table_bits, seg_blocks, segments, seg_variant, msg_words, (uint32_t)n, sc, digests_out);
+}
+
+int cq_sha512_synthesize_segments_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* seg_variant,
+                                      const uint32_t* sources, const uint32_t* init_sources, const uint64_t* words_dev, size_t words_len, size_t n,
+                                      uint64_t* const* cols_dev, uint64_t* digests_dev) {
+  if (!c) return CQ_ERR_ARG;
+  if (!seg_blocks || !seg_variant || !sources || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull || segments > n ||
+      (!words_dev && words_len) || words_len > CQ_SHA512_SOURCE_DIGEST)
+    return c->fail(CQ_ERR_ARG, "sha512: null array, no segment, or a length out of range");
+  if (table_bits < CQ_SHA512_MIN_TABLE_BITS || table_bits > CQ_SHA512_MAX_TABLE_BITS)
+    return c->fail(CQ_ERR_ARG, "sha512: table_bits outside the range the pieces fit");
+  CQ_HIP(c, hipSetDevice(c->device));
+  Sha512Cols sc;
+  for (uint32_t i = 0; i < CQ_SHA256_ADVICE_COLUMNS; i++) {
+    if (!cols_dev[i]) return c->fail(CQ_ERR_ARG, "sha512: null column");
+    sc.p[i] = (Fr*)cols_dev[i];
+  }
+  return sha512_synthesize_segments(c, table_bits, seg_blocks, segments, seg_variant, sources, init_sources, words_dev, words_len, (uint32_t)n, sc,
+                                    digests_dev);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@ The digest words (64 bits each: 8 per SHA-512 message, 6 per SHA-384 message) ar
 are private advice, the initial hash values and the round constants are fixed cells tied to their uses by copy
 constraints.  The cells are laid out by the table of csrc/sha512_layout.hpp, read here through `cq_sha512_layout`; the
 witness is synthesised on the GPU by `cq_sha512_synthesize_dev`.  Several messages in one proof are independent segments
-one behind another; nothing wires one to another.
+one behind another; sha512_segments.py wires segments to each other and to constants.
 """
 from __future__ import annotations
 
@@ -233,10 +233,12 @@ def _constraint_system(tb: int, dense, spread):
     return cs, adv, fcol, inst, cells, word
 
 
-def _assign_segment(fixed, copies, first_region, blocks, variant, public, tb, adv, fcol, inst, cells, word):
+def _assign_segment(fixed, copies, first_region, blocks, variant, public, tb, adv, fcol, inst, cells, word, pinned=None, public_words=None):
     """The fixed cells and the copies of one chain of `blocks` blocks whose regions start at `first_region`: selectors and
-    scales, the round constants, the variant's initial hash value on its first four regions (no q_chain before its second
-    block), and the copies of instance rows public .. public + DIGEST_WORDS[variant] - 1 to the digest words of its tail."""
+    scales, the round constants, the state it starts from on its first four regions (no q_chain before its second block),
+    and the copies of instance rows public .. public + public_words - 1 to the first digest words of its tail.  `pinned`:
+    H[0..7] of the state, each a constant pinned through `const` or None for a cell the caller ties (or leaves free) itself;
+    the default is the variant's initial hash value.  `public_words`: 0 .. 8, by default DIGEST_WORDS[variant]."""
     X = adv[2 * PAIRS]
     regions = BLOCK_REGIONS * blocks + TAIL_REGIONS
     g = np.arange(regions)
@@ -258,12 +260,14 @@ def _assign_segment(fixed, copies, first_region, blocks, variant, public, tb, ad
     rb = base[is_round]
     fixed["const"][rb + krow] = kvals[(in_block[is_round] - 4)]
     copies += [((fcol["const"], int(r) + krow), (X, int(r) + krow)) for r in rb]
-    init, digest_words = IV[variant], DIGEST_WORDS[variant]
+    init = IV[variant] if pinned is None else pinned
+    digest_words = DIGEST_WORDS[variant] if public_words is None else public_words
     for i in range(4):  # region i of the first block holds a_(i-4) = H[3 - i] and e_(i-4) = H[7 - i]
         head, tail = int(base[i]), int(base[BLOCK_REGIONS * blocks + i])
         for row, h in ((arow, 3 - i), (erow, 7 - i)):
-            fixed["const"][head + row] = init[h]
-            copies.append(((fcol["const"], head + row), (X, head + row)))
+            if init[h] is not None:
+                fixed["const"][head + row] = init[h]
+                copies.append(((fcol["const"], head + row), (X, head + row)))
             if h < digest_words:
                 copies.append(((inst, public + h), (X, tail + row)))
 

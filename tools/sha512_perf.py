@@ -7,7 +7,13 @@ circuit hashes in its rows.
 Every timed call ends in a stream synchronise (Sha256Circuit.synthesize: an explicit one here), so a host clock around it
 measures the whole thing.
 
-    python tools/sha512_perf.py [--sizes 14,18] [--reps 15] [--warmup 3]
+Two more legs measure the wired segments (sha512_segments.py) at --segments-k (18): `batch`, the largest batch of one-block
+messages that fits, synthesised through cq_sha512_synthesize_dev (Sha512BatchCircuit, the yardstick) and through
+cq_sha512_synthesize_segments_dev (the `batch` plan: the whole `synthesize`, and the entry point alone on the word buffer as
+it is on the device); and `merkle`, the deepest Merkle tree over 64-byte leaves that fits: the entry point with a stream
+synchronise, then the witness check and one proof.
+
+    python tools/sha512_perf.py [--sizes 14,18] [--legs circuits,batch,merkle] [--segments-k 18] [--reps 15] [--warmup 3]
 """
 import argparse
 import hashlib
@@ -56,9 +62,82 @@ def circuit_row(ctx, name, make, block_bytes, tail_bytes, digest_of, reps, warmu
     return row
 
 
+def segment_legs(ctx, c, inputs, reps, warmup):
+    """The entry point alone (queued, then a stream synchronise), the witness check and one proof of a Sha512SegmentsCircuit
+    whose word buffer `synthesize(*inputs)` has uploaded."""
+    import ctypes as C
+
+    assert c.check(*inputs) == (0, [])
+    ptrs, seed = [b.ptr for b in c.cols], [0]
+    arr = (C.c_void_p * len(ptrs))(*ptrs)
+
+    def entry():
+        c._call(arr)
+        ctx.sync()
+
+    def prove():
+        seed[0] += 1
+        c.pk.create_proof_dev(ptrs, seed=seed[0], instances=c.instances)
+
+    row = {}
+    for leg, fn in (("entry_ms", entry), ("check_ms", lambda: c.pk.check_witness(ptrs, instances=c.instances, max_failures=0)), ("proof_ms", prove)):
+        row[leg], row[leg + "_range"] = median_ms(fn, reps, warmup)
+    return row
+
+
+def batch_rows(ctx, k, reps, warmup):
+    """The largest batch of one-block messages at 2^k rows, through both entry points."""
+    from sha2_on_cq_halo2_amd import sha512_circuit as SC
+    from sha2_on_cq_halo2_amd import sha512_segments as SS
+    from sha2_on_cq_halo2_amd.api import Sha512BatchCircuit, Sha512SegmentsCircuit
+
+    count = SC.usable_rows(k) // SC.rows_for(1)
+    msgs = [bytes((i + 3 * j) % 251 for i in range(j % 112)) for j in range(count)]
+    digests = [hashlib.sha512(m).digest() for m in msgs]
+    old = Sha512BatchCircuit(ctx, k, [1] * count)
+    assert old.check(msgs) == (0, []) and old.digests == digests
+    row = {"leg": "batch", "entry_point": "cq_sha512_synthesize_dev", "k": k, "messages": count, "rows": old.rows}
+    row["synthesize_ms"], row["synthesize_ms_range"] = median_ms(lambda: old.synthesize(msgs), reps, warmup)  # ends in the digests' download
+    old.close()
+    print(json.dumps(row), flush=True)
+    new = Sha512SegmentsCircuit(ctx, k, SS.batch([1] * count))
+    values = [SC.pad(m, 1) for m in msgs]
+    new.synthesize(values)
+    assert new.digests == digests
+    wired = {"leg": "batch", "entry_point": "cq_sha512_synthesize_segments_dev", "k": k, "messages": count, "rows": new.rows, "levels": 1}
+    wired["synthesize_ms"], wired["synthesize_ms_range"] = median_ms(lambda: new.synthesize(values), reps, warmup)  # upload, entry, download
+    wired.update(segment_legs(ctx, new, (values,), reps, warmup))
+    new.close()
+    print(json.dumps(wired), flush=True)
+    print(json.dumps({"leg": "batch", "k": k, "synthesize_segments_over_plain": round(wired["synthesize_ms"] / row["synthesize_ms"], 3)}), flush=True)
+
+
+def merkle_row(ctx, k, reps, warmup):
+    """The deepest Merkle tree over 64-byte leaves at 2^k rows."""
+    from sha2_on_cq_halo2_amd import sha512_circuit as SC
+    from sha2_on_cq_halo2_amd.api import Sha512MerkleCircuit
+
+    depth = 1
+    while ((2 << depth) - 1) * SC.rows_for(2) <= SC.usable_rows(k):
+        depth += 1
+    c = Sha512MerkleCircuit(ctx, k, depth)
+    level = leaves = [bytes((i + 5 * j) % 251 for i in range(64)) for j in range(1 << depth)]
+    while len(level) > 1:
+        level = [hashlib.sha512(level[i] + level[i + 1]).digest() for i in range(0, len(level), 2)]
+    c.synthesize(leaves)
+    assert c.digests == level
+    row = {"leg": "merkle", "k": k, "depth": depth, "leaves": len(leaves), "segments": len(c.plan.segments), "levels": depth, "rows": c.rows,
+           "proof_bytes": c.pk.proof_size}
+    row.update(segment_legs(ctx, c, (leaves,), reps, warmup))
+    c.close()
+    print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="14,18")
+    ap.add_argument("--legs", default="circuits,batch,merkle")
+    ap.add_argument("--segments-k", type=int, default=18)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args()
@@ -68,7 +147,8 @@ def main():
     from sha2_on_cq_halo2_amd.api import Sha256Circuit, Sha512Circuit
 
     ctx = Context(0)
-    for k in (int(s) for s in args.sizes.split(",") if s):
+    legs = args.legs.split(",")
+    for k in (int(s) for s in args.sizes.split(",") if s and "circuits" in legs):
         wide = circuit_row(ctx, "Sha512Circuit", lambda: Sha512Circuit(ctx, k), 128, 17, hashlib.sha512, args.reps, args.warmup)
         print(json.dumps(wide), flush=True)
         narrow = circuit_row(ctx, "Sha256Circuit", lambda: Sha256Circuit(ctx, k), 64, 9, hashlib.sha256, args.reps, args.warmup)
@@ -76,6 +156,10 @@ def main():
         print(json.dumps({"k": k, **{leg + "_sha512_over_sha256": round(wide[leg + "_ms"] / narrow[leg + "_ms"], 3)
                                      for leg in ("synthesize", "check", "proof")},
                           "message_bytes_sha512_over_sha256": round(wide["message_bytes"] / narrow["message_bytes"], 3)}), flush=True)
+    if "batch" in legs:
+        batch_rows(ctx, args.segments_k, args.reps, args.warmup)
+    if "merkle" in legs:
+        merkle_row(ctx, args.segments_k, args.reps, args.warmup)
     ctx.close()
 
 
