@@ -24,24 +24,13 @@
 
 #include "cq.hpp"
 #include "ctx.hpp"
-#include "sha256_layout.hpp"
+#include "sha2.hpp"
 #include "tablehash.hpp"
 
 namespace cq {
 
-// region kinds (Sha256Region::meta, low byte; the round number sits above it)
-constexpr uint32_t SHA_RG_ROUND = 1;  // a compression round: the additions that give a_r and e_r, the copy of K_r
-constexpr uint32_t SHA_RG_SCHED = 2;  // rounds 16 .. 63: W_r is a schedule word
-constexpr uint32_t SHA_RG_CHAIN = 4;  // incoming state of a block after the first, or the digest: H + (a .. h)
-constexpr uint32_t SHA_RG_F3 = 8;     // Maj and Ch are laid out (the two regions before this one hold state words)
-
-struct Sha256Region {
-  uint32_t a, e, w, meta;
-};
-
-struct Sha256Cols {
-  Fr* p[CQ_SHA256_ADVICE_COLUMNS];
-};
+using Sha256 = Sha2Family<uint32_t>;
+using Sha256Region = Sha256::Region;
 
 #define SHA256_K_VALUES \
   0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be, \
@@ -55,26 +44,7 @@ __constant__ const uint32_t SHA256_K_DEV[64] = {SHA256_K_VALUES};
 #define SHA256_IV_VALUES 0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19
 static const uint32_t SHA256_IV[8] = {SHA256_IV_VALUES};
 
-#define SHA_HD __host__ __device__ __forceinline__
-static SHA_HD uint32_t rotr(uint32_t x, uint32_t n) { return (x >> n) | (x << (32 - n)); }
-static SHA_HD uint32_t xor3(uint32_t x, uint32_t y, uint32_t z) { return x ^ y ^ z; }
-static SHA_HD uint32_t maj3(uint32_t x, uint32_t y, uint32_t z) { return (x & y) | (x & z) | (y & z); }
-static SHA_HD uint32_t big_sigma0(uint32_t a) { return xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)); }
-static SHA_HD uint32_t big_sigma1(uint32_t e) { return xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)); }
-static SHA_HD uint32_t small_sigma0(uint32_t w) { return xor3(rotr(w, 7), rotr(w, 18), w >> 3); }
-static SHA_HD uint32_t small_sigma1(uint32_t w) { return xor3(rotr(w, 17), rotr(w, 19), w >> 10); }
-static SHA_HD uint32_t ch3(uint32_t e, uint32_t f, uint32_t g) { return (e & f) | (~e & g); }
-
-// bit i -> bit 2i of a 32-bit word
-static __device__ __forceinline__ uint64_t spread32(uint32_t w) {
-  uint64_t x = w;
-  x = (x | (x << 16)) & 0x0000ffff0000ffffull;
-  x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
-  x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
-  x = (x | (x << 2)) & 0x3333333333333333ull;
-  x = (x | (x << 1)) & 0x5555555555555555ull;
-  return x;
-}
+__device__ __forceinline__ uint32_t Sha2Family<uint32_t>::k(uint32_t t) { return SHA256_K_DEV[t]; }
 
 // cell I of the layout table, if it sits in row r: the bit field of its word, and the spread form where the cell has one.
 // The table entry is a compile-time constant, so `src` and `out` are only ever indexed by constants and stay in registers.
@@ -100,62 +70,22 @@ static __device__ __forceinline__ void sha256_place_all(const uint32_t (&src)[CQ
 // the row's cell of every column, Montgomery-encoded; a fold over the columns, because a loop the compiler declines to
 // unroll would index `out` at run time and send it to scratch memory
 template <uint32_t... I>
-static __device__ __forceinline__ void sha256_store_all(const Sha256Cols& cols, const uint64_t (&out)[CQ_SHA256_ADVICE_COLUMNS], uint32_t row,
+static __device__ __forceinline__ void sha256_store_all(const Sha2Cols& cols, const uint64_t (&out)[CQ_SHA256_ADVICE_COLUMNS], uint32_t row,
                                                         std::integer_sequence<uint32_t, I...>) {
   (st(cols.p[I] + row, out[I] ? Fr::from_u64(out[I]) : Fr::zero()), ...);
 }
 
-// One thread per row.  `regions` holds `nregions` entries; rows behind them are written as zero.  Every index below is
-// guarded by the region kind the host sets and by the region index itself.
+// One thread per row.  `regions` holds `nregions` entries; rows behind them are written as zero.
 __global__ __launch_bounds__(256) void sha256_expand_kernel(const Sha256Region* __restrict__ regions, uint32_t nregions, uint32_t n,
-                                                            uint32_t table_bits, Sha256Cols cols) {
+                                                            uint32_t table_bits, Sha2Cols cols) {
   const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
   const uint32_t g = row / CQ_SHA256_REGION_ROWS, r = row % CQ_SHA256_REGION_ROWS;
   uint64_t out[CQ_SHA256_ADVICE_COLUMNS];
   CQ_UNROLL for (uint32_t i = 0; i < CQ_SHA256_ADVICE_COLUMNS; i++) out[i] = 0;
   if (g < nregions) {
-    const Sha256Region cur = regions[g];
-    const uint32_t kind = cur.meta & 0xffu;
     uint32_t src[CQ_SHA256_SRC_COUNT];
-    CQ_UNROLL for (uint32_t i = 0; i < CQ_SHA256_SRC_COUNT; i++) src[i] = 0;
-    src[CQ_SHA256_SRC_A] = cur.a;
-    src[CQ_SHA256_SRC_E] = cur.e;
-    src[CQ_SHA256_SRC_W] = cur.w;
-    src[CQ_SHA256_SRC_S0_EVEN] = big_sigma0(cur.a);
-    src[CQ_SHA256_SRC_S0_ODD] = maj3(rotr(cur.a, 2), rotr(cur.a, 13), rotr(cur.a, 22));
-    src[CQ_SHA256_SRC_S1_EVEN] = big_sigma1(cur.e);
-    src[CQ_SHA256_SRC_S1_ODD] = maj3(rotr(cur.e, 6), rotr(cur.e, 11), rotr(cur.e, 25));
-    src[CQ_SHA256_SRC_G0_EVEN] = small_sigma0(cur.w);
-    src[CQ_SHA256_SRC_G0_ODD] = maj3(rotr(cur.w, 7), rotr(cur.w, 18), cur.w >> 3);
-    src[CQ_SHA256_SRC_G1_EVEN] = small_sigma1(cur.w);
-    src[CQ_SHA256_SRC_G1_ODD] = maj3(rotr(cur.w, 17), rotr(cur.w, 19), cur.w >> 10);
-    if ((kind & SHA_RG_F3) && g >= 2) {
-      const Sha256Region p1 = regions[g - 1], p2 = regions[g - 2];
-      src[CQ_SHA256_SRC_MAJ_EVEN] = xor3(cur.a, p1.a, p2.a);
-      src[CQ_SHA256_SRC_MAJ_ODD] = maj3(cur.a, p1.a, p2.a);
-      src[CQ_SHA256_SRC_CHP_EVEN] = cur.e ^ p1.e;
-      src[CQ_SHA256_SRC_CHP_ODD] = cur.e & p1.e;
-      src[CQ_SHA256_SRC_CHQ_EVEN] = ~cur.e ^ p2.e;
-      src[CQ_SHA256_SRC_CHQ_ODD] = ~cur.e & p2.e;
-      src[CQ_SHA256_SRC_CH] = ch3(cur.e, p1.e, p2.e);
-    }
-    if ((kind & SHA_RG_ROUND) && g >= 4) {
-      const Sha256Region p1 = regions[g - 1], p2 = regions[g - 2], p3 = regions[g - 3], p4 = regions[g - 4];
-      const uint32_t k = SHA256_K_DEV[(cur.meta >> 8) & 63u];
-      const uint64_t t1 = (uint64_t)p4.e + big_sigma1(p1.e) + ch3(p1.e, p2.e, p3.e) + k + cur.w;
-      src[CQ_SHA256_SRC_K] = k;
-      src[CQ_SHA256_SRC_CARRY_E] = (uint32_t)((t1 + p4.a) >> 32);
-      src[CQ_SHA256_SRC_CARRY_A] = (uint32_t)((t1 + big_sigma0(p1.a) + maj3(p1.a, p2.a, p3.a)) >> 32);
-    }
-    if ((kind & SHA_RG_SCHED) && g >= 16)
-      src[CQ_SHA256_SRC_CARRY_W] = (uint32_t)(((uint64_t)small_sigma1(regions[g - 2].w) + regions[g - 7].w +
-                                               small_sigma0(regions[g - 15].w) + regions[g - 16].w) >> 32);
-    if ((kind & SHA_RG_CHAIN) && g >= CQ_SHA256_BLOCK_REGIONS) {
-      const Sha256Region h = regions[g - CQ_SHA256_BLOCK_REGIONS], v = regions[g - 4];
-      src[CQ_SHA256_SRC_CARRY_A] = (uint32_t)(((uint64_t)h.a + v.a) >> 32);
-      src[CQ_SHA256_SRC_CARRY_E] = (uint32_t)(((uint64_t)h.e + v.e) >> 32);
-    }
+    sha2_fill_src(src, regions, g);
     sha256_place_all(src, out, r, table_bits, std::make_integer_sequence<uint32_t, SHA256_NUM_CELLS>{});
   }
   sha256_store_all(cols, out, row, std::make_integer_sequence<uint32_t, CQ_SHA256_ADVICE_COLUMNS>{});
@@ -190,7 +120,7 @@ static void sha256_regions(const uint32_t* msg, size_t blocks, std::vector<Sha25
   for (int i = 0; i < 8; i++) digest[i] = h[i];
 }
 
-int sha256_synthesize(cq_ctx* c, uint32_t table_bits, const uint32_t* msg_words, size_t blocks, uint32_t n, const Sha256Cols& cols,
+int sha256_synthesize(cq_ctx* c, uint32_t table_bits, const uint32_t* msg_words, size_t blocks, uint32_t n, const Sha2Cols& cols,
                       uint32_t digest[8]) {
   std::vector<Sha256Region> rg;
   sha256_regions(msg_words, blocks, rg, digest);
@@ -207,29 +137,6 @@ int sha256_synthesize(cq_ctx* c, uint32_t table_bits, const uint32_t* msg_words,
 
 // ---- wired segments: the compression chains on the device ------------------------------------------------------------
 
-// One chain of a level's launch: where its regions and its 16 * blocks word sources start, and which segment it is.
-struct Sha256Lane {
-  uint32_t first_region, blocks, first_source, segment;
-};
-
-static __device__ __forceinline__ void sha256_put(Sha256Region* p, uint32_t a, uint32_t e, uint32_t w, uint32_t meta) {
-  *reinterpret_cast<uint4*>(p) = make_uint4(a, e, w, meta);
-}
-
-// a_-4 .. a_-1 = d, c, b, a and e_-4 .. e_-1 = h, g, f, e, as sha256_regions' state_regions lays them out
-static __device__ __forceinline__ void sha256_put_state(Sha256Region* out, const uint32_t (&h)[8], uint32_t chain) {
-  sha256_put(out + 0, h[3], h[7], 0, chain);
-  sha256_put(out + 1, h[2], h[6], 0, chain);
-  sha256_put(out + 2, h[1], h[5], 0, chain | SHA_RG_F3);
-  sha256_put(out + 3, h[0], h[4], 0, chain | SHA_RG_F3);
-}
-
-// A plain source: a word of the caller's buffer or a digest word an earlier level's launch stored.  The host has checked
-// every source against both arrays' lengths.
-static __device__ __forceinline__ uint32_t sha256_load(uint32_t s, const uint32_t* words, const uint32_t* digests) {
-  return *((s & CQ_SHA256_SOURCE_DIGEST) ? digests + (s & (CQ_SHA256_SOURCE_DIGEST - 1)) : words + s);
-}
-
 // One entry of the choice table as the device sees it: the bit's index in the word buffer, the two operands (plain
 // sources), and -- filled in by the host -- the region of the message word that refers to the entry.
 struct Sha256Choice {
@@ -244,40 +151,17 @@ static __device__ __forceinline__ void sha256_fetch(uint32_t (&w)[16], const uin
   const uint32_t s = src[I];
   if (CHOICES && !(s & CQ_SHA256_SOURCE_DIGEST) && s >= CQ_SHA256_SOURCE_CHOICE) {
     const uint4 c = *reinterpret_cast<const uint4*>(choices + (s - CQ_SHA256_SOURCE_CHOICE));
-    const uint32_t bit = words[c.x], zero = sha256_load(c.y, words, digests), one = sha256_load(c.z, words, digests);
+    const uint32_t bit = words[c.x], zero = sha2_load(c.y, words, digests), one = sha2_load(c.z, words, digests);
     w[I] = bit ? one : zero;
   } else {
-    w[I] = sha256_load(s, words, digests);
+    w[I] = sha2_load(s, words, digests);
   }
 }
 
-// Round T0 + I on the 16-word rolling schedule and the state (a .. h), and its region.  I is a compile-time constant, so
-// `w` and `s` are only ever indexed by constants and stay in registers; T0, the group's first round, may be a loop variable.
-template <bool SCHED, uint32_t I>
-static __device__ __forceinline__ void sha256_step(uint32_t (&s)[8], uint32_t (&w)[16], uint32_t t0, Sha256Region* out) {
-  if (SCHED) w[I] += small_sigma1(w[(I + 14) & 15]) + w[(I + 9) & 15] + small_sigma0(w[(I + 1) & 15]);
-  const uint32_t t1 = s[7] + big_sigma1(s[4]) + ch3(s[4], s[5], s[6]) + SHA256_K_DEV[t0 + I] + w[I];
-  const uint32_t t2 = big_sigma0(s[0]) + maj3(s[0], s[1], s[2]);
-  s[7] = s[6], s[6] = s[5], s[5] = s[4], s[4] = s[3] + t1;
-  s[3] = s[2], s[2] = s[1], s[1] = s[0], s[0] = t1 + t2;
-  sha256_put(out + t0 + I, s[0], s[4], w[I], SHA_RG_ROUND | SHA_RG_F3 | (SCHED ? SHA_RG_SCHED : 0) | (t0 + I) << 8);
-}
-template <bool SCHED, uint32_t... I>
-static __device__ __forceinline__ void sha256_steps(uint32_t (&s)[8], uint32_t (&w)[16], uint32_t t0, Sha256Region* out,
-                                                    std::integer_sequence<uint32_t, I...>) {
-  (sha256_step<SCHED, I>(s, w, t0, out), ...);
-}
 template <bool CHOICES, uint32_t... I>
 static __device__ __forceinline__ void sha256_fetch_all(uint32_t (&w)[16], const uint32_t* src, const Sha256Choice* choices, const uint32_t* words,
                                                         const uint32_t* digests, std::integer_sequence<uint32_t, I...>) {
   (sha256_fetch<CHOICES, I>(w, src, choices, words, digests), ...);
-}
-
-// Word I of the state a lane's chain starts from: the IV's on the sentinel, else a plain source -- read from `init_words`,
-// which is the word buffer or a buffer of states of its own.  I is a compile-time constant, so `h` stays in registers.
-template <uint32_t I>
-static __device__ __forceinline__ void sha256_fetch_init(uint32_t (&h)[8], uint32_t s, const uint32_t* init_words, const uint32_t* digests) {
-  if (s != CQ_SHA256_SOURCE_IV) h[I] = sha256_load(s, init_words, digests);
 }
 
 // One lane per segment of one level: what sha256_regions does for one message, with the message words gathered through
@@ -289,41 +173,26 @@ static __device__ __forceinline__ void sha256_fetch_init(uint32_t (&h)[8], uint3
 // (32 bytes, aligned to 16), each CQ_SHA256_SOURCE_IV or a plain source into `init_words` / `digests`, checked by the
 // host like a message word's; lanes of one wave may mix the two.  Without INIT neither pointer is looked at.
 template <bool CHOICES, bool INIT>
-__global__ __launch_bounds__(64) void sha256_chain_kernel(const Sha256Lane* __restrict__ lanes, uint32_t nlanes,
+__global__ __launch_bounds__(64) void sha256_chain_kernel(const Sha2Lane* __restrict__ lanes, uint32_t nlanes,
                                                           const uint32_t* __restrict__ sources, const Sha256Choice* __restrict__ choices,
                                                           const uint32_t* words, uint32_t* digests, Sha256Region* __restrict__ regions,
                                                           const uint32_t* __restrict__ init_sources, const uint32_t* init_words) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nlanes) return;
-  const Sha256Lane lane = lanes[i];
-  using Seq16 = std::make_integer_sequence<uint32_t, 16>;
+  const Sha2Lane lane = lanes[i];
   uint32_t h[8] = {SHA256_IV_VALUES};
-  if (INIT) {
-    const uint4* is = reinterpret_cast<const uint4*>(init_sources + 8 * (size_t)lane.segment);
-    const uint4 lo = is[0], hi = is[1];
-    sha256_fetch_init<0>(h, lo.x, init_words, digests), sha256_fetch_init<1>(h, lo.y, init_words, digests);
-    sha256_fetch_init<2>(h, lo.z, init_words, digests), sha256_fetch_init<3>(h, lo.w, init_words, digests);
-    sha256_fetch_init<4>(h, hi.x, init_words, digests), sha256_fetch_init<5>(h, hi.y, init_words, digests);
-    sha256_fetch_init<6>(h, hi.z, init_words, digests), sha256_fetch_init<7>(h, hi.w, init_words, digests);
-  }
+  if (INIT) sha2_fetch_init_all(h, init_sources + 8 * (size_t)lane.tag, init_words, digests);
   Sha256Region* out = regions + lane.first_region;
   const uint32_t* src = sources + lane.first_source;
-  for (uint32_t b = 0; b < lane.blocks; b++, out += CQ_SHA256_BLOCK_REGIONS, src += 16) {
-    sha256_put_state(out, h, b ? SHA_RG_CHAIN : 0);
-    uint32_t w[16], s[8] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]};
-    sha256_fetch_all<CHOICES>(w, src, choices, words, digests, Seq16{});
-    sha256_steps<false>(s, w, 0, out + 4, Seq16{});
-    for (uint32_t t0 = 16; t0 < 64; t0 += 16) sha256_steps<true>(s, w, t0, out + 4, Seq16{});
-    h[0] += s[0], h[1] += s[1], h[2] += s[2], h[3] += s[3];
-    h[4] += s[4], h[5] += s[5], h[6] += s[6], h[7] += s[7];
-  }
-  sha256_put_state(out, h, SHA_RG_CHAIN);
-  uint32_t* d = digests + 8 * (size_t)lane.segment;
-  d[0] = h[0], d[1] = h[1], d[2] = h[2], d[3] = h[3], d[4] = h[4], d[5] = h[5], d[6] = h[6], d[7] = h[7];
+  for (uint32_t b = 0; b < lane.blocks; b++, out += CQ_SHA256_BLOCK_REGIONS, src += 16)
+    sha2_block(h, out, b ? SHA_RG_CHAIN : 0, [&](uint32_t (&w)[16]) {
+      sha256_fetch_all<CHOICES>(w, src, choices, words, digests, std::make_integer_sequence<uint32_t, 16>{});
+    });
+  sha2_finish(h, out, digests + 8 * (size_t)lane.tag);
 }
 
 // the chain launch of one level: the instantiation that knows no more than the description needs
-static void sha256_launch_chain(cq_ctx* c, bool choices, bool init, uint32_t grid, const Sha256Lane* lanes, uint32_t nlanes, const uint32_t* sources,
+static void sha256_launch_chain(cq_ctx* c, bool choices, bool init, uint32_t grid, const Sha2Lane* lanes, uint32_t nlanes, const uint32_t* sources,
                                 const Sha256Choice* dev_choices, const uint32_t* words, uint32_t* digests, Sha256Region* regions,
                                 const uint32_t* init_sources, const uint32_t* init_words) {
   if (choices && init)
@@ -346,7 +215,7 @@ __global__ __launch_bounds__(64) void sha256_choice_fill_kernel(const Sha256Choi
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nchoices) return;
   const uint4 c = *reinterpret_cast<const uint4*>(choices + i);
-  const uint32_t bit = words[c.x], zero = sha256_load(c.y, words, digests), one = sha256_load(c.z, words, digests);
+  const uint32_t bit = words[c.x], zero = sha2_load(c.y, words, digests), one = sha2_load(c.z, words, digests);
   Fr* cell = y + (size_t)c.w * CQ_SHA256_REGION_ROWS;
   st(cell + CQ_SHA256_CHOICE_ROW_ZERO, zero ? Fr::from_u64(zero) : Fr::zero());
   st(cell + CQ_SHA256_CHOICE_ROW_ONE, one ? Fr::from_u64(one) : Fr::zero());
@@ -369,10 +238,10 @@ __global__ __launch_bounds__(64) void sha256_xor_kernel(const Sha256XorUnit* __r
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nunits) return;
   const uint4 u = *reinterpret_cast<const uint4*>(units + i);
-  const uint32_t x = sha256_load(u.x, words, digests), y = sha256_load(u.y, words, digests);
+  const uint32_t x = sha2_load(u.x, words, digests), y = sha2_load(u.y, words, digests);
   digests[u.z] = x ^ y;
-  sha256_put(regions + u.w, 0, x, 0, 0);
-  sha256_put(regions + u.w + 1, 0, y, x ^ y, SHA_RG_F3);
+  sha2_put<uint32_t>(regions + u.w, 0, x, 0, 0);
+  sha2_put<uint32_t>(regions + u.w + 1, 0, y, x ^ y, SHA_RG_F3);
 }
 
 // Validates the description, then queues the tables' upload, one chain launch per level, the expansion and -- with
@@ -385,15 +254,10 @@ __global__ __launch_bounds__(64) void sha256_xor_kernel(const Sha256XorUnit* __r
 // whose result the level's XOR launch stores at that word of `digests_dev` before the chains that read it run.
 int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* sources,
                                const uint32_t* choices, size_t n_choices, const uint32_t* init_sources, const uint32_t* xors, size_t n_xors,
-                               const uint32_t* words_dev, size_t words_len, uint32_t n, const Sha256Cols& cols, uint32_t* digests_dev) {
+                               const uint32_t* words_dev, size_t words_len, uint32_t n, const Sha2Cols& cols, uint32_t* digests_dev) {
   const uint64_t max_regions = n / CQ_SHA256_REGION_ROWS;
-  uint64_t regions = 0, blocks = 0;
-  for (size_t j = 0; j < segments; j++) {
-    if (seg_blocks[j] == 0) return c->fail(CQ_ERR_ARG, "sha256: segment " + std::to_string(j) + " has no block");
-    blocks += seg_blocks[j];
-    regions += (uint64_t)seg_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS;
-    if (regions > max_regions) return c->fail(CQ_ERR_ARG, "sha256: the segments up to segment " + std::to_string(j) + " do not fit the rows");
-  }
+  uint64_t regions, blocks;
+  CQ_TRY(sha2_count_segments<Sha256>(c, seg_blocks, nullptr, segments, n, regions, blocks));
   if (regions + CQ_SHA256_XOR_REGIONS * (uint64_t)n_xors > max_regions)
     return c->fail(CQ_ERR_ARG, "sha256: the area of " + std::to_string(n_xors) + " xor units behind the segments does not fit the rows");
   for (size_t u = 0; u < n_xors; u++)  // the operands: plain sources, a digest's of a segment that exists (no unit's result)
@@ -408,38 +272,22 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
       }
       if (!bad.empty()) return c->fail(CQ_ERR_ARG, "sha256: xor unit " + std::to_string(u) + (o ? ", operand y" : ", operand x") + bad);
     }
-  std::vector<uint32_t> level(segments, 0), level_count;
+  std::vector<uint32_t> level(segments, 0);
   std::vector<uint32_t> choice_region(n_choices, UINT32_MAX);  // the region of the word that refers to the entry, once one does
   uint32_t seg_region = 0;
   for (size_t j = 0, at = 0; j < segments; seg_region += seg_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS, j++) {
     for (size_t i = 0; init_sources && i < 8; i++) {  // the state the chain starts from: the IV's word or a plain source
       const uint32_t s = init_sources[8 * j + i];
-      std::string bad;
       if (s == CQ_SHA256_SOURCE_IV) continue;
-      if (s & CQ_SHA256_SOURCE_DIGEST) {
-        const size_t ref = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3;
-        if (ref >= j) bad = " reads the digest of segment " + std::to_string(ref) + ", which does not come before it";
-        else if (level[ref] + 1 > level[j]) level[j] = level[ref] + 1;
-      } else if (n_choices && s >= CQ_SHA256_SOURCE_CHOICE) {
-        bad = " is a choice, which an initial word cannot be";
-      } else if (s >= words_len) {
-        bad = " reads word " + std::to_string(s) + " of a buffer of " + std::to_string(words_len);
-      }
+      const std::string bad = !(s & CQ_SHA256_SOURCE_DIGEST) && n_choices && s >= CQ_SHA256_SOURCE_CHOICE
+                                  ? " is a choice, which an initial word cannot be"
+                                  : sha2_plain_source(s, j, words_len, level);
       if (!bad.empty()) return c->fail(CQ_ERR_ARG, "sha256: segment " + std::to_string(j) + ", initial word " + std::to_string(i) + bad);
     }
     for (size_t t = 0; t < 16 * (size_t)seg_blocks[j]; t++, at++) {
       auto where = [&] { return "sha256: segment " + std::to_string(j) + ", word " + std::to_string(t); };
       // a plain source, the word's own or a choice's operand: "" if it is good, and the segment's level follows a digest's
-      auto plain = [&](uint32_t s) -> std::string {
-        if (s & CQ_SHA256_SOURCE_DIGEST) {
-          const size_t ref = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3;
-          if (ref >= j) return " reads the digest of segment " + std::to_string(ref) + ", which does not come before it";
-          if (level[ref] + 1 > level[j]) level[j] = level[ref] + 1;
-        } else if (s >= words_len) {
-          return " reads word " + std::to_string(s) + " of a buffer of " + std::to_string(words_len);
-        }
-        return "";
-      };
+      auto plain = [&](uint32_t s) { return sha2_plain_source(s, j, words_len, level); };
       const uint32_t s = sources[at];
       std::string bad;
       if (n_choices && !(s & CQ_SHA256_SOURCE_DIGEST) && s >= CQ_SHA256_SOURCE_CHOICE) {
@@ -468,12 +316,8 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
   }
   for (size_t e = 0; e < n_choices; e++)
     if (choice_region[e] == UINT32_MAX) return c->fail(CQ_ERR_ARG, "sha256: choice " + std::to_string(e) + " is read by no word");
-  for (uint32_t l : level) {
-    if (l >= level_count.size()) level_count.resize(l + 1, 0);
-    level_count[l]++;
-  }
-  std::vector<uint32_t> level_first(level_count.size(), 0);
-  for (size_t l = 1; l < level_count.size(); l++) level_first[l] = level_first[l - 1] + level_count[l - 1];
+  const Sha2Levels lv = sha2_levels(level);
+  const std::vector<uint32_t>&level_count = lv.count, &level_first = lv.first;
   // a unit is ready at level 0 if it reads no digest, else one level above the highest level it reads: at most one level
   // behind the last chain launch.  Every segment's level is final by now, whether or not a word reads the unit.
   std::vector<uint32_t> xor_level(n_xors, 0), xor_count(n_xors ? level_count.size() + 1 : 0, 0);
@@ -487,30 +331,19 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
   std::vector<uint32_t> xor_first(xor_count.size(), 0);
   for (size_t l = 1; l < xor_count.size(); l++) xor_first[l] = xor_first[l - 1] + xor_count[l - 1];
 
-  static_assert(sizeof(Sha256Region) == 16 && sizeof(Sha256Lane) == 16 && sizeof(Sha256XorUnit) == 16, "four words each");
+  static_assert(sizeof(Sha256Region) == 16 && sizeof(Sha2Lane) == 16 && sizeof(Sha256XorUnit) == 16, "four words each");
   static_assert(sizeof(Sha256XorUnit) == CQ_SHA256_XOR_WORDS * sizeof(uint32_t), "an entry of the xor table as the header states it");
   static_assert(sizeof(Sha256Choice) == CQ_SHA256_CHOICE_WORDS * sizeof(uint32_t), "an entry of the choice table as the header states it");
   // lanes, sources, choices, initial sources, xor units: each a multiple of 16 bytes, so the choice entries, a segment's
   // eight initial sources and the units are aligned for their 16-byte loads
-  const size_t lanes_bytes = segments * sizeof(Sha256Lane), sources_bytes = 16 * blocks * sizeof(uint32_t);
+  const size_t lanes_bytes = segments * sizeof(Sha2Lane), sources_bytes = 16 * blocks * sizeof(uint32_t);
   const size_t choices_bytes = n_choices * sizeof(Sha256Choice), init_bytes = init_sources ? 8 * segments * sizeof(uint32_t) : 0;
   const size_t xors_bytes = n_xors * sizeof(Sha256XorUnit);
   const size_t tables_bytes = lanes_bytes + sources_bytes + choices_bytes + init_bytes + xors_bytes;
   const uint64_t all_regions = regions + CQ_SHA256_XOR_REGIONS * (uint64_t)n_xors;  // the units' regions lie behind the last tail
   void *pin, *dev_regions, *dev_tables;
-  CQ_TRY(c->ensure_pinned_sha(tables_bytes, &pin));
-  CQ_TRY(c->ensure_scratch(Scratch::EntryA, all_regions * sizeof(Sha256Region), &dev_regions));
-  CQ_TRY(c->ensure_scratch(Scratch::EntryB, tables_bytes, &dev_tables));
-  if (!c->sha_staged) CQ_HIP(c, hipEventCreateWithFlags(&c->sha_staged, hipEventDisableTiming));
-  CQ_HIP(c, hipEventSynchronize(c->sha_staged));  // the previous call's copy out of `pin` (at once if there was none)
-  Sha256Lane* lanes = (Sha256Lane*)pin;
-  std::vector<uint32_t> next = level_first;
-  uint32_t first_region = 0, first_source = 0;
-  for (size_t j = 0; j < segments; j++) {  // lanes in level order, segments of one level in row order
-    lanes[next[level[j]]++] = {first_region, seg_blocks[j], first_source, (uint32_t)j};
-    first_region += seg_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS;
-    first_source += 16 * seg_blocks[j];
-  }
+  CQ_TRY(sha2_stage(c, tables_bytes, all_regions * sizeof(Sha256Region), tables_bytes, &pin, &dev_regions, &dev_tables));
+  sha2_fill_lanes<Sha256>((Sha2Lane*)pin, seg_blocks, segments, level, lv, [](size_t j) { return (uint32_t)j; });
   memcpy((char*)pin + lanes_bytes, sources, sources_bytes);
   Sha256Choice* staged = (Sha256Choice*)((char*)pin + lanes_bytes + sources_bytes);
   for (size_t e = 0; e < n_choices; e++)
@@ -521,9 +354,8 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
   for (size_t u = 0; u < n_xors; u++)  // units in level order; unit u keeps its result word and its regions whatever its level
     units[next_unit[xor_level[u]]++] = {xors[CQ_SHA256_XOR_WORDS * u], xors[CQ_SHA256_XOR_WORDS * u + 1], (uint32_t)(8 * segments + u),
                                         (uint32_t)(regions + CQ_SHA256_XOR_REGIONS * u)};
-  CQ_HIP(c, hipMemcpyAsync(dev_tables, pin, tables_bytes, hipMemcpyHostToDevice, c->stream));
-  CQ_HIP(c, hipEventRecord(c->sha_staged, c->stream));
-  const Sha256Lane* dev_lanes = (const Sha256Lane*)dev_tables;
+  CQ_TRY(sha2_upload(c, dev_tables, pin, tables_bytes));
+  const Sha2Lane* dev_lanes = (const Sha2Lane*)dev_tables;
   const uint32_t* dev_sources = (const uint32_t*)((const char*)dev_tables + lanes_bytes);
   const Sha256Choice* dev_choices = (const Sha256Choice*)((const char*)dev_sources + sources_bytes);
   const uint32_t* dev_init = (const uint32_t*)((const char*)dev_choices + choices_bytes);
@@ -562,7 +394,7 @@ struct Sha256VarMsg {
 
 // The segment that holds word `word` of the word buffer: lanes are in segment order there and lane j's words start at
 // first_source, ascending, lane 0's at 0; `word` lies below the buffer's end.
-static __device__ __forceinline__ uint32_t sha256_var_segment(const Sha256Lane* __restrict__ lanes, uint32_t nlanes, uint32_t word) {
+static __device__ __forceinline__ uint32_t sha256_var_segment(const Sha2Lane* __restrict__ lanes, uint32_t nlanes, uint32_t word) {
   uint32_t lo = 0, hi = nlanes;  // lanes[lo].first_source <= word < lanes[hi].first_source (hi = nlanes: the end)
   while (hi - lo > 1) {
     const uint32_t mid = lo + (hi - lo) / 2;
@@ -577,7 +409,7 @@ static SHA_HD uint32_t sha256_var_final_block(uint32_t len) { return (len + 8) /
 // One thread per word of the word buffer (16 per block of every segment, segment after segment): the big-endian word of
 // the padded message -- data bytes, 0x80, zeros, the bit length of base + len bytes in word 15 of the final block (the
 // host has checked that it is a 32-bit word) -- and zero behind the final block.  A byte is loaded only below the message's length, which the host has checked against the buffer.
-__global__ __launch_bounds__(256) void sha256_pad_kernel(const Sha256Lane* __restrict__ lanes, const Sha256VarMsg* __restrict__ msgs,
+__global__ __launch_bounds__(256) void sha256_pad_kernel(const Sha2Lane* __restrict__ lanes, const Sha256VarMsg* __restrict__ msgs,
                                                          uint32_t nlanes, uint32_t nwords, const uint8_t* __restrict__ bytes,
                                                          uint32_t* __restrict__ words) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -615,14 +447,14 @@ static __device__ __forceinline__ uint32_t sha256_var_len(uint32_t g, uint32_t l
 // to the word selected so far; the last block's sum goes to `digests`, over the chain kernel's digest.  25: the final
 // flag.  26: the same sum for the length.  The host has checked that every region of every lane lies below
 // n / CQ_SHA256_REGION_ROWS; `regions` is what the chain kernel left.
-__global__ __launch_bounds__(256) void sha256_varlen_fill_kernel(const Sha256Lane* __restrict__ lanes, const Sha256VarMsg* __restrict__ msgs,
+__global__ __launch_bounds__(256) void sha256_varlen_fill_kernel(const Sha2Lane* __restrict__ lanes, const Sha256VarMsg* __restrict__ msgs,
                                                                  uint32_t nlanes, uint32_t nblocks, const Sha256Region* __restrict__ regions,
-                                                                 Sha256Cols cols, uint32_t* __restrict__ digests) {
+                                                                 Sha2Cols cols, uint32_t* __restrict__ digests) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t gb = i / 32, role = i % 32;
   if (gb >= nblocks || role > 26) return;
   const uint32_t j = sha256_var_segment(lanes, nlanes, 16 * gb);
-  const Sha256Lane lane = lanes[j];
+  const Sha2Lane lane = lanes[j];
   const uint32_t b = gb - lane.first_source / 16, len = msgs[j].len, base = msgs[j].base, fb = sha256_var_final_block(len);
   const uint32_t block_region = lane.first_region + b * CQ_SHA256_BLOCK_REGIONS;
   Fr* const y = cols.p[SHA256_COL_Y];
@@ -673,7 +505,7 @@ __global__ __launch_bounds__(256) void sha256_varlen_fill_kernel(const Sha256Lan
     sha256_var_put(y + row + CQ_SHA256_VAR_ROW_FLAG, b == fb ? 1u : 0u);
     sha256_var_put(y + row + CQ_SHA256_VAR_ROW_VALUE, is_len ? sha256_var_len(16 * b + 15, len, fb, base) : chaining(b, w));
     sha256_var_put(y + row + CQ_SHA256_VAR_ROW_OUT, out);
-    if (!is_len && b + 1 == lane.blocks) digests[8 * (size_t)lane.segment + w] = out;
+    if (!is_len && b + 1 == lane.blocks) digests[8 * (size_t)lane.tag + w] = out;
   }
 }
 
@@ -686,15 +518,10 @@ __global__ __launch_bounds__(256) void sha256_varlen_fill_kernel(const Sha256Lan
 // initial sources, which rides behind the word sources in the same upload.
 int sha256_synthesize_varlen(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_max_blocks, size_t segments, const uint8_t* bytes_dev,
                              size_t bytes_len, const uint64_t* offsets, const uint64_t* lens, const uint32_t* init_states_dev,
-                             const uint64_t* base_lens, uint32_t n, const Sha256Cols& cols, uint32_t* digests_dev) {
-  const uint64_t max_regions = n / CQ_SHA256_REGION_ROWS;
-  uint64_t regions = 0, blocks = 0;
-  for (size_t j = 0; j < segments; j++) {
+                             const uint64_t* base_lens, uint32_t n, const Sha2Cols& cols, uint32_t* digests_dev) {
+  uint64_t regions, blocks;
+  CQ_TRY(sha2_count_segments<Sha256>(c, seg_max_blocks, nullptr, segments, n, regions, blocks, [&](size_t j) {
     auto seg = [&] { return "sha256: segment " + std::to_string(j); };
-    if (seg_max_blocks[j] == 0) return c->fail(CQ_ERR_ARG, seg() + " has no block");
-    blocks += seg_max_blocks[j];
-    regions += (uint64_t)seg_max_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS;
-    if (regions > max_regions) return c->fail(CQ_ERR_ARG, "sha256: the segments up to segment " + std::to_string(j) + " do not fit the rows");
     // n < 2^31 bounds the blocks, so 64 * blocks stays far below 2^29 and 8 * length is a 32-bit word
     if (lens[j] > 64 * (uint64_t)seg_max_blocks[j] - 9)
       return c->fail(CQ_ERR_ARG, seg() + ": a message of " + std::to_string(lens[j]) + " bytes does not pad to " +
@@ -708,34 +535,26 @@ int sha256_synthesize_varlen(cq_ctx* c, uint32_t table_bits, const uint32_t* seg
     if (base_lens && (base_lens[j] > (1ull << 29) || base_lens[j] + 64 * (uint64_t)seg_max_blocks[j] > (1ull << 29)))
       return c->fail(CQ_ERR_ARG, seg() + ": a base of " + std::to_string(base_lens[j]) + " bytes and " + std::to_string(seg_max_blocks[j]) +
                                      " blocks reach past 2^29 bytes");
-  }
+    return (int)CQ_OK;
+  }));
   static_assert(sizeof(Sha256VarMsg) == 16, "four words");
-  const size_t lanes_bytes = segments * sizeof(Sha256Lane), msgs_bytes = segments * sizeof(Sha256VarMsg);
+  const size_t lanes_bytes = segments * sizeof(Sha2Lane), msgs_bytes = segments * sizeof(Sha256VarMsg);
   const size_t nwords = 16 * blocks, words_bytes = nwords * sizeof(uint32_t);
   const size_t init_bytes = init_states_dev ? 8 * segments * sizeof(uint32_t) : 0;
   // the sources: one index per word; each part a multiple of 16 bytes
   const size_t tables_bytes = lanes_bytes + msgs_bytes + words_bytes + init_bytes;
   void *pin, *dev_regions, *dev_tables;
-  CQ_TRY(c->ensure_pinned_sha(tables_bytes, &pin));
-  CQ_TRY(c->ensure_scratch(Scratch::EntryA, regions * sizeof(Sha256Region), &dev_regions));
-  CQ_TRY(c->ensure_scratch(Scratch::EntryB, tables_bytes + words_bytes, &dev_tables));  // behind the tables: the word buffer
-  if (!c->sha_staged) CQ_HIP(c, hipEventCreateWithFlags(&c->sha_staged, hipEventDisableTiming));
-  CQ_HIP(c, hipEventSynchronize(c->sha_staged));  // the previous call's copy out of `pin` (at once if there was none)
-  Sha256Lane* lanes = (Sha256Lane*)pin;
+  CQ_TRY(sha2_stage(c, tables_bytes, regions * sizeof(Sha256Region), tables_bytes + words_bytes, &pin, &dev_regions,
+                    &dev_tables));  // behind the tables: the word buffer
+  Sha2Lane* lanes = (Sha2Lane*)pin;
   Sha256VarMsg* msgs = (Sha256VarMsg*)((char*)pin + lanes_bytes);
   uint32_t* sources = (uint32_t*)((char*)pin + lanes_bytes + msgs_bytes);
-  uint32_t first_region = 0, first_source = 0;
-  for (size_t j = 0; j < segments; j++) {
-    lanes[j] = {first_region, seg_max_blocks[j], first_source, (uint32_t)j};
-    msgs[j] = {offsets[j], (uint32_t)lens[j], base_lens ? (uint32_t)base_lens[j] : 0u};
-    first_region += seg_max_blocks[j] * CQ_SHA256_BLOCK_REGIONS + CQ_SHA256_TAIL_REGIONS;
-    first_source += 16 * seg_max_blocks[j];
-  }
+  sha2_fill_lanes<Sha256>(lanes, seg_max_blocks, segments, {}, {}, [](size_t j) { return (uint32_t)j; });
+  for (size_t j = 0; j < segments; j++) msgs[j] = {offsets[j], (uint32_t)lens[j], base_lens ? (uint32_t)base_lens[j] : 0u};
   for (size_t i = 0; i < nwords; i++) sources[i] = (uint32_t)i;
   for (size_t i = 0; i < init_bytes / sizeof(uint32_t); i++) sources[nwords + i] = (uint32_t)i;
-  CQ_HIP(c, hipMemcpyAsync(dev_tables, pin, tables_bytes, hipMemcpyHostToDevice, c->stream));
-  CQ_HIP(c, hipEventRecord(c->sha_staged, c->stream));
-  const Sha256Lane* dev_lanes = (const Sha256Lane*)dev_tables;
+  CQ_TRY(sha2_upload(c, dev_tables, pin, tables_bytes));
+  const Sha2Lane* dev_lanes = (const Sha2Lane*)dev_tables;
   const Sha256VarMsg* dev_msgs = (const Sha256VarMsg*)((const char*)dev_tables + lanes_bytes);
   const uint32_t* dev_sources = (const uint32_t*)((const char*)dev_msgs + msgs_bytes);
   uint32_t* dev_words = (uint32_t*)((char*)dev_tables + tables_bytes);
@@ -773,14 +592,8 @@ int cq_sha256_layout(uint32_t* cells, size_t cap, size_t* count) {
 int cq_sha256_synthesize_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* msg_words, size_t blocks, size_t n,
                              uint64_t* const* cols_dev, uint32_t digest[8]) {
   if (!c || !msg_words || !cols_dev || !digest || blocks == 0 || n > 0x7fffffffull || blocks > n) return CQ_ERR_ARG;
-  if (table_bits < CQ_SHA256_MIN_TABLE_BITS || table_bits > CQ_SHA256_MAX_TABLE_BITS)
-    return c->fail(CQ_ERR_ARG, "sha256: table_bits outside the range the pieces fit");
-  CQ_HIP(c, hipSetDevice(c->device));
-  Sha256Cols sc;
-  for (uint32_t i = 0; i < CQ_SHA256_ADVICE_COLUMNS; i++) {
-    if (!cols_dev[i]) return c->fail(CQ_ERR_ARG, "sha256: null column");
-    sc.p[i] = (Fr*)cols_dev[i];
-  }
+  Sha2Cols sc;
+  CQ_TRY(sha2_entry(c, "sha256", nullptr, table_bits, CQ_SHA256_MIN_TABLE_BITS, CQ_SHA256_MAX_TABLE_BITS, "the pieces", cols_dev, sc));
   return sha256_synthesize(c, table_bits, msg_words, blocks, (uint32_t)n, sc, digest);
 }
 
@@ -789,20 +602,16 @@ static int sha256_segments_entry(cq_ctx* c, uint32_t table_bits, const uint32_t*
                                  const uint32_t* choices, size_t n_choices, const uint32_t* init_sources, const uint32_t* xors, size_t n_xors,
                                  const uint32_t* words_dev, size_t words_len, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
   if (!c) return CQ_ERR_ARG;
+  const char* bad = nullptr;
   if (!seg_blocks || !sources || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull || (!words_dev && words_len) ||
       words_len > CQ_SHA256_SOURCE_DIGEST)
-    return c->fail(CQ_ERR_ARG, "sha256: null array, no segment, or a length out of range");
-  if (n_choices && (!choices || words_len > CQ_SHA256_SOURCE_CHOICE || n_choices > n))
-    return c->fail(CQ_ERR_ARG, "sha256: null choice table, more choices than rows, or a word buffer that reaches the choice flag");
-  if (n_xors && (!xors || n_xors > n)) return c->fail(CQ_ERR_ARG, "sha256: null xor table, or more xor units than rows");
-  if (table_bits < CQ_SHA256_MIN_TABLE_BITS || table_bits > CQ_SHA256_MAX_TABLE_BITS)
-    return c->fail(CQ_ERR_ARG, "sha256: table_bits outside the range the pieces fit");
-  CQ_HIP(c, hipSetDevice(c->device));
-  Sha256Cols sc;
-  for (uint32_t i = 0; i < CQ_SHA256_ADVICE_COLUMNS; i++) {
-    if (!cols_dev[i]) return c->fail(CQ_ERR_ARG, "sha256: null column");
-    sc.p[i] = (Fr*)cols_dev[i];
-  }
+    bad = SHA2_BAD_ARGS;
+  else if (n_choices && (!choices || words_len > CQ_SHA256_SOURCE_CHOICE || n_choices > n))
+    bad = "null choice table, more choices than rows, or a word buffer that reaches the choice flag";
+  else if (n_xors && (!xors || n_xors > n))
+    bad = "null xor table, or more xor units than rows";
+  Sha2Cols sc;
+  CQ_TRY(sha2_entry(c, "sha256", bad, table_bits, CQ_SHA256_MIN_TABLE_BITS, CQ_SHA256_MAX_TABLE_BITS, "the pieces", cols_dev, sc));
   return sha256_synthesize_segments(c, table_bits, seg_blocks, segments, sources, choices, n_choices, init_sources, xors, n_xors, words_dev,
                                     words_len, (uint32_t)n, sc, digests_dev);
 }
@@ -842,17 +651,11 @@ static int sha256_varlen_entry(cq_ctx* c, uint32_t table_bits, const uint32_t* s
                                size_t msg_bytes_len, const uint64_t* msg_offsets, const uint64_t* msg_lens, const uint32_t* init_states_dev,
                                const uint64_t* base_lens, size_t n, uint64_t* const* cols_dev, uint32_t* digests_dev) {
   if (!c) return CQ_ERR_ARG;
-  if (!seg_max_blocks || !msg_offsets || !msg_lens || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull ||
-      (!msg_bytes_dev && msg_bytes_len))
-    return c->fail(CQ_ERR_ARG, "sha256: null array, no segment, or a length out of range");
-  if (table_bits < CQ_SHA256_VAR_MIN_TABLE_BITS || table_bits > CQ_SHA256_MAX_TABLE_BITS)
-    return c->fail(CQ_ERR_ARG, "sha256: table_bits outside the range the 12-bit halves of a boundary word's bytes fit");
-  CQ_HIP(c, hipSetDevice(c->device));
-  Sha256Cols sc;
-  for (uint32_t i = 0; i < CQ_SHA256_ADVICE_COLUMNS; i++) {
-    if (!cols_dev[i]) return c->fail(CQ_ERR_ARG, "sha256: null column");
-    sc.p[i] = (Fr*)cols_dev[i];
-  }
+  const bool bad = !seg_max_blocks || !msg_offsets || !msg_lens || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull ||
+                   (!msg_bytes_dev && msg_bytes_len);
+  Sha2Cols sc;
+  CQ_TRY(sha2_entry(c, "sha256", bad ? SHA2_BAD_ARGS : nullptr, table_bits, CQ_SHA256_VAR_MIN_TABLE_BITS, CQ_SHA256_MAX_TABLE_BITS,
+                    "the 12-bit halves of a boundary word's bytes", cols_dev, sc));
   return sha256_synthesize_varlen(c, table_bits, seg_max_blocks, segments, msg_bytes_dev, msg_bytes_len, msg_offsets, msg_lens, init_states_dev,
                                   base_lens, (uint32_t)n, sc, digests_dev);
 }

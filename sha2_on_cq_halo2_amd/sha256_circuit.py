@@ -14,18 +14,17 @@ from typing import NamedTuple
 import numpy as np
 
 from . import plonk as GP
-from ._lib import constants, load
+from . import sha2_family as F
+from ._lib import constants
 from ._marshal import fr_to_mont
 from .context import Context
 from .params import ParamsKZG, StaticTable, TableConfig
 from .proving_key import ProvingKey
+from .sha2_family import ADVICE_COLUMNS, FIXED, FORM_PAIR, FORM_SPREAD, FORM_WORD, GATES, PAIRS, SRC, Cell  # noqa: F401
 
 _CQ = constants()
 REGION_ROWS, BLOCK_REGIONS, TAIL_REGIONS = (_CQ["CQ_SHA256_" + s] for s in ("REGION_ROWS", "BLOCK_REGIONS", "TAIL_REGIONS"))
-PAIRS, ADVICE_COLUMNS = _CQ["CQ_SHA256_PAIRS"], _CQ["CQ_SHA256_ADVICE_COLUMNS"]
 MIN_TABLE_BITS, MAX_TABLE_BITS = _CQ["CQ_SHA256_MIN_TABLE_BITS"], _CQ["CQ_SHA256_MAX_TABLE_BITS"]
-FORM_WORD, FORM_PAIR, FORM_SPREAD = (_CQ["CQ_SHA256_FORM_" + s] for s in ("WORD", "PAIR", "SPREAD"))
-SRC = {name[len("CQ_SHA256_SRC_"):]: v for name, v in _CQ.items() if name.startswith("CQ_SHA256_SRC_") and name != "CQ_SHA256_SRC_COUNT"}
 
 K256 = [
     0x428A2F98, 0x71374491, 0xB5C0FBCF, 0xE9B5DBA5, 0x3956C25B, 0x59F111F1, 0x923F82A4, 0xAB1C5ED5,
@@ -38,14 +37,10 @@ K256 = [
     0x748F82EE, 0x78A5636F, 0x84C87814, 0x8CC70208, 0x90BEFFFA, 0xA4506CEB, 0xBEF9A3F7, 0xC67178F2,
 ]
 IV256 = [0x6A09E667, 0xBB67AE85, 0x3C6EF372, 0xA54FF53A, 0x510E527F, 0x9B05688C, 0x1F83D9AB, 0x5BE0CD19]
-SPREAD_ONES = (4 ** 32 - 1) // 3  # the spread form of 0xFFFFFFFF
+FAMILY = F.Family(32, "CQ_SHA256_", "cq_sha256_layout", (((2, 13, 22), None), ((6, 11, 25), None), ((7, 18), 3), ((17, 19), 10)),
+                  tuple(K256), chunk_length_checked=False)
+SPREAD_ONES = FAMILY.spread_ones  # the spread form of 0xFFFFFFFF
 
-# gate polynomials in cs.gates order (the `index` of a FAIL_GATE finding); every one is anchored on row 0 of a region
-GATES = ("a_word", "a_spread", "e_word", "e_spread", "w_word", "Sigma0_even_odd", "Sigma0_word", "Sigma1_even_odd", "Sigma1_word",
-         "sigma0_even_odd", "sigma0_word", "sigma1_even_odd", "sigma1_word", "maj_even_odd", "maj_word", "chp_even_odd",
-         "chq_even_odd", "ch_word", "e_add", "a_add", "w_add", "chain_a", "chain_e")
-# fixed columns in allocation order
-FIXED = ("q_all", "q_f3", "q_round", "q_sched", "q_chain") + tuple(f"scale{j}" for j in range(PAIRS)) + ("const",)
 # the choice variant of the constraint system (plans with a Choice word, sha256_segments.py): one selector behind `const`,
 # two gates behind the others, and three cells in the rows column Y leaves free in a region
 GATES_CHOICE = GATES + ("choice", "choice_bit")
@@ -66,32 +61,13 @@ FIXED_XOR = FIXED + ("q_xor",)
 XOR_REGIONS, XOR_WORDS = _CQ["CQ_SHA256_XOR_REGIONS"], _CQ["CQ_SHA256_XOR_WORDS"]
 
 
-class Cell(NamedTuple):
-    """One entry of the layout table (cq_sha256_layout)."""
-
-    kind: int
-    form: int
-    column: int
-    row: int
-    offset: int
-    per_table_bits: int
-    len: int
-
-
 def layout():
     """The layout table of csrc/sha256_layout.hpp as the library exports it (host only: no GPU needed)."""
-    lib = load()
-    count = C.c_size_t()
-    assert lib.cq_sha256_layout(None, 0, C.byref(count)) == 0
-    words = _CQ["CQ_SHA256_CELL_WORDS"]
-    assert words == len(Cell._fields)
-    arr = (C.c_uint32 * (words * count.value))()
-    assert lib.cq_sha256_layout(arr, count.value, C.byref(count)) == 0
-    return [Cell(*arr[words * i: words * (i + 1)]) for i in range(count.value)]
+    return F.layout(FAMILY)
 
 
 def rows_for(blocks: int) -> int:
-    return (BLOCK_REGIONS * blocks + TAIL_REGIONS) * REGION_ROWS
+    return F.rows_for(FAMILY, blocks)
 
 
 def pad(message: bytes, blocks: int | None = None):
@@ -124,8 +100,7 @@ class Description(NamedTuple):
 
 def _field_of(cell: Cell, tb: int):
     """(bit offset, length) of the cell's field within its word at table size 2^tb."""
-    off = cell.offset + cell.per_table_bits * tb
-    return off, (cell.len if cell.len else max(0, min(tb, 32 - off)))
+    return F.field_of(FAMILY, cell, tb)
 
 
 def describe(k: int, blocks: int, table_bits: int = 12, dense="dense", spread="spread") -> Description:
@@ -147,78 +122,10 @@ def _constraint_system(tb: int, dense, spread, choice: bool = False, varlen: boo
         raise ValueError("a variable-length segment does not combine with choice-wired words")
     if xor and (choice or varlen):
         raise ValueError("XOR-wired words do not combine with choice-wired words or a variable-length segment")
-    cells = layout()
-    cs = GP.ConstraintSystem()
-    adv = [cs.advice_column() for _ in range(ADVICE_COLUMNS)]
-    fcol = {name: cs.fixed_column() for name in (FIXED_CHOICE if choice else FIXED_VARLEN if varlen else FIXED_XOR if xor else FIXED)}
-    inst = cs.instance_column()
-    X, Y = adv[2 * PAIRS], adv[2 * PAIRS + 1]
-    for c in (X, fcol["const"], inst) + ((Y,) if choice or varlen else ()):
-        cs.enable_equality(c)
-
-    pieces = {s: sorted((c for c in cells if c.kind == s and c.form == FORM_PAIR and c.len), key=lambda c: c.offset) for s in SRC.values()}
-    chunks = {s: sorted((c for c in cells if c.kind == s and c.form == FORM_PAIR and not c.len), key=lambda c: c.per_table_bits)
-              for s in SRC.values()}
-    word = {(c.kind, c.form): c for c in cells if c.form != FORM_PAIR}
-
-    def q(cell, spread_form=False, regions_back=0):
-        return cs.query_advice(adv[cell.column + (1 if spread_form else 0)], cell.row - REGION_ROWS * regions_back)
-
-    def lin(terms):
-        acc = None
-        for coef, e in terms:
-            t = e if coef == 1 else e * coef
-            acc = t if acc is None else acc + t
-        return acc
-
-    def w(name, form=FORM_WORD, back=0):
-        return q(word[(SRC[name], form)], regions_back=back)
-
-    def rotated_spread(name, rots, shift):
-        """sum over the rotations (and the one shift) of the word's spread form, from its pieces' spread cells"""
-        terms = []
-        for p in pieces[SRC[name]]:
-            for r in rots:
-                assert p.offset + p.len <= r or p.offset >= r, "a piece straddles a rotation"
-                terms.append((4 ** ((p.offset - r) % 32), q(p, True)))
-            if shift is not None and p.offset >= shift:
-                terms.append((4 ** (p.offset - shift), q(p, True)))
-            assert shift is None or p.offset + p.len <= shift or p.offset >= shift, "a piece straddles the shift"
-        return lin(terms)
-
-    def even_odd(name):
-        return lin([(4 ** (c.per_table_bits * tb) * m, q(c, True)) for m, s in ((1, name + "_EVEN"), (2, name + "_ODD")) for c in chunks[SRC[s]]])
-
-    def from_chunks(*names):
-        return lin([(2 ** (c.per_table_bits * tb), q(c)) for s in names for c in chunks[SRC[s]]])
-
-    def carry(name):
-        (c,) = pieces[SRC[name]]
-        return q(c) * (1 << 32)
-
-    sel = {name: cs.query_fixed(fcol[name]) for name in ("q_all", "q_f3", "q_round", "q_sched", "q_chain")}
-    polys = {}
-    for name, s in (("a", "A"), ("e", "E"), ("w", "W")):
-        polys[name + "_word"] = sel["q_all"] * (w(s) - lin([(2 ** p.offset, q(p)) for p in pieces[SRC[s]]]))
-        if s != "W":
-            polys[name + "_spread"] = sel["q_all"] * (w(s, FORM_SPREAD) - lin([(4 ** p.offset, q(p, True)) for p in pieces[SRC[s]]]))
-    for gate, s, src, rots, shift in (("Sigma0", "S0", "A", (2, 13, 22), None), ("Sigma1", "S1", "E", (6, 11, 25), None),
-                                      ("sigma0", "G0", "W", (7, 18), 3), ("sigma1", "G1", "W", (17, 19), 10)):
-        polys[gate + "_even_odd"] = sel["q_all"] * (rotated_spread(src, rots, shift) - even_odd(s))
-        polys[gate + "_word"] = sel["q_all"] * (w(s + "_EVEN") - from_chunks(s + "_EVEN"))
-    sa, se = (lambda back: w("A", FORM_SPREAD, back)), (lambda back: w("E", FORM_SPREAD, back))
-    polys["maj_even_odd"] = sel["q_f3"] * (sa(0) + sa(1) + sa(2) - even_odd("MAJ"))
-    polys["maj_word"] = sel["q_f3"] * (w("MAJ_ODD") - from_chunks("MAJ_ODD"))
-    polys["chp_even_odd"] = sel["q_f3"] * (se(0) + se(1) - even_odd("CHP"))
-    polys["chq_even_odd"] = sel["q_f3"] * (GP.Expression.constant(SPREAD_ONES) - se(0) + se(2) - even_odd("CHQ"))
-    polys["ch_word"] = sel["q_f3"] * (w("CH") - from_chunks("CHP_ODD", "CHQ_ODD"))
-    # T1 = h + Sigma1(e) + Ch(e, f, g) + K + W with e, f, g, h = e_(r-1) .. e_(r-4); e_r = d + T1; a_r = T1 + Sigma0 + Maj
-    t1 = w("E", back=4) + w("S1_EVEN", back=1) + w("CH", back=1) + w("K") + w("W")
-    polys["e_add"] = sel["q_round"] * (w("E") + carry("CARRY_E") - w("A", back=4) - t1)
-    polys["a_add"] = sel["q_round"] * (w("A") + carry("CARRY_A") - t1 - w("S0_EVEN", back=1) - w("MAJ_ODD", back=1))
-    polys["w_add"] = sel["q_sched"] * (w("W") + carry("CARRY_W") - w("G1_EVEN", back=2) - w("W", back=7) - w("G0_EVEN", back=15) - w("W", back=16))
-    for name, s in (("a", "A"), ("e", "E")):  # H + (a .. h): the same slot one block and four regions back
-        polys["chain_" + name] = sel["q_chain"] * (w(s) + carry("CARRY_" + s) - w(s, back=BLOCK_REGIONS) - w(s, back=4))
+    names = FIXED_CHOICE if choice else FIXED_VARLEN if varlen else FIXED_XOR if xor else FIXED
+    system = F.base_system(FAMILY, tb, names, equality_on_y=choice or varlen)
+    cs, adv, fcol, cells, polys, w = system.cs, system.advice, system.fixed_columns, system.cells, system.polys, system.w
+    Y = adv[2 * PAIRS + 1]
     if choice:  # W = x + d * (y - x) with d boolean: x, y, d in the rows of Y that no layout cell uses
         assert not any(c.column == Y.index and c.row in (CHOICE_ROW_ZERO, CHOICE_ROW_ONE, CHOICE_ROW_BIT) for c in cells)
         q_choice = cs.query_fixed(fcol["q_choice"])
@@ -228,19 +135,11 @@ def _constraint_system(tb: int, dense, spread, choice: bool = False, varlen: boo
     if varlen:
         _varlen_gates(cs, polys, cells, adv, fcol, w)
     if xor:  # W = e_r ^ e_(r-1): under q_f3 `chp_even_odd` makes the CHP_EVEN chunks the even bits of spread(e_r) + spread(e_(r-1))
-        polys["xor_word"] = cs.query_fixed(fcol["q_xor"]) * (w("W") - from_chunks("CHP_EVEN"))
-    gates = GATES_CHOICE if choice else GATES_VARLEN if varlen else GATES_XOR if xor else GATES
-    assert tuple(polys) != () and set(polys) == set(gates)
-    for name in gates:
-        cs.create_gate(name, [polys[name]])
-    # lookups 0 .. 7: (dense_j, spread_j) in (dense, spread); 8 .. 15: dense_j * scale_j in dense -- the length check
-    for j in range(PAIRS):
-        cs.lookup_static(f"pair{j}", [(adv[2 * j], dense), (adv[2 * j + 1], spread)])
-    for j in range(PAIRS):
-        cs.lookup_static(f"length{j}", [(cs.query_advice(adv[2 * j]) * cs.query_fixed(fcol[f"scale{j}"]), dense)])
+        polys["xor_word"] = cs.query_fixed(fcol["q_xor"]) * (w("W") - system.from_chunks("CHP_EVEN"))
+    out = F.finish(system, dense, spread, GATES_CHOICE if choice else GATES_VARLEN if varlen else GATES_XOR if xor else GATES)
     if xor:  # the gate adds three dense cells of row 6 and one fixed column to the queries, nothing to the blinding rows or the degree
         assert (cs.blinding_factors(), cs.degree()) == (20, 4)
-    return cs, adv, fcol, inst, cells, word
+    return out
 
 
 def _varlen_gates(cs, polys, cells, adv, fcol, w):
@@ -301,54 +200,21 @@ def _assign_fixed(k, blocks, tb, cs, adv, fcol, inst, cells, word) -> Descriptio
 
 
 def _assign_segment(fixed, copies, first_region, blocks, public, tb, adv, fcol, inst, cells, word, init=None):
-    """The fixed cells and the copies of one chain of `blocks` blocks whose regions start at `first_region`: selectors and
-    scales, the round constants, the state it starts from on its first four regions (no q_chain before its second block),
-    and -- where `public` is not None -- the copies of instance rows 8 * public .. 8 * public + 7 to the digest words of its
-    tail.  `init`: H[0..7] of that state, each a constant pinned through `const` or None for a cell the caller ties (or
-    leaves free) itself; the default is the IV."""
-    init = IV256 if init is None else init
-    X = adv[2 * PAIRS]
-    regions = BLOCK_REGIONS * blocks + TAIL_REGIONS
-    g = np.arange(regions)
-    in_block, base = g % BLOCK_REGIONS, (first_region + g) * REGION_ROWS
-    is_tail = g >= BLOCK_REGIONS * blocks
-    is_round = (in_block >= 4) & ~is_tail
-    fixed["q_all"][base] = 1
-    fixed["q_f3"][base[in_block >= 2]] = 1
-    fixed["q_round"][base[is_round]] = 1
-    fixed["q_sched"][base[is_round & (in_block >= 20)]] = 1
-    fixed["q_chain"][base[(in_block < 4) & (g >= BLOCK_REGIONS)]] = 1
-    for c in cells:
-        if c.form == FORM_PAIR:
-            _, ln = _field_of(c, tb)
-            fixed[f"scale{c.column // 2}"][base + c.row] = 1 << (tb - ln) if c.len else 1
-    krow = word[(SRC["K"], FORM_WORD)].row
-    arow, erow = word[(SRC["A"], FORM_WORD)].row, word[(SRC["E"], FORM_WORD)].row
-    kvals = np.array(K256, dtype=np.uint64)
-    rb = base[is_round]
-    fixed["const"][rb + krow] = kvals[(in_block[is_round] - 4)]
-    copies += [((fcol["const"], int(r) + krow), (X, int(r) + krow)) for r in rb]
-    for i in range(4):  # region i of the first block holds a_(i-4) = H[3 - i] and e_(i-4) = H[7 - i]
-        head = int(base[i])
-        for row, val in ((arow, init[3 - i]), (erow, init[7 - i])):
-            if val is None:
-                continue
-            fixed["const"][head + row] = val
-            copies.append(((fcol["const"], head + row), (X, head + row)))
-        if public is not None:
-            tail = int(base[BLOCK_REGIONS * blocks + i])
-            copies.append(((inst, 8 * public + 3 - i), (X, tail + arow)))
-            copies.append(((inst, 8 * public + 7 - i), (X, tail + erow)))
+    """F.assign_segment for a SHA-256 chain: where `public` is not None, instance rows 8 * public .. 8 * public + 7 are
+    copied to the digest words of its tail.  `init`: H[0..7] of the state it starts from, each a constant pinned through
+    `const` or None for a cell the caller ties (or leaves free) itself; the default is the IV."""
+    F.assign_segment(FAMILY, fixed, copies, first_region, blocks, IV256 if init is None else init,
+                     lambda h: None if public is None else 8 * public + h, True, tb, adv, fcol, inst, cells, word)
 
 
 def usable_rows(k: int, table_bits: int = 12) -> int:
     """The rows of 2^k a circuit may use: all but the blinding rows and the one behind them."""
-    return (1 << k) - (_constraint_system(table_bits, "dense", "spread")[0].blinding_factors() + 1)
+    return F.usable_rows(FAMILY, k, table_bits)
 
 
 def max_blocks(k: int, table_bits: int = 12) -> int:
     """The largest block count whose rows fit the usable rows of 2^k."""
-    return (usable_rows(k, table_bits) // REGION_ROWS - TAIL_REGIONS) // BLOCK_REGIONS
+    return F.max_blocks(FAMILY, k, table_bits)
 
 
 def _mont_column(vals: np.ndarray) -> np.ndarray:

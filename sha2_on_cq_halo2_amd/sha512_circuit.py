@@ -16,10 +16,12 @@ from typing import NamedTuple
 import numpy as np
 
 from . import plonk as GP
-from ._lib import constants, load
+from . import sha2_family as F
+from ._lib import constants
 from ._marshal import fr_to_mont
 from .context import Context
-from .sha256_circuit import ADVICE_COLUMNS, FORM_PAIR, FORM_SPREAD, FORM_WORD, PAIRS, SRC, Cell, _build_key, _close_key, _mont_column  # noqa: F401
+from .sha256_circuit import _build_key, _close_key, _mont_column  # noqa: F401
+from .sha2_family import ADVICE_COLUMNS, FIXED, FORM_PAIR, FORM_SPREAD, FORM_WORD, GATES, PAIRS, SRC, Cell  # noqa: F401
 
 _CQ = constants()
 REGION_ROWS, BLOCK_REGIONS, TAIL_REGIONS = (_CQ["CQ_SHA512_" + s] for s in ("REGION_ROWS", "BLOCK_REGIONS", "TAIL_REGIONS"))
@@ -50,31 +52,18 @@ IV384 = [0xCBBB9D5DC1059ED8, 0x629A292A367CD507, 0x9159015A3070DD17, 0x152FECD8F
          0x67332667FFC00B31, 0x8EB44A8768581511, 0xDB0C2E0D64F98FA7, 0x47B5481DBEFA4FA4]
 IV = {VARIANT_512: IV512, VARIANT_384: IV384}
 DIGEST_WORDS = {VARIANT_512: 8, VARIANT_384: 6}
-SPREAD_ONES = (4 ** WORD_BITS - 1) // 3  # the spread form of 2^64 - 1
-
-# gate polynomials in cs.gates order (the `index` of a FAIL_GATE finding): the 23 kinds of the SHA-256 circuit, every one
-# anchored on row 0 of a region
-GATES = ("a_word", "a_spread", "e_word", "e_spread", "w_word", "Sigma0_even_odd", "Sigma0_word", "Sigma1_even_odd", "Sigma1_word",
-         "sigma0_even_odd", "sigma0_word", "sigma1_even_odd", "sigma1_word", "maj_even_odd", "maj_word", "chp_even_odd",
-         "chq_even_odd", "ch_word", "e_add", "a_add", "w_add", "chain_a", "chain_e")
-# fixed columns in allocation order
-FIXED = ("q_all", "q_f3", "q_round", "q_sched", "q_chain") + tuple(f"scale{j}" for j in range(PAIRS)) + ("const",)
+FAMILY = F.Family(WORD_BITS, "CQ_SHA512_", "cq_sha512_layout", (((28, 34, 39), None), ((14, 18, 41), None), ((1, 8), 7), ((19, 61), 6)),
+                  tuple(K512), chunk_length_checked=True)
+SPREAD_ONES = FAMILY.spread_ones  # the spread form of 2^64 - 1
 
 
 def layout():
     """The layout table of csrc/sha512_layout.hpp as the library exports it (host only: no GPU needed)."""
-    lib = load()
-    count = C.c_size_t()
-    assert lib.cq_sha512_layout(None, 0, C.byref(count)) == 0
-    words = _CQ["CQ_SHA256_CELL_WORDS"]
-    assert words == len(Cell._fields)
-    arr = (C.c_uint32 * (words * count.value))()
-    assert lib.cq_sha512_layout(arr, count.value, C.byref(count)) == 0
-    return [Cell(*arr[words * i: words * (i + 1)]) for i in range(count.value)]
+    return F.layout(FAMILY)
 
 
 def rows_for(blocks: int) -> int:
-    return (BLOCK_REGIONS * blocks + TAIL_REGIONS) * REGION_ROWS
+    return F.rows_for(FAMILY, blocks)
 
 
 def pad(message: bytes, blocks: int | None = None):
@@ -114,8 +103,7 @@ class Description(NamedTuple):
 def _field_of(cell: Cell, tb: int):
     """(bit offset, length) of the cell's field within its word at table size 2^tb; a chunk that starts at or above
     bit 64 has length 0."""
-    off = cell.offset + cell.per_table_bits * tb
-    return off, (cell.len if cell.len else max(0, min(tb, WORD_BITS - off)))
+    return F.field_of(FAMILY, cell, tb)
 
 
 def describe(k: int, blocks: int, table_bits: int = 12, dense="dense", spread="spread", variant: int = VARIANT_512) -> Description:
@@ -149,137 +137,27 @@ def describe_batch(k: int, blocks_list, variants=None, table_bits: int = 12, den
 
 
 def _constraint_system(tb: int, dense, spread):
-    cells = layout()
-    cs = GP.ConstraintSystem()
-    adv = [cs.advice_column() for _ in range(ADVICE_COLUMNS)]
-    fcol = {name: cs.fixed_column() for name in FIXED}
-    inst = cs.instance_column()
-    X = adv[2 * PAIRS]
-    for c in (X, fcol["const"], inst):
-        cs.enable_equality(c)
-
-    pieces = {s: sorted((c for c in cells if c.kind == s and c.form == FORM_PAIR and c.len), key=lambda c: c.offset) for s in SRC.values()}
-    # a chunk that starts at or above bit 64 holds zero (the length lookup of its cell says so): the gates leave it out
-    chunks = {s: sorted((c for c in cells if c.kind == s and c.form == FORM_PAIR and not c.len and c.per_table_bits * tb < WORD_BITS),
-                        key=lambda c: c.per_table_bits) for s in SRC.values()}
-    word = {(c.kind, c.form): c for c in cells if c.form != FORM_PAIR}
-
-    def q(cell, spread_form=False, regions_back=0):
-        return cs.query_advice(adv[cell.column + (1 if spread_form else 0)], cell.row - REGION_ROWS * regions_back)
-
-    def lin(terms):
-        acc = None
-        for coef, e in terms:
-            t = e if coef == 1 else e * coef
-            acc = t if acc is None else acc + t
-        return acc
-
-    def w(name, form=FORM_WORD, back=0):
-        return q(word[(SRC[name], form)], regions_back=back)
-
-    def rotated_spread(name, rots, shift):
-        """sum over the rotations (and the one shift) of the word's spread form, from its pieces' spread cells"""
-        terms = []
-        for p in pieces[SRC[name]]:
-            for r in rots:
-                assert p.offset + p.len <= r or p.offset >= r, "a piece straddles a rotation"
-                terms.append((4 ** ((p.offset - r) % WORD_BITS), q(p, True)))
-            if shift is not None and p.offset >= shift:
-                terms.append((4 ** (p.offset - shift), q(p, True)))
-            assert shift is None or p.offset + p.len <= shift or p.offset >= shift, "a piece straddles the shift"
-        return lin(terms)
-
-    def even_odd(name):
-        return lin([(4 ** (c.per_table_bits * tb) * m, q(c, True)) for m, s in ((1, name + "_EVEN"), (2, name + "_ODD")) for c in chunks[SRC[s]]])
-
-    def from_chunks(*names):
-        return lin([(2 ** (c.per_table_bits * tb), q(c)) for s in names for c in chunks[SRC[s]]])
-
-    def carry(name):
-        (c,) = pieces[SRC[name]]
-        return q(c) * (1 << WORD_BITS)
-
-    sel = {name: cs.query_fixed(fcol[name]) for name in ("q_all", "q_f3", "q_round", "q_sched", "q_chain")}
-    polys = {}
-    for name, s in (("a", "A"), ("e", "E"), ("w", "W")):
-        polys[name + "_word"] = sel["q_all"] * (w(s) - lin([(2 ** p.offset, q(p)) for p in pieces[SRC[s]]]))
-        if s != "W":
-            polys[name + "_spread"] = sel["q_all"] * (w(s, FORM_SPREAD) - lin([(4 ** p.offset, q(p, True)) for p in pieces[SRC[s]]]))
-    for gate, s, src, rots, shift in (("Sigma0", "S0", "A", (28, 34, 39), None), ("Sigma1", "S1", "E", (14, 18, 41), None),
-                                      ("sigma0", "G0", "W", (1, 8), 7), ("sigma1", "G1", "W", (19, 61), 6)):
-        polys[gate + "_even_odd"] = sel["q_all"] * (rotated_spread(src, rots, shift) - even_odd(s))
-        polys[gate + "_word"] = sel["q_all"] * (w(s + "_EVEN") - from_chunks(s + "_EVEN"))
-    sa, se = (lambda back: w("A", FORM_SPREAD, back)), (lambda back: w("E", FORM_SPREAD, back))
-    polys["maj_even_odd"] = sel["q_f3"] * (sa(0) + sa(1) + sa(2) - even_odd("MAJ"))
-    polys["maj_word"] = sel["q_f3"] * (w("MAJ_ODD") - from_chunks("MAJ_ODD"))
-    polys["chp_even_odd"] = sel["q_f3"] * (se(0) + se(1) - even_odd("CHP"))
-    polys["chq_even_odd"] = sel["q_f3"] * (GP.Expression.constant(SPREAD_ONES) - se(0) + se(2) - even_odd("CHQ"))
-    polys["ch_word"] = sel["q_f3"] * (w("CH") - from_chunks("CHP_ODD", "CHQ_ODD"))
-    # T1 = h + Sigma1(e) + Ch(e, f, g) + K + W with e, f, g, h = e_(r-1) .. e_(r-4); e_r = d + T1; a_r = T1 + Sigma0 + Maj
-    t1 = w("E", back=4) + w("S1_EVEN", back=1) + w("CH", back=1) + w("K") + w("W")
-    polys["e_add"] = sel["q_round"] * (w("E") + carry("CARRY_E") - w("A", back=4) - t1)
-    polys["a_add"] = sel["q_round"] * (w("A") + carry("CARRY_A") - t1 - w("S0_EVEN", back=1) - w("MAJ_ODD", back=1))
-    polys["w_add"] = sel["q_sched"] * (w("W") + carry("CARRY_W") - w("G1_EVEN", back=2) - w("W", back=7) - w("G0_EVEN", back=15) - w("W", back=16))
-    for name, s in (("a", "A"), ("e", "E")):  # H + (a .. h): the same slot one block and four regions back
-        polys["chain_" + name] = sel["q_chain"] * (w(s) + carry("CARRY_" + s) - w(s, back=BLOCK_REGIONS) - w(s, back=4))
-    assert tuple(polys) != () and set(polys) == set(GATES)
-    for name in GATES:
-        cs.create_gate(name, [polys[name]])
-    # lookups 0 .. 7: (dense_j, spread_j) in (dense, spread); 8 .. 15: dense_j * scale_j in dense -- the length check
-    for j in range(PAIRS):
-        cs.lookup_static(f"pair{j}", [(adv[2 * j], dense), (adv[2 * j + 1], spread)])
-    for j in range(PAIRS):
-        cs.lookup_static(f"length{j}", [(cs.query_advice(adv[2 * j]) * cs.query_fixed(fcol[f"scale{j}"]), dense)])
-    return cs, adv, fcol, inst, cells, word
+    return F.finish(F.base_system(FAMILY, tb), dense, spread)
 
 
 def _assign_segment(fixed, copies, first_region, blocks, variant, public, tb, adv, fcol, inst, cells, word, pinned=None, public_words=None):
-    """The fixed cells and the copies of one chain of `blocks` blocks whose regions start at `first_region`: selectors and
-    scales, the round constants, the state it starts from on its first four regions (no q_chain before its second block),
-    and the copies of instance rows public .. public + public_words - 1 to the first digest words of its tail.  `pinned`:
-    H[0..7] of the state, each a constant pinned through `const` or None for a cell the caller ties (or leaves free) itself;
-    the default is the variant's initial hash value.  `public_words`: 0 .. 8, by default DIGEST_WORDS[variant]."""
-    X = adv[2 * PAIRS]
-    regions = BLOCK_REGIONS * blocks + TAIL_REGIONS
-    g = np.arange(regions)
-    in_block, base = g % BLOCK_REGIONS, (first_region + g) * REGION_ROWS
-    is_tail = g >= BLOCK_REGIONS * blocks
-    is_round = (in_block >= 4) & ~is_tail
-    fixed["q_all"][base] = 1
-    fixed["q_f3"][base[in_block >= 2]] = 1
-    fixed["q_round"][base[is_round]] = 1
-    fixed["q_sched"][base[is_round & (in_block >= 20)]] = 1
-    fixed["q_chain"][base[(in_block < 4) & (g >= BLOCK_REGIONS)]] = 1
-    for c in cells:
-        if c.form == FORM_PAIR:  # dense * 2^(tb - len) is in the table: dense < 2^len; a chunk past the word (len 0) is zero
-            _, ln = _field_of(c, tb)
-            fixed[f"scale{c.column // 2}"][base + c.row] = 1 << (tb - ln)
-    krow = word[(SRC["K"], FORM_WORD)].row
-    arow, erow = word[(SRC["A"], FORM_WORD)].row, word[(SRC["E"], FORM_WORD)].row
-    kvals = np.array(K512, dtype=np.uint64)
-    rb = base[is_round]
-    fixed["const"][rb + krow] = kvals[(in_block[is_round] - 4)]
-    copies += [((fcol["const"], int(r) + krow), (X, int(r) + krow)) for r in rb]
-    init = IV[variant] if pinned is None else pinned
+    """F.assign_segment for a SHA-512 / SHA-384 chain: instance rows public .. public + public_words - 1 are copied to the
+    first digest words of its tail.  `pinned`: H[0..7] of the state it starts from, each a constant pinned through `const`
+    or None for a cell the caller ties (or leaves free) itself; the default is the variant's initial hash value.
+    `public_words`: 0 .. 8, by default DIGEST_WORDS[variant]."""
     digest_words = DIGEST_WORDS[variant] if public_words is None else public_words
-    for i in range(4):  # region i of the first block holds a_(i-4) = H[3 - i] and e_(i-4) = H[7 - i]
-        head, tail = int(base[i]), int(base[BLOCK_REGIONS * blocks + i])
-        for row, h in ((arow, 3 - i), (erow, 7 - i)):
-            if init[h] is not None:
-                fixed["const"][head + row] = init[h]
-                copies.append(((fcol["const"], head + row), (X, head + row)))
-            if h < digest_words:
-                copies.append(((inst, public + h), (X, tail + row)))
+    F.assign_segment(FAMILY, fixed, copies, first_region, blocks, IV[variant] if pinned is None else pinned,
+                     lambda h: public + h if h < digest_words else None, False, tb, adv, fcol, inst, cells, word)
 
 
 def usable_rows(k: int, table_bits: int = 12) -> int:
     """The rows of 2^k a circuit may use: all but the blinding rows and the one behind them."""
-    return (1 << k) - (_constraint_system(table_bits, "dense", "spread")[0].blinding_factors() + 1)
+    return F.usable_rows(FAMILY, k, table_bits)
 
 
 def max_blocks(k: int, table_bits: int = 12) -> int:
     """The largest block count of one message whose rows fit the usable rows of 2^k."""
-    return (usable_rows(k, table_bits) // REGION_ROWS - TAIL_REGIONS) // BLOCK_REGIONS
+    return F.max_blocks(FAMILY, k, table_bits)
 
 
 class Sha512BatchCircuit:
