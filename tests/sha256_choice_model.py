@@ -1,15 +1,16 @@
 """Pure-Python model of plans with choice-wired message words (sha256_segments.Var / Choice): the plan is resolved, segment
 by segment, into one whose chosen and shared words are plain private words -- every digest an operand reads comes from
 hashlib over the earlier segment's message -- and the witness is sha256_segments_model's for that plan plus the three cells
-of every choice in column Y.  `findings` is sha256_circuit_model's with the description's own fixed-column names."""
+of every choice in column Y."""
 import hashlib
 import struct
 
-from sha2_on_cq_halo2_amd import plonk as GP
 from sha2_on_cq_halo2_amd import sha256_circuit as SC
 from sha2_on_cq_halo2_amd import sha256_segments as SS
 from tests import sha256_circuit_model as M
 from tests import sha256_segments_model as SM
+
+findings = M.findings  # over the fixed columns the description itself names (`fixed_names`)
 
 
 def resolve(plan, values, shared, bits):
@@ -80,32 +81,6 @@ def witness(plan, values, shared, bits, table_bits, n):
         assert y[r0] == y[r1] == y[rb] == 0, "the layout uses a choice cell"
         y[r0], y[r1], y[rb] = zero, one, bit
     return cols
-
-
-def findings(desc, advice, instance_words):
-    """sha256_circuit_model.findings over the fixed columns the description itself names (`fixed_names`): [(kind, index,
-    row)] of every unsatisfied gate, static lookup and copy on the usable rows."""
-    cs, n = desc.cs, 1 << desc.k
-    usable = n - (cs.blinding_factors() + 1)
-    fixed = [[int(v) for v in desc.fixed[name]] for name in desc.fixed_names]
-    inst = [list(instance_words)]
-    out = []
-    for gi, g in enumerate(cs.gates):
-        assert g.op == "mul" and g.a.op == "query" and g.a.a.kind == GP.COL_FIXED  # selector * (...)
-        selector = fixed[g.a.a.index]
-        out += [("gate", gi, r) for r in range(n) if selector[r] and M.evaluate(g.b, r, n, advice, fixed, inst)]
-    N = 1 << desc.table_bits
-    index = {"dense": {i: i for i in range(N)}, "spread": {M.spread(i): i for i in range(N)}}
-    exprs = iter(cs._lookup_exprs)
-    for li, lk in enumerate(cs.static_lookups):
-        ins = [(next(exprs), t) for _, t in lk]
-        for r in range(usable):
-            rows = {index[t].get(M.evaluate(e, r, n, advice, fixed, inst)) for e, t in ins}
-            if None in rows or len(rows) != 1:
-                out.append(("lookup", li, r))
-    val = lambda col, r: (advice, fixed, inst)[col.kind][col.index][r]
-    out += [("copy", i, lr) for i, ((lc, lr), (rc, rr)) in enumerate(desc.copies) if val(lc, lr) != val(rc, rr)]
-    return out
 
 
 def path_inputs(depth, items, leaf_blocks=None):

@@ -5,25 +5,10 @@ exceed 64 bits (the spread form of a 64-bit word has 128), so the model's intege
 import numpy as np
 
 from sha2_on_cq_halo2_amd import sha512_circuit as SC
-from sha2_on_cq_halo2_amd._marshal import fr_to_mont
 from tests import sha256_direct as D
+from tests.sha_oracle import mont_column  # noqa: F401
 
 GUARD, PATTERN = D.GUARD, D.PATTERN
-
-
-def mont_column(vals) -> np.ndarray:
-    """integers below the modulus -> uint64[n, 4] Montgomery limbs, one conversion per distinct value"""
-    if max(vals) < 1 << 64:
-        return SC._mont_column(np.array(vals, dtype=np.uint64))
-    index, uniq = {}, []
-    inv = np.empty(len(vals), dtype=np.int64)
-    for i, v in enumerate(vals):
-        j = index.get(v)
-        if j is None:
-            j = index[v] = len(uniq)
-            uniq.append(v)
-        inv[i] = j
-    return np.stack([fr_to_mont(u) for u in uniq])[inv]
 
 
 class Columns(D.Columns):

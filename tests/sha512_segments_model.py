@@ -1,109 +1,39 @@
-"""Pure-Python model of wired SHA-512 segments (sha512_segments.Plan): tests/sha512_circuit_model.py's round constants,
-initial hash values, bit sums and spread forms, with the compression restated for any 16 * blocks words and any initial
-state -- that model pads a message and starts from a variant's initial hash value -- and a plan-level witness that resolves
-every source, the initial words included, from the model's own final states, level by level.  The SHA-512/256 initial hash
-value is generated here as FIPS 180-4, 5.3.6 says.  hashlib is the reference the tests hold all of it to."""
+"""Pure-Python model of wired SHA-512 segments (sha512_segments.Plan): tests/sha2_model.py's compression and cells at 64
+bits for any 16 * blocks words and any initial state, the rows of a segment's wired cells, and a plan-level witness that
+resolves every source, the initial words included, from the model's own final states, level by level.  The SHA-512/256
+initial hash value is generated there as FIPS 180-4, 5.3.6 says.  hashlib is the reference the tests hold all of it to."""
 import struct
 
 from sha2_on_cq_halo2_amd import sha512_circuit as SC
 from sha2_on_cq_halo2_amd import sha512_segments as SS
+from tests import sha2_model as M2
 from tests import sha512_circuit_model as M
+from tests.sha2_model import levels  # noqa: F401
 
+W = M.W
 M64 = M.M64
 X = 2 * SC.PAIRS
-_LAYOUT = []
+IV512_256 = W.iv["sha512/256"]
 
 
 def layout():
-    if not _LAYOUT:
-        _LAYOUT.extend(SC.layout())
-    return _LAYOUT
+    return [c for c, _ in M2.layout(W)]
 
 
 def compress(words, blocks, init):
     """(per region (a, e, W, round or None, chained), the chaining values H_0 = `init` .. H_blocks)."""
-    h = list(init)
-    chaining, regions = [list(h)], []
-    for b in range(blocks):
-        regions += [(h[3 - i], h[7 - i], 0, None, b > 0) for i in range(4)]
-        w = list(words[16 * b: 16 * b + 16])
-        for t in range(16, 80):
-            s0 = M.rotr(w[t - 15], 1) ^ M.rotr(w[t - 15], 8) ^ (w[t - 15] >> 7)
-            s1 = M.rotr(w[t - 2], 19) ^ M.rotr(w[t - 2], 61) ^ (w[t - 2] >> 6)
-            w.append((w[t - 16] + s0 + w[t - 7] + s1) & M64)
-        s = list(h)
-        for t in range(80):
-            a, e = s[0], s[4]
-            t1 = s[7] + (M.rotr(e, 14) ^ M.rotr(e, 18) ^ M.rotr(e, 41)) + ((e & s[5]) ^ (~e & M64 & s[6])) + M.K[t] + w[t]
-            t2 = (M.rotr(a, 28) ^ M.rotr(a, 34) ^ M.rotr(a, 39)) + ((a & s[1]) ^ (a & s[2]) ^ (s[1] & s[2]))
-            s = [(t1 + t2) & M64] + s[:3] + [(s[3] + t1) & M64] + s[4:7]
-            regions.append((s[0], s[4], w[t], t, False))
-        h = [(x + y) & M64 for x, y in zip(h, s)]
-        chaining.append(list(h))
-    regions += [(h[3 - i], h[7 - i], 0, None, True) for i in range(4)]
-    return regions, chaining
-
-
-def _iv512_256():
-    """FIPS 180-4, 5.3.6: SHA-512 of the ASCII string "SHA-512/256" from the initial hash value whose words are SHA-512's
-    xor 0xa5a5a5a5a5a5a5a5."""
-    start = [x ^ 0xA5A5A5A5A5A5A5A5 for x in M.IV[SC.VARIANT_512]]
-    return compress(SC.pad(b"SHA-512/256", 1), 1, start)[1][-1]
-
-
-IV512_256 = _iv512_256()
+    return M2.compress(W, words, blocks, init)
 
 
 def cells_of(words, blocks, table_bits, init):
     """(18 columns over the segment's rows, the chaining values): the compression circuit's cells for any 16 * blocks
     words from any state."""
-    regions, chaining = compress(words, blocks, init)
-    out = []
-    for g, (a, e, w_, t, chained) in enumerate(regions):
-        s = {name: 0 for name in SC.SRC}
-        s["A"], s["E"], s["W"] = a, e, w_
-        s["S0_EVEN"], s["S0_ODD"] = M.bitsum(M.rotr(a, 28), M.rotr(a, 34), M.rotr(a, 39))
-        s["S1_EVEN"], s["S1_ODD"] = M.bitsum(M.rotr(e, 14), M.rotr(e, 18), M.rotr(e, 41))
-        s["G0_EVEN"], s["G0_ODD"] = M.bitsum(M.rotr(w_, 1), M.rotr(w_, 8), w_ >> 7)
-        s["G1_EVEN"], s["G1_ODD"] = M.bitsum(M.rotr(w_, 19), M.rotr(w_, 61), w_ >> 6)
-        if g % SC.BLOCK_REGIONS >= 2:
-            (a1, e1), (a2, e2) = regions[g - 1][:2], regions[g - 2][:2]
-            s["MAJ_EVEN"], s["MAJ_ODD"] = M.bitsum(a, a1, a2)
-            s["CHP_EVEN"], s["CHP_ODD"] = M.bitsum(e, e1)
-            s["CHQ_EVEN"], s["CHQ_ODD"] = M.bitsum(~e & M64, e2)
-            s["CH"] = s["CHP_ODD"] + s["CHQ_ODD"]
-        if t is not None:
-            prev = out[g - 1]
-            t1 = regions[g - 4][1] + prev["S1_EVEN"] + prev["CH"] + M.K[t] + w_
-            s["K"] = M.K[t]
-            s["CARRY_E"] = (t1 + regions[g - 4][0]) >> 64
-            s["CARRY_A"] = (t1 + prev["S0_EVEN"] + prev["MAJ_ODD"]) >> 64
-            if t >= 16:
-                s["CARRY_W"] = (out[g - 2]["G1_EVEN"] + regions[g - 7][2] + out[g - 15]["G0_EVEN"] + regions[g - 16][2]) >> 64
-        if chained:
-            s["CARRY_A"] = (regions[g - SC.BLOCK_REGIONS][0] + regions[g - 4][0]) >> 64
-            s["CARRY_E"] = (regions[g - SC.BLOCK_REGIONS][1] + regions[g - 4][1]) >> 64
-        out.append(s)
-    cols = [[0] * SC.rows_for(blocks) for _ in range(SC.ADVICE_COLUMNS)]
-    names = {v: k for k, v in SC.SRC.items()}
-    for g, s in enumerate(out):
-        for c in layout():
-            off = c.offset + c.per_table_bits * table_bits
-            field = (s[names[c.kind]] >> off) & ((1 << (c.len if c.len else table_bits)) - 1)
-            row = g * SC.REGION_ROWS + c.row
-            cols[c.column][row] = M.spread(field) if c.form == SC.FORM_SPREAD else field
-            if c.form == SC.FORM_PAIR:
-                cols[c.column + 1][row] = M.spread(field)
-    return cols, chaining
-
-
-def _word_row(name):
-    return next(c.row for c in layout() if c.kind == SC.SRC[name] and c.form == SC.FORM_WORD)
+    return M2.cells_of(W, words, blocks, table_bits, init)
 
 
 def state_row(first_region: int, word: int) -> int:
     """The row of initial word `word` in column X: region 3 - word % 4 of the first block, the A row or the E row."""
-    return SC.REGION_ROWS * (first_region + 3 - word % 4) + _word_row("A" if word < 4 else "E")
+    return M2.state_row(W, first_region, word)
 
 
 def tail_row(first_region: int, blocks: int, word: int) -> int:
@@ -113,17 +43,7 @@ def tail_row(first_region: int, blocks: int, word: int) -> int:
 
 def message_row(first_region: int, t: int) -> int:
     """The row of message word t's W cell in column X."""
-    return SC.REGION_ROWS * (first_region + SC.BLOCK_REGIONS * (t // 16) + 4 + t % 16) + _word_row("W")
-
-
-def levels(plan):
-    """Every segment's level: 0 if neither its message words nor its initial words read a digest, else one more than the
-    highest level it reads."""
-    out = []
-    for seg in plan.segments:
-        read = [s.segment for s in tuple(seg.sources) + tuple(seg.init or ()) if isinstance(s, SS.DigestWord)]
-        out.append(1 + max(out[r] for r in read) if read else 0)
-    return out
+    return SC.REGION_ROWS * M2.message_region(W, first_region, t) + M2.word_row(W, "W")
 
 
 P16 = (SS.PRIVATE,) * 16
@@ -143,29 +63,7 @@ def plan_witness(plan, values, shared, table_bits, n):
     """(18 advice columns of n integers, every segment's 8 final words, every segment's 8 initial words, the instance
     words): Private words come from `values` (a segment's initial ones first), everything else is resolved from `shared`
     and the model's own final states.  The segments are evaluated level by level, as the device runs them."""
-    cols = [[0] * n for _ in range(SC.ADVICE_COLUMNS)]
-    count = len(plan.segments)
-    states, inits, firsts, level = [None] * count, [None] * count, SS.first_regions(plan), levels(plan)
-    for lv in range(max(level) + 1):
-        done = list(states)  # what this level may read: the levels below, nothing of its own
-        for j in (j for j in range(count) if level[j] == lv):
-            seg, private = plan.segments[j], iter(values[j])
-
-            def resolve(src):
-                if isinstance(src, SS.Private):
-                    return int(next(private))
-                if isinstance(src, SS.Const):
-                    return src.value
-                return int(shared[src.index]) if isinstance(src, SS.Var) else done[src.segment][src.word]
-
-            init = list(M.IV[seg.variant]) if seg.init is None else [resolve(s) for s in seg.init]
-            words = [resolve(s) for s in seg.sources]
-            assert next(private, None) is None
-            part, chaining = cells_of(words, seg.blocks, table_bits, init)
-            at = SC.REGION_ROWS * firsts[j]
-            for col, p in zip(cols, part):
-                col[at: at + len(p)] = p
-            states[j], inits[j] = chaining[-1], chaining[0]
+    cols, states, inits, _ = M2.plan_witness(W, plan, SS.first_regions(plan), lambda seg: M.IV[seg.variant], values, shared, (), table_bits, n)
     instance = [x for s, words in plan.public for x in states[s][:words]] + [x for q in plan.public_init for x in inits[q]]
     return cols, states, inits, instance
 

@@ -1,6 +1,6 @@
 """What the SHA circuit tests share when they hand a circuit to the oracle: the package's constraint system restated in
-oracle/plonk.py expressions (for the oracle's verifier and for tests/witness_check_model.py), and one 32-byte cell written
-into a device column."""
+oracle/plonk.py expressions (for the oracle's verifier and for tests/witness_check_model.py), a model's column of integers
+in Montgomery form, and one 32-byte cell written into a device column."""
 import numpy as np
 
 from oracle import bn254 as B
@@ -8,8 +8,25 @@ from oracle import cq_prover as CP
 from oracle import cq_verifier as CV
 from oracle import plonk as PL
 from sha2_on_cq_halo2_amd import plonk as GP
+from sha2_on_cq_halo2_amd._marshal import fr_to_mont
+from sha2_on_cq_halo2_amd.sha256_circuit import _mont_column
 
 KINDS = {GP.COL_ADVICE: PL.ADVICE, GP.COL_FIXED: PL.FIXED, GP.COL_INSTANCE: PL.INSTANCE}
+
+
+def mont_column(vals) -> np.ndarray:
+    """integers below the modulus -> uint64[n, 4] Montgomery limbs, one conversion per distinct value"""
+    if max(vals) < 1 << 64:
+        return _mont_column(np.array(vals, dtype=np.uint64))
+    index, uniq = {}, []
+    inv = np.empty(len(vals), dtype=np.int64)
+    for i, v in enumerate(vals):
+        j = index.get(v)
+        if j is None:
+            j = index[v] = len(uniq)
+            uniq.append(v)
+        inv[i] = j
+    return np.stack([fr_to_mont(u) for u in uniq])[inv]
 
 
 def spread(x):

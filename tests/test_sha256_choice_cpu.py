@@ -11,14 +11,11 @@ from sha2_on_cq_halo2_amd import sha256_circuit as SC
 from sha2_on_cq_halo2_amd import sha256_segments as SS
 from tests import sha256_choice_model as CM
 from tests import sha256_segments_model as SM
+from tests.sha2_model import words_of
 
 DEPTH, K = 3, 12
 LEAF_MESSAGE = bytes((5 * i + 3) % 256 for i in range(41))
 LEAVES = [hashlib.sha256(bytes([i])).digest() for i in range(1 << DEPTH)]
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
 
 
 def tree_levels(leaves):

@@ -4,7 +4,6 @@ operand, proofs verify against the path's own root only, a bad choice table is r
 the new entry point without choices is the old one byte for byte."""
 import ctypes as C
 import hashlib
-import struct
 
 import numpy as np
 import pytest
@@ -21,6 +20,8 @@ from sha2_on_cq_halo2_amd.api import FAIL_GATE, FAIL_PERMUTATION, Sha256MerklePa
 from tests import sha256_choice_model as CM
 from tests import sha256_circuit_model as M
 from tests import sha256_segments_model as SM
+from tests.sha2_model import words_of
+from tests.sha_oracle import mont_column as _mont
 
 pytestmark = pytest.mark.gpu
 SEED = 0x5348413243515F
@@ -30,10 +31,6 @@ X, Y = 2 * SC.PAIRS, 2 * SC.PAIRS + 1
 
 def node(i, salt=0):
     return hashlib.sha256(bytes([i, salt])).digest()
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
 
 
 LEAF_MESSAGE = bytes((5 * i + 3) % 256 for i in range(41))
@@ -72,10 +69,6 @@ def circuits(ctx):
     yield get
     for c in made.values():
         c.close()
-
-
-def _mont(ints):
-    return SC._mont_column(np.array(ints, dtype=np.uint64))
 
 
 @pytest.mark.parametrize("name", ["path1", "path1_right", "path3", "path3_leaf", "paths2"])

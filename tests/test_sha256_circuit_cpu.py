@@ -9,12 +9,9 @@ import pytest
 from sha2_on_cq_halo2_amd import plonk as GP
 from sha2_on_cq_halo2_amd import sha256_circuit as SC
 from tests import sha256_circuit_model as M
+from tests.sha2_model import message
 
 MESSAGES = {0: 1, 1: 1, 55: 1, 56: 2, 63: 2, 64: 2, 119: 2}
-
-
-def message(length, salt=0):
-    return bytes((7 * i + 13 * salt + 1) % 256 for i in range(length))
 
 
 @pytest.mark.parametrize("length,blocks", sorted(MESSAGES.items()))

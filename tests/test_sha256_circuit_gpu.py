@@ -11,14 +11,12 @@ from sha2_on_cq_halo2_amd.api import FAIL_GATE, FAIL_PERMUTATION, FAIL_STATIC_LO
 from tests import sha256_circuit_model as M
 from tests.sha_oracle import verifier as _verifier
 from tests.sha_oracle import write_cell as _write
+from tests.sha2_model import message
+from tests.sha_oracle import mont_column as _mont
 
 pytestmark = pytest.mark.gpu
 SEED = 0x5348413243515F
 K_FOR = {1: 10, 2: 11, 3: 11}  # the smallest k that holds the block count
-
-
-def message(length, salt=0):
-    return bytes((7 * i + 13 * salt + 1) % 256 for i in range(length))
 
 
 CASES = {"empty": (1, b""), "55": (1, message(55, 1)), "56": (2, message(56, 2)), "119": (2, message(119, 3)), "183": (3, message(183, 4)),
@@ -37,10 +35,6 @@ def circuits(ctx):
     yield get
     for c in made.values():
         c.close()
-
-
-def _mont(ints):
-    return SC._mont_column(np.array(ints, dtype=np.uint64))
 
 
 @pytest.mark.parametrize("case", sorted(CASES))

@@ -4,7 +4,6 @@ oracle's verifier the proof, and a changed result word or operand of any unit is
 region and the copy that ties the cell."""
 import hashlib
 import hmac
-import struct
 
 import numpy as np
 import pytest
@@ -20,6 +19,8 @@ from sha2_on_cq_halo2_amd.api import FAIL_GATE, FAIL_PERMUTATION, HmacSha256Circ
 from tests import sha256_circuit_model as M
 from tests import sha256_xor_model as XM
 from tests.test_sha256_choice_gpu import _oracle_expr
+from tests.sha2_model import words_of
+from tests.sha_oracle import mont_column as _mont
 
 pytestmark = pytest.mark.gpu
 SEED = 0x5348413243515F
@@ -27,10 +28,6 @@ P16 = (SS.PRIVATE,) * 16
 # RFC 4231 test cases 1 and 2; the second at table_bits 11
 CASES = {"rfc1": (b"\x0b" * 20, b"Hi There", 12, "b0344c61d8db38535ca8afceaf0bf12b881dc200c9833da726e9376c2e32cff7"),
          "rfc2": (b"Jefe", b"what do ya want for nothing?", 11, "5bdcc146bf60754e6a042426089575c75a003f089d2739839dec58b964ec3843")}
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
 
 
 def three_unit_plan():
@@ -62,10 +59,6 @@ def circuits(ctx):
     yield get
     for c in made.values():
         c.close()
-
-
-def _mont(ints):
-    return SC._mont_column(np.array(ints, dtype=np.uint64))
 
 
 def _verifier(c, seed):

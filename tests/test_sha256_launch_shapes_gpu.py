@@ -6,7 +6,6 @@ columns and all n rows, with n = rows + 5 (no multiple of 8 or 256: the rows beh
 the guard rows behind n untouched; every digest the device returns is compared with hashlib's."""
 import hashlib
 import random
-import struct
 
 import numpy as np
 import pytest
@@ -19,14 +18,11 @@ from tests import sha256_circuit_model as M
 from tests import sha256_direct as D
 from tests import sha256_segments_model as SM
 from tests import sha256_varlen_model as VM
+from tests.sha2_model import words_of
 
 pytestmark = pytest.mark.gpu
 ERR_ARG = constants()["CQ_ERR_ARG"]
 PAD_32_BYTES = (SS.Const(0x80000000),) + (SS.Const(0),) * 6 + (SS.Const(256),)  # behind 8 words: sha256_segments.double_sha256
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
 
 
 def edgy_bytes(rng, length):

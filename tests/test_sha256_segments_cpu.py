@@ -1,7 +1,6 @@
 """CPU: plans of wired SHA-256 segments -- their descriptions against the pure-Python model's witness (every gate, lookup
 and copy), the instance against hashlib, what a broken wire is reported as, and the plans that must be refused."""
 import hashlib
-import struct
 
 import numpy as np
 import pytest
@@ -10,14 +9,7 @@ from sha2_on_cq_halo2_amd import sha256_circuit as SC
 from sha2_on_cq_halo2_amd import sha256_segments as SS
 from tests import sha256_circuit_model as M
 from tests import sha256_segments_model as SM
-
-
-def message(length, salt=0):
-    return bytes((7 * i + 13 * salt + 1) % 256 for i in range(length))
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
+from tests.sha2_model import message, words_of
 
 
 LEAVES = [hashlib.sha256(bytes([i])).digest() for i in range(4)]

@@ -4,7 +4,6 @@ double digest only, a one-segment plan is the single-message circuit byte for by
 before anything is launched."""
 import ctypes as C
 import hashlib
-import struct
 
 import numpy as np
 import pytest
@@ -21,18 +20,12 @@ from sha2_on_cq_halo2_amd.api import (FAIL_GATE, FAIL_PERMUTATION, Sha256BatchCi
                                       Sha256SegmentsCircuit, fr_to_mont)
 from tests import sha256_circuit_model as M
 from tests import sha256_segments_model as SM
+from tests.sha2_model import message, words_of
+from tests.sha_oracle import mont_column as _mont
 
 pytestmark = pytest.mark.gpu
 SEED = 0x5348413243515F
 ERR_ARG = constants()["CQ_ERR_ARG"]
-
-
-def message(length, salt=0):
-    return bytes((7 * i + 13 * salt + 1) % 256 for i in range(length))
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
 
 
 LEAVES = [hashlib.sha256(bytes([i])).digest() for i in range(4)]
@@ -73,10 +66,6 @@ def circuits(ctx):
     yield get
     for c in made.values():
         c.close()
-
-
-def _mont(ints):
-    return SC._mont_column(np.array(ints, dtype=np.uint64))
 
 
 @pytest.mark.parametrize("name", ["batch", "double", "merkle2"])

@@ -11,12 +11,9 @@ from sha2_on_cq_halo2_amd import sha256_segments as SS
 from sha2_on_cq_halo2_amd import sha256_stream as ST
 from sha2_on_cq_halo2_amd import sha256_varlen as SV
 from tests import sha256_states_model as IM
+from tests.sha2_model import words_of
 
 P16 = (SS.PRIVATE,) * 16
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
 
 
 # ---- 1. descriptions do not move ---------------------------------------------------------------------------------------------

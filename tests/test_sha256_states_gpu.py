@@ -14,15 +14,12 @@ from sha2_on_cq_halo2_amd import sha256_segments as SS
 from sha2_on_cq_halo2_amd._lib import constants
 from tests import sha256_direct as D
 from tests import sha256_states_model as IM
+from tests.sha2_model import words_of
 
 pytestmark = pytest.mark.gpu
 ERR_ARG = constants()["CQ_ERR_ARG"]
 N = 1 << 16
 P16 = (SS.PRIVATE,) * 16
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
 
 
 class StatesJob(D.SegmentsJob):

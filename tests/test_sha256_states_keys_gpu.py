@@ -1,7 +1,6 @@
 """GPU, with keys: the midstate circuit, SHA-224, the continued variable-length circuit and the stream -- witness checker
 and the oracle's verifier on every instance, hashlib for every digest."""
 import hashlib
-import struct
 
 import numpy as np
 import pytest
@@ -17,20 +16,13 @@ from sha2_on_cq_halo2_amd.api import (FAIL_GATE, FAIL_PERMUTATION, Sha224Circuit
                                       fr_to_mont, link)
 from tests import sha256_circuit_model as M
 from tests import sha256_states_model as IM
+from tests.sha2_model import nonzero_message as message, words_of
 
 pytestmark = pytest.mark.gpu
 SEED = 0x5348413243515F
 X, Y = IM.X, IM.Y
 PERM_X, PERM_INSTANCE, PERM_Y = 0, 2, 3  # the permutation columns in enable_equality order: X, const, instance, Y
 LENGTHS = (0, 1, 55, 56, 63, 119, 183)
-
-
-def message(length, salt=0):
-    return bytes((37 * i + 11 + salt) % 251 + 1 for i in range(length))
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
 
 
 @pytest.fixture(scope="module")

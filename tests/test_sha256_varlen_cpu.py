@@ -3,7 +3,6 @@ holds, the variable-length description against the model's witness (every gate, 
 is reported as, and what the variant must leave as it was: the descriptions of the plain, segment and choice plans, the
 degree and the blinding factors."""
 import hashlib
-import struct
 
 import pytest
 
@@ -11,18 +10,11 @@ from sha2_on_cq_halo2_amd import sha256_circuit as SC
 from sha2_on_cq_halo2_amd import sha256_segments as SS
 from sha2_on_cq_halo2_amd import sha256_varlen as SV
 from tests import sha256_varlen_model as VM
+from tests.sha2_model import nonzero_message as message, words_of
 
 K, MAX_BLOCKS = 11, 3
 X, Y = VM.X, VM.Y
 VAR = SC.VAR
-
-
-def message(length, salt=0):
-    return bytes((37 * i + 11 + salt) % 251 + 1 for i in range(length))  # no zero byte: a cleared byte always shows
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
 
 
 def test_the_models_padding_gives_hashlibs_digest_at_every_length():

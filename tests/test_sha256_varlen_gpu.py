@@ -4,7 +4,6 @@ cell for cell and hashlib's digest, the witness checker accepts them and names e
 verify against their own digest (and length) only, and a bad description is refused before anything is launched."""
 import ctypes as C
 import hashlib
-import struct
 
 import numpy as np
 import pytest
@@ -20,6 +19,8 @@ from sha2_on_cq_halo2_amd._lib import constants
 from sha2_on_cq_halo2_amd.api import FAIL_GATE, FAIL_STATIC_LOOKUP, Sha256VarCircuit, fr_to_mont
 from tests import sha256_circuit_model as M
 from tests import sha256_varlen_model as VM
+from tests.sha2_model import nonzero_message as message, words_of
+from tests.sha_oracle import mont_column as _mont
 
 pytestmark = pytest.mark.gpu
 SEED = 0x5348413243515F
@@ -30,14 +31,6 @@ K, MAX_BLOCKS = 11, 3
 # r = 0 .. 3; the boundary in words 13, 14 and 15; padding that spills into the next block (56 .. 63, 120); the final block
 # 0, 1 or 2; the empty message and the longest
 LENGTHS = [0, 1, 3, 4, 5, 52, 55, 56, 59, 60, 63, 64, 119, 120, 183]
-
-
-def message(length, salt=0):
-    return bytes((37 * i + 11 + salt) % 251 + 1 for i in range(length))
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
 
 
 @pytest.fixture(scope="module")
@@ -55,10 +48,6 @@ def circuits(ctx):
     yield get
     for c in made.values():
         c.close()
-
-
-def _mont(ints):
-    return SC._mont_column(np.array(ints, dtype=np.uint64))
 
 
 def _same_cells(c, messages):

@@ -15,6 +15,7 @@ from tests import sha256_segments_model as SM
 from tests import sha256_xor_model as XM
 from tests.test_sha256_segments_cpu import DESCRIBED as DESCRIBED_FIXED_AND_COPIES
 from tests.test_sha256_varlen_cpu import DESCRIBED, description_hash
+from tests.sha2_model import words_of
 
 P16 = (SS.PRIVATE,) * 16
 # description_hash of midstate(2) at k = 11, recorded on the commit before the XOR variant was added to _constraint_system
@@ -25,10 +26,6 @@ CASES = {"rfc4231_1": (b"\x0b" * 20, b"Hi There"), "rfc4231_2": (b"Jefe", b"what
          "key64_empty": (bytes(range(64)), b""), "key0": (b"", b"twelve bytes")}
 RFC_TAGS = {"rfc4231_1": "b0344c61d8db38535ca8afceaf0bf12b881dc200c9833da726e9376c2e32cff7",
             "rfc4231_2": "5bdcc146bf60754e6a042426089575c75a003f089d2739839dec58b964ec3843"}
-
-
-def words_of(data):
-    return list(struct.unpack(f">{len(data) // 4}I", data))
 
 
 def hmac_inputs(plan, key, message):

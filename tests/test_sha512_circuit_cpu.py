@@ -9,14 +9,11 @@ import pytest
 from sha2_on_cq_halo2_amd import plonk as GP
 from sha2_on_cq_halo2_amd import sha512_circuit as SC
 from tests import sha512_circuit_model as M
+from tests.sha2_model import message
 
 MESSAGES = {0: 1, 1: 1, 111: 1, 112: 2, 127: 2, 128: 2, 239: 2}
 HASH = {SC.VARIANT_512: hashlib.sha512, SC.VARIANT_384: hashlib.sha384}
 K_FOR = {1: 11, 2: 12}  # the smallest k that holds the block count
-
-
-def message(length, salt=0):
-    return bytes((7 * i + 13 * salt + 1) % 256 for i in range(length))
 
 
 @pytest.mark.parametrize("length,blocks", sorted(MESSAGES.items()))

@@ -13,6 +13,7 @@ from tests import sha512_circuit_model as M
 from tests.sha512_direct import mont_column
 from tests.sha_oracle import verifier as _verifier
 from tests.sha_oracle import write_cell as _write
+from tests.sha2_model import message
 
 pytestmark = pytest.mark.gpu
 SEED = 0x5348413243515F
@@ -20,10 +21,6 @@ K_FOR = {1: 11, 2: 12}  # the smallest k that holds the block count
 V512, V384 = SC.VARIANT_512, SC.VARIANT_384
 CLASS = {V512: Sha512Circuit, V384: Sha384Circuit}
 HASH = {V512: hashlib.sha512, V384: hashlib.sha384}
-
-
-def message(length, salt=0):
-    return bytes((7 * i + 13 * salt + 1) % 256 for i in range(length))
 
 
 MESSAGES = {"empty": (1, b""), "111": (1, message(111, 1)), "112": (2, message(112, 2)), "239": (2, message(239, 3)),
