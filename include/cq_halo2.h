@@ -1055,6 +1055,28 @@ int cq_sha512_synthesize_segments_dev(cq_ctx* ctx, uint32_t table_bits, const ui
                                       const uint32_t* seg_variant, const uint32_t* sources, const uint32_t* init_sources,
                                       const uint64_t* words_dev, size_t words_len, size_t n, uint64_t* const* cols_dev,
                                       uint64_t* digests_dev);
+/* The same with message words that are the XOR of two plain sources (sha2_on_cq_halo2_amd/sha512_xor.py, DESIGN.md
+ * "XOR-wired message words on the 64-bit circuit"): the 64-bit counterpart of cq_sha256_synthesize_xors_dev.  `xors` is a
+ * host array of `n_xors` units of CQ_SHA512_XOR_WORDS words {x, y, 0, 0}: x and y are plain sources -- a word index or a
+ * digest reference to a segment that exists; no unit's result.  `digests_dev` holds 8 * segments + n_xors 64-bit words:
+ * word 8 * segments + u receives x ^ y of unit u, and a message word reads it through the source value
+ * CQ_SHA512_SOURCE_DIGEST + 8 * segments + u (a message word's own source only: not an initial word).  Any number of
+ * message words may read one unit, none included.  Unit u takes CQ_SHA512_XOR_REGIONS regions directly behind the last
+ * segment's tail, regions R + 2u and R + 2u + 1 (R: the segments' regions): the first holds e = x and nothing else, the
+ * second e = y and W = x ^ y, with the Ch cells of two consecutive e words that the expansion lays out for it.  A unit is
+ * ready at level 0 if it reads no digest, else one level above the highest level it reads; a segment that reads a unit
+ * runs at or above the unit's level.  Per level one launch computes that level's units before the level's chains, and one
+ * more behind the last level those over its digests; then the expansion runs once over all regions.  CQ_ERR_ARG, besides
+ * the cases above and again before anything is queued, naming the unit (and segment and word for a reader): a null table
+ * with n_xors > 0, an operand index outside `words_dev`, a digest operand of a segment that does not exist, a reader in
+ * segment j of a unit with a digest operand of segment >= j, a unit index >= n_xors, an area that does not fit n.
+ * n_xors = 0 (`xors` may be NULL) is cq_sha512_synthesize_segments_dev exactly. */
+#define CQ_SHA512_XOR_WORDS 4
+#define CQ_SHA512_XOR_REGIONS 2
+int cq_sha512_synthesize_xors_dev(cq_ctx* ctx, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments,
+                                  const uint32_t* seg_variant, const uint32_t* sources, const uint32_t* init_sources,
+                                  const uint32_t* xors, size_t n_xors, const uint64_t* words_dev, size_t words_len, size_t n,
+                                  uint64_t* const* cols_dev, uint64_t* digests_dev);
 
 /* ---- harness RNG (not in the reference: its test draws from OsRng) ---------------------------------- */
 void cq_xoshiro256ss_seed(uint64_t seed, uint64_t state[4]);

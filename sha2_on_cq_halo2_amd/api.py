@@ -25,3 +25,4 @@ from .sha512_circuit import Sha384Circuit, Sha512BatchCircuit, Sha512Circuit  # 
 # the plans of the wired SHA-512 segments: `batch`, `merkle_tree` and `midstate` are sha512_segments', not sha256_segments'
 from .sha512_segments import (Sha512_256Circuit, Sha512dCircuit, Sha512MerkleCircuit, Sha512MidstateCircuit, Sha512SegmentsCircuit,  # noqa: F401
                               batch, double_sha512, merkle_tree, midstate, sha512_256)
+from .sha512_xor import HmacSha384Circuit, HmacSha512Circuit, Sha512XorSegmentsCircuit, hmac_sha512  # noqa: F401

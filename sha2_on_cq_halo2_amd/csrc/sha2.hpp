@@ -1,10 +1,11 @@
 // What the SHA-256 and the SHA-512 witness syntheses share, written once over a family record per word width: the bit
 // functions, the words of a region the expansion kernels place, the compression chain the chain kernels run, and the host
-// side's description checks, level order, pinned staging and entry preamble.  sha256.hip and sha512.hip keep what differs:
-// the kernels themselves (names, template parameters and launch shapes are theirs), how a cell's value is placed and
-// encoded (one 64-bit limb or two), the round constants' storage, the 32-bit host chain, choices, XOR units and
-// variable length.
+// side's description checks, level order, the checks and levels of XOR units, pinned staging and entry preamble.
+// sha256.hip and sha512.hip keep what differs: the kernels themselves (names, template parameters and launch shapes are
+// theirs), how a cell's value is placed and encoded (one 64-bit limb or two), the round constants' storage, the 32-bit
+// host chain, choices and variable length.
 #pragma once
+#include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
@@ -277,6 +278,88 @@ static inline Sha2Levels sha2_levels(const std::vector<uint32_t>& level) {
   lv.first.assign(lv.count.size(), 0);
   for (size_t l = 1; l < lv.count.size(); l++) lv.first[l] = lv.first[l - 1] + lv.count[l - 1];
   return lv;
+}
+
+// ---- XOR units: a message word that is the XOR of two plain sources ----------------------------------------------------
+
+// One XOR unit as the device sees it at both widths: its two operands (plain sources), the word of `digests` that takes
+// the result, and -- both filled in by the host -- the first of the unit's two regions.
+struct Sha2XorUnit {
+  uint32_t x, y, result, region;
+};
+static_assert(CQ_SHA512_XOR_WORDS == CQ_SHA256_XOR_WORDS && CQ_SHA512_XOR_REGIONS == CQ_SHA256_XOR_REGIONS, "one table of units, one area");
+static_assert(sizeof(Sha2XorUnit) == CQ_SHA256_XOR_WORDS * sizeof(uint32_t), "an entry of the xor table as the header states it");
+
+// The units' area behind `regions` regions of segments fits n rows, and every operand is a plain source: a word of the
+// buffer or a digest word of a segment that exists (no unit's result).
+template <typename F>
+static int sha2_check_xor_units(cq_ctx* c, const uint32_t* xors, size_t n_xors, size_t segments, size_t words_len, uint64_t regions, uint32_t n) {
+  const std::string name = F::NAME;
+  if (regions + CQ_SHA256_XOR_REGIONS * (uint64_t)n_xors > n / F::REGION_ROWS)
+    return c->fail(CQ_ERR_ARG, name + ": the area of " + std::to_string(n_xors) + " xor units behind the segments does not fit the rows");
+  for (size_t u = 0; u < n_xors; u++)
+    for (uint32_t o = 0; o < 2; o++) {
+      const uint32_t s = xors[CQ_SHA256_XOR_WORDS * u + o];
+      std::string bad;
+      if (s & CQ_SHA256_SOURCE_DIGEST) {
+        const size_t ref = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3;
+        if (ref >= segments) bad = " reads the digest of segment " + std::to_string(ref) + " of " + std::to_string(segments);
+      } else if (s >= words_len) {
+        bad = " reads word " + std::to_string(s) + " of a buffer of " + std::to_string(words_len);
+      }
+      if (!bad.empty()) return c->fail(CQ_ERR_ARG, name + ": xor unit " + std::to_string(u) + (o ? ", operand y" : ", operand x") + bad);
+    }
+  return CQ_OK;
+}
+
+// whether a message word's source names a unit's result: a digest reference behind the segments' own words
+static inline bool sha2_reads_xor_unit(uint32_t s, size_t segments, size_t n_xors) {
+  return n_xors && (s & CQ_SHA256_SOURCE_DIGEST) && (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >= 8 * segments;
+}
+
+// Such a source of a word of segment j: "" if it is good, else what is wrong with it.  The unit's digest operands come
+// before the segment, and the segment runs at or above the unit's level.
+static inline std::string sha2_xor_reader(uint32_t s, size_t j, size_t segments, const uint32_t* xors, size_t n_xors, size_t words_len,
+                                          std::vector<uint32_t>& level) {
+  const size_t u = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) - 8 * segments;
+  if (u >= n_xors) return " reads xor unit " + std::to_string(u) + " of " + std::to_string(n_xors);
+  for (uint32_t o = 0; o < 2; o++) {
+    const std::string bad = sha2_plain_source(xors[CQ_SHA256_XOR_WORDS * u + o], j, words_len, level);
+    if (!bad.empty()) return ", xor unit " + std::to_string(u) + (o ? ", operand y" : ", operand x") + bad;
+  }
+  return "";
+}
+
+// A unit is ready at level 0 if it reads no digest, else one level above the highest level it reads: at most one level
+// behind the last chain launch.  `level`: every segment's, final, whether or not a word reads the unit.  `count` and
+// `first` are per level, as Sha2Levels', with one level more than the chains have; all three are empty without units.
+struct Sha2XorLevels {
+  std::vector<uint32_t> level, count, first;
+};
+static inline Sha2XorLevels sha2_xor_levels(const uint32_t* xors, size_t n_xors, const std::vector<uint32_t>& level, size_t chain_levels) {
+  Sha2XorLevels xl;
+  xl.level.assign(n_xors, 0);
+  xl.count.assign(n_xors ? chain_levels + 1 : 0, 0);
+  for (size_t u = 0; u < n_xors; u++) {
+    for (uint32_t o = 0; o < 2; o++) {
+      const uint32_t s = xors[CQ_SHA256_XOR_WORDS * u + o];
+      if (s & CQ_SHA256_SOURCE_DIGEST) xl.level[u] = std::max(xl.level[u], level[(s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3] + 1);
+    }
+    xl.count[xl.level[u]]++;
+  }
+  xl.first.assign(xl.count.size(), 0);
+  for (size_t l = 1; l < xl.count.size(); l++) xl.first[l] = xl.first[l - 1] + xl.count[l - 1];
+  return xl;
+}
+
+// The units in level order; unit u keeps its result word, 8 * segments + u, and its regions, behind the segments' `regions`,
+// whatever its level.
+static inline void sha2_fill_xor_units(Sha2XorUnit* units, const uint32_t* xors, size_t n_xors, const Sha2XorLevels& xl, size_t segments,
+                                       uint64_t regions) {
+  std::vector<uint32_t> next = xl.first;
+  for (size_t u = 0; u < n_xors; u++)
+    units[next[xl.level[u]]++] = {xors[CQ_SHA256_XOR_WORDS * u], xors[CQ_SHA256_XOR_WORDS * u + 1], (uint32_t)(8 * segments + u),
+                                  (uint32_t)(regions + CQ_SHA256_XOR_REGIONS * u)};
 }
 
 // The lanes in level order, segments of one level in row order; `tag(j)` is Sha2Lane::tag of segment j.  One level (an

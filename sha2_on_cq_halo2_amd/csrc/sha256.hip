@@ -222,18 +222,12 @@ __global__ __launch_bounds__(64) void sha256_choice_fill_kernel(const Sha256Choi
   st(cell + CQ_SHA256_CHOICE_ROW_BIT, bit ? Fr::from_u64(bit) : Fr::zero());
 }
 
-// One XOR unit as the device sees it: its two operands (plain sources), the word of `digests` that takes the result,
-// and -- both filled in by the host -- the first of the unit's two regions.
-struct Sha256XorUnit {
-  uint32_t x, y, result, region;
-};
-
 // One thread per unit of one level, before the level's chains on the same stream: both operands through sha256_load (the
 // digests they may read are earlier levels'), the result word, and the unit's two regions: e = x alone, then e = y with
 // W = x ^ y under SHA_RG_F3, whose CHP_EVEN word the expansion computes as this region's e xor the one before.  `digests`
 // is read and written, hence neither const nor restrict.  The host has checked every operand against both arrays'
 // lengths and that region + 1 lies below n / CQ_SHA256_REGION_ROWS.
-__global__ __launch_bounds__(64) void sha256_xor_kernel(const Sha256XorUnit* __restrict__ units, uint32_t nunits, const uint32_t* words,
+__global__ __launch_bounds__(64) void sha256_xor_kernel(const Sha2XorUnit* __restrict__ units, uint32_t nunits, const uint32_t* words,
                                                         uint32_t* digests, Sha256Region* __restrict__ regions) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nunits) return;
@@ -255,23 +249,9 @@ __global__ __launch_bounds__(64) void sha256_xor_kernel(const Sha256XorUnit* __r
 int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* sources,
                                const uint32_t* choices, size_t n_choices, const uint32_t* init_sources, const uint32_t* xors, size_t n_xors,
                                const uint32_t* words_dev, size_t words_len, uint32_t n, const Sha2Cols& cols, uint32_t* digests_dev) {
-  const uint64_t max_regions = n / CQ_SHA256_REGION_ROWS;
   uint64_t regions, blocks;
   CQ_TRY(sha2_count_segments<Sha256>(c, seg_blocks, nullptr, segments, n, regions, blocks));
-  if (regions + CQ_SHA256_XOR_REGIONS * (uint64_t)n_xors > max_regions)
-    return c->fail(CQ_ERR_ARG, "sha256: the area of " + std::to_string(n_xors) + " xor units behind the segments does not fit the rows");
-  for (size_t u = 0; u < n_xors; u++)  // the operands: plain sources, a digest's of a segment that exists (no unit's result)
-    for (uint32_t o = 0; o < 2; o++) {
-      const uint32_t s = xors[CQ_SHA256_XOR_WORDS * u + o];
-      std::string bad;
-      if (s & CQ_SHA256_SOURCE_DIGEST) {
-        const size_t ref = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3;
-        if (ref >= segments) bad = " reads the digest of segment " + std::to_string(ref) + " of " + std::to_string(segments);
-      } else if (s >= words_len) {
-        bad = " reads word " + std::to_string(s) + " of a buffer of " + std::to_string(words_len);
-      }
-      if (!bad.empty()) return c->fail(CQ_ERR_ARG, "sha256: xor unit " + std::to_string(u) + (o ? ", operand y" : ", operand x") + bad);
-    }
+  CQ_TRY(sha2_check_xor_units<Sha256>(c, xors, n_xors, segments, words_len, regions, n));
   std::vector<uint32_t> level(segments, 0);
   std::vector<uint32_t> choice_region(n_choices, UINT32_MAX);  // the region of the word that refers to the entry, once one does
   uint32_t seg_region = 0;
@@ -301,13 +281,8 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
         for (uint32_t o = 1; o <= 2 && bad.empty(); o++)
           if (!(bad = plain(entry[o])).empty()) bad = std::string(o == 1 ? "'s zero operand" : "'s one operand") + bad;
         if (!bad.empty()) bad = ", choice " + std::to_string(e) + bad;
-      } else if (n_xors && (s & CQ_SHA256_SOURCE_DIGEST) && (s & (CQ_SHA256_SOURCE_DIGEST - 1)) >= 8 * segments) {
-        // a unit's result: the unit's digest operands come before this segment, and the segment runs at or above the unit's level
-        const size_t u = (s & (CQ_SHA256_SOURCE_DIGEST - 1)) - 8 * segments;
-        if (u >= n_xors) return c->fail(CQ_ERR_ARG, where() + " reads xor unit " + std::to_string(u) + " of " + std::to_string(n_xors));
-        for (uint32_t o = 0; o < 2 && bad.empty(); o++)
-          if (!(bad = plain(xors[CQ_SHA256_XOR_WORDS * u + o])).empty())
-            bad = ", xor unit " + std::to_string(u) + (o ? ", operand y" : ", operand x") + bad;
+      } else if (sha2_reads_xor_unit(s, segments, n_xors)) {
+        bad = sha2_xor_reader(s, j, segments, xors, n_xors, words_len, level);
       } else {
         bad = plain(s);
       }
@@ -318,27 +293,16 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
     if (choice_region[e] == UINT32_MAX) return c->fail(CQ_ERR_ARG, "sha256: choice " + std::to_string(e) + " is read by no word");
   const Sha2Levels lv = sha2_levels(level);
   const std::vector<uint32_t>&level_count = lv.count, &level_first = lv.first;
-  // a unit is ready at level 0 if it reads no digest, else one level above the highest level it reads: at most one level
-  // behind the last chain launch.  Every segment's level is final by now, whether or not a word reads the unit.
-  std::vector<uint32_t> xor_level(n_xors, 0), xor_count(n_xors ? level_count.size() + 1 : 0, 0);
-  for (size_t u = 0; u < n_xors; u++) {
-    for (uint32_t o = 0; o < 2; o++) {
-      const uint32_t s = xors[CQ_SHA256_XOR_WORDS * u + o];
-      if (s & CQ_SHA256_SOURCE_DIGEST) xor_level[u] = std::max(xor_level[u], level[(s & (CQ_SHA256_SOURCE_DIGEST - 1)) >> 3] + 1);
-    }
-    xor_count[xor_level[u]]++;
-  }
-  std::vector<uint32_t> xor_first(xor_count.size(), 0);
-  for (size_t l = 1; l < xor_count.size(); l++) xor_first[l] = xor_first[l - 1] + xor_count[l - 1];
+  const Sha2XorLevels xl = sha2_xor_levels(xors, n_xors, level, level_count.size());
+  const std::vector<uint32_t>&xor_count = xl.count, &xor_first = xl.first;
 
-  static_assert(sizeof(Sha256Region) == 16 && sizeof(Sha2Lane) == 16 && sizeof(Sha256XorUnit) == 16, "four words each");
-  static_assert(sizeof(Sha256XorUnit) == CQ_SHA256_XOR_WORDS * sizeof(uint32_t), "an entry of the xor table as the header states it");
+  static_assert(sizeof(Sha256Region) == 16 && sizeof(Sha2Lane) == 16 && sizeof(Sha2XorUnit) == 16, "four words each");
   static_assert(sizeof(Sha256Choice) == CQ_SHA256_CHOICE_WORDS * sizeof(uint32_t), "an entry of the choice table as the header states it");
   // lanes, sources, choices, initial sources, xor units: each a multiple of 16 bytes, so the choice entries, a segment's
   // eight initial sources and the units are aligned for their 16-byte loads
   const size_t lanes_bytes = segments * sizeof(Sha2Lane), sources_bytes = 16 * blocks * sizeof(uint32_t);
   const size_t choices_bytes = n_choices * sizeof(Sha256Choice), init_bytes = init_sources ? 8 * segments * sizeof(uint32_t) : 0;
-  const size_t xors_bytes = n_xors * sizeof(Sha256XorUnit);
+  const size_t xors_bytes = n_xors * sizeof(Sha2XorUnit);
   const size_t tables_bytes = lanes_bytes + sources_bytes + choices_bytes + init_bytes + xors_bytes;
   const uint64_t all_regions = regions + CQ_SHA256_XOR_REGIONS * (uint64_t)n_xors;  // the units' regions lie behind the last tail
   void *pin, *dev_regions, *dev_tables;
@@ -349,17 +313,13 @@ int sha256_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
   for (size_t e = 0; e < n_choices; e++)
     staged[e] = {choices[CQ_SHA256_CHOICE_WORDS * e], choices[CQ_SHA256_CHOICE_WORDS * e + 1], choices[CQ_SHA256_CHOICE_WORDS * e + 2], choice_region[e]};
   if (init_sources) memcpy((char*)pin + lanes_bytes + sources_bytes + choices_bytes, init_sources, init_bytes);
-  Sha256XorUnit* units = (Sha256XorUnit*)((char*)pin + lanes_bytes + sources_bytes + choices_bytes + init_bytes);
-  std::vector<uint32_t> next_unit = xor_first;
-  for (size_t u = 0; u < n_xors; u++)  // units in level order; unit u keeps its result word and its regions whatever its level
-    units[next_unit[xor_level[u]]++] = {xors[CQ_SHA256_XOR_WORDS * u], xors[CQ_SHA256_XOR_WORDS * u + 1], (uint32_t)(8 * segments + u),
-                                        (uint32_t)(regions + CQ_SHA256_XOR_REGIONS * u)};
+  sha2_fill_xor_units((Sha2XorUnit*)((char*)pin + lanes_bytes + sources_bytes + choices_bytes + init_bytes), xors, n_xors, xl, segments, regions);
   CQ_TRY(sha2_upload(c, dev_tables, pin, tables_bytes));
   const Sha2Lane* dev_lanes = (const Sha2Lane*)dev_tables;
   const uint32_t* dev_sources = (const uint32_t*)((const char*)dev_tables + lanes_bytes);
   const Sha256Choice* dev_choices = (const Sha256Choice*)((const char*)dev_sources + sources_bytes);
   const uint32_t* dev_init = (const uint32_t*)((const char*)dev_choices + choices_bytes);
-  const Sha256XorUnit* dev_units = (const Sha256XorUnit*)((const char*)dev_init + init_bytes);
+  const Sha2XorUnit* dev_units = (const Sha2XorUnit*)((const char*)dev_init + init_bytes);
   auto launch_xors = [&](size_t l) {  // the units that are ready at level l, if there are any
     if (l >= xor_count.size() || !xor_count[l]) return true;
     sha256_xor_kernel<<<(xor_count[l] + 63) / 64, 64, 0, c->stream>>>(dev_units + xor_first[l], xor_count[l], words_dev, digests_dev,

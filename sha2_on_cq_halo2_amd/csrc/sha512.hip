@@ -5,6 +5,10 @@
 // is a bit field of a word that a handful of xors and additions of the region's and its neighbours' (a, e, W) give,
 // placed by the layout table of sha512_layout.hpp.  The spread form of a 64-bit word has 128 bits, so a cell value is two
 // 64-bit limbs until it is Montgomery-encoded.
+// XOR units (cq_sha512_synthesize_xors_dev): a message word may be the XOR of two plain sources, as in sha256.hip.  A small
+// kernel per level computes the units that are ready, stores each result behind the segments' digests -- where a message
+// word's fetch finds it like a digest word -- and leaves two regions per unit behind the last segment for the same
+// expansion kernel.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -155,6 +159,23 @@ __global__ __launch_bounds__(64) void sha512_chain_kernel(const Sha2Lane* __rest
   sha2_finish(h, out, digests + 8 * (size_t)segment);
 }
 
+// One thread per XOR unit of one level (cq_sha512_synthesize_xors_dev), before the level's chains on the same stream: both
+// operands through sha2_load (the digests they may read are earlier levels'), the 64-bit result word behind the segments'
+// digests, and the unit's two regions: e = x alone, then e = y with W = x ^ y under SHA_RG_F3, whose CHP_EVEN word the
+// expansion computes as this region's e xor the one before.  `digests` is read and written, hence neither const nor
+// restrict.  The host has checked every operand against both arrays' lengths and that region + 1 lies below
+// n / CQ_SHA512_REGION_ROWS.
+__global__ __launch_bounds__(64) void sha512_xor_kernel(const Sha2XorUnit* __restrict__ units, uint32_t nunits, const uint64_t* words,
+                                                        uint64_t* digests, Sha512Region* __restrict__ regions) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nunits) return;
+  const uint4 u = *reinterpret_cast<const uint4*>(units + i);
+  const uint64_t x = sha2_load(u.x, words, digests), y = sha2_load(u.y, words, digests);
+  digests[u.z] = x ^ y;
+  sha2_put<uint64_t>(regions + u.w, 0, x, 0, 0);
+  sha2_put<uint64_t>(regions + u.w + 1, 0, y, x ^ y, SHA_RG_F3);
+}
+
 // Validates the description, then queues the upload of the lanes and the message words, the chain launch, the expansion
 // and the digests' download on the context's stream, and waits for the stream once.  The staging is pinned; a segment
 // synthesis of sha256.hip queued before this call may still copy out of it, so its event is waited for first.
@@ -190,11 +211,17 @@ int sha512_synthesize(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks
 // function's, sha512_synthesize's or a segment synthesis of sha256.hip's -- is waited for, through the event they share.
 // init_sources = nullptr is the description whose segments all start from their variant's initial hash value: the staged
 // table then holds the sentinel everywhere, so the kernel has one form.
+// n_xors = 0 is the description without XOR units: a digest reference at or above 8 * segments then names a segment that
+// does not exist, and the launches and the staged bytes are those of the plain wired description.  Otherwise such a
+// reference in a message word's own source names unit (index - 8 * segments) of `xors`, whose result the level's XOR
+// launch stores at that word of `digests_dev` before the chains that read it run; the units ride, sorted by level, behind
+// the initial sources in the same staging.
 int sha512_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* seg_variant,
-                               const uint32_t* sources, const uint32_t* init_sources, const uint64_t* words_dev, size_t words_len, uint32_t n,
-                               const Sha2Cols& cols, uint64_t* digests_dev) {
+                               const uint32_t* sources, const uint32_t* init_sources, const uint32_t* xors, size_t n_xors,
+                               const uint64_t* words_dev, size_t words_len, uint32_t n, const Sha2Cols& cols, uint64_t* digests_dev) {
   uint64_t regions, blocks;
   CQ_TRY(sha2_count_segments<Sha512>(c, seg_blocks, seg_variant, segments, n, regions, blocks));
+  CQ_TRY(sha2_check_xor_units<Sha512>(c, xors, n_xors, segments, words_len, regions, n));
   std::vector<uint32_t> level(segments, 0);
   for (size_t j = 0, at = 0; j < segments; j++) {
     // a source of segment j: "" if it is good, and the segment's level follows a digest's
@@ -209,33 +236,48 @@ int sha512_synthesize_segments(cq_ctx* c, uint32_t table_bits, const uint32_t* s
       if (!bad.empty()) return c->fail(CQ_ERR_ARG, "sha512: segment " + std::to_string(j) + ", initial word " + std::to_string(i) + bad);
     }
     for (size_t t = 0; t < 16 * (size_t)seg_blocks[j]; t++, at++) {
-      const std::string bad = check(sources[at]);
+      const uint32_t s = sources[at];
+      const bool unit = s != CQ_SHA512_SOURCE_IV && sha2_reads_xor_unit(s, segments, n_xors);  // a unit's result, read like a digest word
+      const std::string bad = unit ? sha2_xor_reader(s, j, segments, xors, n_xors, words_len, level) : check(s);
       if (!bad.empty()) return c->fail(CQ_ERR_ARG, "sha512: segment " + std::to_string(j) + ", word " + std::to_string(t) + bad);
     }
   }
   const Sha2Levels lv = sha2_levels(level);
+  const Sha2XorLevels xl = sha2_xor_levels(xors, n_xors, level, lv.count.size());
 
-  // lanes, sources, initial sources: each a multiple of 16 bytes, so a segment's eight initial sources are aligned for
-  // their two 16-byte loads
+  // lanes, sources, initial sources, xor units: each a multiple of 16 bytes, so a segment's eight initial sources and the
+  // units are aligned for their 16-byte loads
   const size_t lanes_bytes = segments * sizeof(Sha2Lane), sources_bytes = 16 * blocks * sizeof(uint32_t);
-  const size_t init_bytes = 8 * segments * sizeof(uint32_t), tables_bytes = lanes_bytes + sources_bytes + init_bytes;
+  const size_t init_bytes = 8 * segments * sizeof(uint32_t), xors_bytes = n_xors * sizeof(Sha2XorUnit);
+  const size_t tables_bytes = lanes_bytes + sources_bytes + init_bytes + xors_bytes;
+  const uint64_t all_regions = regions + CQ_SHA512_XOR_REGIONS * (uint64_t)n_xors;  // the units' regions lie behind the last tail
   void *pin, *dev_regions, *dev_tables;
-  CQ_TRY(sha2_stage(c, tables_bytes, regions * sizeof(Sha512Region), tables_bytes, &pin, &dev_regions, &dev_tables));
+  CQ_TRY(sha2_stage(c, tables_bytes, all_regions * sizeof(Sha512Region), tables_bytes, &pin, &dev_regions, &dev_tables));
   sha2_fill_lanes<Sha512>((Sha2Lane*)pin, seg_blocks, segments, level, lv, [&](size_t j) { return (uint32_t)j << 1 | seg_variant[j]; });
   memcpy((char*)pin + lanes_bytes, sources, sources_bytes);
   uint32_t* staged_init = (uint32_t*)((char*)pin + lanes_bytes + sources_bytes);
   if (init_sources) memcpy(staged_init, init_sources, init_bytes);
   else std::fill(staged_init, staged_init + 8 * segments, CQ_SHA512_SOURCE_IV);
+  sha2_fill_xor_units((Sha2XorUnit*)((char*)staged_init + init_bytes), xors, n_xors, xl, segments, regions);
   CQ_TRY(sha2_upload(c, dev_tables, pin, tables_bytes));
   const Sha2Lane* dev_lanes = (const Sha2Lane*)dev_tables;
   const uint32_t* dev_sources = (const uint32_t*)((const char*)dev_tables + lanes_bytes);
   const uint32_t* dev_init = (const uint32_t*)((const char*)dev_sources + sources_bytes);
+  const Sha2XorUnit* dev_units = (const Sha2XorUnit*)((const char*)dev_init + init_bytes);
+  auto launch_xors = [&](size_t l) {  // the units that are ready at level l, if there are any
+    if (l >= xl.count.size() || !xl.count[l]) return true;
+    sha512_xor_kernel<<<(xl.count[l] + 63) / 64, 64, 0, c->stream>>>(dev_units + xl.first[l], xl.count[l], words_dev, digests_dev,
+                                                                    (Sha512Region*)dev_regions);
+    return hipGetLastError() == hipSuccess;
+  };
   for (size_t l = 0; l < lv.count.size(); l++) {
+    if (!launch_xors(l)) return c->fail(CQ_ERR_HIP, "sha512_xor launch failed");
     sha512_chain_kernel<true><<<(lv.count[l] + 63) / 64, 64, 0, c->stream>>>(dev_lanes + lv.first[l], lv.count[l], words_dev, digests_dev,
                                                                             (Sha512Region*)dev_regions, dev_sources, dev_init);
     if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha512_chain launch failed");
   }
-  sha512_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha512Region*)dev_regions, (uint32_t)regions, n, table_bits, cols);
+  if (!launch_xors(lv.count.size())) return c->fail(CQ_ERR_HIP, "sha512_xor launch failed");  // units over the last level's digests
+  sha512_expand_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>((const Sha512Region*)dev_regions, (uint32_t)all_regions, n, table_bits, cols);
   if (hipGetLastError() != hipSuccess) return c->fail(CQ_ERR_HIP, "sha512_expand launch failed");
   return CQ_OK;
 }
@@ -266,16 +308,35 @@ int cq_sha512_synthesize_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg
   return sha512_synthesize(c, table_bits, seg_blocks, segments, seg_variant, msg_words, (uint32_t)n, sc, digests_out);
 }
 
+// both entry points below: the argument checks that need no description, then the host function
+static int sha512_segments_entry(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* seg_variant,
+                                 const uint32_t* sources, const uint32_t* init_sources, const uint32_t* xors, size_t n_xors,
+                                 const uint64_t* words_dev, size_t words_len, size_t n, uint64_t* const* cols_dev, uint64_t* digests_dev) {
+  if (!c) return CQ_ERR_ARG;
+  const char* bad = nullptr;
+  if (!seg_blocks || !seg_variant || !sources || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull || segments > n ||
+      (!words_dev && words_len) || words_len > CQ_SHA512_SOURCE_DIGEST)
+    bad = SHA2_BAD_ARGS;
+  else if (n_xors && (!xors || n_xors > n))
+    bad = "null xor table, or more xor units than rows";
+  Sha2Cols sc;
+  CQ_TRY(sha2_entry(c, "sha512", bad, table_bits, CQ_SHA512_MIN_TABLE_BITS, CQ_SHA512_MAX_TABLE_BITS, "the pieces", cols_dev, sc));
+  return sha512_synthesize_segments(c, table_bits, seg_blocks, segments, seg_variant, sources, init_sources, xors, n_xors, words_dev, words_len,
+                                    (uint32_t)n, sc, digests_dev);
+}
+
 int cq_sha512_synthesize_segments_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* seg_variant,
                                       const uint32_t* sources, const uint32_t* init_sources, const uint64_t* words_dev, size_t words_len, size_t n,
                                       uint64_t* const* cols_dev, uint64_t* digests_dev) {
-  if (!c) return CQ_ERR_ARG;
-  const bool bad = !seg_blocks || !seg_variant || !sources || !cols_dev || !digests_dev || segments == 0 || n > 0x7fffffffull || segments > n ||
-                   (!words_dev && words_len) || words_len > CQ_SHA512_SOURCE_DIGEST;
-  Sha2Cols sc;
-  CQ_TRY(sha2_entry(c, "sha512", bad ? SHA2_BAD_ARGS : nullptr, table_bits, CQ_SHA512_MIN_TABLE_BITS, CQ_SHA512_MAX_TABLE_BITS, "the pieces", cols_dev, sc));
-  return sha512_synthesize_segments(c, table_bits, seg_blocks, segments, seg_variant, sources, init_sources, words_dev, words_len, (uint32_t)n, sc,
-                                    digests_dev);
+  return sha512_segments_entry(c, table_bits, seg_blocks, segments, seg_variant, sources, init_sources, nullptr, 0, words_dev, words_len, n, cols_dev,
+                               digests_dev);
+}
+
+int cq_sha512_synthesize_xors_dev(cq_ctx* c, uint32_t table_bits, const uint32_t* seg_blocks, size_t segments, const uint32_t* seg_variant,
+                                  const uint32_t* sources, const uint32_t* init_sources, const uint32_t* xors, size_t n_xors,
+                                  const uint64_t* words_dev, size_t words_len, size_t n, uint64_t* const* cols_dev, uint64_t* digests_dev) {
+  return sha512_segments_entry(c, table_bits, seg_blocks, segments, seg_variant, sources, init_sources, xors, n_xors, words_dev, words_len, n, cols_dev,
+                               digests_dev);
 }
 
 }  // extern "C"

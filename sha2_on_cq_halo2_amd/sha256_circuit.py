@@ -135,7 +135,7 @@ def _constraint_system(tb: int, dense, spread, choice: bool = False, varlen: boo
     if varlen:
         _varlen_gates(cs, polys, cells, adv, fcol, w)
     if xor:  # W = e_r ^ e_(r-1): under q_f3 `chp_even_odd` makes the CHP_EVEN chunks the even bits of spread(e_r) + spread(e_(r-1))
-        polys["xor_word"] = cs.query_fixed(fcol["q_xor"]) * (w("W") - system.from_chunks("CHP_EVEN"))
+        polys["xor_word"] = F.xor_word(system)
     out = F.finish(system, dense, spread, GATES_CHOICE if choice else GATES_VARLEN if varlen else GATES_XOR if xor else GATES)
     if xor:  # the gate adds three dense cells of row 6 and one fixed column to the queries, nothing to the blinding rows or the degree
         assert (cs.blinding_factors(), cs.degree()) == (20, 4)

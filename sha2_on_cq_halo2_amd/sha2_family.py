@@ -1,7 +1,7 @@
 """What the SHA-256 and the SHA-512 compression circuits share, written once over a `Family` record: the layout table's
 reader, the 23 gates and 16 lookups of the constraint system, and a chain's fixed cells and copies.
 sha256_circuit.py and sha512_circuit.py define their families and everything that is theirs alone: padding, the public
-rows, the 32-bit circuit's choice, XOR and variable-length variants.
+rows, the 32-bit circuit's choice and variable-length variants; the XOR variant's gate polynomial is written here once.
 """
 from __future__ import annotations
 
@@ -177,6 +177,13 @@ def base_system(fam: Family, tb: int, fixed_names=FIXED, equality_on_y: bool = F
     for name, s in (("a", "A"), ("e", "E")):  # H + (a .. h): the same slot one block and four regions back
         polys["chain_" + name] = sel["q_chain"] * (w(s) + carry("CARRY_" + s) - w(s, back=fam.block_regions) - w(s, back=4))
     return System(cs, adv, fcol, inst, cells, word, polys, w, from_chunks)
+
+
+def xor_word(sys: System):
+    """The polynomial of the gate `xor_word` of a circuit's XOR variant, whose fixed column is `q_xor`: W = e_r ^ e_(r-1).
+    Under q_f3 `chp_even_odd` makes the CHP_EVEN chunks the even bits of spread(e_r) + spread(e_(r-1)); the gate, anchored on
+    row 0 of a unit's second region, equates W with the word those chunks make up."""
+    return sys.cs.query_fixed(sys.fixed_columns["q_xor"]) * (sys.w("W") - sys.from_chunks("CHP_EVEN"))
 
 
 def finish(sys: System, dense, spread, gates=GATES):

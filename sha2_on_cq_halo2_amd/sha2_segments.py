@@ -2,7 +2,7 @@
 check, its description -- the fixed columns and the copy constraints, in one order -- its lowering to the arrays of the
 synthesis entry points, the word buffer, and the circuit object ("Wired segments, once for both widths").
 sha256_segments.py and sha512_segments.py define their widths, their `Segment` and `Plan`, the plans and the front ends
-that are theirs alone, and the call of their entry points.
+that are theirs alone, and the call of their entry points; sha512_xor.py is the 64-bit width with `Xor` gated.
 """
 from __future__ import annotations
 

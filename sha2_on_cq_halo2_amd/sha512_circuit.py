@@ -55,6 +55,12 @@ DIGEST_WORDS = {VARIANT_512: 8, VARIANT_384: 6}
 FAMILY = F.Family(WORD_BITS, "CQ_SHA512_", "cq_sha512_layout", (((28, 34, 39), None), ((14, 18, 41), None), ((1, 8), 7), ((19, 61), 6)),
                   tuple(K512), chunk_length_checked=True)
 SPREAD_ONES = FAMILY.spread_ones  # the spread form of 2^64 - 1
+# the XOR variant (plans with an Xor word, sha512_xor.py): one selector behind `const`, one gate behind the others; a unit
+# is XOR_REGIONS regions behind the last segment, and the gate reads cells the layout has already ("XOR-wired
+# message words on the 64-bit circuit")
+GATES_XOR = GATES + ("xor_word",)
+FIXED_XOR = FIXED + ("q_xor",)
+XOR_REGIONS, XOR_WORDS = _CQ["CQ_SHA512_XOR_REGIONS"], _CQ["CQ_SHA512_XOR_WORDS"]
 
 
 def layout():
@@ -136,8 +142,18 @@ def describe_batch(k: int, blocks_list, variants=None, table_bits: int = 12, den
     return Description(cs, adv, fcol, fixed, inst, copies, cells, table_bits, blocks_list, variants, k)
 
 
-def _constraint_system(tb: int, dense, spread):
-    return F.finish(F.base_system(FAMILY, tb), dense, spread)
+def _constraint_system(tb: int, dense, spread, xor: bool = False):
+    """`xor`: the variant for plans with XOR-wired message words -- the fixed column `q_xor` and the gate `xor_word`;
+    everything else is the plain system, built by the same lines."""
+    if not xor:
+        return F.finish(F.base_system(FAMILY, tb), dense, spread)
+    system = F.base_system(FAMILY, tb, FIXED_XOR)
+    system.polys["xor_word"] = F.xor_word(system)
+    out = F.finish(system, dense, spread, GATES_XOR)
+    # the gate adds the dense CHP_EVEN cells that hold a chunk below bit 64 and one fixed column to the queries, nothing to
+    # the blinding rows or the degree: a dense column has at most 16 distinct rotations inside a region, X has more
+    assert (system.cs.blinding_factors(), system.cs.degree()) == (20, 4)
+    return out
 
 
 def _assign_segment(fixed, copies, first_region, blocks, variant, public, tb, adv, fcol, inst, cells, word, pinned=None, public_words=None):

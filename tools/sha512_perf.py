@@ -13,7 +13,12 @@ cq_sha512_synthesize_segments_dev (the `batch` plan: the whole `synthesize`, and
 it is on the device); and `merkle`, the deepest Merkle tree over 64-byte leaves that fits: the entry point with a stream
 synchronise, then the witness check and one proof.
 
-    python tools/sha512_perf.py [--sizes 14,18] [--legs circuits,batch,merkle] [--segments-k 18] [--reps 15] [--warmup 3]
+The `hmac` leg (not run by default) is as many independent HMAC-SHA-512 (64-byte key, one message block) as 2^segments-k
+rows hold in one plan: cq_sha512_synthesize_xors_dev plus a stream synchronise, the same plan with the Xor words as Private
+words through cq_sha512_synthesize_segments_dev -- the difference is what the XOR units cost -- then `synthesize`, the witness
+check and one proof of the keyed circuit.
+
+    python tools/sha512_perf.py [--sizes 14,18] [--legs circuits,batch,merkle[,hmac]] [--segments-k 18] [--reps 15] [--warmup 3]
 """
 import argparse
 import hashlib
@@ -133,6 +138,93 @@ def merkle_row(ctx, k, reps, warmup):
     print(json.dumps(row), flush=True)
 
 
+def hmac_row(ctx, k, reps, warmup):
+    """The largest count of independent HMAC-SHA-512 (64-byte key, 104-byte message: one message block) at 2^k rows."""
+    import ctypes as C
+    import hmac
+
+    import numpy as np
+
+    from sha2_on_cq_halo2_amd import sha512_circuit as SC
+    from sha2_on_cq_halo2_amd import sha512_segments as SS
+    from sha2_on_cq_halo2_amd import sha512_xor as SX
+
+    key_bytes, message_bytes = 64, 104
+    one = SX.hmac_sha512(key_bytes, message_bytes)
+    count, nvars = SC.usable_rows(k) // SX.rows_for(one), key_bytes // 8
+
+    def moved(s, i, strip):  # HMAC i of the plan: its own vars and segments; `strip`: the Xor words as Private words
+        if isinstance(s, SX.Xor):
+            return SS.PRIVATE if strip else SX.Xor(moved(s.x, i, strip), moved(s.y, i, strip))
+        if isinstance(s, SS.Var):
+            return SS.Var(s.index + nvars * i)
+        return SS.DigestWord(s.segment + 2 * i, s.word) if isinstance(s, SS.DigestWord) else s
+
+    def repeated(strip):
+        segs = tuple(SS.Segment(seg.blocks, tuple(moved(s, i, strip) for s in seg.sources)) for i in range(count) for seg in one.segments)
+        return SS.Plan(segs, tuple((2 * i + 1, 8) for i in range(count)))
+
+    keys = [hashlib.sha512(b"key %d" % i).digest() for i in range(count)]
+    messages = [bytes((i + 3 * j) % 256 for j in range(message_bytes)) for i in range(count)]
+    tags = [hmac.new(key, m, "sha512").digest() for key, m in zip(keys, messages)]
+    words = lambda data: [int(x) for x in np.frombuffer(data, dtype=">u8")]
+    n = 1 << k
+    cols = [ctx.alloc(32 * n) for _ in range(SC.ADVICE_COLUMNS)]
+    arr = (C.c_void_p * len(cols))(*[b.ptr for b in cols])
+    row = {"leg": "hmac", "hmac": "independent HMAC-SHA-512, 64-byte key, 104-byte message", "k": k, "hmacs": count, "segments": 2 * count,
+           "blocks": 4 * count, "xor_units": 2 * nvars * count, "rows": count * SX.rows_for(one)}
+    legs, bufs = [], []
+    for strip in (False, True):
+        plan = repeated(strip)
+        low = SX.lower(plan)
+        if strip:  # the key block's words are private words, in word order before the message's
+            values = [x for i in range(count) for x in ([w ^ SX.HMAC_IPAD for w in words(keys[i])] + words(messages[i]), [w ^ SX.HMAC_OPAD for w in words(keys[i])])]
+            buf = SS.word_buffer(low, values)
+        else:
+            buf = SS.word_buffer(low, [x for i in range(count) for x in (words(messages[i]), [])], [w for key in keys for w in words(key)])
+        words_dev, digests_dev = ctx.to_device(buf), ctx.alloc(64 * len(low.seg_blocks) + 8 * len(low.xors))
+        bufs += [words_dev, digests_dev]
+
+        def call(low=low, words_dev=words_dev, digests_dev=digests_dev, strip=strip):
+            head = (ctx.h, 12, low.seg_blocks.ctypes.data, len(low.seg_blocks), low.seg_variant.ctypes.data, low.sources.ctypes.data, None)
+            tail = (words_dev.ptr, low.words_len, n, arr, digests_dev.ptr)
+            if strip:
+                ctx._chk(ctx.lib.cq_sha512_synthesize_segments_dev(*head, *tail))
+            else:
+                ctx._chk(ctx.lib.cq_sha512_synthesize_xors_dev(*head, low.xors.ctypes.data, len(low.xors), *tail))
+            ctx.sync()
+
+        call()
+        got = digests_dev.download((2 * count, 8), np.uint64)[1::2].astype(">u8")
+        assert [t.tobytes() for t in got] == tags
+        legs.append(("segments_dev_private_key_blocks_ms" if strip else "xors_dev_ms", call))
+    for name, fn in legs + [("xors_dev_again_ms", legs[0][1])]:
+        row[name], row[name + "_range"] = median_ms(fn, reps, warmup)
+    for b in cols + bufs:
+        b.close()
+    t0 = time.perf_counter()
+    c = SX.Sha512XorSegmentsCircuit(ctx, k, repeated(False))
+    row["keygen_s"] = round(time.perf_counter() - t0, 2)
+    values, shared = [x for i in range(count) for x in (words(messages[i]), [])], [w for key in keys for w in words(key)]
+    assert c.check(values, shared) == (0, []) and c.digests == tags
+    ptrs, seed = [b.ptr for b in c.cols], [0]
+
+    def prove():
+        seed[0] += 1
+        c.pk.create_proof_dev(ptrs, seed=seed[0], instances=c.instances)
+
+    def synthesize():
+        c.synthesize(values, shared)
+        ctx.sync()
+
+    for name, fn in (("synthesize_ms", synthesize), ("check_ms", lambda: c.pk.check_witness(ptrs, instances=c.instances, max_failures=0)),
+                     ("proof_ms", prove)):
+        row[name], row[name + "_range"] = median_ms(fn, reps, warmup)
+    row["proof_bytes"] = c.pk.proof_size
+    c.close()
+    print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="14,18")
@@ -160,6 +252,8 @@ def main():
         batch_rows(ctx, args.segments_k, args.reps, args.warmup)
     if "merkle" in legs:
         merkle_row(ctx, args.segments_k, args.reps, args.warmup)
+    if "hmac" in legs:
+        hmac_row(ctx, args.segments_k, args.reps, args.warmup)
     ctx.close()
 
 
